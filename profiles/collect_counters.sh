@@ -9,7 +9,7 @@ WL=${3:-cfg3_headline}
 export TMPDIR=/tmp
 OUT=gpurun_out/ctr_$$
 rm -rf $OUT
-rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT -- python3 bench.py --workload $WL --steps 4 --warmup 2 --breakdown-steps 1 --no-cpu-baseline > $OUT.log 2>&1
+rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT -- python3 bench.py --full --workload $WL --steps 4 --warmup 2 --breakdown-steps 1 --no-cpu-baseline > $OUT.log 2>&1
 python3 - "$OUT" "$DST" "$WL" <<'PY'
 import collections, csv, glob, json, os, sys
 out, dst, wl = sys.argv[1:4]

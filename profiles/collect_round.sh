@@ -17,18 +17,18 @@ bash profiles/collect_sq.sh ${TAG} cfg3_headline > gpurun_out/${TAG}_sq.log 2>&1
 cp profiles/pmc_traffic.json profiles/sq_counters.json profiles/${TAG}_sq_counters.json $R/
 echo "counters done" >&2
 E=gpurun_out/${TAG}_bench.err
-python3 bench.py > $R/${TAG}_bench_cfg3.json 2> $E
-GS_PREDICT_SIZES=0 python3 bench.py --no-cpu-baseline > $R/${TAG}_bench_cfg3_exact_sizing.json 2>> $E
-python3 bench.py --no-cpu-baseline --fixed-pose > $R/${TAG}_bench_cfg3_fixed_pose.json 2>> $E
-python3 bench.py --workload cfg2_truck7k --no-cpu-baseline > $R/${TAG}_bench_cfg2.json 2>> $E
-python3 bench.py --workload cfg5_infer2e6 --no-cpu-baseline > $R/${TAG}_bench_cfg5_inference.json 2>> $E
-python3 bench.py --workload cfg5_infer2e6 --rgb-only --no-cpu-baseline > $R/${TAG}_bench_cfg5_inference_rgb_only.json 2>> $E
-python3 bench.py --workload cfg3_1080p --no-cpu-baseline > $R/${TAG}_bench_cfg3_1080p.json 2>> $E
+python3 bench.py --full > $R/${TAG}_bench_cfg3.json 2> $E
+GS_PREDICT_SIZES=0 python3 bench.py --full --no-cpu-baseline > $R/${TAG}_bench_cfg3_exact_sizing.json 2>> $E
+python3 bench.py --full --no-cpu-baseline --fixed-pose > $R/${TAG}_bench_cfg3_fixed_pose.json 2>> $E
+python3 bench.py --full --workload cfg2_truck7k --no-cpu-baseline > $R/${TAG}_bench_cfg2.json 2>> $E
+python3 bench.py --full --workload cfg5_infer2e6 --no-cpu-baseline > $R/${TAG}_bench_cfg5_inference.json 2>> $E
+python3 bench.py --full --workload cfg5_infer2e6 --rgb-only --no-cpu-baseline > $R/${TAG}_bench_cfg5_inference_rgb_only.json 2>> $E
+python3 bench.py --full --workload cfg3_1080p --no-cpu-baseline > $R/${TAG}_bench_cfg3_1080p.json 2>> $E
 for wl in cfg3_clustered cfg2_clustered; do
-  python3 bench.py --workload $wl --no-cpu-baseline > $R/${TAG}_bench_$wl.json 2>> $E
-  GS_BWD_SPLIT_HEAVY=0 python3 bench.py --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_no_heavy_sharing.json 2>> $E
-  GS_BWD_SEGMENTS=0 python3 bench.py --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_no_segments.json 2>> $E
-  GS_BWD_SEGMENTS=1 python3 bench.py --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_segments.json 2>> $E
+  python3 bench.py --full --workload $wl --no-cpu-baseline > $R/${TAG}_bench_$wl.json 2>> $E
+  GS_BWD_SPLIT_HEAVY=0 python3 bench.py --full --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_no_heavy_sharing.json 2>> $E
+  GS_BWD_SEGMENTS=0 python3 bench.py --full --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_no_segments.json 2>> $E
+  GS_BWD_SEGMENTS=1 python3 bench.py --full --workload $wl --no-cpu-baseline > $R/${TAG}_bench_${wl}_segments.json 2>> $E
 done
 echo "bench lines done" >&2
 rm -rf gpurun_out/prof_${TAG}

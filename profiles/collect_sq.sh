@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/sq_$WL
 rm -rf $OUT
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
-    --output-format csv -d $OUT -- python3 bench.py --workload $WL --steps 4 --warmup 2 --breakdown-steps 1 --no-cpu-baseline > $OUT.log 2>&1
+    --output-format csv -d $OUT -- python3 bench.py --full --workload $WL --steps 4 --warmup 2 --breakdown-steps 1 --no-cpu-baseline > $OUT.log 2>&1
 python3 - "$OUT" "profiles/${TAG}_sq_counters.json" "$WL" <<'PY'
 import collections, csv, glob, json, os, sys
 out, dst, wl = sys.argv[1:4]

@@ -3,7 +3,7 @@
 set -e
 O=gpurun_out/r03_repair; mkdir -p $O
 for r in 1 2; do for v in base new; do for wl in cfg2_clustered cfg2_truck7k cfg3_headline cfg3_clustered; do
-  GSRAST_LIB=$PWD/build_ab/libgsrast_$v.so python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${v}_$r.json 2>/dev/null
+  GSRAST_LIB=$PWD/build_ab/libgsrast_$v.so python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${v}_$r.json 2>/dev/null
 done; done; done
 python - <<'PY'
 import json,glob

@@ -7,7 +7,7 @@ for v in s512m512 s512m1024; do
   tail -1 $O/parity_$v.txt
 done
 for r in 1 2; do for v in base s512m1024 s512m768 s512m512; do for wl in cfg2_clustered cfg2_truck7k; do
-  GSRAST_LIB=$PWD/build_ab/libgsrast_$v.so python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${v}_$r.json 2>/dev/null
+  GSRAST_LIB=$PWD/build_ab/libgsrast_$v.so python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${v}_$r.json 2>/dev/null
 done; done; done
 python - <<'PY'
 import json,glob

@@ -5,8 +5,8 @@ mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_stages.py tests/test_gpu_scene_files.py -x -q > $O/gputest.log 2>&1 || { tail -30 $O/gputest.log >&2; exit 1; }
 tail -2 $O/gputest.log >&2
 for wl in cfg3_headline cfg3_clustered cfg2_clustered cfg2_truck7k; do
-  python bench.py --no-cpu-baseline --workload $wl > $O/bench_$wl.json 2>> $O/err.log
-  GS_BWD_SPLIT_HEAVY=0 python bench.py --no-cpu-baseline --workload $wl > $O/bench_${wl}_nosplit.json 2>> $O/err.log
+  python bench.py --full --no-cpu-baseline --workload $wl > $O/bench_$wl.json 2>> $O/err.log
+  GS_BWD_SPLIT_HEAVY=0 python bench.py --full --no-cpu-baseline --workload $wl > $O/bench_${wl}_nosplit.json 2>> $O/err.log
   python tools/bwd_wave_timeline.py $wl > $O/bwd_timeline_$wl.txt 2>> $O/err.log
 done
 python - <<PY

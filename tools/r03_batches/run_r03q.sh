@@ -4,14 +4,14 @@ mkdir -p $O
 for wl in cfg2_clustered cfg2_truck7k; do
  for lib in wpb0 wpb8; do
   for x2 in 2 3 4 6; do
-    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_$lib.so python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${lib}_x$x2.json 2>> $O/err.log
+    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_$lib.so python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${lib}_x$x2.json 2>> $O/err.log
   done
  done
 done
 for wl in cfg3_clustered cfg3_headline; do
  for lib in wpb0 wpb8; do
   for x2 in 4 6; do
-    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_$lib.so python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${lib}_x$x2.json 2>> $O/err.log
+    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_$lib.so python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_${lib}_x$x2.json 2>> $O/err.log
   done
  done
 done

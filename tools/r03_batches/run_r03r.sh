@@ -3,7 +3,7 @@ O=gpurun_out/r03r
 mkdir -p $O
 for wl in cfg3_clustered cfg3_headline; do
   for x2 in 2 3 4 5; do
-    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_wpb8.so python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_wpb8_x$x2.json 2>> $O/err.log
+    GS_BWD_HEAVY_X2=$x2 GSRAST_LIB=$PWD/build_ab/libgsrast_wpb8.so python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_wpb8_x$x2.json 2>> $O/err.log
   done
 done
 python - <<PY

@@ -4,7 +4,7 @@ mkdir -p $O
 for wl in cfg3_clustered cfg3_headline cfg2_clustered; do
  for seg in 0 1; do
   for x2 in 3 4 6; do
-    GS_BWD_SEGMENTS=$seg GS_BWD_HEAVY_X2=$x2 python bench.py --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_seg${seg}_x$x2.json 2>> $O/err.log
+    GS_BWD_SEGMENTS=$seg GS_BWD_HEAVY_X2=$x2 python bench.py --full --no-cpu-baseline --breakdown-steps 50 --steps 200 --workload $wl > $O/${wl}_seg${seg}_x$x2.json 2>> $O/err.log
   done
  done
 done
