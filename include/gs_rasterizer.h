@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 8
+#define GS_ABI_VERSION 9
 #define GS_TILE 16              /* RAST:27-28 TILE_WIDTH = TILE_HEIGHT */
 #define GS_FEATURES 56          /* RAST:208-236 row layout */
 
@@ -321,6 +321,104 @@ int gs_scale_regulariser_grad(gs_ctx* ctx, const float* point_cloud_features, co
  * `step` is the 1-based step count used for the bias corrections. */
 int gs_adam_step(gs_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                  float lr, float beta1, float beta2, float eps, int64_t step, gs_stream stream);
+
+/* ---- adaptive density control: GaussianPointAdaptiveController.py, CTRL below ------------------------
+ * The reference's densification step -- floaters and transparent points pruned, points with large view-space gradients
+ * cloned (under-reconstructed) or split (over-reconstructed) into free rows of the pre-allocated scene -- as device passes
+ * that never wait for the host: every count stays in plan->counts until the caller reads it.  Deterministic (integer
+ * counts only, ascending-id compactions).  A row is valid when point_invalid_mask == 0 and free when it is exactly 1.
+ * Policy (iteration schedule, reset_alpha) stays with the caller (GaussianPointAdaptiveController.py of this package). */
+
+/* The thresholds and switches of GaussianPointAdaptiveControllerConfig (CTRL:54-84) the two passes read, in the
+ * reference's order and with its defaults.  Floats are compared in f32, as torch compares an f32 tensor with a Python
+ * float; the pixel thresholds are integers (an int32 tensor against a Python int). */
+typedef struct gs_density_config {
+    float   transparent_alpha_threshold;                                                  /* -0.5 */
+    float   densification_view_space_position_gradients_threshold;                        /* 6e-6 */
+    float   densification_view_avg_space_position_gradients_threshold;                    /* 1e3  */
+    float   densification_multi_frame_view_space_position_gradients_threshold;            /* 1e3  */
+    float   densification_multi_frame_view_pixel_avg_space_position_gradients_threshold;  /* 1e3  */
+    float   densification_multi_frame_position_gradients_threshold;                       /* 1e3  */
+    float   log_gaussian_split_factor_phi;      /* f32(log(1.6)): the host's log of gaussian_split_factor_phi, rounded once */
+    int32_t floater_near_camrea_num_pixels_threshold;                                     /* 10000 (sic, CTRL:77) */
+    float   floater_depth_threshold;                                                      /* 100  */
+    int32_t under_reconstructed_num_pixels_threshold;                                     /* 512  */
+    float   under_reconstructed_move_factor;                                              /* 100  */
+    int32_t enable_ellipsoid_offset;                                                      /* 0    */
+    int32_t enable_sample_from_point;                                                     /* 1    */
+} gs_density_config;
+
+/* flag bits of plan->flags (one byte per row, rewritten by every gs_density_select) */
+#define GS_DENSITY_FLOATER          1   /* pruned as a floater (CTRL:189-199) */
+#define GS_DENSITY_TRANSPARENT      2   /* pruned as transparent: alpha < threshold or a NaN feature (CTRL:201-209) */
+#define GS_DENSITY_DENSIFY          4   /* in the densify set (CTRL:243-246), valid rows only */
+#define GS_DENSITY_OVER             8   /* densify row with a size reduction: accumulated_num_pixels > threshold (CTRL:253-255) */
+#define GS_DENSITY_CAM_FLOATER     16   /* hook marks of this frame: floater_mask_in_camera (CTRL:192-193) */
+#define GS_DENSITY_CAM_SINGLE      32   /*   single-frame gradient criterion, either threshold (CTRL:217-222) */
+#define GS_DENSITY_CAM_VIEWSPACE   64   /*   its first threshold alone (CTRL:217) */
+
+/* plan->counts, int32 each */
+typedef enum gs_density_count {
+    GS_DC_FLOATERS = 0,             /* select */
+    GS_DC_TRANSPARENT = 1,          /* select */
+    GS_DC_DENSIFY = 2,              /* select: rows in densify_point_id */
+    GS_DC_FILLABLE = 3,             /* apply: min(densify, free rows after pruning) = pairs filled */
+    GS_DC_OVER = 4,                 /* apply: filled pairs that were split */
+    GS_DC_UNDER = 5,                /* apply: filled pairs that were cloned */
+    GS_DC_VALID_BEFORE = 6,         /* apply */
+    GS_DC_VALID_AFTER = 7,          /* apply: valid_before - floaters - transparent + fillable (CTRL:346) */
+    GS_DC_SINGLE_FRAME = 8,         /* select: num_to_densify of CTRL:223 */
+    GS_DC_SINGLE_FRAME_VIEWSPACE = 9, /* select: num_to_densify_by_viewspace of CTRL:219 */
+    GS_DC_COUNT_
+} gs_density_count;
+
+/* Caller-owned device memory of the two passes, every array with (at least) n_points rows.  What select leaves is what
+ * CTRL:256-263 keeps in GaussianPointAdaptiveControllerDensifyPointInfo; apply reads it and fills fill_point_id. */
+typedef struct gs_density_plan {
+    int8_t*  flags;                                         /* (N) GS_DENSITY_* bits */
+    int32_t* densify_point_id;                              /* (N) ascending row ids, counts[GS_DC_DENSIFY] of them */
+    float*   densify_point_position_before_optimization;    /* (N,3) snapshot of point_cloud at select */
+    float*   densify_point_grad_position;                   /* (N,3) accumulated_position_gradients / num_in_camera, NaN -> 0 */
+    float*   densify_size_reduction_factor;                 /* (N)   log(phi) for over-reconstructed rows, else 0 */
+    int32_t* fill_point_id;                                 /* (N) the first free rows, ascending, counts[GS_DC_FILLABLE] used */
+    void*    scratch;                                       /* gs_density_scratch_bytes(n_points) bytes */
+    int32_t* counts;                                        /* (GS_DC_COUNT_) */
+    int64_t  n_points;                                      /* rows the arrays were sized for, >= the scene's */
+} gs_density_plan;
+
+/* The scene as apply edits it, in place (the layouts of gs_scene). */
+typedef struct gs_density_scene {
+    float*   point_cloud;           /* device (N,3) f32 */
+    float*   point_cloud_features;  /* device (N,56) f32 */
+    int8_t*  point_invalid_mask;    /* device (N) i8 */
+    int32_t* point_object_id;       /* device (N) i32 */
+    int64_t  n_points;
+} gs_density_scene;
+
+int64_t gs_density_scratch_bytes(int64_t n_points);
+
+/* _find_densify_points, CTRL:170-265: run inside the backward hook of the densify iteration, before the optimiser step.
+ * The hook arrays are BackwardValidPointHookInput's (M rows, unique ids in [0, N); rows with an id outside are ignored);
+ * acc the six accumulators (N rows).  remove_floaters: iteration_counter > iteration_start_remove_floater (CTRL:191).
+ * Reads the scene, writes only the plan.  M = 0 and N = 0 are valid. */
+int gs_density_select(gs_ctx* ctx, const gs_scene* scene, const gs_controller_accumulators* acc,
+                      const int32_t* point_id_in_camera_list, const int32_t* num_affected_pixels, const float* point_depth,
+                      const float* magnitude_grad_viewspace, int64_t n_in_camera, int32_t remove_floaters,
+                      const gs_density_config* config, const gs_density_plan* plan, gs_stream stream);
+
+/* _add_densify_points, CTRL:290-353: run after the optimiser step on the plan of the last select.  Prunes, then fills
+ * the first free rows (a row pruned by this call included, CTRL:299) with clones / splits of the densify rows.  The two
+ * position samples of a split (GaussianPoint3D.sample, GP3D:391-406) draw from Philox4x32-10 keyed by `seed` with counter
+ * (destination row, call_index, 0 = clone / 1 = original, 0): the result does not depend on launch shape.  The densify
+ * rows are valid rows (select never puts a free row in the densify set) and the fill rows free ones, so no row is both. */
+int gs_density_apply(gs_ctx* ctx, const gs_density_scene* scene, const gs_density_config* config, const gs_density_plan* plan,
+                     uint64_t seed, uint32_t call_index, gs_stream stream);
+
+/* GaussianPointAdaptiveController.update()'s six += (CTRL:133-141) from the hook payload, bit for bit what
+ * gs_backward_out.controller gives: for callers that wire only backward_valid_point_hook.  grad_point_in_camera (M,3). */
+int gs_controller_accumulate(gs_ctx* ctx, const int32_t* point_id_in_camera_list, const int32_t* num_affected_pixels,
+                             const float* magnitude_grad_viewspace, const float* grad_point_in_camera, int64_t n_in_camera,
+                             int64_t n_points, const gs_controller_accumulators* acc, gs_stream stream);
 
 /* Bytes of device memory the context currently owns (arena + frames). */
 int64_t gs_ctx_device_bytes(const gs_ctx* ctx);

@@ -4,3 +4,4 @@ load the HIP library; constructing the operator does, and fails loudly without i
 from .Camera import CameraInfo  # noqa: F401
 from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation  # noqa: F401
 from .controller_stats import ControllerAccumulators  # noqa: F401
+from .GaussianPointAdaptiveController import GaussianPointAdaptiveController  # noqa: F401

@@ -11,7 +11,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSRAST_LIB selects another build of the same library (e.g. the counter-instrumented `make stats` one); no other fallback
 LIB_PATH = os.environ.get("GSRAST_LIB") or os.path.join(_HERE, "lib", "libgsrast.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _I64, _I32, _F32, _VP = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 
@@ -74,6 +74,36 @@ class GsBackwardOut(C.Structure):
                 ("hook_point_uv_in_camera", _VP)]
 
 
+class GsDensityConfig(C.Structure):
+    _fields_ = [("transparent_alpha_threshold", _F32),
+                ("densification_view_space_position_gradients_threshold", _F32),
+                ("densification_view_avg_space_position_gradients_threshold", _F32),
+                ("densification_multi_frame_view_space_position_gradients_threshold", _F32),
+                ("densification_multi_frame_view_pixel_avg_space_position_gradients_threshold", _F32),
+                ("densification_multi_frame_position_gradients_threshold", _F32),
+                ("log_gaussian_split_factor_phi", _F32), ("floater_near_camrea_num_pixels_threshold", _I32),
+                ("floater_depth_threshold", _F32), ("under_reconstructed_num_pixels_threshold", _I32),
+                ("under_reconstructed_move_factor", _F32), ("enable_ellipsoid_offset", _I32), ("enable_sample_from_point", _I32)]
+
+
+class GsDensityPlan(C.Structure):
+    _fields_ = [("flags", _VP), ("densify_point_id", _VP), ("densify_point_position_before_optimization", _VP),
+                ("densify_point_grad_position", _VP), ("densify_size_reduction_factor", _VP), ("fill_point_id", _VP),
+                ("scratch", _VP), ("counts", _VP), ("n_points", _I64)]
+
+
+class GsDensityScene(C.Structure):
+    _fields_ = [("point_cloud", _VP), ("point_cloud_features", _VP), ("point_invalid_mask", _VP),
+                ("point_object_id", _VP), ("n_points", _I64)]
+
+
+# gs_density_plan.flags bits and gs_density_count indices (include/gs_rasterizer.h)
+DENSITY_FLOATER, DENSITY_TRANSPARENT, DENSITY_DENSIFY, DENSITY_OVER = 1, 2, 4, 8
+DENSITY_CAM_FLOATER, DENSITY_CAM_SINGLE, DENSITY_CAM_VIEWSPACE = 16, 32, 64
+DENSITY_COUNTS = ("floaters", "transparent", "densify", "fillable", "over", "under", "valid_before", "valid_after",
+                  "single_frame", "single_frame_viewspace")
+
+
 # gs_export ids (include/gs_rasterizer.h) -> (name, numpy/torch dtype name, trailing shape)
 EXPORTS = {
     "point_id_in_camera_list": (0, "int32", ()),
@@ -99,7 +129,8 @@ SYMBOLS = ["gs_abi_version", "gs_last_error", "gs_create", "gs_destroy", "gs_for
            "gs_frame_export_count", "gs_frame_export", "gs_backward", "gs_frame_release", "gs_frame_heavy_tiles",
            "gs_ctx_device_bytes", "gs_ctx_counter_wait_ns", "gs_kernel_names", "gs_profile_enable", "gs_profile_read",
            "gs_loss_l1_ssim", "gs_loss_maps_floats", "gs_loss_l1_ssim_forward", "gs_loss_l1_ssim_backward", "gs_adam_step", "gs_scale_regulariser", "gs_scale_regulariser_grad",
-           "gs_project_shard", "gs_project_shard_begin", "gs_forward_projected", "gs_backward_projected", "gs_backward_shard"]
+           "gs_project_shard", "gs_project_shard_begin", "gs_forward_projected", "gs_backward_projected", "gs_backward_shard",
+           "gs_density_scratch_bytes", "gs_density_select", "gs_density_apply", "gs_controller_accumulate"]
 
 _lib = None
 
@@ -183,6 +214,13 @@ def lib():
     L.gs_ctx_device_bytes.restype = _I64
     L.gs_ctx_counter_wait_ns.argtypes = [_VP]
     L.gs_ctx_counter_wait_ns.restype = _I64
+    L.gs_density_scratch_bytes.argtypes = [_I64]
+    L.gs_density_scratch_bytes.restype = _I64
+    L.gs_density_select.argtypes = [_VP, C.POINTER(GsScene), C.POINTER(GsControllerAccumulators), _VP, _VP, _VP, _VP, _I64, _I32,
+                                    C.POINTER(GsDensityConfig), C.POINTER(GsDensityPlan), _VP]
+    L.gs_density_apply.argtypes = [_VP, C.POINTER(GsDensityScene), C.POINTER(GsDensityConfig), C.POINTER(GsDensityPlan), C.c_uint64,
+                                   C.c_uint32, _VP]
+    L.gs_controller_accumulate.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _I64, C.POINTER(GsControllerAccumulators), _VP]
     if L.gs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH} has ABI {L.gs_abi_version()}, this package expects {ABI_VERSION}")
     _lib = L

@@ -1157,6 +1157,80 @@ extern "C" int gs_frame_release(gs_ctx* c, gs_frame* h)
     return GS_OK;
 }
 
+// ---- adaptive density control (k_density.hip) -------------------------------------------------------------------------
+extern "C" int64_t gs_density_scratch_bytes(int64_t n_points) { return n_points < 0 ? 0 : (int64_t)gs_density_scratch_size(n_points); }
+
+static int density_plan_check(const char* who, const gs_density_plan* p, int64_t N)
+{
+    if (!p || !p->counts) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": plan or plan->counts is NULL");
+    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_points must be in [0, 2^31)");
+    if (p->n_points < N) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": plan is smaller than the scene");
+    if (N > 0 && (!p->flags || !p->densify_point_id || !p->densify_point_position_before_optimization || !p->densify_point_grad_position ||
+                  !p->densify_size_reduction_factor || !p->fill_point_id || !p->scratch))
+        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL plan array");
+    return GS_OK;
+}
+
+extern "C" int gs_density_select(gs_ctx* c, const gs_scene* scene, const gs_controller_accumulators* acc, const int32_t* ids,
+                                 const int32_t* npix, const float* depth, const float* mag, int64_t M, int32_t remove_floaters,
+                                 const gs_density_config* cfg, const gs_density_plan* plan, gs_stream stream_)
+{
+    if (!c || !scene || !acc || !cfg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL argument");
+    const int64_t N = scene->n_points;
+    if (int rc = density_plan_check("gs_density_select", plan, N)) return rc;
+    if (M < 0 || M > N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: n_in_camera must be in [0, n_points]");
+    if (M > 0 && (!ids || !npix || !depth || !mag)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL hook array");
+    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL scene array");
+    if (N > 0 && (!acc->accumulated_num_in_camera || !acc->accumulated_num_pixels || !acc->accumulated_view_space_position_gradients ||
+                  !acc->accumulated_view_space_position_gradients_avg || !acc->accumulated_position_gradients ||
+                  !acc->accumulated_position_gradients_norm))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: the controller accumulators must all be given");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(enter_stream(c, s));
+    gs_launch_density_select(*scene, *acc, ids, npix, depth, mag, M, remove_floaters != 0, *cfg, *plan, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_density_apply(gs_ctx* c, const gs_density_scene* scene, const gs_density_config* cfg, const gs_density_plan* plan,
+                                uint64_t seed, uint32_t call_index, gs_stream stream_)
+{
+    if (!c || !scene || !cfg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_apply: NULL argument");
+    const int64_t N = scene->n_points;
+    if (int rc = density_plan_check("gs_density_apply", plan, N)) return rc;
+    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask || !scene->point_object_id))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_apply: NULL scene array");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(enter_stream(c, s));
+    gs_launch_density_apply(*scene, *cfg, *plan, seed, call_index, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_controller_accumulate(gs_ctx* c, const int32_t* ids, const int32_t* npix, const float* mag, const float* gpc, int64_t M,
+                                        int64_t N, const gs_controller_accumulators* acc, gs_stream stream_)
+{
+    if (!c || !acc) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: NULL argument");
+    if (N < 0 || N > INT32_MAX || M < 0 || M > N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: need 0 <= n_in_camera <= n_points < 2^31");
+    if (M > 0 && (!ids || !npix || !mag || !gpc)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: NULL hook array");
+    if (M > 0 && (!acc->accumulated_num_in_camera || !acc->accumulated_num_pixels || !acc->accumulated_view_space_position_gradients ||
+                  !acc->accumulated_view_space_position_gradients_avg || !acc->accumulated_position_gradients ||
+                  !acc->accumulated_position_gradients_norm))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: the controller accumulators must all be given");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(enter_stream(c, s));
+    gs_launch_controller_accumulate(ids, npix, mag, gpc, M, N, *acc, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
 // ---- diagnostic build only (make stats): counters of the blend kernels, tools/blend_stats.py ----
 #ifdef GS_STATS
 __device__ unsigned long long gs_stats_counters[32];

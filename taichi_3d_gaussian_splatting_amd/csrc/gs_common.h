@@ -351,3 +351,32 @@ void gs_launch_adam(float* param, const float* grad, float* m, float* v, int64_t
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s);
 void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, const float* value_and_count, const float* upstream,
                         float* grad, hipStream_t s);
+
+// ---- adaptive density controller (k_density.hip; GaussianPointAdaptiveController.py, CTRL) --------------------------------
+// The six accumulator updates of GaussianPointAdaptiveController.update() (CTRL:133-141) for one in-camera point n, in the
+// one operation order both k_bwd_points (from its per-splat sums) and k_controller_accumulate (from the hook payload) use,
+// so that the two wirings give the same bits.  npix / mag / g: the point's num_affected_pixels, magnitude_grad_viewspace
+// and grad_point_in_camera row.
+__device__ __forceinline__ void gs_controller_add(int64_t n, int32_t npix, float mag, float g0, float g1, float g2,
+                                                  int32_t* num_in_camera, int32_t* num_pixels, float* vs_grad, float* vs_grad_avg,
+                                                  float* pos_grad, float* pos_grad_norm)
+{
+    num_in_camera[n] += 1;
+    num_pixels[n] += npix;
+    vs_grad[n] += mag;
+    const float avg = mag / (float)npix;                            // 0/0 -> NaN -> 0 (CTRL:138-139); x/0 -> inf is kept
+    vs_grad_avg[n] += (avg != avg) ? 0.0f : avg;
+    pos_grad[3 * n] += g0; pos_grad[3 * n + 1] += g1; pos_grad[3 * n + 2] += g2;
+    pos_grad_norm[n] += sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
+}
+
+#include "../../include/gs_rasterizer.h"
+// select (CTRL:170-265), apply (CTRL:290-353) and the hook-side accumulation (CTRL:133-141); argument checks are gs_api.hip's
+void gs_launch_density_select(const gs_scene& scene, const gs_controller_accumulators& acc, const int32_t* ids, const int32_t* npix,
+                              const float* depth, const float* mag, int64_t M, int remove_floaters, const gs_density_config& cfg,
+                              const gs_density_plan& plan, hipStream_t s);
+void gs_launch_density_apply(const gs_density_scene& scene, const gs_density_config& cfg, const gs_density_plan& plan, uint64_t seed,
+                             uint32_t call_index, hipStream_t s);
+void gs_launch_controller_accumulate(const int32_t* ids, const int32_t* npix, const float* mag, const float* gpc, int64_t M, int64_t N,
+                                     const gs_controller_accumulators& acc, hipStream_t s);
+size_t gs_density_scratch_size(int64_t N);

@@ -1057,16 +1057,9 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         if (hook_ntiles) hook_ntiles[m] = ntiles[m];
         if (hook_depth) hook_depth[m] = GS_REC(PB, m).w;
         if (hook_uv) { const float4 pa = GS_REC(PA, m); hook_uv[2 * (size_t)m] = pa.x; hook_uv[2 * (size_t)m + 1] = pa.y; }
-        if (c_num_in_camera) {                                          // GaussianPointAdaptiveController.update, CTRL:133-141
-            const int32_t npix = __float_as_int(s[10]);
-            c_num_in_camera[n] += 1;
-            c_num_pixels[n] += npix;
-            c_vs_grad[n] += s[9];
-            const float avg = s[9] / (float)npix;                       // 0/0 -> NaN -> 0 (CTRL:138-139); x/0 -> inf is kept
-            c_vs_grad_avg[n] += (avg != avg) ? 0.0f : avg;
-            c_pos_grad[3 * n] += gt[0]; c_pos_grad[3 * n + 1] += gt[1]; c_pos_grad[3 * n + 2] += gt[2];
-            c_pos_grad_norm[n] += sqrtf(gt[0] * gt[0] + gt[1] * gt[1] + gt[2] * gt[2]);
-        }
+        if (c_num_in_camera)                                            // GaussianPointAdaptiveController.update, CTRL:133-141
+            gs_controller_add(n, __float_as_int(s[10]), s[9], gt[0], gt[1], gt[2],
+                              c_num_in_camera, c_num_pixels, c_vs_grad, c_vs_grad_avg, c_pos_grad, c_pos_grad_norm);
     }   // m >= 0
 
     // ---- rows out: stage, then the wave writes its 64 consecutive rows of grad_feat as one contiguous run ----
