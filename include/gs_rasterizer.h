@@ -138,8 +138,8 @@ typedef struct gs_controller_accumulators {
 } gs_controller_accumulators;
 
 /* Outputs of backward, RAST:1051-1067 + RAST:1127-1140.  The first two are
- * mandatory; every other pointer may be NULL (need_extra_info = false).
- * All N-row arrays are fully written (rows outside the frustum = 0). */
+ * mandatory unless the pose gradient is requested; every other pointer may be NULL
+ * (need_extra_info = false).  All N-row arrays are fully written (rows outside the frustum = 0). */
 typedef struct gs_backward_out {
     float*   grad_pointcloud;                   /* device (N,3)  */
     float*   grad_pointcloud_features;          /* device (N,56) band-masked and factor-scaled (RAST:1102-1125) */
@@ -159,6 +159,14 @@ typedef struct gs_backward_out {
     int32_t* hook_num_overlap_tiles;            /* device (M)    */
     float*   hook_point_depth;                  /* device (M)    */
     float*   hook_point_uv_in_camera;           /* device (M,2)  */
+    /* Pose gradient (trailing fields; the reference always returns None here, RAST:1158-1163): the derivative of the forward as it
+     * is computed, J(p) and view-direction paths included, with respect to the raw q (xyzw) and t of every pose row.  Both
+     * or neither; a row no touched point depends on is exactly zero.  Not affected by the grad factors or the SH band.
+     * Summed per object in fixed order: bitwise reproducible.  With both set, grad_pointcloud and grad_pointcloud_features
+     * may both be NULL (pose-only backward): then no point gradient, hook array or controller accumulator is written.
+     * gs_backward only; gs_backward_shard returns GS_ERR_INVALID_ARGUMENT if either is set. */
+    float*   grad_q_pointcloud_camera;          /* device (n_objects,4) or NULL */
+    float*   grad_t_pointcloud_camera;          /* device (n_objects,3) or NULL */
 } gs_backward_out;
 
 /* Intermediates a frame can copy out, in the reference's layouts (saved tensors

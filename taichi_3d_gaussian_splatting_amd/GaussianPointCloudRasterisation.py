@@ -197,7 +197,8 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                         q_pointcloud_camera, t_pointcloud_camera, camera_info, color_max_sh_band, grad_mode):
                 # ctx.needs_input_grad says whether the inputs require grad, not whether a graph is being recorded (it is True
                 # under torch.no_grad() too, and grad mode is always off inside forward): the caller passes the grad mode in
-                needs_grad = bool(grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
+                needs_grad = bool(grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or
+                                                 ctx.needs_input_grad[4] or ctx.needs_input_grad[5]))
                 outs, frame = module._run_forward(pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
                                                   q_pointcloud_camera, t_pointcloud_camera, camera_info, keep=needs_grad)
                 image, depth, acc_alpha, last, count = outs
@@ -214,8 +215,10 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
 
             @staticmethod
             def backward(ctx, grad_rasterized_image, grad_rasterized_depth, grad_pixel_valid_point_count):
-                grad_pointcloud = grad_pointcloud_features = None
-                if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:      # RAST:1028
+                grad_pointcloud = grad_pointcloud_features = grad_q = grad_t = None
+                want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]      # RAST:1028
+                want_pose = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]        # extension: the reference returns None for the pose
+                if want_points or want_pose:
                     if ctx.frame is None:
                         raise RuntimeError("backward through a forward that ran without gradient tracking")
                     (pointcloud, pointcloud_features, point_invalid_mask, point_object_id, q_pointcloud_camera,
@@ -223,14 +226,15 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                     if grad_rasterized_image is None:       # only the depth was used downstream: its gradient does not flow (RAST:1157-1163)
                         grad_rasterized_image = torch.zeros(ctx.camera_info.camera_height, ctx.camera_info.camera_width, 3,
                                                             dtype=torch.float32, device=pointcloud.device)
-                    grad_pointcloud, grad_pointcloud_features = module._run_backward(
+                    grad_pointcloud, grad_pointcloud_features, grad_q, grad_t = module._run_backward(
                         ctx.frame, pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
                         q_pointcloud_camera, t_pointcloud_camera, ctx.camera_info, acc_alpha, last,
-                        grad_rasterized_image.contiguous(), ctx.color_max_sh_band)
+                        grad_rasterized_image.contiguous(), ctx.color_max_sh_band, want_points=want_points, want_pose=want_pose)
                     # the frame is NOT released here: like the reference's saved tensors it lives as long as the graph
                     # node does, so backward(retain_graph=True) followed by another backward works; it goes back to the
                     # pool when autograd drops the node (_Frame.__del__)
-                return grad_pointcloud, grad_pointcloud_features, None, None, None, None, None, None, None
+                return (grad_pointcloud, grad_pointcloud_features, None, None,
+                        grad_q if ctx.needs_input_grad[4] else None, grad_t if ctx.needs_input_grad[5] else None, None, None, None)
 
         self._module_function = _module_function
 
@@ -310,7 +314,10 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         self.last_forward_outputs = {"pixel_accumulated_alpha": acc_alpha, "pixel_offset_of_last_effective_point": last}
         return (image, depth, acc_alpha, last, count), frame
 
-    def _run_backward(self, frame, pointcloud, features, mask, obj, q, t, camera_info, acc_alpha, last, grad_image, sh_band):
+    def _run_backward(self, frame, pointcloud, features, mask, obj, q, t, camera_info, acc_alpha, last, grad_image, sh_band,
+                      want_points=True, want_pose=False):
+        """-> (grad_pointcloud, grad_pointcloud_features, grad_q, grad_t); the first two are None when not want_points (no hook
+        call and no controller statistics then, as in the reference, RAST:1028), the last two None when not want_pose."""
         dev = pointcloud.device
         N, M = pointcloud.shape[0], frame.n_points_in_camera
         H, W = camera_info.camera_height, camera_info.camera_width
@@ -329,10 +336,17 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
             raise ValueError("grad of rasterized_image must be float32 (H,W,3)")
         # one allocation for both gradients so that data-parallel training all-reduces ONE buffer; the 56-float rows
         # come first: 224*N bytes keep them 16-byte aligned for any N (the kernels store them as float4)
-        flat = torch.empty(N * 59, dtype=torch.float32, device=dev)
-        grad_feat = flat[:N * 56].view(N, 56)
-        grad_pc = flat[N * 56:].view(N, 3)
-        want_hook = self._hook is not None
+        grad_pc = grad_feat = grad_q = grad_t = None
+        if want_points:
+            flat = torch.empty(N * 59, dtype=torch.float32, device=dev)
+            grad_feat = flat[:N * 56].view(N, 56)
+            grad_pc = flat[N * 56:].view(N, 3)
+        if want_pose:
+            # (n_objects,4) and (n_objects,3) float32, one allocation; every row is written
+            pose_flat = torch.empty(q.shape[0] * 7, dtype=torch.float32, device=dev)
+            grad_q = pose_flat[:q.shape[0] * 4].view(q.shape[0], 4)
+            grad_t = pose_flat[q.shape[0] * 4:].view(q.shape[0], 3)
+        want_hook = self._hook is not None and want_points
         grad_uv = mag = mag_img = n_aff = h_pc = h_feat = h_uv = h_mag = h_ids = h_ntiles = h_depth = h_puv = None
         if want_hook:
             # twelve arrays, one buffer and one split (the 56-float rows first: the kernel stores them as float4 and the buffer
@@ -343,7 +357,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
             grad_uv, mag, mag_img = parts[6].view(N, 2), parts[7], parts[8].view(H, W, 2)
             n_aff, h_ids, h_ntiles = parts[9].view(torch.int32), parts[10].view(torch.int32), parts[11].view(torch.int32)
         ctrl = None
-        if self.controller_accumulators is not None:
+        if self.controller_accumulators is not None and want_points:
             ca = self.controller_accumulators
             ca.validate(N, dev)
             ctrl = _native.GsControllerAccumulators(
@@ -353,7 +367,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         out = _native.GsBackwardOut(_ptr(grad_pc), _ptr(grad_feat), _ptr(grad_uv), _ptr(mag), _ptr(mag_img), _ptr(n_aff),
                                     _ptr(h_pc), _ptr(h_feat), _ptr(h_uv), _ptr(h_mag),
                                     C.pointer(ctrl) if ctrl is not None and N > 0 else None,
-                                    _ptr(h_ids), _ptr(h_ntiles), _ptr(h_depth), _ptr(h_puv))
+                                    _ptr(h_ids), _ptr(h_ntiles), _ptr(h_depth), _ptr(h_puv), _ptr(grad_q), _ptr(grad_t))
         stream = torch.cuda.current_stream(dev).cuda_stream
         with _on_device(dev):
             _native.check(_native.lib().gs_backward(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
@@ -368,7 +382,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                 magnitude_grad_viewspace=h_mag, magnitude_grad_viewspace_on_image=mag_img,
                 num_overlap_tiles=h_ntiles, num_affected_pixels=n_aff,
                 point_depth=h_depth, point_uv_in_camera=h_puv))
-        return grad_pc, grad_feat
+        return grad_pc, grad_feat, grad_q, grad_t
 
     # ------------------------------------------------------------------ nn.Module
     def forward(self, input_data: "GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput"):

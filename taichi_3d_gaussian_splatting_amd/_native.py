@@ -71,7 +71,7 @@ class GsBackwardOut(C.Structure):
                 ("hook_grad_pointfeatures_in_camera", _VP), ("hook_grad_viewspace", _VP),
                 ("hook_magnitude_grad_viewspace", _VP), ("controller", C.POINTER(GsControllerAccumulators)),
                 ("hook_point_id_in_camera_list", _VP), ("hook_num_overlap_tiles", _VP), ("hook_point_depth", _VP),
-                ("hook_point_uv_in_camera", _VP)]
+                ("hook_point_uv_in_camera", _VP), ("grad_q_pointcloud_camera", _VP), ("grad_t_pointcloud_camera", _VP)]
 
 
 class GsDensityConfig(C.Structure):

@@ -74,6 +74,7 @@ struct Frame {
     bool live = false;
     int cut_cap = 0;                    // list-cut records the forward of this frame could claim (0: it wrote none)
     int bwd_reference_order = 0;        // gs_config.bwd_reference_order of the forward that made the frame (gs_backward_projected has no config)
+    int n_objects = 0;                  // pose rows of the forward that made the frame (the backward's pose gradient has as many)
     bool max_tiles_known = false;       // k_project of this frame left the largest tile count of one point in the tile arrays (frames from records: no)
     uint32_t generation = 0;
     // gs_project_shard_begin: the hand-over of M (and the object-id check) has not been read yet; slot of the pinned counters
@@ -123,6 +124,7 @@ struct gs_ctx {
     int transient = -1;                 // slot of the frame of the last keep_for_backward == 0 call
     // scratch shared by all frames (stream ordered)
     DevBuf block_counts, block_offsets, tile_block_sums, hist, scan_tmp, counters, partial, visited, zero_row, sums, loss_ws;
+    DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
@@ -182,7 +184,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     for (FrameBufs* b : c->pool) { b->release(&c->device_bytes); delete b; }
     for (Frame* f : c->frames) delete f;
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
-                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint };
+                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : c->prof.spare) (void)hipEventDestroy(e);
@@ -409,6 +411,7 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     ENSURE(B.tile_start, 4 * GS_TILE_INTS(T));    // tile_start | tile_end | tile_work | tile_cut | cut_alloc, cleared together
     ENSURE(B.tile_order, 4 * GS_ORDER_INTS(T));   // + heavy-tile count, item count and item bases behind the order
     ENSURE(B.pose, sizeof(GsPose) * (size_t)cam->n_objects);
+    f->n_objects = cam->n_objects;
     ENSURE(c->block_counts, 4 * (nb + 1)); ENSURE(c->block_offsets, 4 * (nb + 1));
     ENSURE(c->tile_block_sums, 4 * (nb + 1));
 
@@ -932,9 +935,10 @@ static int prepare_backward_points(const Frame* f, const gs_scene* sc, const gs_
     return GS_OK;
 }
 
-static int check_backward_points_args(const Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_backward_out* out, const char* who)
+static int check_backward_points_args(const Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_backward_out* out, const char* who,
+                                      bool pose_only = false)
 {
-    if (sc->n_points > 0 && (!out->grad_pointcloud || !out->grad_pointcloud_features))
+    if (sc->n_points > 0 && !pose_only && (!out->grad_pointcloud || !out->grad_pointcloud_features))
         return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grad_pointcloud / grad_pointcloud_features are mandatory");
     if (sc->n_points != f->info.n_points || cam->camera_height != f->info.camera_height || cam->camera_width != f->info.camera_width)
         return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": scene/camera do not match the frame");
@@ -956,19 +960,29 @@ extern "C" int gs_backward(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_
     if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_backward: not a live frame of this context");
     if (!f->info.kept_for_backward) return fail(GS_ERR_STATE, "gs_backward: frame was not kept for backward");
     if (f->info.stages != (GS_STAGE_PROJECT | GS_STAGE_RASTER)) return fail(GS_ERR_STATE, "gs_backward: frame does not come from gs_forward");
+    // pose gradient: both pointers or neither; with them, the two point gradients may be left out (pose-only backward)
+    const bool pose = out->grad_q_pointcloud_camera || out->grad_t_pointcloud_camera;
+    if (pose && (!out->grad_q_pointcloud_camera || !out->grad_t_pointcloud_camera))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: grad_q_pointcloud_camera and grad_t_pointcloud_camera must be given together");
+    const bool points = !pose || out->grad_pointcloud || out->grad_pointcloud_features;
+    if (pose && cam->n_objects != f->n_objects)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: camera n_objects does not match the frame's forward");
     int rc;
-    if ((rc = check_backward_points_args(f, sc, cam, out, "gs_backward")) != GS_OK) return rc;
+    if ((rc = check_backward_points_args(f, sc, cam, out, "gs_backward", !points)) != GS_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(enter_stream(c, s));
     if (c->sums.ensure((size_t)(f->info.n_points_in_camera > 0 ? f->info.n_points_in_camera : 1) * 48, &c->device_bytes) != hipSuccess)
         return fail(GS_ERR_OUT_OF_MEMORY, "gs_backward: per-point sums buffer");
+    if (pose && c->pose_scratch.ensure(gs_pose_scratch_size((int)f->info.n_points_in_camera, f->n_objects), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_backward: pose-gradient scratch");
     GsBackwardArgs a{};
     if ((rc = prepare_backward_blend(c, f, grad_image, acc_alpha, last, out->magnitude_grad_viewspace_on_image, c->sums.as<float4>(), cfg->bwd_reference_order, s, &a)) != GS_OK) return rc;
     if ((rc = prepare_backward_points(f, sc, cam, cfg, sh_band, out, c->sums.as<float4>(), &a)) != GS_OK) return rc;
     gs_launch_backward_blend(a, s);
     if (a.T > 0 && a.K > 0) c->order_hint_T = a.T;          // k_tile_order ran: the hint is a complete permutation
-    gs_launch_backward_points(a, s);
+    if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics
+    if (pose) gs_launch_pose_grad(a, f->n_objects, c->pose_scratch.p, out->grad_q_pointcloud_camera, out->grad_t_pointcloud_camera, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1009,6 +1023,9 @@ extern "C" int gs_backward_shard(gs_ctx* c, gs_frame* h, const gs_scene* sc, con
     if (!f->info.kept_for_backward) return fail(GS_ERR_STATE, "gs_backward_shard: frame was not kept for backward");
     if (!(f->info.stages & GS_STAGE_PROJECT)) return fail(GS_ERR_STATE, "gs_backward_shard: frame holds no projection stage");
     if (f->info.n_points_in_camera > 0 && !splat_sums) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: splat_sums is NULL");
+    if (out->grad_q_pointcloud_camera || out->grad_t_pointcloud_camera)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: pose gradients are not available on the staged (Gaussian-parallel) path; "
+                                             "use gs_backward");
     int rc;
     if ((rc = check_backward_points_args(f, sc, cam, out, "gs_backward_shard")) != GS_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);

@@ -73,6 +73,77 @@ struct GsPose {
     float pad[2];
 };
 
+// ---- pose gradient (k_pose.hip) ---------------------------------------------------------------------------------
+// d/d(unit direction) of the 16 SH basis values the forward evaluates (GP3D:333-349, SH:10-53), contracted with gY = dL/dY:
+// g = sum_k gY[k] * dY_k/d(x, y, z), the derivative of the polynomial, not of its projection onto the sphere.
+__device__ __forceinline__ void gs_sh16_grad_dir(float x, float y, float z, const float gY[16], float g[3])
+{
+    const float c1 = 0.48860251190291987f, c4 = 1.0925484305920792f, c6 = 0.94617469575755997f, c8 = 0.54627421529603959f;
+    const float c9 = 0.59004358992664352f, c10 = 2.8906114426405538f, c11 = 0.45704579946446572f, c12 = 0.3731763325901154f;
+    const float c14 = 1.4453057213202769f;
+    const float xx = x * x, yy = y * y, zz = z * z;
+    float gx = -c1 * gY[3], gy = -c1 * gY[1], gz = c1 * gY[2];
+    gx += c4 * y * gY[4];                      gy += c4 * x * gY[4];
+    gy += -c4 * z * gY[5];                     gz += -c4 * y * gY[5];
+    gz += 2.0f * c6 * z * gY[6];
+    gx += -c4 * z * gY[7];                     gz += -c4 * x * gY[7];
+    gx += 2.0f * c8 * x * gY[8];               gy += -2.0f * c8 * y * gY[8];
+    gx += -6.0f * c9 * x * y * gY[9];          gy += 3.0f * c9 * (yy - xx) * gY[9];
+    gx += c10 * y * z * gY[10];                gy += c10 * x * z * gY[10];               gz += c10 * x * y * gY[10];
+    gy += c11 * (1.0f - 5.0f * zz) * gY[11];   gz += -10.0f * c11 * y * z * gY[11];
+    gz += c12 * (15.0f * zz - 3.0f) * gY[12];
+    gx += c11 * (1.0f - 5.0f * zz) * gY[13];   gz += -10.0f * c11 * x * z * gY[13];
+    gx += 2.0f * c14 * x * z * gY[14];         gy += -2.0f * c14 * y * z * gY[14];       gz += c14 * (xx - yy) * gY[14];
+    gx += 3.0f * c9 * (yy - xx) * gY[15];      gy += 6.0f * c9 * x * y * gY[15];
+    g[0] = gx; g[1] = gy; g[2] = gz;
+}
+
+// The per-object end of the pose gradient: from g = (dL/dW (9, row-major), dL/dt_cp (3), dL/do (3)) summed over the object's
+// points to dL/dq_pointcloud_camera (4) and dL/dt_pointcloud_camera (3), through what make_pose (k_project.hip) computes:
+//   q' = (-qx, -qy, -qz, qw);  W = R(q') by the un-normalised formula (GP3D:30-48);
+//   t_cp = -(n t_pc n*) with n = q' / |q'| (UTIL:426-432);  o = -W^T t_cp (origin_fwd, UTIL:495-510).
+// P is the frame's pose record: P.q_cp = q', P.origin_bwd = t_pc, P.R = W, P.t = t_cp.
+__device__ __forceinline__ void gs_pose_grad_chain(const GsPose& P, const float g[15], float gq[4], float gt[3])
+{
+    float dW[9], dt[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dW[k] = g[k];
+    const float* dO = g + 12;
+    // o_i = -sum_j W_ji t_j
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) dW[3 * j + i] -= P.t[j] * dO[i];
+        dt[j] = g[9 + j] - ((P.R[3 * j] * dO[0] + P.R[3 * j + 1] * dO[1]) + P.R[3 * j + 2] * dO[2]);
+    }
+    // W = R(q'), q' = (x, y, z, w) not normalised
+    const float x = P.q_cp[0], y = P.q_cp[1], z = P.q_cp[2], w = P.q_cp[3];
+    float gx = 2.0f * (y * (dW[1] + dW[3]) + z * (dW[2] + dW[6]) + w * (dW[7] - dW[5])) - 4.0f * x * (dW[4] + dW[8]);
+    float gy = 2.0f * (x * (dW[1] + dW[3]) + w * (dW[2] - dW[6]) + z * (dW[5] + dW[7])) - 4.0f * y * (dW[0] + dW[8]);
+    float gz = 2.0f * (w * (dW[3] - dW[1]) + x * (dW[2] + dW[6]) + y * (dW[5] + dW[7])) - 4.0f * z * (dW[0] + dW[4]);
+    float gw = 2.0f * (z * (dW[3] - dW[1]) + y * (dW[2] - dW[6]) + x * (dW[7] - dW[5]));
+    // t_cp = -rot, rot = n v n* = (nw^2 - u.u) v + 2 (u.v) u + 2 nw (u x v), u = n.xyz, v = t_pc; h = dL/drot
+    const float nrm = sqrtf(x * x + y * y + z * z + w * w);
+    const float ux = x / nrm, uy = y / nrm, uz = z / nrm, nw = w / nrm;
+    const float vx = P.origin_bwd[0], vy = P.origin_bwd[1], vz = P.origin_bwd[2];
+    const float hx = -dt[0], hy = -dt[1], hz = -dt[2];
+    const float hv = hx * vx + hy * vy + hz * vz, uh = ux * hx + uy * hy + uz * hz, uv = ux * vx + uy * vy + uz * vz;
+    const float uu = ux * ux + uy * uy + uz * uz, ww = nw * nw;
+    // d(h . rot)/du = -2 (h.v) u + 2 (u.h) v + 2 (u.v) h + 2 nw (v x h);  d/dnw = 2 nw (h.v) + 2 h.(u x v)
+    const float gnx = -2.0f * hv * ux + 2.0f * uh * vx + 2.0f * uv * hx + 2.0f * nw * (vy * hz - vz * hy);
+    const float gny = -2.0f * hv * uy + 2.0f * uh * vy + 2.0f * uv * hy + 2.0f * nw * (vz * hx - vx * hz);
+    const float gnz = -2.0f * hv * uz + 2.0f * uh * vz + 2.0f * uv * hz + 2.0f * nw * (vx * hy - vy * hx);
+    const float gnw = 2.0f * nw * hv + 2.0f * (hx * (uy * vz - uz * vy) + hy * (uz * vx - ux * vz) + hz * (ux * vy - uy * vx));
+    // n = q' / |q'|: the tangential part, divided by |q'|
+    const float ng = ux * gnx + uy * gny + uz * gnz + nw * gnw;
+    gx += (gnx - ux * ng) / nrm; gy += (gny - uy * ng) / nrm; gz += (gnz - uz * ng) / nrm; gw += (gnw - nw * ng) / nrm;
+    gq[0] = -gx; gq[1] = -gy; gq[2] = -gz; gq[3] = gw;
+    // d(h . rot)/dv = (nw^2 - u.u) h + 2 (u.h) u + 2 nw (h x u)
+    gt[0] = (ww - uu) * hx + 2.0f * uh * ux + 2.0f * nw * (hy * uz - hz * uy);
+    gt[1] = (ww - uu) * hy + 2.0f * uh * uy + 2.0f * nw * (hz * ux - hx * uz);
+    gt[2] = (ww - uu) * hz + 2.0f * uh * uz + 2.0f * nw * (hx * uy - hy * ux);
+}
+
 // Device-side frame counters, mirrored to pinned host memory once per forward.
 struct GsCounters {
     int32_t M;               // points in camera
@@ -331,6 +402,9 @@ struct GsBackwardArgs {
 };
 void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s);     // tile order, blend backward, per-splat sums -> a.sums
 void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s);    // a.sums -> every gradient / hook array
+// a.sums -> dL/dq_pointcloud_camera (n_objects,4) and dL/dt_pointcloud_camera (n_objects,3) (k_pose.hip); scratch: gs_pose_scratch_size bytes
+size_t gs_pose_scratch_size(int M, int n_objects);
+void gs_launch_pose_grad(const GsBackwardArgs& a, int n_objects, void* scratch, float* grad_q, float* grad_t, hipStream_t s);
 
 struct GsExportArgs { int what; int64_t N; int M; uint32_t K; int T; int depth_bits; int key64;
     const int32_t* ids; const float4 *PA, *PB, *PC, *PD; const int32_t* ntiles; const uint32_t* offsets;

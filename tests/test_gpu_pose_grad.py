@@ -1,0 +1,286 @@
+"""GPU (-m gpu): gradients with respect to q_pointcloud_camera and t_pointcloud_camera (k_pose.hip), against the float64
+reference of tests/pose_ref.py; that requesting them changes nothing else; the pose-only backward; determinism; pose recovery;
+and the staged path's refusal."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import parity_util as P
+import pose_ref
+from oracle import oracle
+from taichi_3d_gaussian_splatting_amd import _native
+from taichi_3d_gaussian_splatting_amd.controller_stats import ControllerAccumulators
+from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
+
+pytestmark = pytest.mark.gpu
+
+ELEM_RTOL, ELEM_FLOOR, TENSOR_TOL = 2e-5, 5e-6, 1e-4
+
+
+def _tiny(seed, n, sigma0, width, height):
+    """The scenes of test_oracle_autograd (non-unit pose quaternion)."""
+    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
+    ang = 0.05
+    q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32)
+    t = np.array([[0.03, -0.02, 0.1]], np.float32)
+    return s, q, t, int(width % 16 != 0 or height % 16 != 0)
+
+
+def _module(partial=False, strict=False, hook=None, ctrl=None, **factors):
+    cfg = P.Rast.GaussianPointCloudRasterisationConfig()
+    cfg.allow_partial_tiles = bool(partial)
+    cfg.backward_reference_order = bool(strict)
+    for k, v in factors.items():
+        setattr(cfg, k, v)
+    return P.Rast(cfg, backward_valid_point_hook=hook, controller_accumulators=ctrl)
+
+
+def _input(scene, q, t, points=True, pose=True, band=3):
+    inp = P.make_input(scene, q, t, band, requires_grad=points)
+    inp.q_pointcloud_camera.requires_grad_(pose)
+    inp.t_pointcloud_camera.requires_grad_(pose)
+    return inp
+
+
+def _target(shape, seed=0):
+    return torch.tensor(np.random.default_rng(seed).uniform(0, 1, shape).astype(np.float32), device=P.DEV)
+
+
+def _run(module, inp, seed=0, retain=False):
+    """forward + backward of sum(g * image), g = 2 (image - target); returns (outs, g_image)"""
+    outs = module(inp)
+    g = 2.0 * (outs[0].detach() - _target(outs[0].shape, seed))
+    outs[0].backward(g, retain_graph=retain)
+    return outs, g
+
+
+def _check_against_ref(scene, q, t, partial, gq, gt, g_image, per_element=True):
+    cfg = oracle.default_config(allow_partial_tiles=int(partial))
+    f, feat_after = P.run_oracle(scene, q, t, cfg)
+    assert f.K > 0
+    rq, rt, sq, st = pose_ref.pose_gradients(scene, q, t, f, feat_after, g_image)
+    for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
+        assert a.shape == ref.shape, name
+        scale = np.abs(ref).max()
+        assert scale > 0, name
+        err = np.abs(a.astype(np.float64) - ref)
+        assert err.max() / scale < TENSOR_TOL, (name, err.max() / scale, a, ref)
+        if per_element:
+            bar = ELEM_RTOL * np.abs(ref) + ELEM_FLOOR * summed
+            assert np.all(err <= bar), (name, (err / np.maximum(bar, 1e-300)).max(), a, ref)
+        assert not a[summed == 0].any(), name          # rows no touched point depends on: exact zeros
+    return rq, rt
+
+
+SCENES = [("tiny", (0, 48, 0.25, 32, 32)), ("tiny", (1, 64, 0.6, 32, 32)), ("tiny", (2, 24, 1.2, 32, 32)),
+          ("tiny", (3, 56, 0.5, 41, 27)), ("soak", 29), ("soak", 54), ("soak", 182)]
+
+
+def _scene(kind, arg):
+    if kind == "tiny":
+        return _tiny(*arg)
+    c = P.soak_case(arg)
+    return c["scene"], c["q"], c["t"], c["partial"]
+
+
+@pytest.mark.parametrize("strict", [False, True])
+@pytest.mark.parametrize("kind,arg", SCENES)
+def test_pose_gradient_matches_float64_reference(kind, arg, strict):
+    s, q, t, partial = _scene(kind, arg)
+    module = _module(partial, strict)
+    inp = _input(s, q, t)
+    outs, g = _run(module, inp)
+    assert inp.q_pointcloud_camera.grad is not None and inp.t_pointcloud_camera.grad is not None
+    assert inp.q_pointcloud_camera.grad.shape == (1, 4) and inp.t_pointcloud_camera.grad.shape == (1, 3)
+    _check_against_ref(s, q, t, partial, inp.q_pointcloud_camera.grad.cpu().numpy(), inp.t_pointcloud_camera.grad.cpu().numpy(),
+                       g.cpu().numpy())
+
+
+def _multi_object(seed, n_objects, n=64, width=32, height=32, empty_last=False):
+    s, q, t, partial = _tiny(seed, n, 0.5, width, height)
+    rng = np.random.default_rng(seed + 7)
+    s.point_object_id[:] = rng.integers(0, n_objects, n).astype(np.int32)
+    q = np.repeat(q, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 4)).astype(np.float32)
+    t = np.repeat(t, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 3)).astype(np.float32)
+    if empty_last:                     # its points are behind the camera: no visible point depends on the last row
+        t[-1] = [0.0, 0.0, 50.0]
+    return s, q.astype(np.float32), t.astype(np.float32), partial
+
+
+@pytest.mark.parametrize("n_objects,empty_last", [(3, True), (64, False)])
+def test_multi_object_rows(n_objects, empty_last):
+    """Kobj = 3 at the full bar.  Kobj = 64 (about one point per object, several objects per wave and block) at the tensor
+    bar: the per-element floor sums |per-point terms|, and with one point per object that floor is the point's own term,
+    while the upstream that term is made from (loop 1's per-splat sums) is accurate relative to ITS summed per-pixel
+    magnitude, which can be much larger (the floor of the point-gradient bar, parity_util.ELEM_FLOOR)."""
+    s, q, t, partial = _multi_object(11, n_objects, empty_last=empty_last)
+    module = _module(partial)
+    inp = _input(s, q, t)
+    outs, g = _run(module, inp)
+    gq, gt = inp.q_pointcloud_camera.grad.cpu().numpy(), inp.t_pointcloud_camera.grad.cpu().numpy()
+    assert gq.shape == (n_objects, 4) and gt.shape == (n_objects, 3)
+    rq, rt = _check_against_ref(s, q, t, partial, gq, gt, g.cpu().numpy(), per_element=n_objects <= 3)
+    if empty_last:
+        assert (s.point_object_id == n_objects - 1).any()
+        assert np.all(gq[-1] == 0) and np.all(gt[-1] == 0)
+        assert np.abs(gq[:-1]).min(axis=1).max() > 0
+
+
+HOOK_FIELDS = ["point_id_in_camera_list", "grad_point_in_camera", "grad_pointfeatures_in_camera", "grad_viewspace",
+               "magnitude_grad_viewspace", "magnitude_grad_viewspace_on_image", "num_overlap_tiles", "num_affected_pixels",
+               "point_depth", "point_uv_in_camera"]
+
+
+def _bits(x):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return a.view(np.uint8) if a.dtype != np.bool_ else a
+
+
+def _full_run(scene, q, t, pose):
+    got = {}
+    ctrl = ControllerAccumulators.zeros(scene.point_cloud.shape[0], P.DEV)
+    module = _module(hook=lambda h: got.setdefault("hook", {k: getattr(h, k).clone() for k in HOOK_FIELDS}), ctrl=ctrl)
+    inp = _input(scene, q, t, points=True, pose=pose)
+    outs, _ = _run(module, inp)
+    torch.cuda.synchronize()
+    res = {"image": outs[0], "depth": outs[1], "count": outs[2], "grad_pc": inp.point_cloud.grad,
+           "grad_feat": inp.point_cloud_features.grad}
+    res.update({"hook." + k: v for k, v in got["hook"].items()})
+    for k in ("accumulated_num_in_camera", "accumulated_num_pixels", "accumulated_view_space_position_gradients",
+              "accumulated_view_space_position_gradients_avg", "accumulated_position_gradients", "accumulated_position_gradients_norm"):
+        res["ctrl." + k] = getattr(ctrl, k).clone()
+    return res, inp
+
+
+def test_requesting_pose_gradients_changes_nothing_else():
+    s = synth(6000, 256, 192, 0.05, sh_deg=3, seed=5)
+    q, t = view_pose(1, 3)
+    base, inp0 = _full_run(s, q, t, pose=False)
+    with_pose, inp1 = _full_run(s, q, t, pose=True)
+    assert inp0.q_pointcloud_camera.grad is None and inp1.q_pointcloud_camera.grad is not None
+    assert len(base) == 5 + 10 + 6
+    for k in base:
+        assert np.array_equal(_bits(base[k]), _bits(with_pose[k])), k
+
+
+def test_pose_only_backward():
+    s = synth(6000, 256, 192, 0.05, sh_deg=3, seed=6)
+    q, t = view_pose(2, 3)
+    joint = _input(s, q, t, points=True, pose=True)
+    _run(_module(), joint)
+    calls = []
+    ctrl = ControllerAccumulators.zeros(s.point_cloud.shape[0], P.DEV)
+    only = _input(s, q, t, points=False, pose=True)
+    _run(_module(hook=calls.append, ctrl=ctrl), only)
+    torch.cuda.synchronize()
+    assert not calls                                                            # the hook belongs to the point gradient (RAST:1028)
+    for k in ("accumulated_num_in_camera", "accumulated_num_pixels", "accumulated_view_space_position_gradients",
+              "accumulated_view_space_position_gradients_avg", "accumulated_position_gradients", "accumulated_position_gradients_norm"):
+        assert not getattr(ctrl, k).any(), k
+    assert only.point_cloud.grad is None and only.point_cloud_features.grad is None
+    for a, b in ((joint.q_pointcloud_camera, only.q_pointcloud_camera), (joint.t_pointcloud_camera, only.t_pointcloud_camera)):
+        assert np.array_equal(_bits(a.grad), _bits(b.grad))
+        assert b.grad.abs().max() > 0
+    # grad factors and the SH band scale / mask feature gradients only
+    other = _input(s, q, t, points=False, pose=True, band=0)
+    _run(_module(grad_color_factor=3.0, grad_high_order_color_factor=0.25, grad_s_factor=7.0, grad_q_factor=2.0,
+                 grad_alpha_factor=0.1), other)
+    for a, b in ((only.q_pointcloud_camera, other.q_pointcloud_camera), (only.t_pointcloud_camera, other.t_pointcloud_camera)):
+        assert np.array_equal(_bits(a.grad), _bits(b.grad))
+
+
+@pytest.mark.parametrize("n_objects", [1, 8])
+def test_pose_gradient_is_deterministic(n_objects):
+    s = synth(40000, 512, 384, 0.02, sh_deg=3, seed=9)
+    q, t = view_pose()
+    s.point_object_id[:] = np.random.default_rng(3).integers(0, n_objects, s.point_object_id.shape[0]).astype(np.int32)
+    q, t = np.repeat(q, n_objects, 0), np.repeat(t, n_objects, 0)
+    grads = []
+    inp = _input(s, q, t, points=True, pose=True)
+    module = _module()
+    outs = module(inp)
+    g = 2.0 * (outs[0].detach() - _target(outs[0].shape))
+    for _ in range(2):                                                          # the same frame twice (retain_graph)
+        inp.q_pointcloud_camera.grad = inp.t_pointcloud_camera.grad = None
+        outs[0].backward(g, retain_graph=True)
+        grads.append((inp.q_pointcloud_camera.grad.clone(), inp.t_pointcloud_camera.grad.clone()))
+    for _ in range(2):                                                          # fresh runs
+        inp = _input(s, q, t, points=True, pose=True)
+        _run(_module(), inp)
+        grads.append((inp.q_pointcloud_camera.grad.clone(), inp.t_pointcloud_camera.grad.clone()))
+    assert grads[0][0].abs().max() > 0
+    for gq, gt in grads[1:]:
+        assert np.array_equal(_bits(gq), _bits(grads[0][0])) and np.array_equal(_bits(gt), _bits(grads[0][1]))
+
+
+def _rotation_error(q, q_ref):
+    a, b = q / np.linalg.norm(q), q_ref / np.linalg.norm(q_ref)
+    return 2.0 * np.arccos(min(1.0, abs(float(np.dot(a, b)))))
+
+
+def test_pose_recovery():
+    """Localise a camera against a fixed scene: only q and t are optimised (q through a differentiable normalisation, i.e. a
+    non-leaf pose), with Adam, against the image rendered at the true pose."""
+    s = synth(4000, 128, 128, 0.12, sh_deg=3, seed=21)
+    q_true, t_true = view_pose()
+    module = _module()
+    with torch.no_grad():
+        target = module(P.make_input(s, q_true, t_true, 3, requires_grad=False))[0].clone()
+    axis = np.array([1.0, 1.0, 0.3]) / np.linalg.norm([1.0, 1.0, 0.3])
+    ang = np.deg2rad(2.0)
+    dq = np.concatenate([np.sin(ang / 2) * axis, [np.cos(ang / 2)]])          # a 2 degree rotation, composed with the true one
+    qt = q_true[0].astype(np.float64)
+    q0 = np.concatenate([dq[3] * qt[:3] + qt[3] * dq[:3] + np.cross(dq[:3], qt[:3]), [dq[3] * qt[3] - dq[:3] @ qt[:3]]]).astype(np.float32)
+    t0 = (t_true[0] + np.array([0.15, -0.1, 0.12])).astype(np.float32)               # ~3 % of the scene depth (2 .. 10)
+    q_param = torch.nn.Parameter(torch.tensor(q0[None], device=P.DEV))
+    t_param = torch.nn.Parameter(torch.tensor(t0[None], device=P.DEV))
+    opt = torch.optim.Adam([q_param, t_param], lr=2e-3)
+    inp = P.make_input(s, q_true, t_true, 3, requires_grad=False)
+    r0, e0 = _rotation_error(q0, q_true[0]), float(np.linalg.norm(t0 - t_true[0]))
+    for _ in range(300):
+        opt.zero_grad()
+        inp.q_pointcloud_camera = q_param / q_param.norm(dim=-1, keepdim=True)
+        inp.t_pointcloud_camera = t_param
+        image = module(inp)[0]
+        loss = ((image - target) ** 2).mean()
+        loss.backward()
+        opt.step()
+    r1 = _rotation_error(q_param.detach().cpu().numpy()[0].astype(np.float64), q_true[0])
+    e1 = float(np.linalg.norm(t_param.detach().cpu().numpy()[0] - t_true[0]))
+    assert r1 * 5 <= r0 and e1 * 5 <= e0, (r0, r1, e0, e1)
+
+
+def test_staged_path_refuses_pose_gradients():
+    s, q, t, partial = _tiny(0, 48, 0.25, 32, 32)
+    module = _module(partial)
+    inp = _input(s, q, t)
+    module(inp)
+    fr = module.last_frame
+    dev = inp.point_cloud.device
+    scene, cam, cfg = module._marshal(inp.point_cloud, inp.point_cloud_features, inp.point_invalid_mask, inp.point_object_id,
+                                      inp.q_pointcloud_camera, inp.t_pointcloud_camera, inp.camera_info)
+    N, M = s.point_cloud.shape[0], fr.n_points_in_camera
+    gpc = torch.zeros(N, 3, device=dev)
+    gfeat = torch.zeros(N, 56, device=dev)
+    gq = torch.zeros(1, 4, device=dev)
+    gt = torch.zeros(1, 3, device=dev)
+    sums = torch.zeros(max(M, 1), 12, device=dev)
+    L = _native.lib()
+    ptr = lambda x: C.c_void_p(x.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    out = _native.GsBackwardOut(ptr(gpc), ptr(gfeat))
+    out.grad_q_pointcloud_camera, out.grad_t_pointcloud_camera = gq.data_ptr(), gt.data_ptr()
+    rc = L.gs_backward_shard(module._ctx_for(dev), fr.handle, C.byref(scene), C.byref(cam), C.byref(cfg), ptr(sums), 3,
+                             C.byref(out), stream)
+    assert rc == -1 and b"pose" in L.gs_last_error()
+    # gs_backward: both pose pointers or neither
+    img = torch.zeros(s.height, s.width, 3, device=dev)
+    acc = module.last_forward_outputs["pixel_accumulated_alpha"]
+    last = module.last_forward_outputs["pixel_offset_of_last_effective_point"]
+    out.grad_t_pointcloud_camera = None
+    rc = L.gs_backward(module._ctx_for(dev), fr.handle, C.byref(scene), C.byref(cam), C.byref(cfg), ptr(img), ptr(acc), ptr(last),
+                       3, C.byref(out), stream)
+    assert rc == -1 and b"together" in L.gs_last_error()
+    torch.cuda.synchronize()
