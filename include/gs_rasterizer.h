@@ -316,7 +316,8 @@ int gs_loss_l1_ssim_backward(gs_ctx* ctx, const gs_loss_image* predicted_image, 
                              const float* maps, const float* upstream, const gs_loss_image* grad_predicted, gs_stream stream);
 
 /* Scale regulariser of LossFunction.py:40-51: mean over valid points (point_invalid_mask == 0) of
- * || exp(features[:, 4:7]) ||_2.  value_and_count: device float[2] = {mean, number of valid points}. */
+ * || exp(features[:, 4:7]) ||_2.  value_and_count: device float[2] = {mean, number of valid points}.
+ * No valid point (n_points == 0 included) gives {NaN, 0}, like torch's mean of an empty tensor. */
 int gs_scale_regulariser(gs_ctx* ctx, const float* point_cloud_features, const int8_t* point_invalid_mask, int64_t n_points,
                          float* value_and_count, gs_stream stream);
 /* Its gradient: writes the whole (N,56) array (zero outside columns 4:7 and for invalid rows), scaled by the

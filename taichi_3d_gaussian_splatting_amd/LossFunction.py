@@ -20,6 +20,39 @@ except Exception:  # pragma: no cover
         pass
 
 
+def check_loss_images(predicted, ground_truth):
+    """Raise unless both images are float32 (3,H,W) tensors on the same GPU with H, W >= 11 (the SSIM window).  Reads no
+    data and launches nothing: the kernels take raw pointers, and a host pointer handed to them faults the device."""
+    if predicted.dim() != 3 or predicted.shape[0] != 3 or predicted.shape != ground_truth.shape:
+        raise ValueError("predicted_image and ground_truth_image must both be (3,H,W)")
+    if predicted.dtype != torch.float32 or ground_truth.dtype != torch.float32 or not predicted.is_cuda:
+        raise TypeError("images must be float32 tensors on the GPU")
+    if ground_truth.device != predicted.device:
+        raise ValueError(f"ground_truth_image is on {ground_truth.device}, predicted_image on {predicted.device}")
+    if predicted.shape[1] < 11 or predicted.shape[2] < 11:
+        raise ValueError(f"images of {predicted.shape[1]}x{predicted.shape[2]} are smaller than the 11x11 SSIM window")
+
+
+def check_regulariser_inputs(features, invalid_mask):
+    """Raise unless features is a contiguous float32 (N,56) GPU tensor and invalid_mask an (N,) bool or integer tensor on
+    the same device.  Returns the mask as the contiguous int8 (N,) tensor the kernels read (the input itself when it
+    already is one; a copy otherwise).  Reads no data and launches nothing."""
+    if features.dtype != torch.float32 or not features.is_cuda or not features.is_contiguous() or features.dim() != 2 \
+            or features.shape[1] != 56:
+        raise TypeError("pointcloud_features must be a contiguous float32 (N,56) GPU tensor")
+    if invalid_mask.device != features.device:
+        raise ValueError(f"point_invalid_mask is on {invalid_mask.device}, pointcloud_features on {features.device}")
+    if invalid_mask.dim() != 1 or invalid_mask.shape[0] != features.shape[0]:
+        raise ValueError(f"point_invalid_mask must be ({features.shape[0]},), got {tuple(invalid_mask.shape)}")
+    if invalid_mask.dtype == torch.int8:
+        mask = invalid_mask
+    elif invalid_mask.dtype == torch.bool or not (invalid_mask.is_floating_point() or invalid_mask.is_complex()):
+        mask = (invalid_mask != 0).to(torch.int8)               # (a plain .to(int8) would wrap 256 to 0)
+    else:
+        raise TypeError(f"point_invalid_mask must be bool or integer, got {invalid_mask.dtype}")
+    return mask.contiguous()
+
+
 class _L1SSIM(torch.autograd.Function):
     """Forward: gs_loss_l1_ssim_forward (value; the derivative maps stay in a tensor this node owns).  Backward:
     gs_loss_l1_ssim_backward, scaled by the incoming gradient on the device.  The predicted image is read through its strides:
@@ -28,10 +61,7 @@ class _L1SSIM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, predicted, ground_truth, lambda_value, clamp_predicted):
-        if predicted.dim() != 3 or predicted.shape[0] != 3 or predicted.shape != ground_truth.shape:
-            raise ValueError("predicted_image and ground_truth_image must both be (3,H,W)")
-        if predicted.dtype != torch.float32 or ground_truth.dtype != torch.float32 or not predicted.is_cuda:
-            raise TypeError("images must be float32 tensors on the GPU")
+        check_loss_images(predicted, ground_truth)
         dev = predicted.device
         H, W = int(predicted.shape[1]), int(predicted.shape[2])
         L = _native.lib()
@@ -75,9 +105,7 @@ class _ScaleRegulariser(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, invalid_mask):
-        if features.dtype != torch.float32 or not features.is_cuda or not features.is_contiguous() or features.shape[1] != 56:
-            raise TypeError("pointcloud_features must be a contiguous float32 (N,56) GPU tensor")
-        mask = invalid_mask if invalid_mask.dtype == torch.int8 else invalid_mask.to(torch.int8)
+        mask = check_regulariser_inputs(features, invalid_mask)
         dev = features.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
         idx = dev.index if dev.index is not None else torch.cuda.current_device()

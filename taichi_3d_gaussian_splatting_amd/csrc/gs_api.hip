@@ -850,11 +850,12 @@ static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_i
     const size_t Mp = (size_t)(f->info.n_points_in_camera > 0 ? f->info.n_points_in_camera : 1);
     // Row flags (K*G bytes) and per-point `touched` bytes behind them.  They are TAGGED, not cleared: a backward writes its own tag
     // (1..255) and reads a flag as set only if it holds that tag, so the 6 MB clear per backward is gone; the buffer is zeroed when it
-    // is (re)allocated and when the tags wrap round.
-    const void* before = c->visited.p;
+    // is (re)allocated and when the tags wrap round.  A reallocation is told by the capacity, never by the address: the allocator
+    // may hand back the block just freed, and a grown tail left uncleared holds stray bytes equal to the current tag.
+    const size_t cap_before = c->visited.cap;
     e = c->visited.ensure(flag_bytes + Mp + 16, &c->device_bytes);
     if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "backward: visited buffer");
-    if (c->visited.p != before || c->visit_gen == 255) {
+    if (c->visited.cap != cap_before || c->visit_gen == 255) {
         HIP_TRY(hipMemsetAsync(c->visited.p, 0, c->visited.cap, stream));
         c->visit_gen = 0;
     }

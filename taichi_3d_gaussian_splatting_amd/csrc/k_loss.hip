@@ -432,8 +432,8 @@ __global__ __launch_bounds__(256) void k_reg_grad(const float* __restrict__ feat
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s)
 {
     const int nb = (int)((N + 255) / 256);
-    if (nb == 0) { (void)hipMemsetAsync(out, 0, 2 * sizeof(float), s); return; }
-    k_reg_partials<<<nb, 256, 0, s>>>(feat, invalid, N, workspace, workspace + nb);
+    if (nb > 0) k_reg_partials<<<nb, 256, 0, s>>>(feat, invalid, N, workspace, workspace + nb);
+    // N = 0: the finish sums no partials and writes {NaN, 0}, torch's mean of an empty selection
     k_reg_finish<<<1, 1024, 0, s>>>(workspace, workspace + nb, nb, out);
 }
 
@@ -456,7 +456,9 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ param, const f
     if (i >= n) return;
     const float g = grad[i];
     const float m = beta1 * exp_avg[i] + (1.0f - beta1) * g;          // exp_avg.lerp_(grad, 1 - beta1)
-    const float v = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2); g * g first, as torch's GPU addcmul: a gradient whose square
+    // overflows f32 makes v infinite (and the step zero) there too, rather than finite through (1 - beta2) g first
+    const float v = beta2 * exp_avg_sq[i] + (1.0f - beta2) * (g * g);
     exp_avg[i] = m; exp_avg_sq[i] = v;
     const float denom = sqrtf(v) / bias2_sqrt + eps;
     param[i] = param[i] - (lr / bias1) * (m / denom);

@@ -5,27 +5,11 @@ unpinned" against the package itself.  Adam is checked against torch.optim.Adam.
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from loss_ref import ssim_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def ssim_ref(X, Y):
-    """pytorch_msssim.ssim(X, Y, data_range=1, size_average=True) restated; X, Y (1,3,H,W) float64."""
-    coords = torch.arange(11, dtype=X.dtype, device=X.device) - 5
-    g = torch.exp(-(coords ** 2) / (2 * 1.5 ** 2))
-    g = (g / g.sum()).reshape(1, 1, 1, 11).repeat(3, 1, 1, 1)
-
-    def gf(t):
-        t = F.conv2d(t, g.transpose(2, 3), groups=3)       # along H first, then W
-        return F.conv2d(t, g, groups=3)
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    mu1, mu2 = gf(X), gf(Y)
-    s1, s2, s12 = gf(X * X) - mu1 ** 2, gf(Y * Y) - mu2 ** 2, gf(X * Y) - mu1 * mu2
-    cs = (2 * s12 + C2) / (s1 + s2 + C2)
-    ssim_map = ((2 * mu1 * mu2 + C1) / (mu1 ** 2 + mu2 ** 2 + C1)) * cs
-    return ssim_map.flatten(2).mean(-1).mean()
 
 
 @pytest.mark.parametrize("H,W", [(48, 64), (33, 75), (1088, 1920)])
