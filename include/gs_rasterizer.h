@@ -231,6 +231,27 @@ int gs_backward(gs_ctx* ctx, gs_frame* frame, const gs_scene* scene, const gs_ca
 
 /* May be called any number of times between forward and release (backward(retain_graph=True) in PyTorch terms). */
 
+/* EXTENSION: upstream gradients of the two other image-sized outputs of gs_forward (the reference drops the depth
+ * gradient, RAST:1157-1163, and has no accumulated-alpha output).  All device (H,W) f32 contiguous. */
+typedef struct gs_backward_extra {
+    const float* grad_rasterized_depth;         /* device (H,W) or NULL */
+    const float* rasterized_depth;              /* device (H,W), the forward's output; required with the above */
+    const float* grad_pixel_accumulated_alpha;  /* device (H,W) or NULL */
+} gs_backward_extra;
+
+/* gs_backward with the depth D = sum(w d) / A and the accumulated alpha A = 1 - T_final = sum(w) differentiable too
+ * (w = alpha T the blend weight, d the splat's camera-space z; DESIGN.md "Depth and alpha gradients").  Their terms join
+ * d alpha per contribution and (depth) d p_cam z per splat, so every output of gs_backward_out -- point and pose gradients,
+ * the view-space gradient and its magnitudes, the hook arrays and the controller statistics -- is that of the total loss.
+ * extra NULL, or both gradients NULL: exactly gs_backward.  Otherwise the blend backward walks every tile's list whole
+ * (no use of the forward's list cuts), so on a frame with HEAVY tiles an all-zero depth gradient gives gs_backward's result
+ * up to summation order.  A depth gradient without rasterized_depth: GS_ERR_INVALID_ARGUMENT.
+ * The staged path (gs_backward_projected, gs_backward_shard) stays image-only: its sum rows keep column 11 = 0. */
+int gs_backward_ex(gs_ctx* ctx, gs_frame* frame, const gs_scene* scene, const gs_camera* camera, const gs_config* config,
+                   const float* grad_rasterized_image, const gs_backward_extra* extra,
+                   const float* pixel_accumulated_alpha, const int32_t* pixel_offset_of_last_effective_point,
+                   int32_t color_max_sh_band, const gs_backward_out* out, gs_stream stream);
+
 /* Diagnostic: n_out[0] = how many tiles the last backward blend of this frame treated as HEAVY (a workgroup of four cooperating
  * waves instead of one wave; k_backward.hip), n_out[1] = how many work items they were handed out as (a heavy tile whose list the
  * forward cut is walked in segments of 512 entries, one item each).  n_out: host int32[2].  Synchronises the stream. */
@@ -248,7 +269,8 @@ int gs_frame_release(gs_ctx* ctx, gs_frame* frame);
  * sums are the accumulators of RAST:674-696 (grad_uv, cov buffer, colour buffer, opacity, magnitude, pixel count).
  *
  * Record layout (GS_RECORD_FLOATS): u v conic_a conic_b | conic_c rescale opacity depth | r g b alpha_cut | x y z(camera) radius.
- * Sum row layout (GS_SPLAT_SUM_FLOATS): d uv (2) | d cov xx xy yy (3) | d colour (3) | d opacity | sum |d uv| | pixel count (i32 bits) | 0;
+ * Sum row layout (GS_SPLAT_SUM_FLOATS): d uv (2) | d cov xx xy yy (3) | d colour (3) | d opacity | sum |d uv| | pixel count (i32 bits) | 0
+ * (gs_backward_ex alone puts d depth in that last column; here it is always 0);
  * rows are pre-factor sums exactly as k_blend_bwd_tile leaves them (opacity, 0.5 and (1-o)o are applied by the shard half). */
 
 /* Per-point half of the forward for a shard of the scene: frustum filter, compaction (ascending ids), projection.

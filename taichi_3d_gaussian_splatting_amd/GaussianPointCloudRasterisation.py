@@ -151,6 +151,9 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         # extension: True runs the backward's per-contribution Gaussian gradient (utils.py:331-348) in the reference's own f32
         # operation order instead of the faster, algebraically equal form (gs_config.bwd_reference_order)
         backward_reference_order = False
+        # extension: True makes rasterized_depth differentiable (the reference drops its gradient, RAST:1157-1163): a loss on
+        # the depth map then reaches the point and pose gradients (gs_backward_ex).  Read at forward time; no effect with rgb_only
+        differentiable_depth = False
 
     @dataclass
     class GaussianPointCloudRasterisationInput:
@@ -194,7 +197,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         class _module_function(torch.autograd.Function):
             @staticmethod
             def forward(ctx, pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
-                        q_pointcloud_camera, t_pointcloud_camera, camera_info, color_max_sh_band, grad_mode):
+                        q_pointcloud_camera, t_pointcloud_camera, camera_info, color_max_sh_band, grad_mode, return_alpha):
                 # ctx.needs_input_grad says whether the inputs require grad, not whether a graph is being recorded (it is True
                 # under torch.no_grad() too, and grad mode is always off inside forward): the caller passes the grad mode in
                 needs_grad = bool(grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or
@@ -205,16 +208,22 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                 ctx.frame = frame if needs_grad else None
                 ctx.camera_info = camera_info
                 ctx.color_max_sh_band = color_max_sh_band
+                # extension: the depth gradient flows only with config.differentiable_depth (as of this forward)
+                ctx.differentiable_depth = bool(getattr(module.config, "differentiable_depth", False)) and not module.config.rgb_only
                 ctx.save_for_backward(pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
-                                      q_pointcloud_camera, t_pointcloud_camera, acc_alpha, last)
+                                      q_pointcloud_camera, t_pointcloud_camera, acc_alpha, last,
+                                      depth if ctx.differentiable_depth else None)
                 ctx.mark_non_differentiable(count)
-                # the depth gradient is ignored (RAST:1157-1163) and the count has none: do not let autograd materialise
-                # two image-sized zero tensors (two fill launches) per backward for them
+                # an output nothing downstream used gets None, not an image-sized zero tensor (a fill launch each): the count
+                # (no gradient), the depth unless differentiable_depth (ignored then, RAST:1157-1163) and the alpha.  backward
+                # therefore takes gs_backward_ex only for a depth or alpha gradient that actually arrives
                 ctx.set_materialize_grads(False)
+                if return_alpha:                            # extension: pixel_accumulated_alpha as a differentiable output
+                    return image, depth, count, acc_alpha
                 return image, depth, count
 
             @staticmethod
-            def backward(ctx, grad_rasterized_image, grad_rasterized_depth, grad_pixel_valid_point_count):
+            def backward(ctx, grad_rasterized_image, grad_rasterized_depth, grad_pixel_valid_point_count, *grad_alpha):
                 grad_pointcloud = grad_pointcloud_features = grad_q = grad_t = None
                 want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]      # RAST:1028
                 want_pose = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]        # extension: the reference returns None for the pose
@@ -222,19 +231,23 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                     if ctx.frame is None:
                         raise RuntimeError("backward through a forward that ran without gradient tracking")
                     (pointcloud, pointcloud_features, point_invalid_mask, point_object_id, q_pointcloud_camera,
-                     t_pointcloud_camera, acc_alpha, last) = ctx.saved_tensors
-                    if grad_rasterized_image is None:       # only the depth was used downstream: its gradient does not flow (RAST:1157-1163)
+                     t_pointcloud_camera, acc_alpha, last, depth) = ctx.saved_tensors
+                    if not ctx.differentiable_depth:        # the reference's behaviour: the depth gradient does not flow (RAST:1157-1163)
+                        grad_rasterized_depth = None
+                    grad_acc_alpha = grad_alpha[0] if grad_alpha else None
+                    if grad_rasterized_image is None:       # only the depth (or alpha) was used downstream
                         grad_rasterized_image = torch.zeros(ctx.camera_info.camera_height, ctx.camera_info.camera_width, 3,
                                                             dtype=torch.float32, device=pointcloud.device)
                     grad_pointcloud, grad_pointcloud_features, grad_q, grad_t = module._run_backward(
                         ctx.frame, pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
                         q_pointcloud_camera, t_pointcloud_camera, ctx.camera_info, acc_alpha, last,
-                        grad_rasterized_image.contiguous(), ctx.color_max_sh_band, want_points=want_points, want_pose=want_pose)
+                        grad_rasterized_image.contiguous(), ctx.color_max_sh_band, want_points=want_points, want_pose=want_pose,
+                        grad_depth=grad_rasterized_depth, depth=depth, grad_alpha=grad_acc_alpha)
                     # the frame is NOT released here: like the reference's saved tensors it lives as long as the graph
                     # node does, so backward(retain_graph=True) followed by another backward works; it goes back to the
                     # pool when autograd drops the node (_Frame.__del__)
                 return (grad_pointcloud, grad_pointcloud_features, None, None,
-                        grad_q if ctx.needs_input_grad[4] else None, grad_t if ctx.needs_input_grad[5] else None, None, None, None)
+                        grad_q if ctx.needs_input_grad[4] else None, grad_t if ctx.needs_input_grad[5] else None, None, None, None, None)
 
         self._module_function = _module_function
 
@@ -315,9 +328,10 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         return (image, depth, acc_alpha, last, count), frame
 
     def _run_backward(self, frame, pointcloud, features, mask, obj, q, t, camera_info, acc_alpha, last, grad_image, sh_band,
-                      want_points=True, want_pose=False):
+                      want_points=True, want_pose=False, grad_depth=None, depth=None, grad_alpha=None):
         """-> (grad_pointcloud, grad_pointcloud_features, grad_q, grad_t); the first two are None when not want_points (no hook
-        call and no controller statistics then, as in the reference, RAST:1028), the last two None when not want_pose."""
+        call and no controller statistics then, as in the reference, RAST:1028), the last two None when not want_pose.
+        grad_depth (with the forward's depth) and grad_alpha, (H,W) or None: gs_backward_ex when either is given."""
         dev = pointcloud.device
         N, M = pointcloud.shape[0], frame.n_points_in_camera
         H, W = camera_info.camera_height, camera_info.camera_width
@@ -369,10 +383,25 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                                     C.pointer(ctrl) if ctrl is not None and N > 0 else None,
                                     _ptr(h_ids), _ptr(h_ntiles), _ptr(h_depth), _ptr(h_puv), _ptr(grad_q), _ptr(grad_t))
         stream = torch.cuda.current_stream(dev).cuda_stream
+        extra = None
+        if grad_depth is not None or grad_alpha is not None:
+            if grad_depth is not None and depth is None:
+                raise ValueError("a depth gradient needs the forward's rasterized_depth")
+            for g, name in ((grad_depth, "rasterized_depth"), (grad_alpha, "accumulated_alpha")):
+                if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (H, W)):
+                    raise ValueError(f"grad of {name} must be float32 (H,W)")
+            grad_depth = grad_depth.contiguous() if grad_depth is not None else None
+            grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
+            extra = _native.GsBackwardExtra(_ptr(grad_depth), _ptr(depth) if grad_depth is not None else None, _ptr(grad_alpha))
         with _on_device(dev):
-            _native.check(_native.lib().gs_backward(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
-                                                    _ptr(grad_image), _ptr(acc_alpha), _ptr(last), int(sh_band),
-                                                    C.byref(out), C.c_void_p(stream)), "gs_backward")
+            if extra is None:
+                _native.check(_native.lib().gs_backward(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
+                                                        _ptr(grad_image), _ptr(acc_alpha), _ptr(last), int(sh_band),
+                                                        C.byref(out), C.c_void_p(stream)), "gs_backward")
+            else:
+                _native.check(_native.lib().gs_backward_ex(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
+                                                           _ptr(grad_image), C.byref(extra), _ptr(acc_alpha), _ptr(last), int(sh_band),
+                                                           C.byref(out), C.c_void_p(stream)), "gs_backward_ex")
         self.last_backward_extras = dict(grad_viewspace=grad_uv, magnitude_grad_viewspace=mag,
                                          magnitude_grad_viewspace_on_image=mag_img, num_affected_pixels=n_aff)
         if want_hook:                                                                   # RAST:1127-1142
@@ -385,12 +414,17 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         return grad_pc, grad_feat, grad_q, grad_t
 
     # ------------------------------------------------------------------ nn.Module
-    def forward(self, input_data: "GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput"):
+    def forward(self, input_data: "GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput",
+                return_accumulated_alpha: bool = False):
+        """-> (rasterized_image, rasterized_depth, pixel_valid_point_count), as the reference; with return_accumulated_alpha
+        (extension) a fourth output, pixel_accumulated_alpha (H,W) = 1 - final transmittance, which is differentiable."""
         camera_info = input_data.camera_info
         if not getattr(self.config, "allow_partial_tiles", False):
             assert camera_info.camera_width % TILE_WIDTH == 0        # RAST:1193-1194
             assert camera_info.camera_height % TILE_HEIGHT == 0
+        if return_accumulated_alpha and self.config.rgb_only:
+            raise ValueError("return_accumulated_alpha needs the full forward: rgb_only computes no accumulated alpha")
         return self._module_function.apply(
             input_data.point_cloud, input_data.point_cloud_features, input_data.point_invalid_mask,
             input_data.point_object_id, input_data.q_pointcloud_camera, input_data.t_pointcloud_camera,
-            camera_info, input_data.color_max_sh_band, torch.is_grad_enabled())
+            camera_info, input_data.color_max_sh_band, torch.is_grad_enabled(), bool(return_accumulated_alpha))

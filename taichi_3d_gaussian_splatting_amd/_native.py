@@ -74,6 +74,11 @@ class GsBackwardOut(C.Structure):
                 ("hook_point_uv_in_camera", _VP), ("grad_q_pointcloud_camera", _VP), ("grad_t_pointcloud_camera", _VP)]
 
 
+class GsBackwardExtra(C.Structure):
+    """gs_backward_extra: upstream gradients of rasterized_depth / pixel_accumulated_alpha for gs_backward_ex"""
+    _fields_ = [("grad_rasterized_depth", _VP), ("rasterized_depth", _VP), ("grad_pixel_accumulated_alpha", _VP)]
+
+
 class GsDensityConfig(C.Structure):
     _fields_ = [("transparent_alpha_threshold", _F32),
                 ("densification_view_space_position_gradients_threshold", _F32),
@@ -126,7 +131,7 @@ EXPORTS = {
 
 # every symbol include/gs_rasterizer.h declares
 SYMBOLS = ["gs_abi_version", "gs_last_error", "gs_create", "gs_destroy", "gs_forward", "gs_frame_get_info",
-           "gs_frame_export_count", "gs_frame_export", "gs_backward", "gs_frame_release", "gs_frame_heavy_tiles",
+           "gs_frame_export_count", "gs_frame_export", "gs_backward", "gs_backward_ex", "gs_frame_release", "gs_frame_heavy_tiles",
            "gs_ctx_device_bytes", "gs_ctx_counter_wait_ns", "gs_kernel_names", "gs_profile_enable", "gs_profile_read",
            "gs_loss_l1_ssim", "gs_loss_maps_floats", "gs_loss_l1_ssim_forward", "gs_loss_l1_ssim_backward", "gs_adam_step", "gs_scale_regulariser", "gs_scale_regulariser_grad",
            "gs_project_shard", "gs_project_shard_begin", "gs_forward_projected", "gs_backward_projected", "gs_backward_shard",
@@ -197,6 +202,8 @@ def lib():
                                     C.POINTER(GsBackwardOut), _VP]
     L.gs_backward.argtypes = [_VP, _VP, C.POINTER(GsScene), C.POINTER(GsCamera), C.POINTER(GsConfig),
                               _VP, _VP, _VP, _I32, C.POINTER(GsBackwardOut), _VP]
+    L.gs_backward_ex.argtypes = [_VP, _VP, C.POINTER(GsScene), C.POINTER(GsCamera), C.POINTER(GsConfig),
+                                 _VP, C.POINTER(GsBackwardExtra), _VP, _VP, _I32, C.POINTER(GsBackwardOut), _VP]
     L.gs_frame_release.argtypes = [_VP, _VP]
     L.gs_frame_heavy_tiles.argtypes = [_VP, _VP, C.POINTER(_I32), _VP]
     L.gs_ctx_device_bytes.argtypes = [_VP]

@@ -950,9 +950,10 @@ static int check_backward_points_args(const Frame* f, const gs_scene* sc, const 
     return GS_OK;
 }
 
-extern "C" int gs_backward(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
-                           const float* grad_image, const float* acc_alpha, const int32_t* last,
-                           int32_t sh_band, const gs_backward_out* out, gs_stream stream_)
+// gs_backward, and gs_backward_ex with a depth and/or an alpha gradient (extra != NULL: checked by the caller)
+static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
+                         const float* grad_image, const gs_backward_extra* extra, const float* acc_alpha, const int32_t* last,
+                         int32_t sh_band, const gs_backward_out* out, gs_stream stream_)
 {
     if (!c || !sc || !cam || !cfg || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: NULL argument");
     if (!grad_image || !acc_alpha || !last) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: NULL image-sized input");
@@ -980,12 +981,35 @@ extern "C" int gs_backward(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_
     GsBackwardArgs a{};
     if ((rc = prepare_backward_blend(c, f, grad_image, acc_alpha, last, out->magnitude_grad_viewspace_on_image, c->sums.as<float4>(), cfg->bwd_reference_order, s, &a)) != GS_OK) return rc;
     if ((rc = prepare_backward_points(f, sc, cam, cfg, sh_band, out, c->sums.as<float4>(), &a)) != GS_OK) return rc;
+    if (extra) {                    // the AUX kernels, walking every heavy tile whole (no cut records: k_backward.hip)
+        a.grad_depth = extra->grad_rasterized_depth; a.depth = extra->rasterized_depth;
+        a.grad_alpha = extra->grad_pixel_accumulated_alpha;
+        a.aux = 1;
+        a.cuts = nullptr;
+    }
     gs_launch_backward_blend(a, s);
     if (a.T > 0 && a.K > 0) c->order_hint_T = a.T;          // k_tile_order ran: the hint is a complete permutation
     if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics
     if (pose) gs_launch_pose_grad(a, f->n_objects, c->pose_scratch.p, out->grad_q_pointcloud_camera, out->grad_t_pointcloud_camera, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
+}
+
+extern "C" int gs_backward(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
+                           const float* grad_image, const float* acc_alpha, const int32_t* last,
+                           int32_t sh_band, const gs_backward_out* out, gs_stream stream_)
+{
+    return backward_impl(c, h, sc, cam, cfg, grad_image, nullptr, acc_alpha, last, sh_band, out, stream_);
+}
+
+extern "C" int gs_backward_ex(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
+                              const float* grad_image, const gs_backward_extra* extra, const float* acc_alpha, const int32_t* last,
+                              int32_t sh_band, const gs_backward_out* out, gs_stream stream_)
+{
+    if (extra && extra->grad_rasterized_depth && !extra->rasterized_depth)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_ex: grad_rasterized_depth needs rasterized_depth (the forward's output)");
+    if (extra && !extra->grad_rasterized_depth && !extra->grad_pixel_accumulated_alpha) extra = nullptr;   // exactly gs_backward
+    return backward_impl(c, h, sc, cam, cfg, grad_image, extra, acc_alpha, last, sh_band, out, stream_);
 }
 
 extern "C" int gs_backward_projected(gs_ctx* c, gs_frame* h, const float* grad_image, const float* acc_alpha, const int32_t* last,

@@ -379,7 +379,10 @@ struct GsBackwardArgs {
     const float4 *PA, *PB, *PC, *PD; const ushort4* box; const uint32_t* offsets; const int32_t* ntiles;
     const int32_t* ids; const int32_t* cam_index;
     const float* grad_image; const float* acc_alpha; const int32_t* last;
-    int G;                          // waves per tile in k_blend_bwd_tile (1, 2 or 4) = rows of `partial` per (point, tile) pair
+    // gs_backward_ex: upstream gradients of rasterized_depth (with the forward's depth) and of pixel_accumulated_alpha, (H,W) or
+    // NULL; aux = 1 selects the AUX kernels (k_blend_bwd_tile, k_sum_rows, k_bwd_points, k_pose_points) and requires cuts = NULL
+    const float* grad_depth; const float* depth; const float* grad_alpha; int aux;
+    int G;                         // waves per tile in k_blend_bwd_tile (1, 2 or 4) = rows of `partial` per (point, tile) pair
     int32_t* n_heavy;               // device: number of heavy tiles at the head of tile_order (k_tile_order -> k_blend_bwd_tile); n_items and item_base follow it
     const float4* cuts; float2* cut_mag; const int32_t* tile_cut;    // list cuts of the forward (NULL: none), per-segment |d uv| partial sums
     int item_cap;                   // work items of heavy tiles the launch has room for when there are cuts

@@ -21,7 +21,7 @@
 #include <cstdlib>
 
 #define RED_STRIDE 68   // floats per value row of the LDS transpose (64 lanes + 4 pad: conflict-free b128 reads)
-#define PW 12     // floats per partial row: vs0 vs1 | cov00 cov01 cov11 | col r g b | opacity | |vs| | count (int32 bits) | pad
+#define PW 12     // floats per partial row: vs0 vs1 | cov00 cov01 cov11 | col r g b | opacity | |vs| | count (int32 bits) | pad (AUX: d depth)
 
 // ---------------------------------------------------------------------------------
 // Loop 1: ONE WAVE PER TILE, four pixels per lane (one per 8x8 quadrant).
@@ -172,6 +172,13 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
 // (RAST:656) only ever enter through this dot product (RAST:653-657), so one scalar per pixel carries them.
 struct QuadState { float T, W, gr, gg, gb, tot0, tot1; int last; };
 
+// AUX (gs_backward_ex): upstream gradients of the depth D = sum w d / A and of the accumulated alpha A = 1 - T_final (DESIGN.md
+// "Depth and alpha gradients").  Per pixel kD = gD / max(A, 1e-6), kA = gA T_final, the forward's D, and R = sum over the
+// contributions behind of w (d - D); per contribution d alpha += kD (T (d - D) - R / (1 - alpha)) + kA / (1 - alpha),
+// d depth = kD w (row column 11), R += w (d - D).  Either gradient pointer may be NULL (depth is required with grad_depth).
+struct BwdAux { const float* grad_depth; const float* depth; const float* grad_alpha; };
+struct AuxState { float kD, kA, D, R; };
+
 // NQ = quadrants per wave: 4 (one wave per tile), 2 (two waves per tile, upper / lower half) or 1.
 // With G = 4/NQ waves per tile every (point, tile) pair owns G consecutive rows of `partial`.
 // STRICT (gs_config.bwd_reference_order): grad_point_probability_density_from_conic_and_rescale in the reference's own f32
@@ -203,7 +210,7 @@ struct BwdCoop { unsigned long long* done; int32_t* slot; int32_t* point; int32_
                  // walks the tile again in one piece, over the same rows.
                  int32_t* redo; };
 
-template <int NQ, bool STRICT, bool COOP>
+template <int NQ, bool STRICT, bool COOP, bool AUX = false>
 __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, const int G_rows, float4 (*sRec)[3], float* sRed, const BwdCoop coop,
                                                  const int32_t* __restrict__ tile_start, const int32_t* __restrict__ tile_end,
                                                  const int32_t* __restrict__ sorted_vals,
@@ -213,8 +220,9 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                                                  const float* __restrict__ grad_image, const float* __restrict__ acc_alpha,
                                                  const int32_t* __restrict__ last_in, int W, int H, int tiles_x,
                                                  float* __restrict__ partial, uint8_t* __restrict__ visited, uint8_t* __restrict__ touched,
-                                                 const uint8_t gen, float* __restrict__ mag_image)
+                                                 const uint8_t gen, float* __restrict__ mag_image, const BwdAux aux = BwdAux{})
 {
+    constexpr int NV = AUX ? 11 : 10;            // values summed over the pixels per contribution (AUX: + d depth)
 #ifdef GS_STATS
     const unsigned long long gs_t0 = wall_clock64();
 #endif
@@ -226,6 +234,7 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
     const int seg_hi = (COOP && coop.nseg > 1 && coop.seg < coop.nseg - 1) ? start + (coop.seg + 1) * GS_SEG : end;
     const int lx = lane & 7, ly = lane >> 3;
     QuadState Q[NQ];
+    AuxState X[AUX ? NQ : 1];
     float t_end[COOP ? NQ : 1];                  // COOP: the pixel's 1 - accumulated_alpha (the segment check at the end)
     int qlast[NQ];
     float rx0[NQ], ry0[NQ];
@@ -239,6 +248,14 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
         Q[qi].last = inside ? last_in[o] : start;                    // RAST:558
         Q[qi].T = 1.0f - acc_alpha[o];                               // RAST:559-560
         if constexpr (COOP) t_end[qi] = Q[qi].T;
+        if constexpr (AUX) {                                         // (pixels outside the image: zeros)
+            const float A = inside ? acc_alpha[o] : 0.0f;
+            const float gD = inside && aux.grad_depth ? aux.grad_depth[o] : 0.0f;
+            X[qi].kD = gD / (A > 1e-6f ? A : 1e-6f);
+            X[qi].kA = inside && aux.grad_alpha ? aux.grad_alpha[o] * Q[qi].T : 0.0f;
+            X[qi].D = inside && aux.grad_depth ? aux.depth[o] : 0.0f;
+            X[qi].R = 0.0f;
+        }
         Q[qi].W = 0.0f;
         Q[qi].gr = grad_image[3 * o]; Q[qi].gg = grad_image[3 * o + 1]; Q[qi].gb = grad_image[3 * o + 2];
         Q[qi].tot0 = Q[qi].tot1 = 0.0f;
@@ -281,6 +298,10 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
         float t = 0.0f;
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) t += ((Q[qi].gr + Q[qi].gg) + Q[qi].gb) + Q[qi].T;
+        if constexpr (AUX) {
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) t += (X[qi].kD + X[qi].kA) + X[qi].D;
+        }
         pixels_finite = gs_ballot(!(t - t == 0.0f)) == 0ull;
     }
     float pxq[NQ], pyq[NQ];                      // pixel centres of this lane in its NQ quadrants
@@ -315,6 +336,11 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
             fsum = valid ? fsum : 0.0f;
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) fsum += Q[qi].W;              // (a NaN colour met in an earlier batch lives on in W)
+            if constexpr (AUX) {                                              // the splat depths (B.w) and the running sums R
+                fsum += valid ? B.w : 0.0f;
+#pragma unroll
+                for (int qi = 0; qi < NQ; ++qi) fsum += X[qi].R;
+            }
             const bool clean = pixels_finite && gs_ballot(!(fsum - fsum == 0.0f)) == 0ull;
             unsigned long long done = 0ull;                                   // COOP: splats this wave left a sum for in its slab
             if (U) {
@@ -333,9 +359,9 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                     GS_STAT(9, 1);
                     const float4 a4 = sRec[j][0], b4 = sRec[j][1], c4 = sRec[j][2];
                     const float a = a4.z, b = a4.w, c = b4.x, apt = b4.z;
-                    float v[10];
+                    float v[NV];
 #pragma unroll
-                    for (int k = 0; k < 10; ++k) v[k] = 0.0f;
+                    for (int k = 0; k < NV; ++k) v[k] = 0.0f;
                     int n_use = 0;                                            // contributions of this splat in this tile (wave-uniform)
 #pragma unroll
                     for (int qi = 0; qi < NQ; ++qi) {
@@ -393,8 +419,14 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                             const float inv = __builtin_amdgcn_rcpf(one_m);
                             const float Tn = Q[qi].T * inv;
                             const float cg = c4.x * Q[qi].gr + c4.y * Q[qi].gg + c4.z * Q[qi].gb;
-                            const float ag = Tn * cg - inv * Q[qi].W;
+                            float ag = Tn * cg - inv * Q[qi].W;
                             const float d_rgb = alpha * Tn;
+                            if constexpr (AUX) {                      // (an idle lane: w = 0, so v[10] and R take exact zeros)
+                                const float dd = b4.w - X[qi].D;
+                                ag += X[qi].kD * (Tn * dd - inv * X[qi].R) + X[qi].kA * inv;
+                                v[10] = X[qi].kD * d_rgb;
+                                X[qi].R = __builtin_fmaf(d_rgb, dd, X[qi].R);
+                            }
                             const float agg = ag * gg;
                             const float vs0 = agg * cix, vs1 = agg * ciy;
                             v[0] = vs0; v[1] = vs1;
@@ -417,8 +449,14 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                             const float Tn = Q[qi].T * inv;                        // RAST:643 (v_rcp_f32: 1 ulp)
                             // d alpha: sum_c (colour_c*T - accumulated_c/(1-alpha)) * g_c, RAST:653-657, with the sums over c taken first
                             const float cg = c4.x * Q[qi].gr + c4.y * Q[qi].gg + c4.z * Q[qi].gb;
-                            const float ag = Tn * cg - inv * Q[qi].W;
+                            float ag = Tn * cg - inv * Q[qi].W;
                             const float d_rgb = alpha * Tn;                     // RAST:649
+                            if constexpr (AUX) {                                // depth and accumulated alpha, see BwdAux
+                                const float dd = b4.w - X[qi].D;
+                                ag += X[qi].kD * (Tn * dd - inv * X[qi].R) + X[qi].kA * inv;
+                                v[10] = __builtin_fmaf(X[qi].kD, d_rgb, v[10]);
+                                X[qi].R = __builtin_fmaf(d_rgb, dd, X[qi].R);
+                            }
                             // Per-splat constant factors are applied once per point in k_bwd_points instead of once per
                             // contribution: opacity on v[0..4] and v[9] (RAST:662), 0.5 on v[2..4], (1-opacity)*opacity on v[8]
                             const float agg = ag * g;
@@ -449,12 +487,14 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                     // keeps the reads conflict-free) and two quad DPP adds fold s.  About 30 VALU issue slots
                     // instead of 130+ for six half-rate DPP steps on eleven registers.  The eleventh value, the
                     // number of contributions (RAST:695-696), is the population count of the vote masks.
+                    // (AUX: the eleventh value, d depth, is summed by lanes 44..47 and leaves as column 11)
 #pragma unroll
-                    for (int k = 0; k < 10; ++k) sRed[k * RED_STRIDE + lane] = v[k];
+                    for (int k = 0; k < NV; ++k) sRed[k * RED_STRIDE + lane] = v[k];
                     __builtin_amdgcn_wave_barrier();
                     float t = 0.0f;
-                    if (lane < 40) {
-                        const float4* src = reinterpret_cast<const float4*>(sRed + (lane >> 2) * RED_STRIDE + 16 * (lane & 3));
+                    if (AUX ? (lane < 40 || (lane >= 44 && lane < 48)) : lane < 40) {
+                        const int krow = AUX && lane >= 44 ? 10 : (lane >> 2);
+                        const float4* src = reinterpret_cast<const float4*>(sRed + krow * RED_STRIDE + 16 * (lane & 3));
                         const float4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
                         t = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) +
                             (((x2.x + x2.y) + (x2.z + x2.w)) + ((x3.x + x3.y) + (x3.z + x3.w)));
@@ -469,7 +509,7 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                     } else {
                         const uint32_t sj = (uint32_t)__builtin_amdgcn_readlane((int)slot, j);
                         float* row = partial + (size_t)sj * PW;
-                        if ((lane & 3) == 0 && lane < 48) row[lane >> 2] = t;              // 12 floats (pad = 0), one store
+                        if ((lane & 3) == 0 && lane < 48) row[lane >> 2] = t;              // 12 floats (pad = 0; AUX: d depth), one store
                         if (lane == 63) { visited[sj] = gen; touched[__builtin_amdgcn_readlane(p, j)] = gen; }   // row written; point has a contribution (this backward's tag)
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -490,7 +530,10 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                     if ((coop.done[w] >> tj) & 1ull) {
                         const float* src = &coop.slab[w][tj][3 * part];
                         r0 += src[0];
-                        if (part == 3) cnt += __float_as_int(src[1]);                       // column 10: an integer
+                        if (part == 3) {
+                            cnt += __float_as_int(src[1]);                                  // column 10: an integer
+                            if constexpr (AUX) r2 += src[2];                                // column 11: d depth
+                        }
                         else { r1 += src[1]; r2 += src[2]; }
                         any = true;
                     }
@@ -498,7 +541,7 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                 if (any) {
                     const uint32_t sj = (uint32_t)coop.slot[tj];
                     float* row = partial + (size_t)sj * PW + 3 * part;
-                    row[0] = r0; row[1] = part == 3 ? __int_as_float(cnt) : r1; row[2] = r2;      // (column 11 is padding: 0)
+                    row[0] = r0; row[1] = part == 3 ? __int_as_float(cnt) : r1; row[2] = r2;      // (column 11: 0, AUX: d depth)
                     if (part == 0) { visited[sj] = gen; touched[coop.point[tj]] = gen; }
                 }
                 __syncthreads();                                                            // the slabs are free for the next batch
@@ -555,7 +598,9 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
 #ifndef GS_BWD_MIN_WAVES
 #define GS_BWD_MIN_WAVES 4        // waves per SIMD the register allocator must leave room for (6 spills 17 registers: measured slower)
 #endif
-template <int NQ, bool STRICT>
+// AUX: the depth / accumulated-alpha form (gs_backward_ex, BwdAux), always launched without cut records (cuts = NULL): a heavy tile
+// is then one item, walked whole by its four waves from 1 - accumulated_alpha.
+template <int NQ, bool STRICT, bool AUX>
 __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const int32_t* __restrict__ tile_order, const int32_t* __restrict__ n_heavy_ptr, int T,
                                                         const int32_t* __restrict__ tile_start, const int32_t* __restrict__ tile_end,
                                                         const int32_t* __restrict__ sorted_vals,
@@ -566,7 +611,8 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
                                                         const int32_t* __restrict__ last_in, int W, int H, int tiles_x,
                                                         float* __restrict__ partial, uint8_t* __restrict__ visited, uint8_t* __restrict__ touched,
                                                         const uint8_t gen, float* __restrict__ mag_image,
-                                                        const float4* __restrict__ cuts, float2* __restrict__ cut_mag, const int32_t* __restrict__ tile_cut)
+                                                        const float4* __restrict__ cuts, float2* __restrict__ cut_mag, const int32_t* __restrict__ tile_cut,
+                                                        const BwdAux aux)
 {
     __shared__ float4 sRecAll[4][64][3];             // per wave: the batch's splat records (COOP: then the per-quadrant sums)
     __shared__ __attribute__((aligned(16))) float sRedAll[4][11 * RED_STRIDE];
@@ -595,15 +641,17 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
             coop.cut_rec = cuts + first; coop.mag_part = cut_mag + first;
             coop.redo = const_cast<int32_t*>(n_heavy_ptr) + GS_ORDER_REDO_OFFSET + h;
         }
-        gs_bwd_tile_body<1, STRICT, true>(tile, wave, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
-                                          PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen, mag_image);
+        gs_bwd_tile_body<1, STRICT, true, AUX>(tile, wave, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
+                                               PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen,
+                                               mag_image, aux);
         return;
     }
     const int item = lb * 4 + wave;                                    // work item among the ordinary (tile, quadrant group) pairs
     const int ti = n_heavy + item / G;
     if (ti >= T) return;
-    gs_bwd_tile_body<NQ, STRICT, false>(tile_order[ti], item % G, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
-                                        PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen, mag_image);
+    gs_bwd_tile_body<NQ, STRICT, false, AUX>(tile_order[ti], item % G, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
+                                             PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen,
+                                             mag_image, aux);
 }
 
 // Heavy tiles whose segments found the forward's transmittance at a cut at odds with their own walk (BwdCoop::redo): the whole
@@ -645,8 +693,8 @@ __global__ __launch_bounds__(256) void k_blend_bwd_repair(const int32_t* __restr
 #define SUM_ROWS_SMALL 32
 #define SUM_ROWS_GIANT 1024
 // rows first, first + STRIDE, ... of one point: four per thread in flight (flags, then the rows; an unvisited row reads the shared zero
-// row), added in index order
-template <int STRIDE>
+// row), added in index order.  AUX: column 11 (d depth) too, into w[10].
+template <int STRIDE, bool AUX>
 __device__ __forceinline__ void gs_sum_rows_strided(const float4* __restrict__ rows, const uint8_t* __restrict__ vis, const uint8_t gen,
                                                     const float4* __restrict__ zero_row, const int first, const int cnt, float (&w)[11], int& wpix)
 {
@@ -665,6 +713,7 @@ __device__ __forceinline__ void gs_sum_rows_strided(const float4* __restrict__ r
         for (int k = 0; k < 4; ++k) {
             w[0] += a[k].x; w[1] += a[k].y; w[2] += a[k].z; w[3] += a[k].w; w[4] += b[k].x; w[5] += b[k].y; w[6] += b[k].z; w[7] += b[k].w;
             w[8] += c[k].x; w[9] += c[k].y; wpix += __float_as_int(c[k].z);
+            if constexpr (AUX) w[10] += c[k].w;
         }
     }
 }
@@ -692,6 +741,8 @@ __device__ __forceinline__ void gs_fold_mag(const GsMagFold& fold)
         fold.mag_image[2 * o] = a; fold.mag_image[2 * o + 1] = b;
 }
 
+// AUX: also column 11 (d depth), in the same slot order; otherwise it is written as 0 (the staged path's sums keep it so)
+template <bool AUX>
 __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_t* __restrict__ offsets, const int32_t* __restrict__ ntiles,
                                                   const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ touched,
                                                   const uint8_t gen, const float4* __restrict__ zero_row, float4* __restrict__ sums, const GsMagFold fold,
@@ -742,6 +793,7 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
                 v[0] += a[k].x; v[1] += a[k].y; v[2] += a[k].z; v[3] += a[k].w;
                 v[4] += b[k].x; v[5] += b[k].y; v[6] += b[k].z; v[7] += b[k].w;
                 v[8] += c[k].x; v[9] += c[k].y; npix += __float_as_int(c[k].z);
+                if constexpr (AUX) v[10] += c[k].w;
             }
         }
     }
@@ -753,7 +805,7 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
     if (valid && q == 0 && cnt <= SUM_ROWS_SMALL) {
         sums[3 * (size_t)m] = make_float4(v[0], v[1], v[2], v[3]);
         sums[3 * (size_t)m + 1] = make_float4(v[4], v[5], v[6], v[7]);
-        sums[3 * (size_t)m + 2] = make_float4(v[8], v[9], __int_as_float(npix), 0.0f);
+        sums[3 * (size_t)m + 2] = make_float4(v[8], v[9], __int_as_float(npix), AUX ? v[10] : 0.0f);
     }
     // wave-cooperative pass over the large points of this wave (one vote per quad leader); the GIANT ones (a background splat over
     // the whole image: thousands of rows, 350 KB) are left to the whole block below
@@ -777,17 +829,18 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
                     const float4 a = rows[3 * i], b = rows[3 * i + 1], c = rows[3 * i + 2];
                     w[0] += a.x; w[1] += a.y; w[2] += a.z; w[3] += a.w; w[4] += b.x; w[5] += b.y; w[6] += b.z; w[7] += b.w;
                     w[8] += c.x; w[9] += c.y; wpix += __float_as_int(c.z);
+                    if constexpr (AUX) w[10] += c.w;
                 }
             }
         } else {
-            gs_sum_rows_strided<64>(rows, vis, gen, zero_row, lane, bcnt, w, wpix);
+            gs_sum_rows_strided<64, AUX>(rows, vis, gen, zero_row, lane, bcnt, w, wpix);
         }
         gs_wave_sum11_row3(w);
         wpix = gs_wave_sum_i(wpix);
         if (lane == 63) {
             sums[3 * (size_t)bm] = make_float4(w[0], w[1], w[2], w[3]);
             sums[3 * (size_t)bm + 1] = make_float4(w[4], w[5], w[6], w[7]);
-            sums[3 * (size_t)bm + 2] = make_float4(w[8], w[9], __int_as_float(wpix), 0.0f);
+            sums[3 * (size_t)bm + 2] = make_float4(w[8], w[9], __int_as_float(wpix), AUX ? w[10] : 0.0f);
         }
     }
     // block-cooperative pass over the giant points of this block: its 256 threads stride over the rows, four per thread in flight; the
@@ -808,13 +861,14 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
             int wpix = 0;
 #pragma unroll
             for (int k = 0; k < 11; ++k) w[k] = 0.0f;
-            gs_sum_rows_strided<256>(reinterpret_cast<const float4*>(partial + (size_t)boff * PW), visited + boff, gen, zero_row, (int)threadIdx.x, bcnt, w, wpix);
+            gs_sum_rows_strided<256, AUX>(reinterpret_cast<const float4*>(partial + (size_t)boff * PW), visited + boff, gen, zero_row, (int)threadIdx.x, bcnt, w, wpix);
             gs_wave_sum11_row3(w);
             wpix = gs_wave_sum_i(wpix);
             if (lane == 63) {
 #pragma unroll
                 for (int k = 0; k < 10; ++k) sPart[wave][k] = w[k];
                 sPart[wave][10] = __int_as_float(wpix);
+                if constexpr (AUX) sPart[wave][11] = w[10];
             }
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -822,9 +876,10 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
 #pragma unroll
                 for (int k = 0; k < 10; ++k) r[k] = ((sPart[0][k] + sPart[1][k]) + sPart[2][k]) + sPart[3][k];
                 const int np = (__float_as_int(sPart[0][10]) + __float_as_int(sPart[1][10])) + (__float_as_int(sPart[2][10]) + __float_as_int(sPart[3][10]));
+                const float rd = AUX ? ((sPart[0][11] + sPart[1][11]) + sPart[2][11]) + sPart[3][11] : 0.0f;
                 sums[3 * (size_t)bm] = make_float4(r[0], r[1], r[2], r[3]);
                 sums[3 * (size_t)bm + 1] = make_float4(r[4], r[5], r[6], r[7]);
-                sums[3 * (size_t)bm + 2] = make_float4(r[8], r[9], __int_as_float(np), 0.0f);
+                sums[3 * (size_t)bm + 2] = make_float4(r[8], r[9], __int_as_float(np), rd);
             }
             __syncthreads();
         }
@@ -833,6 +888,8 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
 
 // ---------------------------------------------------------------------------------
 #define ROW_LDS 60
+// AUX: the sums carry d depth in column 11 (gs_backward_ex); it joins the camera-space z gradient of the position
+template <bool AUX>
 __global__ __launch_bounds__(256) void k_bwd_points(
     int64_t N, const int32_t* __restrict__ cam_index, const float4* __restrict__ sums, const float4* __restrict__ PD,
     const float* __restrict__ pc, const float* __restrict__ feat, const int32_t* __restrict__ obj,
@@ -923,6 +980,10 @@ __global__ __launch_bounds__(256) void k_bwd_points(
             const float j0 = (d[0] * P.R[j] + d[1] * P.R[3 + j]) + d[2] * P.R[6 + j];
             const float j1 = (d[3] * P.R[j] + d[4] * P.R[3 + j]) + d[5] * P.R[6 + j];
             gt[j] = guv0 * j0 + guv1 * j1;
+        }
+        if constexpr (AUX) {                                            // depth = p_cam z = (W x + t)_z: d/dx = row 2 of W
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gt[j] += s[11] * P.R[6 + j];
         }
         // ---- d Sigma' / d(q, s), GP3D:237-331, contracted with (g00 g01; g01 g11) ----
         const float4 pd = GS_REC(PD, m);                                        // translation_camera, RAST:737-738
@@ -1094,20 +1155,24 @@ __global__ __launch_bounds__(256) void k_bwd_points(
 
 void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
 {
+    // (a.aux: the caller has set a.cuts = NULL -- the depth / alpha backward walks every heavy tile whole, see k_blend_bwd_tile)
+    const BwdAux aux{a.grad_depth, a.depth, a.grad_alpha};
     if (a.T > 0 && a.K > 0) {
         // (the `visited` / `touched` flags are not cleared per backward: a flag counts only if it holds THIS backward's tag, a.gen)
         GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(a.tile_work, a.T, a.tile_order, a.order_hint, a.n_heavy, a.heavy_factor_x2,
                                                                               a.tile_start, a.tile_end, a.cuts ? a.tile_cut : nullptr, a.cuts ? a.item_cap : gs_heavy_cap(a.T)));
         // workgroups: room for every segment of every heavy tile (no cuts: one item per heavy tile) + the ordinary work items four to a workgroup
         const unsigned groups = (unsigned)(a.cuts ? a.item_cap : gs_heavy_cap(a.T)) + (unsigned)(((size_t)a.T * (size_t)a.G + 3) / 4);
-#define GS_BWD_LAUNCH(NQ_, STRICT_)                                                                                                    \
-        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_><<<groups, 256, 0, s>>>(a.tile_order, a.n_heavy, a.T, a.tile_start,  \
-                 a.tile_end, a.vals_sorted, a.PA, a.PB, a.PC, a.box, a.offsets, a.grad_image, a.acc_alpha, a.last, a.W, a.H, a.tiles_x,   \
-                 a.partial, a.visited, a.touched, a.gen, a.mag_image, a.cuts, a.cut_mag, a.tile_cut))
-        if (a.G == 1) { if (a.strict) GS_BWD_LAUNCH(4, true); else GS_BWD_LAUNCH(4, false); }
-        else if (a.G == 2) { if (a.strict) GS_BWD_LAUNCH(2, true); else GS_BWD_LAUNCH(2, false); }
-        else { if (a.strict) GS_BWD_LAUNCH(1, true); else GS_BWD_LAUNCH(1, false); }
+#define GS_BWD_LAUNCH_(NQ_, STRICT_, AUX_)                                                                                             \
+        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups, 256, 0, s>>>(a.tile_order, a.n_heavy, a.T,      \
+                 a.tile_start, a.tile_end, a.vals_sorted, a.PA, a.PB, a.PC, a.box, a.offsets, a.grad_image, a.acc_alpha, a.last, a.W,     \
+                 a.H, a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image, a.cuts, a.cut_mag, a.tile_cut, aux))
+#define GS_BWD_LAUNCH(NQ_, STRICT_) { if (a.aux) GS_BWD_LAUNCH_(NQ_, STRICT_, true); else GS_BWD_LAUNCH_(NQ_, STRICT_, false); }
+        if (a.G == 1) { if (a.strict) GS_BWD_LAUNCH(4, true) else GS_BWD_LAUNCH(4, false) }
+        else if (a.G == 2) { if (a.strict) GS_BWD_LAUNCH(2, true) else GS_BWD_LAUNCH(2, false) }
+        else { if (a.strict) GS_BWD_LAUNCH(1, true) else GS_BWD_LAUNCH(1, false) }
 #undef GS_BWD_LAUNCH
+#undef GS_BWD_LAUNCH_
         if (a.cuts && gs_heavy_cap(a.T) > 0) {                 // (fewer than eight tiles: no tile can be heavy)
 #define GS_BWD_REPAIR(STRICT_)                                                                                                          \
             GS_TIMED(a.prof, KID_BLEND_BWD_REPAIR, s, k_blend_bwd_repair<STRICT_><<<(unsigned)gs_heavy_cap(a.T), 256, 0, s>>>(a.tile_order, a.n_heavy, a.G, \
@@ -1125,8 +1190,12 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
         fold.n_heavy = a.n_heavy; fold.tile_order = a.tile_order; fold.tile_cut = a.tile_cut; fold.cut_mag = a.cut_mag;
         fold.mag_image = a.cuts ? a.mag_image : nullptr; fold.W = a.W; fold.H = a.H; fold.tiles_x = a.tiles_x;
         const unsigned fold_blocks = fold.mag_image ? (unsigned)gs_heavy_cap(a.T) : 0u;
-        GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, a.offsets, a.ntiles, a.partial, a.visited, a.touched,
-                                                                                  a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
+        if (a.aux)
+            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<true><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, a.offsets, a.ntiles, a.partial, a.visited,
+                                                                                  a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
+        else
+            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<false><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, a.offsets, a.ntiles, a.partial, a.visited,
+                                                                                  a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
     }
     else if (a.M > 0)
         (void)hipMemsetAsync(a.sums, 0, sizeof(float) * PW * (size_t)a.M, s);          // no pairs at all: every sum is zero
@@ -1137,10 +1206,13 @@ void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s)
     const int nb = (int)((a.N + 255) / 256);
     if (nb == 0) return;
     int keep = a.sh_band <= 0 ? 1 : a.sh_band == 1 ? 4 : a.sh_band == 2 ? 9 : 16;
-    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<<<nb, 256, 0, s>>>(a.N, a.cam_index, a.sums, a.PD, a.point_cloud, a.features,
-                                                                    a.object_id, a.Kmat, a.pose, keep, a.f_color, a.f_high, a.f_s, a.f_q, a.f_alpha,
-                                                                    a.grad_pc, a.grad_feat, a.grad_uv, a.mag, a.n_affected,
-                                                                    a.hook_gpc, a.hook_gfeat, a.hook_guv, a.hook_mag,
-                                                                    a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, a.PA, a.PB, a.ntiles,
-                                                                    a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm));
+#define GS_BWD_POINTS(AUX_)                                                                                                             \
+    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<AUX_><<<nb, 256, 0, s>>>(a.N, a.cam_index, a.sums, a.PD, a.point_cloud, a.features,   \
+                                                                    a.object_id, a.Kmat, a.pose, keep, a.f_color, a.f_high, a.f_s, a.f_q, a.f_alpha, \
+                                                                    a.grad_pc, a.grad_feat, a.grad_uv, a.mag, a.n_affected,                \
+                                                                    a.hook_gpc, a.hook_gfeat, a.hook_guv, a.hook_mag,                      \
+                                                                    a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, a.PA, a.PB, a.ntiles, \
+                                                                    a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm))
+    if (a.aux) GS_BWD_POINTS(true); else GS_BWD_POINTS(false);
+#undef GS_BWD_POINTS
 }

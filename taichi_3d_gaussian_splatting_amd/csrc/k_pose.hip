@@ -23,6 +23,8 @@ __device__ __forceinline__ float pose_wave_sum(float v)
     return v;
 }
 
+// AUX: the sums carry d depth in column 11 (gs_backward_ex): it joins dL/dp_cam z
+template <bool AUX>
 __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects, int cap,
     const int32_t* __restrict__ ids, const float4* __restrict__ sums,
     const float4* __restrict__ PB, const float4* __restrict__ PC, const float4* __restrict__ PD,
@@ -109,6 +111,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
         gp[0] += B[2] * -fx2;
         gp[1] += B[5] * -fy2;
         gp[2] += (B[0] * -fx2 + B[2] * (2.0f * fx2 * px / pz)) + (B[4] * -fy2 + B[5] * (2.0f * fy2 * py / pz));
+        if constexpr (AUX) gp[2] += r2.w;                                  // the splat's depth is p_z
         // ---- p = W x + t_cp ----
         const float xv[3] = { x, y, z };
 #pragma unroll
@@ -241,8 +244,11 @@ void gs_launch_pose_grad(const GsBackwardArgs& a, int n_objects, void* scratch, 
     const int cap = pose_block_cap(n_objects);
     float* rec = static_cast<float*>(scratch);
     int32_t* n_rec = reinterpret_cast<int32_t*>(rec + (size_t)nb * cap * POSE_REC);
-    if (nb > 0)
-        k_pose_points<<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.ids, a.sums, a.PB, a.PC, a.PD, a.point_cloud, a.features,
-                                                a.object_id, a.Kmat, a.pose, rec, n_rec);
+    if (nb > 0 && a.aux)
+        k_pose_points<true><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.ids, a.sums, a.PB, a.PC, a.PD, a.point_cloud, a.features,
+                                                      a.object_id, a.Kmat, a.pose, rec, n_rec);
+    else if (nb > 0)
+        k_pose_points<false><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.ids, a.sums, a.PB, a.PC, a.PD, a.point_cloud, a.features,
+                                                       a.object_id, a.Kmat, a.pose, rec, n_rec);
     k_pose_reduce<<<n_objects, POSE_REDUCE_THREADS, 0, s>>>(nb, cap, rec, n_rec, a.pose, grad_q, grad_t);
 }
