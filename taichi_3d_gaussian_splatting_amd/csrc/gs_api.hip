@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -52,7 +53,6 @@ struct DevBuf {
 // What RAST:998-1019 saves for backward, in this library's layouts (DESIGN.md "HBM layout").
 struct FrameBufs {
     DevBuf mask, ids, cam_index, rec, box, ntiles, depth_codes, offsets, keys_a, keys_b, vals_a, vals_b, tile_start, pose, tile_order, cuts, cut_mag;
-    bool in_use = false;
     void release(int64_t* total)
     {
         DevBuf* all[] = { &mask, &ids, &cam_index, &rec, &box, &ntiles, &depth_codes, &offsets, &keys_a, &keys_b, &vals_a, &vals_b,
@@ -65,7 +65,7 @@ struct FrameBufs {
 // that is resolved under the ctx mutex on every use, so a released, recycled or foreign handle is an error, never a
 // dereference of freed memory.
 struct Frame {
-    FrameBufs* bufs = nullptr;
+    FrameBufs bufs;                     // kept (grow-only) when the slot is recycled
     gs_frame_info info{};
     int depth_bits = 0;
     void* keys_sorted = nullptr;
@@ -119,7 +119,6 @@ struct gs_ctx {
     GsProf prof;
     std::mutex mu;
     int64_t device_bytes = 0;
-    std::vector<FrameBufs*> pool;
     std::vector<Frame*> frames;         // slot i of the ticket space (recycled, generation-tagged)
     int transient = -1;                 // slot of the frame of the last keep_for_backward == 0 call
     // scratch shared by all frames (stream ordered)
@@ -181,8 +180,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     if (!c) return GS_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (FrameBufs* b : c->pool) { b->release(&c->device_bytes); delete b; }
-    for (Frame* f : c->frames) delete f;
+    for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch };
     for (DevBuf* b : all) b->release(&c->device_bytes);
@@ -224,6 +222,42 @@ extern "C" int gs_profile_read(gs_ctx* c, double* total_ms, int64_t* launches, i
 extern "C" int64_t gs_ctx_device_bytes(const gs_ctx* c) { return c ? c->device_bytes : 0; }
 extern "C" int64_t gs_ctx_counter_wait_ns(const gs_ctx* c) { return c ? c->counter_wait_ns : 0; }
 
+// Entering a call that launches on stream s (mutex held).
+static hipError_t enter_stream(gs_ctx* c, hipStream_t s)
+{
+    if (c->has_stream && c->last_stream != s) {
+        hipError_t e = hipEventRecord(c->switch_event, c->last_stream);
+        if (e != hipSuccess) return e;
+        e = hipStreamWaitEvent(s, c->switch_event, 0);
+        if (e != hipSuccess) return e;
+    }
+    c->has_stream = true; c->last_stream = s;
+    return hipSuccess;
+}
+
+// The prologue of every call that launches work (mutex held), after the checks that can refuse the call: the ctx's device,
+// then the stream hand-over.  *s_out = the call's stream.
+static int enter_call(gs_ctx* c, gs_stream stream_, hipStream_t* s_out)
+{
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(enter_stream(c, s));
+    *s_out = s;
+    return GS_OK;
+}
+
+// A buffer a stage grows before it queues anything; the out-of-memory error names the first one that cannot grow.
+struct Need { DevBuf* buf; size_t bytes; const char* name; };
+#define NEED(buf, bytes) Need{ &(buf), (bytes), #buf }
+
+static int grow(gs_ctx* c, std::initializer_list<Need> needs)
+{
+    for (const Need& n : needs)
+        if (n.buf->ensure(n.bytes, &c->device_bytes) != hipSuccess)
+            return fail(GS_ERR_OUT_OF_MEMORY, std::string("device allocation failed: ") + n.name);
+    return GS_OK;
+}
+
 // ---- frame tickets ------------------------------------------------------------------------------------------------
 static gs_frame* ticket_of(int slot, uint32_t generation)
 {
@@ -231,24 +265,14 @@ static gs_frame* ticket_of(int slot, uint32_t generation)
 }
 
 // resolves a ticket (mutex held); nullptr for anything that is not a live frame of THIS ctx
-static Frame* resolve(gs_ctx* c, const gs_frame* h, int* slot_out = nullptr)
+static Frame* resolve(gs_ctx* c, const gs_frame* h)
 {
     const uint64_t v = (uint64_t)(uintptr_t)h;
     const uint32_t lo = (uint32_t)v, gen = (uint32_t)(v >> 32);
     if (lo == 0 || lo > c->frames.size()) return nullptr;
     Frame* f = c->frames[lo - 1];
     if (!f->live || f->generation != gen) return nullptr;
-    if (slot_out) *slot_out = (int)lo - 1;
     return f;
-}
-
-static FrameBufs* acquire_bufs(gs_ctx* c)
-{
-    for (FrameBufs* b : c->pool) if (!b->in_use) { b->in_use = true; return b; }
-    FrameBufs* b = new FrameBufs();
-    b->in_use = true;
-    c->pool.push_back(b);
-    return b;
 }
 
 static Frame* acquire_frame(gs_ctx* c, int* slot)
@@ -267,61 +291,64 @@ static void drop_frame(gs_ctx* c, Frame* f)
     if (!f || !f->live) return;
     if (f->pending_slot > 0) c->slots_busy &= ~(1ull << f->pending_slot);      // a late write into a freed slot is harmless: tickets are unique
     f->pending_slot = -1;
-    if (f->bufs) f->bufs->in_use = false;
-    f->bufs = nullptr; f->live = false;
+    f->live = false;
     for (size_t i = 0; i < c->frames.size(); ++i) if (c->frames[i] == f && c->transient == (int)i) c->transient = -1;
 }
 
-// Entering a call that launches on stream s (mutex held).
-static hipError_t enter_stream(gs_ctx* c, hipStream_t s)
+// The frame of a forward-type call (mutex held, stream entered); the transient frame of the last keep == 0 call goes first.
+// Whoever begins a frame drops it again if one of its stages fails.
+static Frame* begin_frame(gs_ctx* c, const gs_camera* cam, int T, int keep, int* slot)
 {
-    if (c->has_stream && c->last_stream != s) {
-        hipError_t e = hipEventRecord(c->switch_event, c->last_stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(s, c->switch_event, 0);
-        if (e != hipSuccess) return e;
-    }
-    c->has_stream = true; c->last_stream = s;
-    return hipSuccess;
+    if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
+    Frame* f = acquire_frame(c, slot);
+    f->info = gs_frame_info{};
+    // (known before the stages run: a kept frame gets list cuts for its backward, and the tile count lays out the tile arrays)
+    f->info.kept_for_backward = keep ? 1 : 0;
+    f->info.n_tiles = T; f->info.camera_height = cam->camera_height; f->info.camera_width = cam->camera_width;
+    return f;
+}
+
+static void finish_frame(gs_ctx* c, Frame* f, int slot, int64_t N, int M, uint32_t K, int stages, gs_frame** frame_out)
+{
+    f->info.n_points = N; f->info.n_points_in_camera = M; f->info.n_keys = K;
+    f->info.stages = stages;
+    if (!f->info.kept_for_backward) c->transient = slot;
+    *frame_out = ticket_of(slot, f->generation);
+}
+
+// The one description of a frame's device buffers.  Records: one 64-byte row per point.  Tile arrays (GS_TILE_INTS):
+// tile_start | tile_end | tile_work | tile_cut (T each) | cut_alloc, max tiles, two spare.  Tile order (GS_ORDER_INTS):
+// order (T) | n_heavy | n_items | pad pad | item_base.
+static GsFrameView frame_view(const Frame& f)
+{
+    const FrameBufs& B = f.bufs;
+    const int T = f.info.n_tiles;
+    GsFrameView v{};
+    float4* rec = B.rec.as<float4>();
+    v.PA = rec; v.PB = rec + 1; v.PC = rec + 2; v.PD = rec + 3;
+    v.box = B.box.as<ushort4>(); v.ntiles = B.ntiles.as<int32_t>(); v.depth_codes = B.depth_codes.as<int32_t>(); v.offsets = B.offsets.as<uint32_t>();
+    v.ids = B.ids.as<int32_t>(); v.cam_index = B.cam_index.as<int32_t>(); v.mask = B.mask.as<int8_t>(); v.pose = B.pose.as<GsPose>();
+    v.T = T;
+    int32_t* tiles = B.tile_start.as<int32_t>();
+    v.tile_start = tiles; v.tile_end = tiles + T; v.tile_work = tiles + 2 * (size_t)T; v.tile_cut = tiles + 3 * (size_t)T;
+    v.cut_alloc = tiles + 4 * (size_t)T;
+    v.max_tiles = tiles + GS_TILE_INTS(T) - GS_TILE_SPARE_MAX_TILES;
+    v.tile_ints = (int)GS_TILE_INTS(T);
+    v.tile_order = B.tile_order.as<int32_t>(); v.n_heavy = v.tile_order + T;
+    v.keys_sorted = f.keys_sorted; v.vals_sorted = f.vals_sorted;
+    v.cuts = f.cut_cap > 0 ? B.cuts.as<float4>() : nullptr; v.cut_mag = B.cut_mag.as<float2>();
+    return v;
 }
 
 static int waves_per_tile(int n_tiles);
 static int bits_for(uint32_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b < 1 ? 1 : b; }
 
-#define ENSURE(buf, bytes)                                                                 \
-    do {                                                                                   \
-        hipError_t e__ = (buf).ensure((bytes), &c->device_bytes);                          \
-        if (e__ != hipSuccess) { drop_frame(c, f); return fail(GS_ERR_OUT_OF_MEMORY, std::string("device allocation failed: " #buf)); } \
-    } while (0)
-
-#define HIP_TRY_F(expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            drop_frame(c, f);                                                                      \
-            return fail(GS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));          \
-        }                                                                                          \
-    } while (0)
-
-static void set_records(GsProjectArgs& pa, const FrameBufs& B, size_t rows)
-{   // GS_RS == 4: one 64-byte row per point; GS_RS == 1: four planes of `rows` records
-    float4* rec = B.rec.as<float4>();
-    const size_t plane = GS_RS == 4 ? 1 : rows;
-    pa.PA = rec; pa.PB = rec + plane; pa.PC = rec + 2 * plane; pa.PD = rec + 3 * plane;
-}
-
+// ---- the counter hand-over ------------------------------------------------------------------------------------------
 // The one device->host hand-over of a frame: M, K, the depth-code range (and the bad-object-id count).  The last
 // prologue kernel writes them into pinned host memory and then the ticket; spinning on it costs a few microseconds
-// where a copy + stream synchronisation left the GPU idle for ~30.
-static int wait_counters(gs_ctx* c, hipStream_t s, int32_t ticket, int slot = 0)
+// where a copy + stream synchronisation left the GPU idle for ~30.  Waits for `ticket` in counter slot `slot`.
+static int read_counters(gs_ctx* c, hipStream_t s, int32_t ticket, int slot, GsCounters* out)
 {
-    static const bool wait_on_stream = []{ const char* e = getenv("GS_COUNTERS_WAIT"); return e && std::strcmp(e, "stream") == 0; }();
-    if (wait_on_stream) {                   // diagnostic alternative: block in the runtime instead of spinning
-        const auto t0s = std::chrono::steady_clock::now();
-        HIP_TRY(hipStreamSynchronize(s));
-        c->counter_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0s).count();
-        return GS_OK;
-    }
     volatile GsCounters* hc = c->host_counters + slot;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0; hc->reserved != ticket; ++spin) {
@@ -338,6 +365,37 @@ static int wait_counters(gs_ctx* c, hipStream_t s, int32_t ticket, int slot = 0)
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     c->counter_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    *out = c->host_counters[slot];
+    if (out->bad_object_ids != 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "point_object_id holds " + std::to_string(out->bad_object_ids) +
+                                             " value(s) outside [0, n_objects) on valid rows");
+    return GS_OK;
+}
+
+// Reads the hand-over of a frame begun with gs_project_shard_begin (mutex held): M, K and the object-id verdict.  A frame
+// whose read fails is dropped.
+static int resolve_pending(gs_ctx* c, Frame* f)
+{
+    if (f->pending_slot <= 0) return GS_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    GsCounters hc;
+    const int rc = read_counters(c, f->pending_stream, f->pending_ticket, f->pending_slot, &hc);
+    if (rc != GS_OK) { drop_frame(c, f); return rc; }          // (which frees the frame's counter slot)
+    c->slots_busy &= ~(1ull << f->pending_slot);
+    f->pending_slot = -1;
+    f->info.n_points_in_camera = hc.M;
+    f->info.n_keys = hc.K;
+    return GS_OK;
+}
+
+// The live frame of this ctx that handle h names (mutex held); with `pending`, its deferred hand-over is read first.
+static int lookup(gs_ctx* c, const gs_frame* h, const char* who, bool pending, Frame** out)
+{
+    Frame* f = resolve(c, h);
+    if (!f) return fail(GS_ERR_STATE, std::string(who) + ": not a live frame of this context");
+    if (pending)
+        if (const int rc = resolve_pending(c, f)) return rc;
+    *out = f;
     return GS_OK;
 }
 
@@ -379,56 +437,40 @@ static int check_forward_out(const gs_forward_out* out, const gs_config* cfg, in
 // ---- per-point half: filter, compaction, projection (+ tile counts, scan, publication) ----------------------------
 // On success the frame's buffers hold mask / ids / cam_index / records / box / ntiles.  The counters (M, K, depth-code range,
 // bad object ids) are handed over through pinned memory; `wait` says when the host reads them:
-//   WAIT_NOW    before this function returns (M, K, max_code are filled in);
+//   WAIT_NOW    before this function returns (M and K are filled in);
 //   WAIT_LATER  the caller reads slot 0 itself (read_counters) after it has queued more work -- nothing else may publish before;
 //   WAIT_FRAME  the frame keeps a slot of its own and whoever needs M first reads it (resolve_pending, gs_project_shard_begin).
 enum CounterWait { WAIT_NOW, WAIT_LATER, WAIT_FRAME };
 
-static int read_counters(gs_ctx* c, Frame* f, hipStream_t s, int32_t ticket, int* M_out, uint32_t* K_out, int* max_code_out)
+static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg, hipStream_t s,
+                             CounterWait wait, GsProjectArgs* pa_out, int* M_out, uint32_t* K_out)
 {
-    const int rc = wait_counters(c, s, ticket);
-    if (rc != GS_OK) { drop_frame(c, f); return rc; }
-    if (c->host_counters->bad_object_ids != 0) {
-        drop_frame(c, f);
-        return fail(GS_ERR_INVALID_ARGUMENT, "point_object_id holds " + std::to_string(c->host_counters->bad_object_ids) +
-                                             " value(s) outside [0, n_objects) on valid rows");
-    }
-    *M_out = c->host_counters->M; *K_out = c->host_counters->K; *max_code_out = c->host_counters->max_depth_code;
-    return GS_OK;
-}
-
-static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg, int T,
-                             hipStream_t s, GsProjectArgs* pa_out, int* M_out, uint32_t* K_out, int* max_code_out, CounterWait wait = WAIT_NOW)
-{
-    FrameBufs& B = *f->bufs;
+    FrameBufs& B = f->bufs;
     const int64_t N = sc->n_points;
-    const int H = cam->camera_height, W = cam->camera_width;
+    const int T = f->info.n_tiles;
     const size_t nb = (size_t)((N + 255) / 256);
     const size_t Np = (size_t)(N > 0 ? N : 1);
-    ENSURE(B.mask, Np); ENSURE(B.ids, 4 * Np); ENSURE(B.cam_index, 4 * Np);
-    ENSURE(B.rec, 64 * Np);
-    ENSURE(B.box, 8 * Np); ENSURE(B.ntiles, 4 * Np); ENSURE(B.depth_codes, 4 * Np); ENSURE(B.offsets, 4 * Np);
-    ENSURE(B.tile_start, 4 * GS_TILE_INTS(T));    // tile_start | tile_end | tile_work | tile_cut | cut_alloc, cleared together
-    ENSURE(B.tile_order, 4 * GS_ORDER_INTS(T));   // + heavy-tile count, item count and item bases behind the order
-    ENSURE(B.pose, sizeof(GsPose) * (size_t)cam->n_objects);
+    int rc = grow(c, { NEED(B.mask, Np), NEED(B.ids, 4 * Np), NEED(B.cam_index, 4 * Np),
+                       NEED(B.rec, 64 * Np),
+                       NEED(B.box, 8 * Np), NEED(B.ntiles, 4 * Np), NEED(B.depth_codes, 4 * Np), NEED(B.offsets, 4 * Np),
+                       NEED(B.tile_start, 4 * GS_TILE_INTS(T)),    // tile_start | tile_end | tile_work | tile_cut | cut_alloc, cleared together
+                       NEED(B.tile_order, 4 * GS_ORDER_INTS(T)),   // + heavy-tile count, item count and item bases behind the order
+                       NEED(B.pose, sizeof(GsPose) * (size_t)cam->n_objects),
+                       NEED(c->block_counts, 4 * (nb + 1)), NEED(c->block_offsets, 4 * (nb + 1)),
+                       NEED(c->tile_block_sums, 4 * (nb + 1)) });
+    if (rc != GS_OK) return rc;
     f->n_objects = cam->n_objects;
-    ENSURE(c->block_counts, 4 * (nb + 1)); ENSURE(c->block_offsets, 4 * (nb + 1));
-    ENSURE(c->tile_block_sums, 4 * (nb + 1));
 
     GsProjectArgs pa{};
     pa.prof = &c->prof;
     pa.point_cloud = sc->point_cloud; pa.features = sc->point_cloud_features; pa.invalid = sc->point_invalid_mask;
     pa.object_id = sc->point_object_id; pa.N = N; pa.q_pc = cam->q_pointcloud_camera; pa.t_pc = cam->t_pointcloud_camera;
-    pa.n_objects = cam->n_objects; pa.Kmat = cam->camera_intrinsics; pa.H = H; pa.W = W;
+    pa.n_objects = cam->n_objects; pa.Kmat = cam->camera_intrinsics; pa.H = cam->camera_height; pa.W = cam->camera_width;
     pa.near_plane = cfg->near_plane; pa.far_plane = cfg->far_plane; pa.depth_scale = cfg->depth_to_sort_key_scale;
-    pa.pose = B.pose.as<GsPose>(); pa.mask = B.mask.as<int8_t>();
+    pa.v = frame_view(*f);
     pa.block_counts = c->block_counts.as<int32_t>(); pa.block_offsets = c->block_offsets.as<int32_t>();
-    pa.ids = B.ids.as<int32_t>(); pa.cam_index = B.cam_index.as<int32_t>();
-    set_records(pa, B, Np);
-    pa.box = B.box.as<ushort4>(); pa.ntiles = B.ntiles.as<int32_t>(); pa.depth_codes = B.depth_codes.as<int32_t>();
     pa.tile_block_sums = c->tile_block_sums.as<uint32_t>();
     pa.counters = c->counters.as<GsCounters>();
-    pa.tile_arrays = B.tile_start.as<int32_t>(); pa.tile_ints = (int)GS_TILE_INTS(T);
     int slot = 0;
     if (wait == WAIT_FRAME && N > 0) {
         const uint64_t free_slots = ~c->slots_busy;
@@ -438,14 +480,46 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     if (c->ticket == 0x7fffffff) c->ticket = 0;
     gs_launch_project(pa, s, wait != WAIT_LATER);      // WAIT_LATER: the caller decides who publishes the counters (run_forward_tail)
     f->max_tiles_known = true;
-    HIP_TRY_F(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     *pa_out = pa;
-    *M_out = 0; *K_out = 0u; *max_code_out = 0;
+    *M_out = 0; *K_out = 0u;
     if (slot > 0) {
         f->pending_slot = slot; f->pending_ticket = pa.ticket; f->pending_stream = s;
         return GS_OK;
     }
-    if (N > 0 && wait != WAIT_LATER) return read_counters(c, f, s, pa.ticket, M_out, K_out, max_code_out);
+    if (N > 0 && wait != WAIT_LATER) {
+        GsCounters hc;
+        if ((rc = read_counters(c, s, pa.ticket, 0, &hc)) != GS_OK) return rc;
+        *M_out = hc.M; *K_out = hc.K;
+    }
+    return GS_OK;
+}
+
+// The per-point half of gs_forward_projected: the records arrive from elsewhere; the frame keeps its own copy for backward,
+// and tile boxes, counts and depth codes are recomputed from them.  The counters are published from run_forward_tail.
+static int run_records_stage(gs_ctx* c, Frame* f, const float* records, int64_t m, const gs_config* cfg, hipStream_t s,
+                             GsProjectArgs* pa_out)
+{
+    FrameBufs& B = f->bufs;
+    const int T = f->info.n_tiles;
+    const size_t Mp = (size_t)(m > 0 ? m : 1);
+    const size_t nb = (size_t)((m + 255) / 256);
+    const int rc = grow(c, { NEED(B.rec, 64 * Mp), NEED(B.box, 8 * Mp), NEED(B.ntiles, 4 * Mp), NEED(B.depth_codes, 4 * Mp), NEED(B.offsets, 4 * Mp),
+                             NEED(B.tile_start, 4 * GS_TILE_INTS(T)), NEED(B.tile_order, 4 * GS_ORDER_INTS(T)),
+                             NEED(c->tile_block_sums, 4 * (nb + 1)) });
+    if (rc != GS_OK) return rc;
+    if (m > 0) HIP_TRY(hipMemcpyAsync(B.rec.p, records, (size_t)m * 64, hipMemcpyDeviceToDevice, s));
+    GsProjectArgs pa{};
+    pa.prof = &c->prof; pa.N = m; pa.H = f->info.camera_height; pa.W = f->info.camera_width; pa.depth_scale = cfg->depth_to_sort_key_scale;
+    pa.v = frame_view(*f);
+    pa.tile_block_sums = c->tile_block_sums.as<uint32_t>();
+    pa.counters = c->counters.as<GsCounters>();
+    pa.host_mirror = c->host_counters_dev; pa.ticket = ++c->ticket;
+    if (c->ticket == 0x7fffffff) c->ticket = 0;
+    gs_launch_boxes_from_records(pa, (int)m, s, false);
+    f->max_tiles_known = false;
+    HIP_TRY(hipGetLastError());
+    *pa_out = pa;
     return GS_OK;
 }
 
@@ -454,9 +528,10 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
 // Both may be PREDICTIONS (run_forward_tail): the kernels take the frame's real pair count from the device counters and stay
 // inside K_bound whatever it is, and any depth_bits >= the real width sorts into the same order.
 static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_t n_rows, int M_bound, uint32_t K_bound, int depth_bits,
-                            int H, int W, int tiles_x, int T, const gs_config* cfg, const gs_forward_out* out, hipStream_t s, bool publish)
+                            const gs_config* cfg, const gs_forward_out* out, hipStream_t s, bool publish)
 {
-    FrameBufs& B = *f->bufs;
+    FrameBufs& B = f->bufs;
+    const int T = f->info.n_tiles, H = f->info.camera_height, W = f->info.camera_width, tiles_x = (W + GS_TILE - 1) / GS_TILE;
     // list cuts for the backward's heavy tiles (k_blend_fwd): only a frame that will be back-propagated wants them.
     // Policy (measured): segments pay where the ordinary waves do not fill the chip anyway (T * G waves for 5120
     // slots: cfg2_clustered 0.38 -> 0.22 ms) and cost where they do (cfg3_clustered 0.31 -> 0.34 ms: more, shorter work items in a
@@ -469,51 +544,49 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
         // is claimed at run time: a capacity that could run out would make WHICH lists get cuts, and with it the last bits of the
         // gradients, depend on the order of the claims.)
         cut_cap = (int)std::min<uint64_t>((uint64_t)K_bound / GS_SEG + (uint64_t)T + 2, 0x7fffffffu);
-        ENSURE(B.cuts, (size_t)cut_cap * 256 * sizeof(float4)); ENSURE(B.cut_mag, (size_t)cut_cap * 256 * sizeof(float2));
+        if (const int rc = grow(c, { NEED(B.cuts, (size_t)cut_cap * 256 * sizeof(float4)), NEED(B.cut_mag, (size_t)cut_cap * 256 * sizeof(float2)) }))
+            return rc;
     }
     f->cut_cap = cut_cap;
     const int tile_bits = bits_for((uint32_t)(T > 1 ? T - 1 : 1));
     const int key64 = depth_bits + tile_bits > 32 ? 1 : 0;      // compact 32-bit keys whenever they fit
-    if (depth_bits + tile_bits > 63) { drop_frame(c, f); return fail(GS_ERR_INVALID_ARGUMENT, "sort key needs more than 63 bits"); }
+    if (depth_bits + tile_bits > 63) return fail(GS_ERR_INVALID_ARGUMENT, "sort key needs more than 63 bits");
     const size_t Kp = K_bound > 0 ? K_bound : 1;
     const size_t key_bytes = key64 ? 8 : 4;
-    ENSURE(B.keys_a, key_bytes * Kp); ENSURE(B.keys_b, key_bytes * Kp); ENSURE(B.vals_a, 4 * Kp); ENSURE(B.vals_b, 4 * Kp);
     const size_t hist_elems = gs_sort_hist_elems(K_bound);
-    ENSURE(c->hist, 4 * hist_elems); ENSURE(c->scan_tmp, 4 * gs_scan_tmp_elems(hist_elems));
+    if (const int rc = grow(c, { NEED(B.keys_a, key_bytes * Kp), NEED(B.keys_b, key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
+                                 NEED(c->hist, 4 * hist_elems), NEED(c->scan_tmp, 4 * gs_scan_tmp_elems(hist_elems)) }))
+        return rc;
 
     GsBinArgs ba{};
     ba.prof = &c->prof;
     ba.N = n_rows; ba.M = M_bound; ba.K = K_bound; ba.counters = c->counters.as<GsCounters>();
-    ba.H = H; ba.W = W; ba.tiles_x = tiles_x; ba.depth_scale = cfg->depth_to_sort_key_scale;
+    ba.tiles_x = tiles_x; ba.depth_scale = cfg->depth_to_sort_key_scale;
     ba.depth_bits = depth_bits; ba.key_bits = depth_bits + tile_bits;
-    ba.PA = pa.PA; ba.PB = pa.PB; ba.box = pa.box; ba.ntiles = pa.ntiles; ba.depth_codes = pa.depth_codes; ba.tile_block_sums = pa.tile_block_sums;
+    ba.v = frame_view(*f);
+    ba.tile_block_sums = pa.tile_block_sums;
     ba.counters_rw = pa.counters; ba.host_mirror = publish ? pa.host_mirror : nullptr; ba.ticket = pa.ticket;   // publish: k_keygen's last block hands the counters over
     ba.block_offsets = pa.block_offsets; ba.block_counts = pa.block_counts;     // NULL for records that did not come from k_project
-    ba.offsets = B.offsets.as<uint32_t>();
     ba.keys_a = B.keys_a.p; ba.keys_b = B.keys_b.p; ba.key64 = key64;
     ba.vals_a = B.vals_a.as<int32_t>(); ba.vals_b = B.vals_b.as<int32_t>();
     ba.hist = c->hist.as<uint32_t>(); ba.scan_tmp = c->scan_tmp.as<uint32_t>();
-    ba.tile_start = B.tile_start.as<int32_t>(); ba.tile_end = B.tile_start.as<int32_t>() + T; ba.T = T;
     ba.keys_sorted = &f->keys_sorted; ba.vals_sorted = &f->vals_sorted;
     gs_launch_binning(ba, s);
-    HIP_TRY_F(hipGetLastError());
+    HIP_TRY(hipGetLastError());
 
     GsBlendFwdArgs fa{};
     fa.prof = &c->prof;
-    fa.H = H; fa.W = W; fa.tiles_x = tiles_x; fa.T = T; fa.rgb_only = cfg->rgb_only;
-    fa.tile_start = ba.tile_start; fa.tile_end = ba.tile_end; fa.vals_sorted = f->vals_sorted;
-    fa.keys_sorted = f->keys_sorted; fa.key64 = key64; fa.depth_bits = depth_bits; fa.K = K_bound; fa.counters = ba.counters;
-    fa.PA = pa.PA; fa.PB = pa.PB; fa.PC = pa.PC;
+    fa.H = H; fa.W = W; fa.tiles_x = tiles_x; fa.rgb_only = cfg->rgb_only;
+    fa.v = frame_view(*f);                  // (taken after the binning, which said where the sorted pairs are)
+    fa.key64 = key64; fa.depth_bits = depth_bits; fa.K = K_bound; fa.counters = ba.counters;
     fa.image = out->rasterized_image; fa.depth = out->rasterized_depth; fa.acc_alpha = out->pixel_accumulated_alpha;
     fa.last = out->pixel_offset_of_last_effective_point; fa.count = out->pixel_valid_point_count;
-    fa.tile_work = B.tile_start.as<int32_t>() + 2 * (size_t)T;
-    fa.cuts = cut_cap > 0 ? B.cuts.as<float4>() : nullptr; fa.tile_cut = B.tile_start.as<int32_t>() + 3 * (size_t)T;
-    fa.cut_alloc = B.tile_start.as<int32_t>() + 4 * (size_t)T; fa.cut_cap = cut_cap;
+    fa.cut_cap = cut_cap;
     static const bool use_hint = []{ const char* e = getenv("GS_FWD_ORDER_HINT"); return !(e && e[0] == '0'); }();
     fa.order_hint = (use_hint && c->order_hint_T == T && T > 0) ? c->order_hint.as<int32_t>() : nullptr;
     // tile ranges are all zero when K == 0, so the kernel writes the "no contributor" values itself
     gs_launch_blend_fwd(fa, s);
-    HIP_TRY_F(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     f->depth_bits = depth_bits;
     f->key64 = key64;
     f->info.sort_key_bits = depth_bits + tile_bits;
@@ -532,61 +605,49 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
 // capacity, or depth codes wider than the key field), grows the buffers and queues the per-pixel half again with the exact
 // sizes before the call returns (GS_SIZING_REDONE; the caller's outputs are simply written a second time, in stream order).
 // The first frame of a ctx, a new image size and GS_PREDICT_SIZES=0 take the exact path: wait, then queue (GS_SIZING_EXACT).
-static int run_forward_tail(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_t n_rows, int M_known, int32_t ticket,
-                            int H, int W, int tiles_x, int T, const gs_config* cfg, const gs_forward_out* out, hipStream_t s,
-                            int* M_out, uint32_t* K_out)
+static int run_forward_tail(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_t n_rows, int M_known, const gs_config* cfg,
+                            const gs_forward_out* out, hipStream_t s, int* M_out, uint32_t* K_out)
 {
     static const bool predict = []{ const char* e = getenv("GS_PREDICT_SIZES"); return !(e && e[0] == '0'); }();
-    int rc, M = 0, max_code = 0; uint32_t K = 0;
+    const int T = f->info.n_tiles, H = f->info.camera_height, W = f->info.camera_width;
+    int rc;
     f->info.sizing = GS_SIZING_EXACT;
-    if (n_rows == 0) {                                     // nothing was published: an empty frame
-        if ((rc = run_raster_stage(c, f, pa, 0, 0, 0u, 1, H, W, tiles_x, T, cfg, out, s, false)) != GS_OK) return rc;
-        *M_out = 0; *K_out = 0u;
-        return GS_OK;
-    }
+    *M_out = 0; *K_out = 0u;
+    if (n_rows == 0)                                       // nothing was published: an empty frame
+        return run_raster_stage(c, f, pa, 0, 0, 0u, 1, cfg, out, s, false);
     const int tile_bits = bits_for((uint32_t)(T > 1 ? T - 1 : 1));
+    bool predicted = false;
+    int bits_p = 0; uint32_t K_p = 0;
     if (predict && c->seen.valid && c->seen.H == H && c->seen.W == W) {
-        const int bits_p = bits_for((uint32_t)(c->seen.max_code + c->seen.max_code / 4));
+        bits_p = bits_for((uint32_t)(c->seen.max_code + c->seen.max_code / 4));
         const uint64_t want = (uint64_t)c->seen.K + c->seen.K / 4 + 4096;      // buffers grow to this if they have to (once)
-        const uint32_t K_p = (uint32_t)std::min<uint64_t>(want, 0x7fffffffu);
-        if (K_p > 0 && bits_p + tile_bits <= 63) {
-            if ((rc = run_raster_stage(c, f, pa, n_rows, M_known >= 0 ? M_known : (int)n_rows, K_p, bits_p, H, W, tiles_x, T, cfg, out, s, true)) != GS_OK) return rc;
-            if ((rc = read_counters(c, f, s, ticket, &M, &K, &max_code)) != GS_OK) return rc;
-            if (K >= (1u << 31)) { drop_frame(c, f); return fail(GS_ERR_INVALID_ARGUMENT, "more than 2^31 sort pairs (tile ranges are int32, RAST:954-957)"); }
-            const int bits = bits_for((uint32_t)(max_code > 0 ? max_code : 0));
-            if (K <= K_p && bits <= bits_p) {
-                f->info.sizing = GS_SIZING_PREDICTED;
-            } else {
-                // the per-pixel half ran on sizes that did not hold: its results are void (not out of bounds).  Again, exactly.
-                HIP_TRY_F(hipMemsetAsync(pa.tile_arrays, 0, sizeof(int32_t) * (size_t)pa.tile_ints, s));
-                f->max_tiles_known = false;                 // (k_project's word went with them: the backward's row sum then looks for giant points itself)
-                if ((rc = run_raster_stage(c, f, pa, n_rows, M, K, bits, H, W, tiles_x, T, cfg, out, s, false)) != GS_OK) return rc;
-                f->info.sizing = GS_SIZING_REDONE;
-            }
-            c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = K; c->seen.max_code = max_code;
-            *M_out = M; *K_out = K;
-            return GS_OK;
-        }
+        K_p = (uint32_t)std::min<uint64_t>(want, 0x7fffffffu);
+        predicted = K_p > 0 && bits_p + tile_bits <= 63;
     }
-    gs_launch_publish(pa, (int)((n_rows + 255) / 256), s);            // exact sizing: the hand-over is a launch of its own, and the host waits for it here
-    HIP_TRY_F(hipGetLastError());
-    if ((rc = read_counters(c, f, s, ticket, &M, &K, &max_code)) != GS_OK) return rc;
-    if (K >= (1u << 31)) { drop_frame(c, f); return fail(GS_ERR_INVALID_ARGUMENT, "more than 2^31 sort pairs (tile ranges are int32, RAST:954-957)"); }
-    if ((rc = run_raster_stage(c, f, pa, n_rows, M, K, bits_for((uint32_t)(max_code > 0 ? max_code : 0)), H, W, tiles_x, T, cfg, out, s, false)) != GS_OK) return rc;
-    c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = K; c->seen.max_code = max_code;
-    *M_out = M; *K_out = K;
+    if (predicted) {
+        if ((rc = run_raster_stage(c, f, pa, n_rows, M_known >= 0 ? M_known : (int)n_rows, K_p, bits_p, cfg, out, s, true)) != GS_OK) return rc;
+    } else {
+        gs_launch_publish(pa, (int)((n_rows + 255) / 256), s);            // exact sizing: the hand-over is a launch of its own, and the host waits for it here
+        HIP_TRY(hipGetLastError());
+    }
+    GsCounters hc;
+    if ((rc = read_counters(c, s, pa.ticket, 0, &hc)) != GS_OK) return rc;
+    if (hc.K >= (1u << 31)) return fail(GS_ERR_INVALID_ARGUMENT, "more than 2^31 sort pairs (tile ranges are int32, RAST:954-957)");
+    const int bits = bits_for((uint32_t)(hc.max_depth_code > 0 ? hc.max_depth_code : 0));
+    if (predicted && hc.K <= K_p && bits <= bits_p) {
+        f->info.sizing = GS_SIZING_PREDICTED;
+    } else {
+        if (predicted) {
+            // the per-pixel half ran on sizes that did not hold: its results are void (not out of bounds).  Again, exactly.
+            HIP_TRY(hipMemsetAsync(pa.v.tile_start, 0, sizeof(int32_t) * (size_t)pa.v.tile_ints, s));
+            f->max_tiles_known = false;                 // (k_project's word went with them: the backward's row sum then looks for giant points itself)
+            f->info.sizing = GS_SIZING_REDONE;
+        }
+        if ((rc = run_raster_stage(c, f, pa, n_rows, hc.M, hc.K, bits, cfg, out, s, false)) != GS_OK) return rc;
+    }
+    c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = hc.K; c->seen.max_code = hc.max_depth_code;
+    *M_out = hc.M; *K_out = hc.K;
     return GS_OK;
-}
-
-static void finish_frame(gs_ctx* c, Frame* f, int slot, int64_t N, int M, uint32_t K, int T, int H, int W, int keep, int stages,
-                         gs_frame** frame_out)
-{
-    f->info.n_points = N; f->info.n_points_in_camera = M; f->info.n_keys = K; f->info.n_tiles = T;
-    f->info.camera_height = H; f->info.camera_width = W;
-    f->info.kept_for_backward = keep ? 1 : 0;
-    f->info.stages = stages;
-    if (!keep) c->transient = slot;
-    *frame_out = ticket_of(slot, f->generation);
 }
 
 extern "C" int gs_forward(gs_ctx* c, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
@@ -598,22 +659,25 @@ extern "C" int gs_forward(gs_ctx* c, const gs_scene* sc, const gs_camera* cam, c
     if ((rc = check_scene(sc, cam, "gs_forward")) != GS_OK) return rc;
     if ((rc = check_forward_out(out, cfg, keep, "gs_forward")) != GS_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
-    if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     int slot = -1;
-    Frame* f = acquire_frame(c, &slot);
-    f->bufs = acquire_bufs(c);
-    f->info = gs_frame_info{};
-    f->info.kept_for_backward = keep ? 1 : 0;      // (known before the stages run: a kept frame gets list cuts for its backward)
-    const int T = tiles_x * tiles_y;
+    Frame* f = begin_frame(c, cam, tiles_x * tiles_y, keep, &slot);
     GsProjectArgs pa{};
-    int M = 0, max_code = 0; uint32_t K = 0;
-    if ((rc = run_project_stage(c, f, sc, cam, cfg, T, s, &pa, &M, &K, &max_code, WAIT_LATER)) != GS_OK) return rc;
-    if ((rc = run_forward_tail(c, f, pa, sc->n_points, -1, pa.ticket, cam->camera_height, cam->camera_width, tiles_x, T, cfg, out, s, &M, &K)) != GS_OK) return rc;
+    int M = 0; uint32_t K = 0;
+    rc = run_project_stage(c, f, sc, cam, cfg, s, WAIT_LATER, &pa, &M, &K);
+    if (rc == GS_OK) rc = run_forward_tail(c, f, pa, sc->n_points, -1, cfg, out, s, &M, &K);
+    if (rc != GS_OK) { drop_frame(c, f); return rc; }
     f->bwd_reference_order = cfg->bwd_reference_order;
-    finish_frame(c, f, slot, sc->n_points, M, K, T, cam->camera_height, cam->camera_width, keep, GS_STAGE_PROJECT | GS_STAGE_RASTER, frame_out);
+    finish_frame(c, f, slot, sc->n_points, M, K, GS_STAGE_PROJECT | GS_STAGE_RASTER, frame_out);
+    return GS_OK;
+}
+
+// gs_project_shard: the frame's (M,16) record rows and ids, copied out
+static int copy_projection(const Frame* f, int M, float* records_out, int32_t* ids_out, hipStream_t s)
+{
+    HIP_TRY(hipMemcpyAsync(records_out, f->bufs.rec.p, (size_t)M * 64, hipMemcpyDeviceToDevice, s));
+    if (ids_out) HIP_TRY(hipMemcpyAsync(ids_out, f->bufs.ids.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
     return GS_OK;
 }
 
@@ -627,45 +691,16 @@ extern "C" int gs_project_shard(gs_ctx* c, const gs_scene* sc, const gs_camera* 
     if ((rc = check_geometry(cam, cfg, "gs_project_shard", &tiles_x, &tiles_y)) != GS_OK) return rc;
     if ((rc = check_scene(sc, cam, "gs_project_shard")) != GS_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
-    if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     int slot = -1;
-    Frame* f = acquire_frame(c, &slot);
-    f->bufs = acquire_bufs(c);
-    f->info = gs_frame_info{};
-    f->info.kept_for_backward = keep ? 1 : 0;      // (known before the stages run: a kept frame gets list cuts for its backward)
-    const int T = tiles_x * tiles_y;
+    Frame* f = begin_frame(c, cam, tiles_x * tiles_y, keep, &slot);
     GsProjectArgs pa{};
-    int M = 0, max_code = 0; uint32_t K = 0;
-    if ((rc = run_project_stage(c, f, sc, cam, cfg, T, s, &pa, &M, &K, &max_code)) != GS_OK) return rc;
-    static_assert(GS_RS == 4, "the staged entry points hand records over as (M,16) rows");
-    if (M > 0) {
-        HIP_TRY_F(hipMemcpyAsync(records_out, f->bufs->rec.p, (size_t)M * 64, hipMemcpyDeviceToDevice, s));
-        if (ids_out) HIP_TRY_F(hipMemcpyAsync(ids_out, f->bufs->ids.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
-    }
-    finish_frame(c, f, slot, sc->n_points, M, K, T, cam->camera_height, cam->camera_width, keep, GS_STAGE_PROJECT, frame_out);
-    return GS_OK;
-}
-
-// Reads the hand-over of a frame begun with gs_project_shard_begin (mutex held): M, K and the object-id verdict.
-static int resolve_pending(gs_ctx* c, Frame* f)
-{
-    if (!f || f->pending_slot <= 0) return GS_OK;
-    const int slot = f->pending_slot;
-    HIP_TRY(hipSetDevice(c->device));
-    const int rc = wait_counters(c, f->pending_stream, f->pending_ticket, slot);
-    const GsCounters hc = c->host_counters[slot];
-    c->slots_busy &= ~(1ull << slot);
-    f->pending_slot = -1;
+    int M = 0; uint32_t K = 0;
+    rc = run_project_stage(c, f, sc, cam, cfg, s, WAIT_NOW, &pa, &M, &K);
+    if (rc == GS_OK && M > 0) rc = copy_projection(f, M, records_out, ids_out, s);
     if (rc != GS_OK) { drop_frame(c, f); return rc; }
-    if (hc.bad_object_ids != 0) {
-        drop_frame(c, f);
-        return fail(GS_ERR_INVALID_ARGUMENT, "point_object_id holds " + std::to_string(hc.bad_object_ids) + " value(s) outside [0, n_objects) on valid rows");
-    }
-    f->info.n_points_in_camera = hc.M;
-    f->info.n_keys = hc.K;
+    finish_frame(c, f, slot, sc->n_points, M, K, GS_STAGE_PROJECT, frame_out);
     return GS_OK;
 }
 
@@ -677,20 +712,15 @@ extern "C" int gs_project_shard_begin(gs_ctx* c, const gs_scene* sc, const gs_ca
     if ((rc = check_geometry(cam, cfg, "gs_project_shard_begin", &tiles_x, &tiles_y)) != GS_OK) return rc;
     if ((rc = check_scene(sc, cam, "gs_project_shard_begin")) != GS_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
-    if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     int slot = -1;
-    Frame* f = acquire_frame(c, &slot);
-    f->bufs = acquire_bufs(c);
-    f->info = gs_frame_info{};
-    f->info.kept_for_backward = keep ? 1 : 0;      // (known before the stages run: a kept frame gets list cuts for its backward)
-    const int T = tiles_x * tiles_y;
+    Frame* f = begin_frame(c, cam, tiles_x * tiles_y, keep, &slot);
     GsProjectArgs pa{};
-    int M = 0, max_code = 0; uint32_t K = 0;
-    if ((rc = run_project_stage(c, f, sc, cam, cfg, T, s, &pa, &M, &K, &max_code, WAIT_FRAME)) != GS_OK) return rc;
-    finish_frame(c, f, slot, sc->n_points, M, K, T, cam->camera_height, cam->camera_width, keep, GS_STAGE_PROJECT, frame_out);
+    int M = 0; uint32_t K = 0;
+    rc = run_project_stage(c, f, sc, cam, cfg, s, WAIT_FRAME, &pa, &M, &K);
+    if (rc != GS_OK) { drop_frame(c, f); return rc; }
+    finish_frame(c, f, slot, sc->n_points, M, K, GS_STAGE_PROJECT, frame_out);
     return GS_OK;
 }
 
@@ -704,39 +734,17 @@ extern "C" int gs_forward_projected(gs_ctx* c, const float* records, int64_t m, 
     if ((rc = check_geometry(cam, cfg, "gs_forward_projected", &tiles_x, &tiles_y)) != GS_OK) return rc;
     if ((rc = check_forward_out(out, cfg, keep, "gs_forward_projected")) != GS_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
-    if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     int slot = -1;
-    Frame* f = acquire_frame(c, &slot);
-    f->bufs = acquire_bufs(c);
-    f->info = gs_frame_info{};
-    f->info.kept_for_backward = keep ? 1 : 0;      // (known before the stages run: a kept frame gets list cuts for its backward)
-    FrameBufs& B = *f->bufs;
-    const int T = tiles_x * tiles_y, H = cam->camera_height, W = cam->camera_width;
-    const size_t Mp = (size_t)(m > 0 ? m : 1);
-    const size_t nb = (size_t)((m + 255) / 256);
-    ENSURE(B.rec, 64 * Mp); ENSURE(B.box, 8 * Mp); ENSURE(B.ntiles, 4 * Mp); ENSURE(B.depth_codes, 4 * Mp); ENSURE(B.offsets, 4 * Mp);
-    ENSURE(B.tile_start, 4 * GS_TILE_INTS(T)); ENSURE(B.tile_order, 4 * GS_ORDER_INTS(T));
-    ENSURE(c->tile_block_sums, 4 * (nb + 1));
-    if (m > 0) HIP_TRY_F(hipMemcpyAsync(B.rec.p, records, (size_t)m * 64, hipMemcpyDeviceToDevice, s));   // the frame keeps its own copy for backward
+    Frame* f = begin_frame(c, cam, tiles_x * tiles_y, keep, &slot);
     GsProjectArgs pa{};
-    pa.prof = &c->prof; pa.N = m; pa.H = H; pa.W = W; pa.depth_scale = cfg->depth_to_sort_key_scale;
-    set_records(pa, B, Mp);
-    pa.box = B.box.as<ushort4>(); pa.ntiles = B.ntiles.as<int32_t>(); pa.depth_codes = B.depth_codes.as<int32_t>();
-    pa.tile_block_sums = c->tile_block_sums.as<uint32_t>();
-    pa.counters = c->counters.as<GsCounters>();
-    pa.tile_arrays = B.tile_start.as<int32_t>(); pa.tile_ints = (int)GS_TILE_INTS(T);
-    pa.host_mirror = c->host_counters_dev; pa.ticket = ++c->ticket;
-    if (c->ticket == 0x7fffffff) c->ticket = 0;
-    gs_launch_boxes_from_records(pa, (int)m, s, false);       // the counters are published from run_forward_tail
-    f->max_tiles_known = false;
-    HIP_TRY_F(hipGetLastError());
-    uint32_t K = 0; int M_seen = 0;
-    if ((rc = run_forward_tail(c, f, pa, m, (int)m, pa.ticket, H, W, tiles_x, T, cfg, out, s, &M_seen, &K)) != GS_OK) return rc;
+    int M_seen = 0; uint32_t K = 0;
+    rc = run_records_stage(c, f, records, m, cfg, s, &pa);
+    if (rc == GS_OK) rc = run_forward_tail(c, f, pa, m, (int)m, cfg, out, s, &M_seen, &K);
+    if (rc != GS_OK) { drop_frame(c, f); return rc; }
     f->bwd_reference_order = cfg->bwd_reference_order;
-    finish_frame(c, f, slot, m, (int)m, K, T, H, W, keep, GS_STAGE_RASTER, frame_out);
+    finish_frame(c, f, slot, m, (int)m, K, GS_STAGE_RASTER, frame_out);
     return GS_OK;
 }
 
@@ -744,9 +752,8 @@ extern "C" int gs_frame_get_info(gs_ctx* c, const gs_frame* h, gs_frame_info* in
 {
     if (!c || !info) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_get_info: NULL argument");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f) return fail(GS_ERR_STATE, "gs_frame_get_info: not a live frame of this context");
-    if (const int rc = resolve_pending(c, f)) return rc;
+    Frame* f;
+    if (const int rc = lookup(c, h, "gs_frame_get_info", true, &f)) return rc;
     *info = f->info;
     return GS_OK;
 }
@@ -779,45 +786,31 @@ extern "C" int64_t gs_frame_export_count(gs_ctx* c, const gs_frame* h, gs_export
     return f ? export_count(f, what) : -1;
 }
 
-static void set_records(GsBackwardArgs& a, const FrameBufs& B, size_t rows)
-{
-    const float4* rec = B.rec.as<float4>();
-    const size_t plane = GS_RS == 4 ? 1 : rows;
-    a.PA = rec; a.PB = rec + plane; a.PC = rec + 2 * plane; a.PD = rec + 3 * plane;
-}
-
 extern "C" int gs_frame_export(gs_ctx* c, const gs_frame* h, gs_export what, void* dst, gs_stream stream_)
 {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_export: ctx is NULL");
     if (!dst) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_export: dst is NULL");
     if (what < 0 || what >= GS_X_COUNT_) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_export: unknown export id");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_frame_export: not a live frame of this context");
-    if (const int rc = resolve_pending(c, f)) return rc;
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_frame_export", true, &f)) != GS_OK) return rc;
     if (export_count(f, what) < 0) return fail(GS_ERR_STATE, "gs_frame_export: this frame does not hold that stage");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
-    const FrameBufs& B = *f->bufs;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    const GsFrameView v = frame_view(*f);
     if (what == GS_X_RECORDS) {                  // the (M,16) rows as they are: what the owner of a shard sends to the renderers
-        static_assert(GS_RS == 4, "records are exported as (M,16) rows");
         if (f->info.n_points_in_camera > 0)
-            HIP_TRY(hipMemcpyAsync(dst, B.rec.p, (size_t)f->info.n_points_in_camera * 64, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(dst, v.PA, (size_t)f->info.n_points_in_camera * 64, hipMemcpyDeviceToDevice, s));
         return GS_OK;
     }
     GsExportArgs a{};
     a.what = (int)what; a.N = f->info.n_points; a.M = (int)f->info.n_points_in_camera; a.K = (uint32_t)f->info.n_keys;
-    a.T = f->info.n_tiles; a.depth_bits = f->depth_bits; a.key64 = f->key64;
-    a.ids = B.ids.as<int32_t>();
-    {
-        const float4* rec = B.rec.as<float4>();
-        const size_t plane = GS_RS == 4 ? 1 : (size_t)(f->info.n_points > 0 ? f->info.n_points : 1);
-        a.PA = rec; a.PB = rec + plane; a.PC = rec + 2 * plane; a.PD = rec + 3 * plane;
-    }
-    a.ntiles = B.ntiles.as<int32_t>(); a.offsets = B.offsets.as<uint32_t>();
-    a.keys_sorted = f->keys_sorted; a.vals_sorted = f->vals_sorted;
-    a.tile_start = B.tile_start.as<int32_t>(); a.tile_end = B.tile_start.as<int32_t>() + f->info.n_tiles; a.mask = B.mask.as<int8_t>();
+    a.T = v.T; a.depth_bits = f->depth_bits; a.key64 = f->key64;
+    a.ids = v.ids; a.PA = v.PA; a.PB = v.PB; a.PC = v.PC; a.PD = v.PD;
+    a.ntiles = v.ntiles; a.offsets = v.offsets;
+    a.keys_sorted = v.keys_sorted; a.vals_sorted = v.vals_sorted;
+    a.tile_start = v.tile_start; a.tile_end = v.tile_end; a.mask = v.mask;
     a.dst = dst;
     gs_launch_export(a, s);
     HIP_TRY(hipGetLastError());
@@ -869,25 +862,18 @@ static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_i
         if (c->order_hint.ensure(4 * (size_t)(f->info.n_tiles > 0 ? f->info.n_tiles : 1), &c->device_bytes) != hipSuccess)
             return fail(GS_ERR_OUT_OF_MEMORY, "backward: tile order buffer");
     }
-    const FrameBufs& B = *f->bufs;
     GsBackwardArgs a{};
     a.prof = &c->prof;
     a.order_hint = c->order_hint.as<int32_t>();
     a.N = f->info.n_points; a.M = (int)f->info.n_points_in_camera; a.K = K;
-    a.H = f->info.camera_height; a.W = f->info.camera_width; a.T = f->info.n_tiles;
+    a.H = f->info.camera_height; a.W = f->info.camera_width;
     a.tiles_x = (a.W + GS_TILE - 1) / GS_TILE;
-    a.tile_start = B.tile_start.as<int32_t>(); a.tile_end = B.tile_start.as<int32_t>() + f->info.n_tiles; a.vals_sorted = f->vals_sorted;
-    a.tile_work = B.tile_start.as<int32_t>() + 2 * (size_t)f->info.n_tiles; a.tile_order = B.tile_order.as<int32_t>();
-    set_records(a, B, (size_t)(f->info.n_points > 0 ? f->info.n_points : 1));
-    a.box = B.box.as<ushort4>(); a.offsets = B.offsets.as<uint32_t>(); a.ntiles = B.ntiles.as<int32_t>();
+    a.v = frame_view(*f);
     a.grad_image = grad_image; a.acc_alpha = acc_alpha; a.last = last;
     a.partial = c->partial.as<float>();
     a.visited = c->visited.as<uint8_t>();
     a.G = G;
-    a.n_heavy = B.tile_order.as<int32_t>() + f->info.n_tiles;
-    a.cuts = f->cut_cap > 0 ? B.cuts.as<float4>() : nullptr; a.cut_mag = B.cut_mag.as<float2>();
     a.item_cap = f->cut_cap;                          // >= the segments of all heavy tiles together (never binds: deterministic)
-    a.tile_cut = B.tile_start.as<int32_t>() + 3 * (size_t)f->info.n_tiles;
     // heavy-tile threshold in half-means of work: sharing a tile among four waves costs more work in total and shortens the launch
     // only where long walks are what the launch waits for; twice the mean measured best on both clustered workloads and changes
     // nothing on the uniform ones (max / mean = 2).  GS_BWD_HEAVY_X2 overrides; GS_BWD_SPLIT_HEAVY=0 = no heavy tiles.
@@ -898,7 +884,7 @@ static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_i
     a.gen = c->visit_gen;
     a.touched = c->visited.as<uint8_t>() + flag_bytes;
     a.zero_row = c->zero_row.as<float4>();
-    a.max_tiles_hint = f->max_tiles_known ? B.tile_start.as<int32_t>() + GS_TILE_INTS(f->info.n_tiles) - GS_TILE_SPARE_MAX_TILES : nullptr;
+    a.max_tiles_hint = f->max_tiles_known ? a.v.max_tiles : nullptr;
     a.sums = sums_out;
     a.mag_image = mag_image;
     *a_out = a;
@@ -908,14 +894,11 @@ static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_i
 static int prepare_backward_points(const Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
                                    int32_t sh_band, const gs_backward_out* out, const float4* sums, GsBackwardArgs* a)
 {
-    const FrameBufs& B = *f->bufs;
     a->N = f->info.n_points; a->M = (int)f->info.n_points_in_camera;
-    set_records(*a, B, (size_t)(f->info.n_points > 0 ? f->info.n_points : 1));
-    a->ntiles = B.ntiles.as<int32_t>();
-    a->ids = B.ids.as<int32_t>(); a->cam_index = B.cam_index.as<int32_t>();
+    a->v = frame_view(*f);
     a->sums = const_cast<float4*>(sums);
     a->point_cloud = sc->point_cloud; a->features = sc->point_cloud_features; a->object_id = sc->point_object_id;
-    a->Kmat = cam->camera_intrinsics; a->pose = B.pose.as<GsPose>();
+    a->Kmat = cam->camera_intrinsics;
     a->sh_band = sh_band; a->f_color = cfg->grad_color_factor; a->f_high = cfg->grad_high_order_color_factor;
     a->f_s = cfg->grad_s_factor; a->f_q = cfg->grad_q_factor; a->f_alpha = cfg->grad_alpha_factor;
     a->grad_pc = out->grad_pointcloud; a->grad_feat = out->grad_pointcloud_features; a->grad_uv = out->grad_viewspace;
@@ -934,6 +917,13 @@ static int prepare_backward_points(const Frame* f, const gs_scene* sc, const gs_
         a->c_pos_grad = ca->accumulated_position_gradients; a->c_pos_grad_norm = ca->accumulated_position_gradients_norm;
     }
     return GS_OK;
+}
+
+// The blend half of a backward (tile order, blend backward, per-splat sums); the tile order it writes is the next forward's hint.
+static void launch_backward_blend(gs_ctx* c, const GsBackwardArgs& a, hipStream_t s)
+{
+    gs_launch_backward_blend(a, s);
+    if (a.v.T > 0 && a.K > 0) c->order_hint_T = a.v.T;      // k_tile_order ran: the hint is a complete permutation
 }
 
 static int check_backward_points_args(const Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_backward_out* out, const char* who,
@@ -958,8 +948,9 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
     if (!c || !sc || !cam || !cfg || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: NULL argument");
     if (!grad_image || !acc_alpha || !last) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: NULL image-sized input");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_backward: not a live frame of this context");
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_backward", false, &f)) != GS_OK) return rc;
     if (!f->info.kept_for_backward) return fail(GS_ERR_STATE, "gs_backward: frame was not kept for backward");
     if (f->info.stages != (GS_STAGE_PROJECT | GS_STAGE_RASTER)) return fail(GS_ERR_STATE, "gs_backward: frame does not come from gs_forward");
     // pose gradient: both pointers or neither; with them, the two point gradients may be left out (pose-only backward)
@@ -969,11 +960,9 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
     const bool points = !pose || out->grad_pointcloud || out->grad_pointcloud_features;
     if (pose && cam->n_objects != f->n_objects)
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward: camera n_objects does not match the frame's forward");
-    int rc;
     if ((rc = check_backward_points_args(f, sc, cam, out, "gs_backward", !points)) != GS_OK) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     if (c->sums.ensure((size_t)(f->info.n_points_in_camera > 0 ? f->info.n_points_in_camera : 1) * 48, &c->device_bytes) != hipSuccess)
         return fail(GS_ERR_OUT_OF_MEMORY, "gs_backward: per-point sums buffer");
     if (pose && c->pose_scratch.ensure(gs_pose_scratch_size((int)f->info.n_points_in_camera, f->n_objects), &c->device_bytes) != hipSuccess)
@@ -985,10 +974,9 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
         a.grad_depth = extra->grad_rasterized_depth; a.depth = extra->rasterized_depth;
         a.grad_alpha = extra->grad_pixel_accumulated_alpha;
         a.aux = 1;
-        a.cuts = nullptr;
+        a.v.cuts = nullptr;
     }
-    gs_launch_backward_blend(a, s);
-    if (a.T > 0 && a.K > 0) c->order_hint_T = a.T;          // k_tile_order ran: the hint is a complete permutation
+    launch_backward_blend(c, a, s);
     if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics
     if (pose) gs_launch_pose_grad(a, f->n_objects, c->pose_scratch.p, out->grad_q_pointcloud_camera, out->grad_t_pointcloud_camera, s);
     HIP_TRY(hipGetLastError());
@@ -1019,19 +1007,17 @@ extern "C" int gs_backward_projected(gs_ctx* c, gs_frame* h, const float* grad_i
     if (!grad_image || !acc_alpha || !last) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_projected: NULL image-sized input");
     if (((uintptr_t)splat_sums_out & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_projected: splat_sums_out must be 16-byte aligned");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_backward_projected: not a live frame of this context");
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_backward_projected", false, &f)) != GS_OK) return rc;
     if (!f->info.kept_for_backward) return fail(GS_ERR_STATE, "gs_backward_projected: frame was not kept for backward");
     if (!(f->info.stages & GS_STAGE_RASTER)) return fail(GS_ERR_STATE, "gs_backward_projected: frame holds no raster stage");
     if (f->info.n_points_in_camera > 0 && !splat_sums_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_projected: splat_sums_out is NULL");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     GsBackwardArgs a{};
-    int rc;
     if ((rc = prepare_backward_blend(c, f, grad_image, acc_alpha, last, mag_image, reinterpret_cast<float4*>(splat_sums_out), f->bwd_reference_order, s, &a)) != GS_OK) return rc;
-    gs_launch_backward_blend(a, s);
-    if (a.T > 0 && a.K > 0) c->order_hint_T = a.T;          // k_tile_order ran: the hint is a complete permutation
+    launch_backward_blend(c, a, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1042,20 +1028,18 @@ extern "C" int gs_backward_shard(gs_ctx* c, gs_frame* h, const gs_scene* sc, con
     if (!c || !sc || !cam || !cfg || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: NULL argument");
     if (((uintptr_t)splat_sums & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: splat_sums must be 16-byte aligned");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_backward_shard: not a live frame of this context");
-    if (const int rp = resolve_pending(c, f)) return rp;
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_backward_shard", true, &f)) != GS_OK) return rc;
     if (!f->info.kept_for_backward) return fail(GS_ERR_STATE, "gs_backward_shard: frame was not kept for backward");
     if (!(f->info.stages & GS_STAGE_PROJECT)) return fail(GS_ERR_STATE, "gs_backward_shard: frame holds no projection stage");
     if (f->info.n_points_in_camera > 0 && !splat_sums) return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: splat_sums is NULL");
     if (out->grad_q_pointcloud_camera || out->grad_t_pointcloud_camera)
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_backward_shard: pose gradients are not available on the staged (Gaussian-parallel) path; "
                                              "use gs_backward");
-    int rc;
     if ((rc = check_backward_points_args(f, sc, cam, out, "gs_backward_shard")) != GS_OK) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     GsBackwardArgs a{};
     a.prof = &c->prof;
     if ((rc = prepare_backward_points(f, sc, cam, cfg, sh_band, out, reinterpret_cast<const float4*>(splat_sums), &a)) != GS_OK) return rc;
@@ -1084,12 +1068,12 @@ extern "C" int gs_loss_l1_ssim_forward(gs_ctx* c, const gs_loss_image* pred, con
     if (!c || !maps || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_forward: NULL argument");
     if (int rc = loss_check("gs_loss_l1_ssim_forward", pred, gt, H, W)) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
     hipError_t e = c->loss_ws.ensure(gs_loss_partials_floats(H, W) * sizeof(float), &c->device_bytes);
     if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim_forward: workspace");
-    HIP_TRY(enter_stream(c, reinterpret_cast<hipStream_t>(stream_)));
-    gs_launch_loss_forward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, c->loss_ws.as<float>(), loss_terms,
-                           reinterpret_cast<hipStream_t>(stream_));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_loss_forward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, c->loss_ws.as<float>(), loss_terms, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1101,10 +1085,9 @@ extern "C" int gs_loss_l1_ssim_backward(gs_ctx* c, const gs_loss_image* pred, co
     if (!c || !maps || !grad_pred || !grad_pred->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_backward: NULL argument");
     if (int rc = loss_check("gs_loss_l1_ssim_backward", pred, gt, H, W)) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, reinterpret_cast<hipStream_t>(stream_)));
-    gs_launch_loss_backward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, upstream, loss_image(grad_pred, 0),
-                            reinterpret_cast<hipStream_t>(stream_));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_loss_backward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, upstream, loss_image(grad_pred, 0), s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1116,12 +1099,12 @@ extern "C" int gs_loss_l1_ssim(gs_ctx* c, const float* pred, const float* gt, in
     if (!c || !pred || !gt || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim: NULL argument");
     if (H < 11 || W < 11) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim: image smaller than the 11x11 SSIM window");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
     const size_t maps_floats = gs_loss_maps_size(H, W);
     hipError_t e = c->loss_ws.ensure((maps_floats + gs_loss_partials_floats(H, W)) * sizeof(float), &c->device_bytes);
     if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim: workspace");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
     GsLossImage X{ pred, (long long)H * W, (long long)W, 1, 0 }, Y{ gt, (long long)H * W, (long long)W, 1, 0 };
     float* maps = c->loss_ws.as<float>();
     gs_launch_loss_forward(X, Y, H, W, lambda_value, maps, maps + maps_floats, loss_terms, s);
@@ -1138,11 +1121,12 @@ extern "C" int gs_scale_regulariser(gs_ctx* c, const float* feat, const int8_t* 
     if (!c || !out || (n > 0 && (!feat || !mask))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser: NULL argument");
     if (n < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser: n_points < 0");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
     hipError_t e = c->loss_ws.ensure((size_t)(2 * ((n + 255) / 256) + 16) * sizeof(float), &c->device_bytes);
     if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_scale_regulariser: workspace");
-    HIP_TRY(enter_stream(c, reinterpret_cast<hipStream_t>(stream_)));
-    gs_launch_reg_value(feat, mask, n, c->loss_ws.as<float>(), out, reinterpret_cast<hipStream_t>(stream_));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_reg_value(feat, mask, n, c->loss_ws.as<float>(), out, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1154,9 +1138,9 @@ extern "C" int gs_scale_regulariser_grad(gs_ctx* c, const float* feat, const int
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser_grad: NULL argument");
     if (grad && ((uintptr_t)grad & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser_grad: grad must be 16-byte aligned");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, reinterpret_cast<hipStream_t>(stream_)));
-    gs_launch_reg_grad(feat, mask, n, value_and_count, upstream, grad, reinterpret_cast<hipStream_t>(stream_));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_reg_grad(feat, mask, n, value_and_count, upstream, grad, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1167,9 +1151,9 @@ extern "C" int gs_adam_step(gs_ctx* c, float* param, const float* grad, float* e
     if (!c || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step: NULL argument");
     if (n < 0 || step < 1) return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step: n must be >= 0 and step >= 1");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, reinterpret_cast<hipStream_t>(stream_)));
-    gs_launch_adam(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, reinterpret_cast<hipStream_t>(stream_));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_adam(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1178,13 +1162,13 @@ extern "C" int gs_frame_heavy_tiles(gs_ctx* c, const gs_frame* h, int32_t* n_out
 {
     if (!c || !n_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_heavy_tiles: NULL argument");
     std::lock_guard<std::mutex> lock(c->mu);
-    Frame* f = resolve(c, h);
-    if (!f || !f->bufs) return fail(GS_ERR_STATE, "gs_frame_heavy_tiles: not a live frame of this context");
-    if (!(f->info.stages & GS_STAGE_RASTER) || f->info.n_tiles <= 0 || f->info.n_keys <= 0 || !f->bufs->tile_order.p) { n_out[0] = n_out[1] = 0; return GS_OK; }
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
-    HIP_TRY(hipMemcpyAsync(n_out, f->bufs->tile_order.as<int32_t>() + f->info.n_tiles, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_frame_heavy_tiles", false, &f)) != GS_OK) return rc;
+    if (!(f->info.stages & GS_STAGE_RASTER) || f->info.n_tiles <= 0 || f->info.n_keys <= 0 || !f->bufs.tile_order.p) { n_out[0] = n_out[1] = 0; return GS_OK; }
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(n_out, frame_view(*f).n_heavy, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return GS_OK;
 }
@@ -1229,9 +1213,8 @@ extern "C" int gs_density_select(gs_ctx* c, const gs_scene* scene, const gs_cont
                   !acc->accumulated_position_gradients_norm))
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: the controller accumulators must all be given");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_density_select(*scene, *acc, ids, npix, depth, mag, M, remove_floaters != 0, *cfg, *plan, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
@@ -1246,9 +1229,8 @@ extern "C" int gs_density_apply(gs_ctx* c, const gs_density_scene* scene, const 
     if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask || !scene->point_object_id))
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_apply: NULL scene array");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_density_apply(*scene, *cfg, *plan, seed, call_index, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
@@ -1265,9 +1247,8 @@ extern "C" int gs_controller_accumulate(gs_ctx* c, const int32_t* ids, const int
                   !acc->accumulated_position_gradients_norm))
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: the controller accumulators must all be given");
     std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(enter_stream(c, s));
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_controller_accumulate(ids, npix, mag, gpc, M, N, *acc, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;

@@ -30,14 +30,11 @@ extern __device__ unsigned long long gs_stats_wave_times[2 * 65536];   // start,
 #define GS_STAT(i, n) do { } while (0)
 #endif
 // Projected splat records: four float4 per in-camera point -- A {u, v, conic a, conic b}, B {conic c, rescale, opacity, depth},
-// C {r, g, b, log-domain alpha cut}, D {x, y, z in camera, radius} -- kept as ONE 64-byte row per point (GS_RS = 4: the
-// pointers PA..PD are rec, rec+1, rec+2, rec+3), so that the blend kernels' gather by sorted index touches one
-// 64-byte segment per splat instead of three cache lines, and so that a shard's records are one contiguous
-// (M,16) float array for the Gaussian-parallel exchange.  GS_RS = 1 selects four separate planes (A/B measurement).
-#ifndef GS_RS
-#define GS_RS 4
-#endif
-#define GS_REC(ptr, i) (ptr)[(size_t)(i) * GS_RS]
+// C {r, g, b, log-domain alpha cut}, D {x, y, z in camera, radius} -- kept as ONE 64-byte row per point (the pointers PA..PD
+// are rec, rec+1, rec+2, rec+3), so that the blend kernels' gather by sorted index touches one 64-byte segment per splat
+// instead of three cache lines, and so that a shard's records are one contiguous (M,16) float array for the Gaussian-parallel
+// exchange.  (Four separate planes measured no faster: DESIGN.md, row f-3.)
+#define GS_REC(ptr, i) (ptr)[(size_t)(i) * 4]
 #define GS_BOUNDARY_TILES 3          // reference RAST:26
 #define GS_ALPHA_EPS 0.00392156862745098f   // 1./255. (RAST:451, RAST:634)
 #define GS_ALPHA_MAX 0.99f           // RAST:453
@@ -317,16 +314,35 @@ void gs_prof_end(GsProf* p, int rec, hipStream_t s);
     } while (0)
 
 // ---- host-side launch wrappers (implemented in the k_*.hip files) --------------
+// A frame's device buffers, sliced into what its kernels read and write (gs_api.hip: frame_view, the one place that knows how
+// they are laid out).
+struct GsFrameView {
+    float4 *PA, *PB, *PC, *PD;                  // record rows A..D of each point (GS_REC)
+    ushort4* box; int32_t* ntiles;
+    int32_t* depth_codes;                       // (M) i32(depth * scale) per in-camera point, for the key build
+    uint32_t* offsets;                          // (M) exclusive scan of ntiles, written by keygen
+    int32_t* ids; int32_t* cam_index; int8_t* mask; GsPose* pose;
+    int T;
+    // the tile arrays, cleared together by the frame's first kernel (tile_ints ints from tile_start on)
+    int32_t *tile_start, *tile_end;             // written by the forward blend (each tile's block finds its range in the sorted keys)
+    int32_t* tile_work;                         // (T) max over the tile's pixels of last - start (k_blend_fwd)
+    int32_t* tile_cut; int32_t* cut_alloc;      // (T) first cut record of each tile + 1, 0 = none; unused claim counter
+    int32_t* max_tiles;                         // the frame's largest tile count of one point (k_project -> k_sum_rows)
+    int tile_ints;
+    int32_t* tile_order;                        // (T) scheduling: heaviest tiles first (k_tile_order)
+    int32_t* n_heavy;                           // number of heavy tiles at the head of tile_order (k_tile_order -> k_blend_bwd_tile); n_items and item_base follow it
+    const void* keys_sorted; const int32_t* vals_sorted;   // the sorted pairs: whichever of the ping-pong buffers holds them
+    float4* cuts; float2* cut_mag;              // list cuts of the forward (NULL: none), per-segment |d uv| partial sums
+};
+
 struct GsProjectArgs {
     GsProf* prof;
     const float* point_cloud; float* features; const int8_t* invalid; const int32_t* object_id;
     int64_t N; const float* q_pc; const float* t_pc; int n_objects; const float* Kmat;
     int H, W; float near_plane, far_plane, depth_scale;
-    GsPose* pose; int8_t* mask; int32_t* block_counts; int32_t* block_offsets; int32_t* ids; int32_t* cam_index;
-    float4 *PA, *PB, *PC, *PD; ushort4* box; int32_t* ntiles; uint32_t* tile_block_sums;
-    int32_t* depth_codes;                       // (M) i32(depth * scale) per in-camera point, for the key build
+    GsFrameView v;                              // written: pose, mask, ids, cam_index, records, box, ntiles, depth codes; tile arrays cleared before the binning
+    int32_t* block_counts; int32_t* block_offsets; uint32_t* tile_block_sums;
     GsCounters* counters;
-    int32_t* tile_arrays; int tile_ints;        // tile_start | tile_end | tile_work, cleared before the binning
     GsCounters* host_mirror; int32_t ticket;    // pinned host copy of the counters; .reserved = ticket once they are valid
 };
 void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish);
@@ -340,16 +356,15 @@ struct GsBinArgs {
     // M and K are BOUNDS here: the per-pixel half may be queued before the host has read the frame's counters (gs_api.hip,
     // "predicted sizing").  M bounds the in-camera offsets (N rows when unknown); K is the pair capacity the launch geometry and
     // the buffers were sized for -- every kernel works on min(counters->K, K) pairs, read on the device.
-    int64_t N; int M; uint32_t K; const GsCounters* counters; int H, W, tiles_x; float depth_scale; int depth_bits; int key_bits;
-    const float4 *PA, *PB; const ushort4* box; const int32_t* ntiles; const int32_t* depth_codes; const uint32_t* tile_block_sums;
+    int64_t N; int M; uint32_t K; const GsCounters* counters; int tiles_x; float depth_scale; int depth_bits; int key_bits;
+    GsFrameView v;                              // read: box, ntiles, depth codes; written: offsets
+    const uint32_t* tile_block_sums;
     GsCounters* counters_rw; GsCounters* host_mirror; int32_t ticket;   // host_mirror != NULL: the last k_keygen block publishes the frame counters
     const int32_t *block_offsets, *block_counts;   // k_project's blocks (first in-camera offset, count); NULL: 256 consecutive records per block
-    uint32_t* offsets;                          // (M) exclusive scan of ntiles, written by keygen
     void *keys_a, *keys_b; int32_t *vals_a, *vals_b;       // ping-pong (K); keys are u32, or u64 when key64
     int key64;                                             // depth bits + tile bits > 32
     uint32_t* hist;                             // (256 * sort_blocks) + scratch
     uint32_t* scan_tmp;                         // 256 digit totals of the current pass
-    int32_t *tile_start, *tile_end; int T;
     void** keys_sorted; int32_t** vals_sorted;       // out: which of a/b holds the result
 };
 void gs_launch_binning(const GsBinArgs& a, hipStream_t s);
@@ -358,33 +373,25 @@ size_t gs_scan_tmp_elems(size_t n);
 
 struct GsBlendFwdArgs {
     GsProf* prof;
-    int H, W, tiles_x, T; int rgb_only;
-    int32_t *tile_start, *tile_end;      // written by the blend kernel itself (each tile's block finds its range in the sorted keys)
-    const void* keys_sorted; int key64, depth_bits; uint32_t K; const GsCounters* counters;   // min(counters->K, K) pairs (see GsBinArgs)
-    const int32_t* vals_sorted;
-    const float4 *PA, *PB, *PC;
+    int H, W, tiles_x; int rgb_only;
+    GsFrameView v;                 // read: sorted pairs, records; written: tile ranges, tile_work, list cuts for the backward (v.cuts NULL: none wanted)
+    int key64, depth_bits; uint32_t K; const GsCounters* counters;   // min(counters->K, K) pairs (see GsBinArgs)
     float* image; float* depth; float* acc_alpha; int32_t* last; int32_t* count;
-    int32_t* tile_work;            // (T) zeroed together with the tile ranges; max over the tile's pixels of last - start
-    float4* cuts; int32_t* tile_cut; int32_t* cut_alloc; int cut_cap;    // list cuts for the backward (cut_cap == 0: none wanted)
+    int cut_cap;
     const int32_t* order_hint;     // (T) or NULL: a permutation of the tiles, heaviest first, from an earlier frame of this ctx (scheduling only)
 };
 void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s);
 
 struct GsBackwardArgs {
     GsProf* prof;
-    int64_t N; int M; uint32_t K; int H, W, tiles_x, T;
-    const int32_t *tile_start, *tile_end; const int32_t* vals_sorted;
-    const int32_t* tile_work; int32_t* tile_order;   // scheduling: heaviest tiles first
+    int64_t N; int M; uint32_t K; int H, W, tiles_x;
+    GsFrameView v;                                   // the frame's records, pairs, tile arrays, tile order and cuts
     int32_t* order_hint;                             // (T) or NULL: a second copy of tile_order that outlives the frame (the next forward's dispatch order)
-    const float4 *PA, *PB, *PC, *PD; const ushort4* box; const uint32_t* offsets; const int32_t* ntiles;
-    const int32_t* ids; const int32_t* cam_index;
     const float* grad_image; const float* acc_alpha; const int32_t* last;
     // gs_backward_ex: upstream gradients of rasterized_depth (with the forward's depth) and of pixel_accumulated_alpha, (H,W) or
-    // NULL; aux = 1 selects the AUX kernels (k_blend_bwd_tile, k_sum_rows, k_bwd_points, k_pose_points) and requires cuts = NULL
+    // NULL; aux = 1 selects the AUX kernels (k_blend_bwd_tile, k_sum_rows, k_bwd_points, k_pose_points) and requires v.cuts = NULL
     const float* grad_depth; const float* depth; const float* grad_alpha; int aux;
     int G;                         // waves per tile in k_blend_bwd_tile (1, 2 or 4) = rows of `partial` per (point, tile) pair
-    int32_t* n_heavy;               // device: number of heavy tiles at the head of tile_order (k_tile_order -> k_blend_bwd_tile); n_items and item_base follow it
-    const float4* cuts; float2* cut_mag; const int32_t* tile_cut;    // list cuts of the forward (NULL: none), per-segment |d uv| partial sums
     int item_cap;                   // work items of heavy tiles the launch has room for when there are cuts
     int heavy_factor_x2;            // a tile is heavy from this many half-means of work on; 0: no tile is (GS_BWD_SPLIT_HEAVY=0)
     int strict;                     // gs_config.bwd_reference_order: loop 1's UTIL:331-348 in the reference's own operation order
@@ -393,9 +400,9 @@ struct GsBackwardArgs {
     uint8_t gen;                    // this backward's tag (1..255): flags are never cleared per backward, a stale one just does not match
     uint8_t* touched;               // (M) == gen where some pixel took a contribution from the point
     const float4* zero_row;         // that row
-    const int32_t* max_tiles_hint;  // device: the frame's largest tile count of one point (k_project), or NULL when nobody computed it
+    const int32_t* max_tiles_hint;  // device: v.max_tiles when k_project computed it, or NULL
     float4* sums;                   // (M,3) per-point sums of the visited rows (count as int32 bits in [10])
-    const float* point_cloud; const float* features; const int32_t* object_id; const float* Kmat; const GsPose* pose;
+    const float* point_cloud; const float* features; const int32_t* object_id; const float* Kmat;
     int sh_band; float f_color, f_high, f_s, f_q, f_alpha;
     float* grad_pc; float* grad_feat; float* grad_uv; float* mag; float* mag_image; int32_t* n_affected;
     float* hook_gpc; float* hook_gfeat; float* hook_guv; float* hook_mag;
@@ -409,6 +416,7 @@ void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s);    // a.
 size_t gs_pose_scratch_size(int M, int n_objects);
 void gs_launch_pose_grad(const GsBackwardArgs& a, int n_objects, void* scratch, float* grad_q, float* grad_t, hipStream_t s);
 
+// the argument of k_export, passed by value
 struct GsExportArgs { int what; int64_t N; int M; uint32_t K; int T; int depth_bits; int key64;
     const int32_t* ids; const float4 *PA, *PB, *PC, *PD; const int32_t* ntiles; const uint32_t* offsets;
     const void* keys_sorted; const int32_t* vals_sorted; const int32_t *tile_start, *tile_end; const int8_t* mask; void* dst; };

@@ -1155,28 +1155,29 @@ __global__ __launch_bounds__(256) void k_bwd_points(
 
 void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
 {
-    // (a.aux: the caller has set a.cuts = NULL -- the depth / alpha backward walks every heavy tile whole, see k_blend_bwd_tile)
+    const GsFrameView& v = a.v;
+    // (a.aux: the caller has set v.cuts = NULL -- the depth / alpha backward walks every heavy tile whole, see k_blend_bwd_tile)
     const BwdAux aux{a.grad_depth, a.depth, a.grad_alpha};
-    if (a.T > 0 && a.K > 0) {
+    if (v.T > 0 && a.K > 0) {
         // (the `visited` / `touched` flags are not cleared per backward: a flag counts only if it holds THIS backward's tag, a.gen)
-        GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(a.tile_work, a.T, a.tile_order, a.order_hint, a.n_heavy, a.heavy_factor_x2,
-                                                                              a.tile_start, a.tile_end, a.cuts ? a.tile_cut : nullptr, a.cuts ? a.item_cap : gs_heavy_cap(a.T)));
+        GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(v.tile_work, v.T, v.tile_order, a.order_hint, v.n_heavy, a.heavy_factor_x2,
+                                                                              v.tile_start, v.tile_end, v.cuts ? v.tile_cut : nullptr, v.cuts ? a.item_cap : gs_heavy_cap(v.T)));
         // workgroups: room for every segment of every heavy tile (no cuts: one item per heavy tile) + the ordinary work items four to a workgroup
-        const unsigned groups = (unsigned)(a.cuts ? a.item_cap : gs_heavy_cap(a.T)) + (unsigned)(((size_t)a.T * (size_t)a.G + 3) / 4);
+        const unsigned groups = (unsigned)(v.cuts ? a.item_cap : gs_heavy_cap(v.T)) + (unsigned)(((size_t)v.T * (size_t)a.G + 3) / 4);
 #define GS_BWD_LAUNCH_(NQ_, STRICT_, AUX_)                                                                                             \
-        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups, 256, 0, s>>>(a.tile_order, a.n_heavy, a.T,      \
-                 a.tile_start, a.tile_end, a.vals_sorted, a.PA, a.PB, a.PC, a.box, a.offsets, a.grad_image, a.acc_alpha, a.last, a.W,     \
-                 a.H, a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image, a.cuts, a.cut_mag, a.tile_cut, aux))
+        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups, 256, 0, s>>>(v.tile_order, v.n_heavy, v.T,      \
+                 v.tile_start, v.tile_end, v.vals_sorted, v.PA, v.PB, v.PC, v.box, v.offsets, a.grad_image, a.acc_alpha, a.last, a.W,     \
+                 a.H, a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image, v.cuts, v.cut_mag, v.tile_cut, aux))
 #define GS_BWD_LAUNCH(NQ_, STRICT_) { if (a.aux) GS_BWD_LAUNCH_(NQ_, STRICT_, true); else GS_BWD_LAUNCH_(NQ_, STRICT_, false); }
         if (a.G == 1) { if (a.strict) GS_BWD_LAUNCH(4, true) else GS_BWD_LAUNCH(4, false) }
         else if (a.G == 2) { if (a.strict) GS_BWD_LAUNCH(2, true) else GS_BWD_LAUNCH(2, false) }
         else { if (a.strict) GS_BWD_LAUNCH(1, true) else GS_BWD_LAUNCH(1, false) }
 #undef GS_BWD_LAUNCH
 #undef GS_BWD_LAUNCH_
-        if (a.cuts && gs_heavy_cap(a.T) > 0) {                 // (fewer than eight tiles: no tile can be heavy)
+        if (v.cuts && gs_heavy_cap(v.T) > 0) {                 // (fewer than eight tiles: no tile can be heavy)
 #define GS_BWD_REPAIR(STRICT_)                                                                                                          \
-            GS_TIMED(a.prof, KID_BLEND_BWD_REPAIR, s, k_blend_bwd_repair<STRICT_><<<(unsigned)gs_heavy_cap(a.T), 256, 0, s>>>(a.tile_order, a.n_heavy, a.G, \
-                     a.tile_start, a.tile_end, a.vals_sorted, a.PA, a.PB, a.PC, a.box, a.offsets, a.grad_image, a.acc_alpha, a.last, a.W, a.H,  \
+            GS_TIMED(a.prof, KID_BLEND_BWD_REPAIR, s, k_blend_bwd_repair<STRICT_><<<(unsigned)gs_heavy_cap(v.T), 256, 0, s>>>(v.tile_order, v.n_heavy, a.G, \
+                     v.tile_start, v.tile_end, v.vals_sorted, v.PA, v.PB, v.PC, v.box, v.offsets, a.grad_image, a.acc_alpha, a.last, a.W, a.H,  \
                      a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image))
             if (a.strict) GS_BWD_REPAIR(true); else GS_BWD_REPAIR(false);
 #undef GS_BWD_REPAIR
@@ -1184,17 +1185,17 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
     }
     else if (a.mag_image)
         (void)hipMemsetAsync(a.mag_image, 0, sizeof(float) * 2 * (size_t)a.H * (size_t)a.W, s);
-    if (a.M > 0 && a.T > 0 && a.K > 0) {
+    if (a.M > 0 && v.T > 0 && a.K > 0) {
         GsMagFold fold{};
         fold.first_block = (unsigned)(((size_t)a.M * 4 + 255) / 256);
-        fold.n_heavy = a.n_heavy; fold.tile_order = a.tile_order; fold.tile_cut = a.tile_cut; fold.cut_mag = a.cut_mag;
-        fold.mag_image = a.cuts ? a.mag_image : nullptr; fold.W = a.W; fold.H = a.H; fold.tiles_x = a.tiles_x;
-        const unsigned fold_blocks = fold.mag_image ? (unsigned)gs_heavy_cap(a.T) : 0u;
+        fold.n_heavy = v.n_heavy; fold.tile_order = v.tile_order; fold.tile_cut = v.tile_cut; fold.cut_mag = v.cut_mag;
+        fold.mag_image = v.cuts ? a.mag_image : nullptr; fold.W = a.W; fold.H = a.H; fold.tiles_x = a.tiles_x;
+        const unsigned fold_blocks = fold.mag_image ? (unsigned)gs_heavy_cap(v.T) : 0u;
         if (a.aux)
-            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<true><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, a.offsets, a.ntiles, a.partial, a.visited,
+            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<true><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, v.offsets, v.ntiles, a.partial, a.visited,
                                                                                   a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
         else
-            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<false><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, a.offsets, a.ntiles, a.partial, a.visited,
+            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<false><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, v.offsets, v.ntiles, a.partial, a.visited,
                                                                                   a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
     }
     else if (a.M > 0)
@@ -1203,15 +1204,16 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
 
 void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s)
 {
+    const GsFrameView& v = a.v;
     const int nb = (int)((a.N + 255) / 256);
     if (nb == 0) return;
     int keep = a.sh_band <= 0 ? 1 : a.sh_band == 1 ? 4 : a.sh_band == 2 ? 9 : 16;
 #define GS_BWD_POINTS(AUX_)                                                                                                             \
-    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<AUX_><<<nb, 256, 0, s>>>(a.N, a.cam_index, a.sums, a.PD, a.point_cloud, a.features,   \
-                                                                    a.object_id, a.Kmat, a.pose, keep, a.f_color, a.f_high, a.f_s, a.f_q, a.f_alpha, \
+    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<AUX_><<<nb, 256, 0, s>>>(a.N, v.cam_index, a.sums, v.PD, a.point_cloud, a.features,   \
+                                                                    a.object_id, a.Kmat, v.pose, keep, a.f_color, a.f_high, a.f_s, a.f_q, a.f_alpha, \
                                                                     a.grad_pc, a.grad_feat, a.grad_uv, a.mag, a.n_affected,                \
                                                                     a.hook_gpc, a.hook_gfeat, a.hook_guv, a.hook_mag,                      \
-                                                                    a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, a.PA, a.PB, a.ntiles, \
+                                                                    a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, v.PA, v.PB, v.ntiles, \
                                                                     a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm))
     if (a.aux) GS_BWD_POINTS(true); else GS_BWD_POINTS(false);
 #undef GS_BWD_POINTS

@@ -308,7 +308,7 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
     if (a.N == 0 || a.M == 0) return;
     const unsigned kg_blocks = a.block_offsets ? (unsigned)((a.N + 255) / 256) : (unsigned)((a.M + 255) / 256);
     GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT><<<kg_blocks, 256, 0, s>>>(
-        a.depth_codes, a.box, a.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_scale, a.depth_bits, a.K, a.offsets, keys_a, a.vals_a,
+        a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_scale, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
         a.counters_rw, a.host_mirror, a.ticket));
     if (a.K == 0) return;
     int nb, tpb;

@@ -230,11 +230,12 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
 
 void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s)
 {
-    if (a.T <= 0) return;
+    const GsFrameView& v = a.v;
+    if (v.T <= 0) return;
     if (a.rgb_only)
-        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<true><<<a.T, 256, 0, s>>>(a.tile_start, a.tile_end, a.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, a.vals_sorted, a.PA, a.PB, a.PC, a.W, a.H,
-                                                                             a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, a.tile_work, a.order_hint, a.cuts, a.tile_cut, a.cut_alloc, a.cut_cap));
+        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<true><<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
+                                                                             a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, v.cut_alloc, a.cut_cap));
     else
-        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<false><<<a.T, 256, 0, s>>>(a.tile_start, a.tile_end, a.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, a.vals_sorted, a.PA, a.PB, a.PC, a.W, a.H,
-                                                                              a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, a.tile_work, a.order_hint, a.cuts, a.tile_cut, a.cut_alloc, a.cut_cap));
+        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<false><<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
+                                                                              a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, v.cut_alloc, a.cut_cap));
 }

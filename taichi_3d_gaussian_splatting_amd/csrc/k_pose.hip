@@ -245,10 +245,10 @@ void gs_launch_pose_grad(const GsBackwardArgs& a, int n_objects, void* scratch, 
     float* rec = static_cast<float*>(scratch);
     int32_t* n_rec = reinterpret_cast<int32_t*>(rec + (size_t)nb * cap * POSE_REC);
     if (nb > 0 && a.aux)
-        k_pose_points<true><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.ids, a.sums, a.PB, a.PC, a.PD, a.point_cloud, a.features,
-                                                      a.object_id, a.Kmat, a.pose, rec, n_rec);
+        k_pose_points<true><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.v.ids, a.sums, a.v.PB, a.v.PC, a.v.PD, a.point_cloud, a.features,
+                                                      a.object_id, a.Kmat, a.v.pose, rec, n_rec);
     else if (nb > 0)
-        k_pose_points<false><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.ids, a.sums, a.PB, a.PC, a.PD, a.point_cloud, a.features,
-                                                       a.object_id, a.Kmat, a.pose, rec, n_rec);
-    k_pose_reduce<<<n_objects, POSE_REDUCE_THREADS, 0, s>>>(nb, cap, rec, n_rec, a.pose, grad_q, grad_t);
+        k_pose_points<false><<<nb, POSE_BLOCK, 0, s>>>(a.M, n_objects, cap, a.v.ids, a.sums, a.v.PB, a.v.PC, a.v.PD, a.point_cloud, a.features,
+                                                       a.object_id, a.Kmat, a.v.pose, rec, n_rec);
+    k_pose_reduce<<<n_objects, POSE_REDUCE_THREADS, 0, s>>>(nb, cap, rec, n_rec, a.v.pose, grad_q, grad_t);
 }

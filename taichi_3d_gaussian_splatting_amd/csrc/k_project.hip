@@ -290,7 +290,6 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         depth_codes[idx] = depth_code;          // for the key build: 4 bytes instead of a 64-byte record row per point
     }
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#if GS_RS == 4
     {
         float4* mine = sOut[wave];
         mine[lane] = recA; mine[64 + lane] = recB; mine[128 + lane] = recC; mine[192 + lane] = recD;
@@ -304,9 +303,6 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
             if ((e >> 2) < n_rec) dst[e] = mine[(e & 3) * 64 + (e >> 2)];
         }
     }
-#else
-    if ((int)threadIdx.x < cnt) { GS_REC(PA, idx) = recA; GS_REC(PB, idx) = recB; GS_REC(PC, idx) = recC; GS_REC(PD, idx) = recD; }
-#endif
     int s = gs_wave_sum_i(count);
     int mx = gs_wave_max_i(depth_code);
     int mn = gs_wave_max_i(count);
@@ -393,30 +389,31 @@ void gs_launch_publish(const GsProjectArgs& a, int n_blocks, hipStream_t s)
 
 void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish)
 {
+    const GsFrameView& v = a.v;
     const int nb = (int)((a.N + 255) / 256);
     if (nb == 0) {
-        (void)hipMemsetAsync(a.tile_arrays, 0, sizeof(int32_t) * (size_t)a.tile_ints, s);     // empty scene: nothing else clears them
+        (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s);     // empty scene: nothing else clears them
         return;
     }
     GS_TIMED(a.prof, KID_FILTER, s, k_filter<<<nb, 256, 0, s>>>(a.point_cloud, a.invalid, a.object_id, a.Kmat, a.q_pc, a.t_pc, a.n_objects,
-                                                            a.pose, a.counters, a.N, a.W, a.H, a.near_plane, a.far_plane, a.mask,
-                                                            a.block_counts, a.tile_arrays, a.tile_ints));
-    GS_TIMED(a.prof, KID_PROJECT, s, k_project<<<nb, 256, 0, s>>>(a.point_cloud, a.features, a.object_id, a.Kmat, a.pose, a.mask, a.block_counts, a.N,
-                                                              a.ids, a.cam_index, a.block_offsets, a.W, a.H,
-                                                              a.depth_scale, a.PA, a.PB, a.PC, a.PD, a.box, a.ntiles,
-                                                              a.tile_block_sums, a.counters, a.depth_codes,
-                                                              a.tile_arrays ? a.tile_arrays + a.tile_ints - GS_TILE_SPARE_MAX_TILES : nullptr));
+                                                            v.pose, a.counters, a.N, a.W, a.H, a.near_plane, a.far_plane, v.mask,
+                                                            a.block_counts, v.tile_start, v.tile_ints));
+    GS_TIMED(a.prof, KID_PROJECT, s, k_project<<<nb, 256, 0, s>>>(a.point_cloud, a.features, a.object_id, a.Kmat, v.pose, v.mask, a.block_counts, a.N,
+                                                              v.ids, v.cam_index, a.block_offsets, a.W, a.H,
+                                                              a.depth_scale, v.PA, v.PB, v.PC, v.PD, v.box, v.ntiles,
+                                                              a.tile_block_sums, a.counters, v.depth_codes, v.max_tiles));
     if (publish) gs_launch_publish(a, nb, s);
 }
 
 void gs_launch_boxes_from_records(const GsProjectArgs& a, int M, hipStream_t s, bool publish)
 {
+    const GsFrameView& v = a.v;
     const int nb = (M + 255) / 256;
     if (nb == 0) {
-        (void)hipMemsetAsync(a.tile_arrays, 0, sizeof(int32_t) * (size_t)a.tile_ints, s);
+        (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s);
         return;
     }
-    GS_TIMED(a.prof, KID_PROJECT, s, k_boxes_from_records<<<nb, 256, 0, s>>>(a.PA, a.PB, a.PD, M, a.W, a.H, a.depth_scale, a.box, a.ntiles,
-                                                                          a.tile_block_sums, a.counters, a.depth_codes, a.tile_arrays, a.tile_ints));
+    GS_TIMED(a.prof, KID_PROJECT, s, k_boxes_from_records<<<nb, 256, 0, s>>>(v.PA, v.PB, v.PD, M, a.W, a.H, a.depth_scale, v.box, v.ntiles,
+                                                                          a.tile_block_sums, a.counters, v.depth_codes, v.tile_start, v.tile_ints));
     if (publish) gs_launch_publish(a, nb, s);
 }
