@@ -70,31 +70,7 @@ struct GsPose {
     float pad[2];
 };
 
-// ---- pose gradient (k_pose.hip) ---------------------------------------------------------------------------------
-// d/d(unit direction) of the 16 SH basis values the forward evaluates (GP3D:333-349, SH:10-53), contracted with gY = dL/dY:
-// g = sum_k gY[k] * dY_k/d(x, y, z), the derivative of the polynomial, not of its projection onto the sphere.
-__device__ __forceinline__ void gs_sh16_grad_dir(float x, float y, float z, const float gY[16], float g[3])
-{
-    const float c1 = 0.48860251190291987f, c4 = 1.0925484305920792f, c6 = 0.94617469575755997f, c8 = 0.54627421529603959f;
-    const float c9 = 0.59004358992664352f, c10 = 2.8906114426405538f, c11 = 0.45704579946446572f, c12 = 0.3731763325901154f;
-    const float c14 = 1.4453057213202769f;
-    const float xx = x * x, yy = y * y, zz = z * z;
-    float gx = -c1 * gY[3], gy = -c1 * gY[1], gz = c1 * gY[2];
-    gx += c4 * y * gY[4];                      gy += c4 * x * gY[4];
-    gy += -c4 * z * gY[5];                     gz += -c4 * y * gY[5];
-    gz += 2.0f * c6 * z * gY[6];
-    gx += -c4 * z * gY[7];                     gz += -c4 * x * gY[7];
-    gx += 2.0f * c8 * x * gY[8];               gy += -2.0f * c8 * y * gY[8];
-    gx += -6.0f * c9 * x * y * gY[9];          gy += 3.0f * c9 * (yy - xx) * gY[9];
-    gx += c10 * y * z * gY[10];                gy += c10 * x * z * gY[10];               gz += c10 * x * y * gY[10];
-    gy += c11 * (1.0f - 5.0f * zz) * gY[11];   gz += -10.0f * c11 * y * z * gY[11];
-    gz += c12 * (15.0f * zz - 3.0f) * gY[12];
-    gx += c11 * (1.0f - 5.0f * zz) * gY[13];   gz += -10.0f * c11 * x * z * gY[13];
-    gx += 2.0f * c14 * x * z * gY[14];         gy += -2.0f * c14 * y * z * gY[14];       gz += c14 * (xx - yy) * gY[14];
-    gx += 3.0f * c9 * (yy - xx) * gY[15];      gy += 6.0f * c9 * x * y * gY[15];
-    g[0] = gx; g[1] = gy; g[2] = gz;
-}
-
+// ---- pose gradient (k_pose.hip; the per-point part of its math is in gs_point_math.h) -----------------------------------
 // The per-object end of the pose gradient: from g = (dL/dW (9, row-major), dL/dt_cp (3), dL/do (3)) summed over the object's
 // points to dL/dq_pointcloud_camera (4) and dL/dt_pointcloud_camera (3), through what make_pose (k_project.hip) computes:
 //   q' = (-qx, -qy, -qz, qw);  W = R(q') by the un-normalised formula (GP3D:30-48);
@@ -288,6 +264,14 @@ __device__ __forceinline__ int gs_wave_sum_i(int v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// a float over the 64 lanes, every lane the total: butterfly from distance 1 up (the order is part of the pose gradient's bits)
+__device__ __forceinline__ float gs_wave_sum_f(float v)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 

@@ -16,7 +16,12 @@
 //                 every output row exactly once (zero for rows outside the frustum), including
 //                 the BackwardValidPointHookInput gathers (RAST:1128-1140).
 // k_blend_bwd_tile is VALU/latency bound, k_bwd_points HBM bound: see DESIGN.md.
-#include "gs_common.h"
+// Stated once, used by every form of these kernels: one contribution of loop 1 (gs_bwd_contribution), the LDS of a blend workgroup
+// (gs_bwd_lds), a row of sums by column (GsRow, gs_row_add, gs_row_store: gs_point_math.h) and the per-point math loop 2 shares with
+// the projection (same header).  k_bwd_points still unpacks its row into s[0..11] (columns as PW below lists them) and writes a
+// point's outputs in two places, zeros and values: both as GsRow / one writer compiled to other code that measured 1.5 - 4 % slower
+// on the clustered 976x544 workload (profiles/backward_refactor_ab.json), so that kernel's code is the previous one.
+#include "gs_point_math.h"
 #include "gs_cull.h"
 #include <cstdlib>
 
@@ -178,6 +183,65 @@ struct QuadState { float T, W, gr, gg, gb, tot0, tot1; int last; };
 // d depth = kD w (row column 11), R += w (d - D).  Either gradient pointer may be NULL (depth is required with grad_depth).
 struct BwdAux { const float* grad_depth; const float* depth; const float* grad_alpha; };
 struct AuxState { float kD, kA, D, R; };
+
+// min(prod_alpha, 0.99), RAST:636: both positive, so the integer minimum of the bit patterns (no canonicalise)
+__device__ __forceinline__ float gs_clamp_alpha(float prod_alpha)
+{
+    return __int_as_float(min(__float_as_int(prod_alpha), __float_as_int(GS_ALPHA_MAX)));
+}
+// acc + a * b, or just a * b where the first quadrant WRITES the sum (FIRST).  Every helper that forms a sum carries the contraction
+// pragma itself: it is block-scoped, and without it `acc + a` is a v_add behind a v_mul instead of the one v_fma_f32 (other bits).
+template <bool FIRST> __device__ __forceinline__ float gs_acc(float a, float b, float acc) { return FIRST ? a * b : __builtin_fmaf(a, b, acc); }
+template <bool FIRST> __device__ __forceinline__ float gs_acc1(float a, float acc)
+{
+#pragma clang fp contract(fast)
+    return FIRST ? a : acc + a;
+}
+// ONE contribution of loop 1: a splat with (clamped) alpha and falloff g at one pixel of quadrant state Q (AUX: X), added to -- FIRST:
+// written into -- the values v[] that are summed over the tile's pixels.  cix, ciy = Sigma^-1 d; m00, m01, m11 = Sigma^-1 (d d^T) Sigma^-1
+// (STRICT only); c4 the splat's colour, depth its camera-space z (AUX only), apt its opacity.
+template <bool STRICT, bool AUX, bool FIRST, int NV>
+__device__ __forceinline__ void gs_bwd_contribution(QuadState& Q, AuxState& X, float (&v)[NV], const float alpha, const float g,
+                                                    const float cix, const float ciy, const float m00, const float m01, const float m11,
+                                                    const float4 c4, const float depth, const float apt)
+{
+    // float outputs only from here on: let the compiler fuse multiply-adds
+#pragma clang fp contract(fast)
+    const float one_m = 1.0f - alpha;
+    const float inv = __builtin_amdgcn_rcpf(one_m);
+    const float Tn = Q.T * inv;                            // RAST:643 (v_rcp_f32: 1 ulp)
+    // d alpha: sum_c (colour_c*T - accumulated_c/(1-alpha)) * g_c, RAST:653-657, with the sums over c taken first
+    const float cg = c4.x * Q.gr + c4.y * Q.gg + c4.z * Q.gb;
+    float ag = Tn * cg - inv * Q.W;
+    const float d_rgb = alpha * Tn;                        // RAST:649
+    if constexpr (AUX) {                                   // depth and accumulated alpha, see BwdAux
+        const float dd = depth - X.D;
+        ag += X.kD * (Tn * dd - inv * X.R) + X.kA * inv;
+        v[10] = gs_acc<FIRST>(X.kD, d_rgb, v[10]);
+        X.R = __builtin_fmaf(d_rgb, dd, X.R);
+    }
+    // Per-splat constant factors are applied once per point in k_bwd_points instead of once per
+    // contribution: opacity on v[0..4] and v[9] (RAST:662), 0.5 on v[2..4], (1-opacity)*opacity on v[8]
+    const float agg = ag * g;
+    const float vs0 = agg * cix, vs1 = agg * ciy;          // RAST:664-665 without the opacity factor
+    v[0] = gs_acc1<FIRST>(vs0, v[0]); v[1] = gs_acc1<FIRST>(vs1, v[1]);
+    if (STRICT) {
+        v[2] = gs_acc<FIRST>(agg, m00, v[2]); v[3] = gs_acc<FIRST>(agg, m01, v[3]); v[4] = gs_acc<FIRST>(agg, m11, v[4]);
+    } else {
+        v[2] = gs_acc<FIRST>(vs0, cix, v[2]);
+        v[3] = gs_acc<FIRST>(vs0, ciy, v[3]);
+        v[4] = gs_acc<FIRST>(vs1, ciy, v[4]);
+    }
+    v[5] = gs_acc<FIRST>(d_rgb, Q.gr, v[5]);               // RAST:650
+    v[6] = gs_acc<FIRST>(d_rgb, Q.gg, v[6]);
+    v[7] = gs_acc<FIRST>(d_rgb, Q.gb, v[7]);
+    v[8] = gs_acc1<FIRST>(agg, v[8]);                      // RAST:658-661
+    v[9] = gs_acc1<FIRST>(__builtin_amdgcn_sqrtf(vs0 * vs0 + vs1 * vs1), v[9]);   // RAST:691-694
+    Q.T = Tn;
+    Q.W = __builtin_fmaf(cg, d_rgb, Q.W);                  // RAST:656
+    Q.tot0 = __builtin_fmaf(fabsf(vs0), apt, Q.tot0);      // RAST:666-667
+    Q.tot1 = __builtin_fmaf(fabsf(vs1), apt, Q.tot1);
+}
 
 // NQ = quadrants per wave: 4 (one wave per tile), 2 (two waves per tile, upper / lower half) or 1.
 // With G = 4/NQ waves per tile every (point, tile) pair owns G consecutive rows of `partial`.
@@ -408,76 +472,16 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
                         if (qi == 0 && clean) {                               // wave-uniform
                             // The first quadrant WRITES the ten sums, and all 64 lanes run the block: a lane that does not contribute
                             // computes on alpha = 0 and g = 0 (two selects), which makes each of its terms an exact zero and leaves its
-                            // T and W as they were.  Clearing ten registers first and masking exec around the block (scalar
-                            // instructions and a branch, in a kernel whose waves mostly wait on each other's latencies) costs more:
-                            // 0.242 -> 0.228 ms.  Contributing lanes execute exactly the masked form's operations.
-#pragma clang fp contract(fast)
+                            // T and W as they were (AUX: w = 0, so v[10] and R take exact zeros too).  Clearing ten registers first and
+                            // masking exec around the block (scalar instructions and a branch, in a kernel whose waves mostly wait on
+                            // each other's latencies) costs more: 0.242 -> 0.228 ms.  Contributing lanes execute exactly the masked
+                            // form's operations.
                             const bool use = __builtin_amdgcn_inverse_ballot_w64(use_m);
-                            const float alpha = use ? __int_as_float(min(__float_as_int(prod_alpha), __float_as_int(GS_ALPHA_MAX))) : 0.0f;
-                            const float gg = use ? g : 0.0f;
-                            const float one_m = 1.0f - alpha;
-                            const float inv = __builtin_amdgcn_rcpf(one_m);
-                            const float Tn = Q[qi].T * inv;
-                            const float cg = c4.x * Q[qi].gr + c4.y * Q[qi].gg + c4.z * Q[qi].gb;
-                            float ag = Tn * cg - inv * Q[qi].W;
-                            const float d_rgb = alpha * Tn;
-                            if constexpr (AUX) {                      // (an idle lane: w = 0, so v[10] and R take exact zeros)
-                                const float dd = b4.w - X[qi].D;
-                                ag += X[qi].kD * (Tn * dd - inv * X[qi].R) + X[qi].kA * inv;
-                                v[10] = X[qi].kD * d_rgb;
-                                X[qi].R = __builtin_fmaf(d_rgb, dd, X[qi].R);
-                            }
-                            const float agg = ag * gg;
-                            const float vs0 = agg * cix, vs1 = agg * ciy;
-                            v[0] = vs0; v[1] = vs1;
-                            if (STRICT) { v[2] = agg * m00; v[3] = agg * m01; v[4] = agg * m11; }
-                            else { v[2] = vs0 * cix; v[3] = vs0 * ciy; v[4] = vs1 * ciy; }
-                            v[5] = d_rgb * Q[qi].gr; v[6] = d_rgb * Q[qi].gg; v[7] = d_rgb * Q[qi].gb;
-                            v[8] = agg;
-                            v[9] = __builtin_amdgcn_sqrtf(vs0 * vs0 + vs1 * vs1);
-                            Q[qi].T = Tn;
-                            Q[qi].W = __builtin_fmaf(cg, d_rgb, Q[qi].W);
-                            Q[qi].tot0 = __builtin_fmaf(fabsf(vs0), apt, Q[qi].tot0);
-                            Q[qi].tot1 = __builtin_fmaf(fabsf(vs1), apt, Q[qi].tot1);
+                            gs_bwd_contribution<STRICT, AUX, true>(Q[qi], X[AUX ? qi : 0], v, use ? gs_clamp_alpha(prod_alpha) : 0.0f, use ? g : 0.0f,
+                                                                   cix, ciy, m00, m01, m11, c4, b4.w, apt);
                         } else if (__builtin_amdgcn_inverse_ballot_w64(use_m)) {                // exec-masked: idle lanes add nothing
-                            // float outputs only from here on: let the compiler fuse multiply-adds
-#pragma clang fp contract(fast)
-                            // min(prod_alpha, 0.99), RAST:636: both positive, so the integer minimum of the bit patterns (no canonicalise)
-                            const float alpha = __int_as_float(min(__float_as_int(prod_alpha), __float_as_int(GS_ALPHA_MAX)));
-                            const float one_m = 1.0f - alpha;
-                            const float inv = __builtin_amdgcn_rcpf(one_m);
-                            const float Tn = Q[qi].T * inv;                        // RAST:643 (v_rcp_f32: 1 ulp)
-                            // d alpha: sum_c (colour_c*T - accumulated_c/(1-alpha)) * g_c, RAST:653-657, with the sums over c taken first
-                            const float cg = c4.x * Q[qi].gr + c4.y * Q[qi].gg + c4.z * Q[qi].gb;
-                            float ag = Tn * cg - inv * Q[qi].W;
-                            const float d_rgb = alpha * Tn;                     // RAST:649
-                            if constexpr (AUX) {                                // depth and accumulated alpha, see BwdAux
-                                const float dd = b4.w - X[qi].D;
-                                ag += X[qi].kD * (Tn * dd - inv * X[qi].R) + X[qi].kA * inv;
-                                v[10] = __builtin_fmaf(X[qi].kD, d_rgb, v[10]);
-                                X[qi].R = __builtin_fmaf(d_rgb, dd, X[qi].R);
-                            }
-                            // Per-splat constant factors are applied once per point in k_bwd_points instead of once per
-                            // contribution: opacity on v[0..4] and v[9] (RAST:662), 0.5 on v[2..4], (1-opacity)*opacity on v[8]
-                            const float agg = ag * g;
-                            const float vs0 = agg * cix, vs1 = agg * ciy;       // RAST:664-665 without the opacity factor
-                            v[0] += vs0; v[1] += vs1;
-                            if (STRICT) {
-                                v[2] = __builtin_fmaf(agg, m00, v[2]); v[3] = __builtin_fmaf(agg, m01, v[3]); v[4] = __builtin_fmaf(agg, m11, v[4]);
-                            } else {
-                                v[2] = __builtin_fmaf(vs0, cix, v[2]);
-                                v[3] = __builtin_fmaf(vs0, ciy, v[3]);
-                                v[4] = __builtin_fmaf(vs1, ciy, v[4]);
-                            }
-                            v[5] = __builtin_fmaf(d_rgb, Q[qi].gr, v[5]);         // RAST:650
-                            v[6] = __builtin_fmaf(d_rgb, Q[qi].gg, v[6]);
-                            v[7] = __builtin_fmaf(d_rgb, Q[qi].gb, v[7]);
-                            v[8] += agg;                                         // RAST:658-661
-                            v[9] += __builtin_amdgcn_sqrtf(vs0 * vs0 + vs1 * vs1);   // RAST:691-694
-                            Q[qi].T = Tn;
-                            Q[qi].W = __builtin_fmaf(cg, d_rgb, Q[qi].W);        // RAST:656
-                            Q[qi].tot0 = __builtin_fmaf(fabsf(vs0), apt, Q[qi].tot0);   // RAST:666-667
-                            Q[qi].tot1 = __builtin_fmaf(fabsf(vs1), apt, Q[qi].tot1);
+                            gs_bwd_contribution<STRICT, AUX, false>(Q[qi], X[AUX ? qi : 0], v, gs_clamp_alpha(prod_alpha), g,
+                                                                    cix, ciy, m00, m01, m11, c4, b4.w, apt);
                         }
                     }
                     if (n_use == 0) continue;
@@ -590,6 +594,23 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
     }
 }
 
+// The LDS of a workgroup of k_blend_bwd_tile / k_blend_bwd_repair: per wave the batch's splat records and the transpose buffer, and
+// what four waves that share a tile exchange (BwdCoop, set up for a walk of the whole list: one segment, no cut records).
+struct BwdLds { float4 (*rec)[64][3]; float (*red)[11 * RED_STRIDE]; BwdCoop coop; };
+__device__ __forceinline__ BwdLds gs_bwd_lds()
+{
+    __shared__ float4 sRecAll[4][64][3];             // per wave: the batch's splat records (COOP: then the per-quadrant sums)
+    __shared__ __attribute__((aligned(16))) float sRedAll[4][11 * RED_STRIDE];
+    __shared__ unsigned long long sDone[4];
+    __shared__ int32_t sSlot[64], sPoint[64], sTileLast[4];
+    BwdLds l;
+    l.rec = sRecAll; l.red = sRedAll;
+    l.coop.done = sDone; l.coop.slot = sSlot; l.coop.point = sPoint; l.coop.tile_last = sTileLast;
+    l.coop.slab = reinterpret_cast<float (*)[64][12]>(&sRecAll[0][0][0]);
+    l.coop.seg = 0; l.coop.nseg = 1; l.coop.cut_rec = nullptr; l.coop.mag_part = nullptr; l.coop.redo = nullptr;
+    return l;
+}
+
 // One launch for the whole backward blend.  Workgroups of four waves: the first n_items workgroups take one work item of a HEAVY
 // tile each (k_tile_order put those tiles at the head of the order and counted their items: a segment of the tile's cut list, or
 // the whole list) and share it cooperatively, a quadrant per wave; every later workgroup takes four (tile, quadrant group) work
@@ -614,18 +635,12 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
                                                         const float4* __restrict__ cuts, float2* __restrict__ cut_mag, const int32_t* __restrict__ tile_cut,
                                                         const BwdAux aux)
 {
-    __shared__ float4 sRecAll[4][64][3];             // per wave: the batch's splat records (COOP: then the per-quadrant sums)
-    __shared__ __attribute__((aligned(16))) float sRedAll[4][11 * RED_STRIDE];
-    __shared__ unsigned long long sDone[4];
-    __shared__ int32_t sSlot[64], sPoint[64], sTileLast[4];
+    BwdLds lds = gs_bwd_lds();
+    BwdCoop& coop = lds.coop;
     constexpr int G = 4 / NQ;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n_heavy = n_heavy_ptr[0], n_items = n_heavy_ptr[1];
     const int32_t* item_base = n_heavy_ptr + 4;
-    BwdCoop coop;
-    coop.done = sDone; coop.slot = sSlot; coop.point = sPoint; coop.tile_last = sTileLast;
-    coop.slab = reinterpret_cast<float (*)[64][12]>(&sRecAll[0][0][0]);
-    coop.seg = 0; coop.nseg = 1; coop.cut_rec = nullptr; coop.mag_part = nullptr; coop.redo = nullptr;
     // (heavy items first: handing them out BEHIND the ordinary tiles, as the short jobs they are, measured slower -- DESIGN.md section 5)
     const int hb = (int)blockIdx.x < n_items ? (int)blockIdx.x : -1;
     const int lb = (int)blockIdx.x - n_items;
@@ -641,7 +656,7 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
             coop.cut_rec = cuts + first; coop.mag_part = cut_mag + first;
             coop.redo = const_cast<int32_t*>(n_heavy_ptr) + GS_ORDER_REDO_OFFSET + h;
         }
-        gs_bwd_tile_body<1, STRICT, true, AUX>(tile, wave, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
+        gs_bwd_tile_body<1, STRICT, true, AUX>(tile, wave, G, lds.rec[wave], lds.red[wave], coop, tile_start, tile_end, sorted_vals,
                                                PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen,
                                                mag_image, aux);
         return;
@@ -649,7 +664,7 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
     const int item = lb * 4 + wave;                                    // work item among the ordinary (tile, quadrant group) pairs
     const int ti = n_heavy + item / G;
     if (ti >= T) return;
-    gs_bwd_tile_body<NQ, STRICT, false, AUX>(tile_order[ti], item % G, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
+    gs_bwd_tile_body<NQ, STRICT, false, AUX>(tile_order[ti], item % G, G, lds.rec[wave], lds.red[wave], coop, tile_start, tile_end, sorted_vals,
                                              PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen,
                                              mag_image, aux);
 }
@@ -671,16 +686,9 @@ __global__ __launch_bounds__(256) void k_blend_bwd_repair(const int32_t* __restr
 {
     const int h = (int)blockIdx.x;
     if (h >= n_heavy_ptr[0] || n_heavy_ptr[GS_ORDER_REDO_OFFSET + h] == 0) return;
-    __shared__ float4 sRecAll[4][64][3];
-    __shared__ __attribute__((aligned(16))) float sRedAll[4][11 * RED_STRIDE];
-    __shared__ unsigned long long sDone[4];
-    __shared__ int32_t sSlot[64], sPoint[64], sTileLast[4];
+    const BwdLds lds = gs_bwd_lds();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    BwdCoop coop;
-    coop.done = sDone; coop.slot = sSlot; coop.point = sPoint; coop.tile_last = sTileLast;
-    coop.slab = reinterpret_cast<float (*)[64][12]>(&sRecAll[0][0][0]);
-    coop.seg = 0; coop.nseg = 1; coop.cut_rec = nullptr; coop.mag_part = nullptr; coop.redo = nullptr;
-    gs_bwd_tile_body<1, STRICT, true>(tile_order[h], wave, G, sRecAll[wave], sRedAll[wave], coop, tile_start, tile_end, sorted_vals,
+    gs_bwd_tile_body<1, STRICT, true>(tile_order[h], wave, G, lds.rec[wave], lds.red[wave], lds.coop, tile_start, tile_end, sorted_vals,
                                       PA, PB, PC, boxes, offsets, grad_image, acc_alpha, last_in, W, H, tiles_x, partial, visited, touched, gen, mag_image);
 }
 
@@ -710,11 +718,7 @@ __device__ __forceinline__ void gs_sum_rows_strided(const float4* __restrict__ r
 #pragma unroll
         for (int k = 0; k < 4; ++k) { a[k] = r[k][0]; b[k] = r[k][1]; c[k] = r[k][2]; }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            w[0] += a[k].x; w[1] += a[k].y; w[2] += a[k].z; w[3] += a[k].w; w[4] += b[k].x; w[5] += b[k].y; w[6] += b[k].z; w[7] += b[k].w;
-            w[8] += c[k].x; w[9] += c[k].y; wpix += __float_as_int(c[k].z);
-            if constexpr (AUX) w[10] += c[k].w;
-        }
+        for (int k = 0; k < 4; ++k) gs_row_add<AUX>(w, wpix, a[k], b[k], c[k]);
     }
 }
 struct GsMagFold { unsigned first_block; const int32_t* n_heavy; const int32_t* tile_order; const int32_t* tile_cut; const float2* cut_mag;
@@ -789,12 +793,7 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
 #pragma unroll
             for (int k = 0; k < 4; ++k) { a[k] = r[h + k][0]; b[k] = r[h + k][1]; c[k] = r[h + k][2]; }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                v[0] += a[k].x; v[1] += a[k].y; v[2] += a[k].z; v[3] += a[k].w;
-                v[4] += b[k].x; v[5] += b[k].y; v[6] += b[k].z; v[7] += b[k].w;
-                v[8] += c[k].x; v[9] += c[k].y; npix += __float_as_int(c[k].z);
-                if constexpr (AUX) v[10] += c[k].w;
-            }
+            for (int k = 0; k < 4; ++k) gs_row_add<AUX>(v, npix, a[k], b[k], c[k]);
         }
     }
     GS_DPP11("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
@@ -802,11 +801,7 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
     asm volatile("s_nop 1");
     npix += __builtin_amdgcn_update_dpp(0, npix, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
     npix += __builtin_amdgcn_update_dpp(0, npix, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
-    if (valid && q == 0 && cnt <= SUM_ROWS_SMALL) {
-        sums[3 * (size_t)m] = make_float4(v[0], v[1], v[2], v[3]);
-        sums[3 * (size_t)m + 1] = make_float4(v[4], v[5], v[6], v[7]);
-        sums[3 * (size_t)m + 2] = make_float4(v[8], v[9], __int_as_float(npix), AUX ? v[10] : 0.0f);
-    }
+    if (valid && q == 0 && cnt <= SUM_ROWS_SMALL) gs_row_store<AUX>(sums + 3 * (size_t)m, v, npix);
     // wave-cooperative pass over the large points of this wave (one vote per quad leader); the GIANT ones (a background splat over
     // the whole image: thousands of rows, 350 KB) are left to the whole block below
     const bool leader = valid && q == 0;
@@ -825,23 +820,14 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
         for (int k = 0; k < 11; ++k) w[k] = 0.0f;
         if (bcnt <= 256) {
             for (int i = lane; i < bcnt; i += 64) {
-                if (vis[i] == gen) {
-                    const float4 a = rows[3 * i], b = rows[3 * i + 1], c = rows[3 * i + 2];
-                    w[0] += a.x; w[1] += a.y; w[2] += a.z; w[3] += a.w; w[4] += b.x; w[5] += b.y; w[6] += b.z; w[7] += b.w;
-                    w[8] += c.x; w[9] += c.y; wpix += __float_as_int(c.z);
-                    if constexpr (AUX) w[10] += c.w;
-                }
+                if (vis[i] == gen) gs_row_add<AUX>(w, wpix, rows[3 * i], rows[3 * i + 1], rows[3 * i + 2]);
             }
         } else {
             gs_sum_rows_strided<64, AUX>(rows, vis, gen, zero_row, lane, bcnt, w, wpix);
         }
         gs_wave_sum11_row3(w);
         wpix = gs_wave_sum_i(wpix);
-        if (lane == 63) {
-            sums[3 * (size_t)bm] = make_float4(w[0], w[1], w[2], w[3]);
-            sums[3 * (size_t)bm + 1] = make_float4(w[4], w[5], w[6], w[7]);
-            sums[3 * (size_t)bm + 2] = make_float4(w[8], w[9], __int_as_float(wpix), AUX ? w[10] : 0.0f);
-        }
+        if (lane == 63) gs_row_store<AUX>(sums + 3 * (size_t)bm, w, wpix);
     }
     // block-cooperative pass over the giant points of this block: its 256 threads stride over the rows, four per thread in flight; the
     // four waves' sums are added in wave order.  Which points are giant is a function of their tile counts alone: fixed order, fixed bits.
@@ -872,14 +858,12 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
             }
             __syncthreads();
             if (threadIdx.x == 0) {
-                float r[10];
+                float r[11];
 #pragma unroll
                 for (int k = 0; k < 10; ++k) r[k] = ((sPart[0][k] + sPart[1][k]) + sPart[2][k]) + sPart[3][k];
                 const int np = (__float_as_int(sPart[0][10]) + __float_as_int(sPart[1][10])) + (__float_as_int(sPart[2][10]) + __float_as_int(sPart[3][10]));
-                const float rd = AUX ? ((sPart[0][11] + sPart[1][11]) + sPart[2][11]) + sPart[3][11] : 0.0f;
-                sums[3 * (size_t)bm] = make_float4(r[0], r[1], r[2], r[3]);
-                sums[3 * (size_t)bm + 1] = make_float4(r[4], r[5], r[6], r[7]);
-                sums[3 * (size_t)bm + 2] = make_float4(r[8], r[9], __int_as_float(np), rd);
+                r[10] = AUX ? ((sPart[0][11] + sPart[1][11]) + sPart[2][11]) + sPart[3][11] : 0.0f;
+                gs_row_store<AUX>(sums + 3 * (size_t)bm, r, np);
             }
             __syncthreads();
         }
@@ -958,11 +942,7 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         const float g00 = s[2], g01 = s[3], g11 = s[4];
         const float4* row4 = reinterpret_cast<const float4*>(feat + (size_t)GS_NFEAT * n);
         float row[GS_NFEAT];
-#pragma unroll
-        for (int k = 0; k < GS_NFEAT / 4; ++k) {
-            float4 v = row4[k];
-            row[4 * k] = v.x; row[4 * k + 1] = v.y; row[4 * k + 2] = v.z; row[4 * k + 3] = v.w;
-        }
+        gs_load_feat_row(row4, row);
         const GsPose& P = pose[obj[n]];
         float Km[9];
 #pragma unroll
@@ -987,8 +967,8 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         }
         // ---- d Sigma' / d(q, s), GP3D:237-331, contracted with (g00 g01; g01 g11) ----
         const float4 pd = GS_REC(PD, m);                                        // translation_camera, RAST:737-738
-        const float fx = Km[0], fy = Km[4];
-        float J[6] = { fx / pd.z, 0.0f, -(fx * pd.x) / (pd.z * pd.z), 0.0f, fy / pd.z, -(fy * pd.y) / (pd.z * pd.z) };
+        float J[6];
+        gs_projection_jacobian(Km[0], Km[4], pd.x, pd.y, pd.z, J);
         float U[6];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -997,12 +977,7 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         }
         const float qx = row[0], qy = row[1], qz = row[2], qw = row[3];
         float R[9];
-        {
-            float xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = qw * qx, wy = qw * qy, wz = qw * qz;
-            R[0] = 1.0f - 2.0f * (yy + zz); R[1] = 2.0f * (xy - wz); R[2] = 2.0f * (xz + wy);
-            R[3] = 2.0f * (xy + wz); R[4] = 1.0f - 2.0f * (xx + zz); R[5] = 2.0f * (yz - wx);
-            R[6] = 2.0f * (xz - wy); R[7] = 2.0f * (yz + wx); R[8] = 1.0f - 2.0f * (xx + yy);
-        }
+        rotation_from_quaternion(row, R);
         const float es[3] = { gs_expf(row[4]), gs_expf(row[5]), gs_expf(row[6]) };
         float Mm[9];
 #pragma unroll
@@ -1072,25 +1047,10 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         float dn = sqrtf(dx * dx + dy * dy + dz * dz);
         float ux = dx / dn, uy = dy / dn, uz = dz / dn;
         float sh[16];
-        sh[0] = 0.28209479177387814f;
-        sh[1] = -0.48860251190291987f * uy;
-        sh[2] = 0.48860251190291987f * uz;
-        sh[3] = -0.48860251190291987f * ux;
-        sh[4] = 1.0925484305920792f * ux * uy;
-        sh[5] = -1.0925484305920792f * uy * uz;
-        sh[6] = 0.94617469575755997f * uz * uz - 0.31539156525251999f;
-        sh[7] = -1.0925484305920792f * ux * uz;
-        sh[8] = 0.54627421529603959f * ux * ux - 0.54627421529603959f * uy * uy;
-        sh[9] = 0.59004358992664352f * uy * (-3.0f * ux * ux + uy * uy);
-        sh[10] = 2.8906114426405538f * ux * uy * uz;
-        sh[11] = 0.45704579946446572f * uy * (1.0f - 5.0f * uz * uz);
-        sh[12] = 0.3731763325901154f * uz * (5.0f * uz * uz - 3.0f);
-        sh[13] = 0.45704579946446572f * ux * (1.0f - 5.0f * uz * uz);
-        sh[14] = 1.4453057213202769f * uz * (ux * ux - uy * uy);
-        sh[15] = 0.59004358992664352f * ux * (-ux * ux + 3.0f * uy * uy);
+        gs_sh16(ux, uy, uz, sh);
         out[0] = gq[0] * f_q; out[1] = gq[1] * f_q; out[2] = gq[2] * f_q; out[3] = gq[3] * f_q;      // RAST:1105-1106
         out[4] = gs_[0] * f_s; out[5] = gs_[1] * f_s; out[6] = gs_[2] * f_s;                          // RAST:1107-1108
-        out[7] = s[8] * f_alpha;                                                                      // RAST:1109-1110
+        out[7] = s[8] * f_alpha;                                                                     // RAST:1109-1110
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const float* f = row + 8 + 16 * ch;

@@ -16,7 +16,7 @@
 //
 // No float atomics, no host waits: the counts the host would learn with .item() (CTRL:220,223,244,301,318) are read
 // on the device by the next kernel.  Integer atomics only for the over / under tallies of the fill pass.
-#include "gs_common.h"
+#include "gs_point_math.h"
 
 #include <algorithm>
 
@@ -48,16 +48,6 @@ __device__ __forceinline__ uint4 gs_philox4x32_10(uint4 c, uint32_t k0, uint32_t
 // 24 random bits -> (0, 1]: log never sees 0
 __device__ __forceinline__ float gs_unit(uint32_t x) { return (float)((x >> 8) + 1u) * 5.9604644775390625e-8f; }
 
-// GP3D:31-49 rotation_matrix_from_quaternion, q = xyzw as stored (not normalised, as in the reference)
-__device__ __forceinline__ void gs_rotation(const float* q, float R[3][3])
-{
-    const float x = q[0], y = q[1], z = q[2], w = q[3];
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    R[0][0] = 1.0f - 2.0f * (yy + zz); R[0][1] = 2.0f * (xy - wz);        R[0][2] = 2.0f * (xz + wy);
-    R[1][0] = 2.0f * (xy + wz);        R[1][1] = 1.0f - 2.0f * (xx + zz); R[1][2] = 2.0f * (yz - wx);
-    R[2][0] = 2.0f * (xz - wy);        R[2][1] = 2.0f * (yz + wx);        R[2][2] = 1.0f - 2.0f * (xx + yy);
-}
-
 // GP3D:391-406 GaussianPoint3D.sample(): centre + R S (z1, z2, z3), z from Box-Muller (GP3D:91-94) on four uniforms
 __device__ __forceinline__ void gs_sample_point(const float* centre, const float* feat, uint4 ctr, uint32_t k0, uint32_t k1, float out[3])
 {
@@ -67,7 +57,7 @@ __device__ __forceinline__ void gs_sample_point(const float* centre, const float
     const float r1 = sqrtf(-2.0f * logf(u1)), r3 = sqrtf(-2.0f * logf(u3));
     const float z[3] = { r1 * cosf(two_pi * u2), r1 * sinf(two_pi * u2), r3 * cosf(two_pi * u4) };
     float R[3][3];
-    gs_rotation(feat, R);
+    rotation_from_quaternion(feat, &R[0][0]);
     const float s[3] = { gs_expf(feat[4]), gs_expf(feat[5]), gs_expf(feat[6]) };
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -84,7 +74,7 @@ __device__ __forceinline__ void gs_foci_vector(const float* feat, float out[3])
     if (sx < sy && sy > sz) axis = 1;
     else if (sx < sz && sy < sz) axis = 2;
     float R[3][3];
-    gs_rotation(feat, R);
+    rotation_from_quaternion(feat, &R[0][0]);
     const float ex = gs_expf(sx), ey = gs_expf(sy), ez = gs_expf(sz);
     const float rc = fmaxf(fmaxf(ex, ey), ez), ra = fminf(fminf(ex, ey), ez);
     const float len = sqrtf(rc * rc - ra * ra);

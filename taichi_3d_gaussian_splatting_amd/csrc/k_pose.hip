@@ -7,7 +7,9 @@
 //                  order, and stored as (object, 15 floats) records, at most min(n_objects, 256) per block;
 //   k_pose_reduce  one workgroup per object: every block's record of that object in block order, the workgroup's sum in fixed
 //                  order, then the object's chain to dL/dq (4) and dL/dt (3) (gs_pose_grad_chain).  No touched point: exact zeros.
-#include "gs_common.h"
+// The forward's expressions come from where k_project takes them (gs_point_math.h: feature row, Sigma, J, gs_sh16_grad_dir beside
+// gs_sh16), the sums' columns from GsRow, the wave sum from gs_common.h (gs_wave_sum_f).
+#include "gs_point_math.h"
 
 #define POSE_G 15          // floats of a point's contribution
 #define POSE_REC 16        // object id (int bits) + POSE_G
@@ -15,13 +17,6 @@
 #define POSE_REDUCE_THREADS 1024
 
 static inline int pose_block_cap(int n_objects) { return n_objects < POSE_BLOCK ? n_objects : POSE_BLOCK; }
-
-__device__ __forceinline__ float pose_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // AUX: the sums carry d depth in column 11 (gs_backward_ex): it joins dL/dp_cam z
 template <bool AUX>
@@ -46,15 +41,14 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
     const int n = m < M ? ids[m] : 0;
     const int oid = m < M ? obj[n] : -1;
     // touched points only, as k_bwd_points (an untouched point's sums are all zero)
-    if (m < M && __float_as_int(r2.z) != 0 && oid >= 0 && oid < n_objects) {
+    if (m < M && gs_row_count(r2) != 0 && oid >= 0 && oid < n_objects) {
         o = oid;
-        const float4 r0 = sums[3 * (size_t)m], r1 = sums[3 * (size_t)m + 1];
+        const GsRow s = gs_row(sums[3 * (size_t)m], sums[3 * (size_t)m + 1], r2);
         // the per-splat factors k_blend_bwd_tile left out: opacity, 0.5 opacity (k_bwd_points)
         const float apt = GS_REC(PB, m).z;
-        const float a0 = r0.x * apt, a1 = r0.y * apt;
+        const float a0 = s.vs0 * apt, a1 = s.vs1 * apt;
         const float hf = 0.5f * apt;
-        const float G00 = r0.z * hf, G01 = r0.w * hf, G11 = r1.x * hf;
-        const float cb[3] = { r1.y, r1.z, r1.w };
+        const float G00 = s.cov00 * hf, G01 = s.cov01 * hf, G11 = s.cov11 * hf;
         const GsPose& P = pose[o];
         float Km[9];
 #pragma unroll
@@ -69,29 +63,11 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
         // ---- Sigma' = J W Sigma W^T J^T: H = G J W Sigma; dL/dW += 2 J^T H; dL/dJ = 2 G J V = 2 H W^T ----
         const float4* row4 = reinterpret_cast<const float4*>(feat + (size_t)GS_NFEAT * n);
         float row[GS_NFEAT];
-#pragma unroll
-        for (int k = 0; k < GS_NFEAT / 4; ++k) {
-            const float4 v = row4[k];
-            row[4 * k] = v.x; row[4 * k + 1] = v.y; row[4 * k + 2] = v.z; row[4 * k + 3] = v.w;
-        }
+        gs_load_feat_row(row4, row);
         const float fx = Km[0], fy = Km[4];
-        const float J[6] = { fx / pz, 0.0f, -(fx * px) / pz2, 0.0f, fy / pz, -(fy * py) / pz2 };
-        float Sigma[9];
-        {
-            const float qx = row[0], qy = row[1], qz = row[2], qw = row[3];
-            const float xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz;
-            const float wx = qw * qx, wy = qw * qy, wz = qw * qz;
-            const float R[9] = { 1.0f - 2.0f * (yy + zz), 2.0f * (xy - wz), 2.0f * (xz + wy),
-                                 2.0f * (xy + wz), 1.0f - 2.0f * (xx + zz), 2.0f * (yz - wx),
-                                 2.0f * (xz - wy), 2.0f * (yz + wx), 1.0f - 2.0f * (xx + yy) };
-            const float es0 = gs_expf(row[4]), es1 = gs_expf(row[5]), es2 = gs_expf(row[6]);
-            const float S[9] = { es0, 0.0f, 0.0f, 0.0f, es1, 0.0f, 0.0f, 0.0f, es2 };
-            const float Rt[9] = { R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8] };
-            float RS[9], RSS[9];
-            gs_mm<3, 3, 3>(R, S, RS);
-            gs_mm<3, 3, 3>(RS, S, RSS);
-            gs_mm<3, 3, 3>(RSS, Rt, Sigma);
-        }
+        float J[6], Sigma[9];
+        gs_projection_jacobian(fx, fy, px, py, pz, J);
+        gs_sigma_from_row(row, Sigma);
         float JW[6], JWS[6], H[6];
         gs_mm<2, 3, 3>(J, P.R, JW);
         gs_mm<2, 3, 3>(JW, Sigma, JWS);
@@ -111,7 +87,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
         gp[0] += B[2] * -fx2;
         gp[1] += B[5] * -fy2;
         gp[2] += (B[0] * -fx2 + B[2] * (2.0f * fx2 * px / pz)) + (B[4] * -fy2 + B[5] * (2.0f * fy2 * py / pz));
-        if constexpr (AUX) gp[2] += r2.w;                                  // the splat's depth is p_z
+        if constexpr (AUX) gp[2] += s.depth;                                 // the splat's depth is p_z
         // ---- p = W x + t_cp ----
         const float xv[3] = { x, y, z };
 #pragma unroll
@@ -124,7 +100,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
         const float dn = sqrtf(dx * dx + dy * dy + dz * dz);
         const float ux = dx / dn, uy = dy / dn, uz = dz / dn;
         const float4 col = GS_REC(PC, m);                                  // the forward's sigmoid values
-        const float ga[3] = { cb[0] * (col.x * (1.0f - col.x)), cb[1] * (col.y * (1.0f - col.y)), cb[2] * (col.z * (1.0f - col.z)) };
+        const float ga[3] = { s.col[0] * (col.x * (1.0f - col.x)), s.col[1] * (col.y * (1.0f - col.y)), s.col[2] * (col.z * (1.0f - col.z)) };
         float gY[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) gY[k] = (ga[0] * row[8 + k] + ga[1] * row[24 + k]) + ga[2] * row[40 + k];
@@ -143,7 +119,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_points(int M, int n_objects
         const bool mine = o == cur;
         float v[POSE_G];
 #pragma unroll
-        for (int j = 0; j < POSE_G; ++j) v[j] = pose_wave_sum(mine ? g[j] : 0.0f);
+        for (int j = 0; j < POSE_G; ++j) v[j] = gs_wave_sum_f(mine ? g[j] : 0.0f);
         if (lane == 0) {
             sWave[wave][k][0] = __int_as_float(cur);
 #pragma unroll
@@ -205,7 +181,7 @@ __global__ __launch_bounds__(POSE_REDUCE_THREADS) void k_pose_reduce(int n_block
         }
     }
 #pragma unroll
-    for (int j = 0; j < POSE_G; ++j) acc[j] = pose_wave_sum(acc[j]);
+    for (int j = 0; j < POSE_G; ++j) acc[j] = gs_wave_sum_f(acc[j]);
     hits = gs_wave_sum_i(hits);
     if (lane == 0) {
 #pragma unroll

@@ -6,7 +6,7 @@
 //   k_project        point_id[mask] (RAST:861-870, ascending ids) + generate_point_attributes_in_camera_plane RAST:239-315
 //                    + generate_num_overlap_tiles RAST:106-128 in one kernel
 // All HBM-bound streaming kernels; layouts in DESIGN.md.
-#include "gs_common.h"
+#include "gs_point_math.h"
 
 #ifndef GS_RADIUS_FROM_PREBLUR_COV
 #define GS_RADIUS_FROM_PREBLUR_COV 1
@@ -21,17 +21,6 @@ __device__ __forceinline__ void quat_mul(const float a[4], const float b[4], flo
     o[1] = w0 * y1 - x0 * z1 + y0 * w1 + z0 * x1;
     o[2] = w0 * z1 + x0 * y1 - y0 * x1 + z0 * w1;
     o[3] = w0 * w1 - x0 * x1 - y0 * y1 - z0 * z1;
-}
-
-__device__ __forceinline__ void rotation_from_quaternion(const float q[4], float R[9])
-{   // GP3D:30-48
-    float x = q[0], y = q[1], z = q[2], w = q[3];
-    float xx = x * x, yy = y * y, zz = z * z;
-    float xy = x * y, xz = x * z, yz = y * z;
-    float wx = w * x, wy = w * y, wz = w * z;
-    R[0] = 1.0f - 2.0f * (yy + zz); R[1] = 2.0f * (xy - wz);        R[2] = 2.0f * (xz + wy);
-    R[3] = 2.0f * (xy + wz);        R[4] = 1.0f - 2.0f * (xx + zz); R[5] = 2.0f * (yz - wx);
-    R[6] = 2.0f * (xz - wy);        R[7] = 2.0f * (yz + wx);        R[8] = 1.0f - 2.0f * (xx + yy);
 }
 
 // Pose record of one object: inverse_SE3_qt_torch (UTIL:426-432) + rotation_matrix_from_quaternion (GP3D:30-48)
@@ -176,6 +165,8 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         int pid = sIds[threadIdx.x];
         float4* row4 = reinterpret_cast<float4*>(feat + (size_t)GS_NFEAT * pid);
         float row[GS_NFEAT];
+        // (gs_load_feat_row, written out: through the helper two VALU instructions of this kernel come out with their operands swapped,
+        // and this file's code is held to the parent's to the instruction; the row is also written back below through row4)
 #pragma unroll
         for (int k = 0; k < GS_NFEAT / 4; ++k) {
             float4 v = row4[k];
@@ -200,18 +191,9 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         float uv[2], pcam[3];
         project_point(P.R, P.t, Km, x, y, z, uv, pcam);
         // ---- project_to_camera_covariance, GP3D:161-191 (same product chain as the Python) ----
-        float fx = Km[0], fy = Km[4];
-        float J[6] = { fx / pcam[2], 0.0f, -(fx * pcam[0]) / (pcam[2] * pcam[2]),
-                       0.0f, fy / pcam[2], -(fy * pcam[1]) / (pcam[2] * pcam[2]) };
-        float R[9];
-        rotation_from_quaternion(row, R);
-        float es0 = gs_expf(row[4]), es1 = gs_expf(row[5]), es2 = gs_expf(row[6]);
-        float S[9] = { es0, 0.0f, 0.0f, 0.0f, es1, 0.0f, 0.0f, 0.0f, es2 };   // S == S^T
-        float Rt[9] = { R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8] };
-        float RS[9], RSS[9], Sigma[9];
-        gs_mm<3, 3, 3>(R, S, RS);
-        gs_mm<3, 3, 3>(RS, S, RSS);
-        gs_mm<3, 3, 3>(RSS, Rt, Sigma);
+        float J[6], Sigma[9];
+        gs_projection_jacobian(Km[0], Km[4], pcam[0], pcam[1], pcam[2], J);
+        gs_sigma_from_row(row, Sigma);
         float Wt[9] = { P.R[0], P.R[3], P.R[6], P.R[1], P.R[4], P.R[7], P.R[2], P.R[5], P.R[8] };
         float Jt[6] = { J[0], J[3], J[1], J[4], J[2], J[5] };
         float Wm[9];
@@ -237,22 +219,7 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         float dn = sqrtf(dx * dx + dy * dy + dz * dz);
         float sx = dx / dn, sy = dy / dn, sz = dz / dn;
         float sh[16];
-        sh[0] = 0.28209479177387814f;
-        sh[1] = -0.48860251190291987f * sy;
-        sh[2] = 0.48860251190291987f * sz;
-        sh[3] = -0.48860251190291987f * sx;
-        sh[4] = 1.0925484305920792f * sx * sy;
-        sh[5] = -1.0925484305920792f * sy * sz;
-        sh[6] = 0.94617469575755997f * sz * sz - 0.31539156525251999f;
-        sh[7] = -1.0925484305920792f * sx * sz;
-        sh[8] = 0.54627421529603959f * sx * sx - 0.54627421529603959f * sy * sy;
-        sh[9] = 0.59004358992664352f * sy * (-3.0f * sx * sx + sy * sy);
-        sh[10] = 2.8906114426405538f * sx * sy * sz;
-        sh[11] = 0.45704579946446572f * sy * (1.0f - 5.0f * sz * sz);
-        sh[12] = 0.3731763325901154f * sz * (5.0f * sz * sz - 3.0f);
-        sh[13] = 0.45704579946446572f * sx * (1.0f - 5.0f * sz * sz);
-        sh[14] = 1.4453057213202769f * sz * (sx * sx - sy * sy);
-        sh[15] = 0.59004358992664352f * sx * (-sx * sx + 3.0f * sy * sy);
+        gs_sh16(sx, sy, sz, sh);
         float col[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
