@@ -5,21 +5,22 @@ Same class, nested dataclass names and fields, method names and iteration schedu
 and edits of _find_densify_points / _add_densify_points (CTRL:170-353, two Taichi kernels and ~40 torch launches with
 host syncs in the reference) are two library calls, gs_density_select and gs_density_apply, that never wait for the
 host; update()'s six accumulations (CTRL:133-141) are gs_controller_accumulate or, when the rasteriser was given the
-controller's accumulators, the backward kernel itself.  There is no Taichi and no fallback path.
+controller's accumulators, the backward kernel itself.  There is no Taichi and no fallback path; the library calls go
+through _native.call().
 
 Deviation (DESIGN.md "Numerics"): the split samples of GaussianPoint3D.sample() draw from Philox4x32-10 keyed by
 `seed`, not from Taichi's ti.random(): the same distribution, a different (reproducible) stream.
 Not for data-parallel training as is: the single-frame and floater criteria come from one rank's view, so replicas
 would take different decisions (ControllerAccumulators.all_reduce covers only the statistics).
 """
-import ctypes as C
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import _native
-from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation, _ConfigBase, _on_device, _ptr, _require
+from ._host import _ConfigBase, _require
+from ._native import ptr as _ptr
+from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .controller_stats import ControllerAccumulators
 
 
@@ -89,7 +90,7 @@ class GaussianPointAdaptiveController:
         self.refinement_calls = 0                               # densifications applied so far (the sample counter)
         self._selected = False
         self._device = dev
-        self._context = _native.Context(dev.index if dev.index is not None else torch.cuda.current_device())
+        self._context = _native.Context(_native.device_index(dev))
         # the plan: caller-owned device arrays, allocated once for N rows
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
         self._flags = z(n, dtype=torch.int8)
@@ -100,8 +101,11 @@ class GaussianPointAdaptiveController:
         self._fill_ids = z(n, dtype=torch.int32)
         self._scratch = z(int(_native.lib().gs_density_scratch_bytes(n)), dtype=torch.uint8)
         self._counts = z(len(_native.DENSITY_COUNTS), dtype=torch.int32)
-        self._plan = _native.GsDensityPlan(_ptr(self._flags), _ptr(self._densify_ids), _ptr(self._densify_pos), _ptr(self._densify_grad),
-                                           _ptr(self._densify_factor), _ptr(self._fill_ids), _ptr(self._scratch), _ptr(self._counts), n)
+        self._plan = _native.GsDensityPlan(
+            flags=_ptr(self._flags), densify_point_id=_ptr(self._densify_ids),
+            densify_point_position_before_optimization=_ptr(self._densify_pos), densify_point_grad_position=_ptr(self._densify_grad),
+            densify_size_reduction_factor=_ptr(self._densify_factor), fill_point_id=_ptr(self._fill_ids), scratch=_ptr(self._scratch),
+            counts=_ptr(self._counts), n_points=n)
 
     # the reference keeps the six statistics as attributes of the controller (CTRL:114-127)
     def __getattr__(self, name):
@@ -113,29 +117,12 @@ class GaussianPointAdaptiveController:
     def _n(self) -> int:
         return self.maintained_parameters.pointcloud.shape[0]
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+    def _call(self, name, *args):
+        _native.call(name, self._device, self._context.handle, *args)
 
-    def _c_accumulators(self):
-        a = self.accumulators
-        return _native.GsControllerAccumulators(
-            _ptr(a.accumulated_num_in_camera), _ptr(a.accumulated_num_pixels), _ptr(a.accumulated_view_space_position_gradients),
-            _ptr(a.accumulated_view_space_position_gradients_avg), _ptr(a.accumulated_position_gradients),
-            _ptr(a.accumulated_position_gradients_norm))
-
-    def _c_config(self):
-        c = self.config
-        floor_int = lambda v: int(max(min(np.floor(v), 2 ** 31 - 1), -2 ** 31))   # int32 > x  <=>  int32 > floor(x)
-        return _native.GsDensityConfig(
-            c.transparent_alpha_threshold, c.densification_view_space_position_gradients_threshold,
-            c.densification_view_avg_space_position_gradients_threshold,
-            c.densification_multi_frame_view_space_position_gradients_threshold,
-            c.densification_multi_frame_view_pixel_avg_space_position_gradients_threshold,
-            c.densification_multi_frame_position_gradients_threshold,
-            float(np.float32(np.log(c.gaussian_split_factor_phi))),                  # CTRL:255 np.log, then stored as f32
-            floor_int(c.floater_near_camrea_num_pixels_threshold), c.floater_depth_threshold,
-            floor_int(c.under_reconstructed_num_pixels_threshold), c.under_reconstructed_move_factor,
-            1 if c.enable_ellipsoid_offset else 0, 1 if c.enable_sample_from_point else 0)
+    def _c_scene(self):
+        mp = self.maintained_parameters
+        return _native.GsScene.of(mp.pointcloud, mp.pointcloud_features, mp.point_invalid_mask, mp.point_object_id)
 
     def _check_scene(self):
         mp = self.maintained_parameters
@@ -155,11 +142,9 @@ class GaussianPointAdaptiveController:
                 _require(input_data.num_affected_pixels, "num_affected_pixels", torch.int32, (), dev)
                 _require(input_data.magnitude_grad_viewspace, "magnitude_grad_viewspace", torch.float32, (), dev)
                 _require(input_data.grad_point_in_camera, "grad_point_in_camera", torch.float32, (3,), dev)
-                acc = self._c_accumulators()
-                with _on_device(dev):
-                    _native.check(_native.lib().gs_controller_accumulate(
-                        self._context.handle, _ptr(ids), _ptr(input_data.num_affected_pixels), _ptr(input_data.magnitude_grad_viewspace),
-                        _ptr(input_data.grad_point_in_camera), m, self._n(), C.byref(acc), self._stream()), "gs_controller_accumulate")
+                self._call("gs_controller_accumulate", _ptr(ids), _ptr(input_data.num_affected_pixels),
+                           _ptr(input_data.magnitude_grad_viewspace), _ptr(input_data.grad_point_in_camera), m, self._n(),
+                           _native.GsControllerAccumulators.of(self.accumulators))
             if self.iteration_counter < self.config.num_iterations_warm_up:
                 pass
             elif self.iteration_counter % self.config.num_iterations_densify == 0:
@@ -181,7 +166,6 @@ class GaussianPointAdaptiveController:
         """CTRL:170-265 as one library call, inside the backward, before the optimiser step: the masks, the densify ids
         and the snapshots of their positions and position gradients stay in the plan on the device."""
         self._check_scene()
-        mp = self.maintained_parameters
         dev = self._device
         ids = input_data.point_id_in_camera_list
         for t, name, dtype in [(ids, "point_id_in_camera_list", torch.int32), (input_data.num_affected_pixels, "num_affected_pixels", torch.int32),
@@ -190,15 +174,10 @@ class GaussianPointAdaptiveController:
             _require(t, name, dtype, (), dev)
             if t.shape[0] != ids.shape[0]:
                 raise ValueError("the hook arrays disagree on M")
-        scene = _native.GsScene(_ptr(mp.pointcloud), _ptr(mp.pointcloud_features), _ptr(mp.point_invalid_mask), _ptr(mp.point_object_id),
-                                self._n())
-        acc, cfg = self._c_accumulators(), self._c_config()
         remove_floaters = 1 if self.iteration_counter > self.config.iteration_start_remove_floater else 0   # CTRL:191
-        with _on_device(dev):
-            _native.check(_native.lib().gs_density_select(
-                self._context.handle, C.byref(scene), C.byref(acc), _ptr(ids), _ptr(input_data.num_affected_pixels),
-                _ptr(input_data.point_depth), _ptr(input_data.magnitude_grad_viewspace), ids.shape[0], remove_floaters,
-                C.byref(cfg), C.byref(self._plan), self._stream()), "gs_density_select")
+        self._call("gs_density_select", self._c_scene(), _native.GsControllerAccumulators.of(self.accumulators), _ptr(ids),
+                   _ptr(input_data.num_affected_pixels), _ptr(input_data.point_depth), _ptr(input_data.magnitude_grad_viewspace),
+                   ids.shape[0], remove_floaters, _native.GsDensityConfig.of(self.config), self._plan)
         self._selected = True
         if self.verbose:
             c = self.last_refinement_counts()
@@ -210,13 +189,8 @@ class GaussianPointAdaptiveController:
         """CTRL:290-353 as one library call, after the optimiser step."""
         assert self._selected, "refinement() at a densify iteration without the backward hook having run (CTRL:291)"
         self._check_scene()
-        mp = self.maintained_parameters
-        scene = _native.GsDensityScene(_ptr(mp.pointcloud), _ptr(mp.pointcloud_features), _ptr(mp.point_invalid_mask),
-                                       _ptr(mp.point_object_id), self._n())
-        cfg = self._c_config()
-        with _on_device(self._device):
-            _native.check(_native.lib().gs_density_apply(self._context.handle, C.byref(scene), C.byref(cfg), C.byref(self._plan),
-                                                         self.seed, self.refinement_calls & 0xFFFFFFFF, self._stream()), "gs_density_apply")
+        self._call("gs_density_apply", self._c_scene(), _native.GsDensityConfig.of(self.config), self._plan, self.seed,
+                   self.refinement_calls & 0xFFFFFFFF)
         self.refinement_calls += 1
         self._selected = False
         if self.verbose:

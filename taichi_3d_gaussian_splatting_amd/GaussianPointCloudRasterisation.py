@@ -5,132 +5,20 @@ libgsrast.so (hand-written HIP for MI355X / gfx950) through its C ABI.
 Same class, nested dataclass names, field order, forward() contract and backward-hook
 payload as the reference.  The Python side only validates arguments, allocates the output
 tensors, keeps the opaque frame handle alive between forward and backward and dispatches
-the hook; all arithmetic happens in the library.  There is no fallback path.
+the hook; all arithmetic happens in the library (called through _native.call()).  There is no fallback path.
 """
-import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, Optional
 
 import torch
 
 from . import _native
+from ._host import _ConfigBase, _Contexts, _Frame, _marshal
 from .Camera import CameraInfo
 from .controller_stats import ControllerAccumulators
 
 TILE_WIDTH = 16
 TILE_HEIGHT = 16
-
-try:  # the reference mixes in dataclass_wizard.YAMLWizard (RAST:777); optional here
-    from dataclass_wizard import YAMLWizard as _ConfigBase
-except Exception:  # pragma: no cover - not installed in the build image
-    class _ConfigBase:
-        pass
-
-_TORCH_DTYPES = {"float32": torch.float32, "int32": torch.int32, "int64": torch.int64, "int8": torch.int8}
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
-
-
-def _require(t: torch.Tensor, name: str, dtype, shape_tail, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must live on a GPU (cuda/hip device), got {t.device}")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name} is on {t.device}, expected {device}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    if tuple(t.shape[1:]) != tuple(shape_tail):
-        raise ValueError(f"{name} must have shape (*, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}")
-
-
-class _on_device:
-    """torch.cuda.device(dev) only when dev is not already current (the context manager costs microseconds per call)."""
-
-    def __init__(self, dev):
-        self._cm = None if dev.index is None or torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self._cm is not None:
-            self._cm.__enter__()
-
-    def __exit__(self, *exc):
-        if self._cm is not None:
-            return self._cm.__exit__(*exc)
-        return False
-
-
-class _Frame:
-    """Owner of a gs_frame ticket: what ctx.save_for_backward keeps in the reference (RAST:998-1021).  Holds the
-    context alive (the ticket is meaningless without it) and gives the ticket back when it dies."""
-
-    def __init__(self, context: "_native.Context", handle, device, owned=True, lazy=False):
-        """lazy: the frame was only begun (gs_project_shard_begin); its counts are read -- which waits for its kernels -- the
-        first time one of them is asked for."""
-        self._context, self._h, self.device, self._owned = context, handle, device, owned
-        self.marshalled = None              # (gs_scene, gs_camera, gs_config) of the forward that made the frame
-        if not lazy:
-            self._read_info()
-
-    def _read_info(self):
-        info = _native.GsFrameInfo()
-        _native.check(_native.lib().gs_frame_get_info(self._context.handle, self.handle, C.byref(info)), "gs_frame_get_info")
-        self.n_points, self.n_points_in_camera, self.n_keys = info.n_points, info.n_points_in_camera, info.n_keys
-        self.n_tiles, self.sort_key_bits, self.stages = info.n_tiles, info.sort_key_bits, info.stages
-        self.sizing = ("exact", "predicted", "redone")[info.sizing]      # gs_frame_info.sizing: how the per-pixel half was sized
-
-    def __getattr__(self, name):            # only reached for attributes not set yet: the counts of a lazy frame
-        if name in ("n_points", "n_points_in_camera", "n_keys", "n_tiles", "sort_key_bits", "stages", "sizing"):
-            self._read_info()
-            return self.__dict__[name]
-        raise AttributeError(name)
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise RuntimeError("frame already released")
-        return self._h
-
-    def export(self, name: str) -> torch.Tensor:
-        eid, dtype, tail = _native.EXPORTS[name]
-        L = _native.lib()
-        n = L.gs_frame_export_count(self._context.handle, self.handle, eid)
-        if n < 0:
-            raise RuntimeError(f"gs_frame_export_count({name}) failed: the frame is no longer live or does not hold that stage")
-        rows = n
-        for d in tail:
-            rows //= d
-        out = torch.empty((rows, *tail), dtype=_TORCH_DTYPES[dtype], device=self.device)
-        if n > 0:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _native.check(L.gs_frame_export(self._context.handle, self.handle, eid, _ptr(out), C.c_void_p(stream)), f"gs_frame_export({name})")
-        return out
-
-    def heavy_tiles(self, items: bool = False) -> int:
-        """Diagnostic: tiles the last backward blend of this frame shared among four waves, or (items=True) the work items they were
-        handed out as -- one per 512-entry segment of a list the forward cut (gs_frame_heavy_tiles)."""
-        n = (C.c_int32 * 2)(0, 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _native.check(_native.lib().gs_frame_heavy_tiles(self._context.handle, self.handle, n, C.c_void_p(stream)), "gs_frame_heavy_tiles")
-        return int(n[1] if items else n[0])
-
-    def release(self):
-        """Hands the ticket back.  Transient frames (forward without gradient tracking) belong to the context and are
-        recycled by its next forward; their ticket then simply stops resolving."""
-        if self._h is not None:
-            if self._owned and self._context.handle:
-                _native.lib().gs_frame_release(self._context.handle, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 class GaussianPointCloudRasterisation(torch.nn.Module):
@@ -189,7 +77,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         self.config = config
         self._hook = backward_valid_point_hook
         self.controller_accumulators = controller_accumulators
-        self._ctxs = {}                     # device index -> _native.Context (owner of the gs_ctx)
+        self._ctxs = _Contexts()            # device index -> _native.Context (owner of the gs_ctx)
         self.last_frame: Optional[_Frame] = None   # inspection aid (tests / profiling); replaced every call
         self.last_forward_outputs = {}
         module = self
@@ -252,74 +140,21 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         self._module_function = _module_function
 
     # ------------------------------------------------------------------ helpers
-    def _context_for(self, device: torch.device) -> "_native.Context":
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if idx not in self._ctxs:
-            self._ctxs[idx] = _native.Context(idx)
-        return self._ctxs[idx]
-
     def _ctx_for(self, device: torch.device):
         """The raw gs_ctx* of this module on `device` (profiling / diagnostics)."""
-        return self._context_for(device).handle
-
-    def _c_config(self):
-        c = self.config
-        return _native.GsConfig(c.near_plane, c.far_plane, c.depth_to_sort_key_scale, 1 if c.rgb_only else 0,
-                                c.grad_color_factor, c.grad_high_order_color_factor, c.grad_s_factor,
-                                c.grad_q_factor, c.grad_alpha_factor, 1 if getattr(c, "allow_partial_tiles", False) else 0,
-                                1 if getattr(c, "backward_reference_order", False) else 0)
-
-    @staticmethod
-    def _c_scene(pointcloud, features, mask, obj):
-        return _native.GsScene(_ptr(pointcloud), _ptr(features), _ptr(mask), _ptr(obj), pointcloud.shape[0])
-
-    @staticmethod
-    def _c_camera(q, t, camera_info, Kmat):
-        return _native.GsCamera(_ptr(q), _ptr(t), q.shape[0], _ptr(Kmat), camera_info.camera_height, camera_info.camera_width)
-
-    def _marshal(self, pointcloud, features, mask, obj, q, t, camera_info):
-        Kmat = self._validate(pointcloud, features, mask, obj, q, t, camera_info)
-        return self._c_scene(pointcloud, features, mask, obj), self._c_camera(q, t, camera_info, Kmat), self._c_config()
-
-    def _validate(self, pointcloud, features, mask, obj, q, t, camera_info):
-        dev = pointcloud.device
-        _require(pointcloud, "point_cloud", torch.float32, (3,))
-        _require(features, "point_cloud_features", torch.float32, (56,), dev)
-        if features.shape[0] != pointcloud.shape[0] or mask.shape[0] != pointcloud.shape[0] or obj.shape[0] != pointcloud.shape[0]:
-            raise ValueError("point_cloud, point_cloud_features, point_invalid_mask and point_object_id disagree on N")
-        _require(mask, "point_invalid_mask", torch.int8, (), dev)
-        _require(obj, "point_object_id", torch.int32, (), dev)
-        _require(q, "q_pointcloud_camera", torch.float32, (4,), dev)
-        _require(t, "t_pointcloud_camera", torch.float32, (3,), dev)
-        if q.shape[0] != t.shape[0] or q.shape[0] < 1:
-            raise ValueError("q_pointcloud_camera and t_pointcloud_camera must have the same, non-zero number of rows")
-        Kmat = camera_info.camera_intrinsics
-        if tuple(Kmat.shape) != (3, 3):
-            raise ValueError("camera_intrinsics must be 3x3")
-        if Kmat.dtype != torch.float32 or Kmat.device != dev or not Kmat.is_contiguous():
-            Kmat = Kmat.to(device=dev, dtype=torch.float32).contiguous()
-        return Kmat
+        return self._ctxs.of(device).handle
 
     def _run_forward(self, pointcloud, features, mask, obj, q, t, camera_info, keep):
-        Kmat = self._validate(pointcloud, features, mask, obj, q, t, camera_info)
+        scene, cam, cfg, Kmat = _marshal(self.config, pointcloud, features, mask, obj, q, t, camera_info)
         dev = pointcloud.device
         H, W = camera_info.camera_height, camera_info.camera_width
-        rgb_only = bool(self.config.rgb_only)
         image = torch.empty(H, W, 3, dtype=torch.float32, device=dev)                   # RAST:967-976
         depth = torch.empty(H, W, dtype=torch.float32, device=dev)
         acc_alpha = torch.empty(H, W, dtype=torch.float32, device=dev)
         last = torch.empty(H, W, dtype=torch.int32, device=dev)
         count = torch.empty(H, W, dtype=torch.int32, device=dev)
-        out = _native.GsForwardOut(_ptr(image), _ptr(depth), _ptr(acc_alpha), _ptr(last), _ptr(count))
-        context = self._context_for(dev)
-        ctxh = context.handle
-        frame_h = C.c_void_p()
-        scene, cam, cfg = self._c_scene(pointcloud, features, mask, obj), self._c_camera(q, t, camera_info, Kmat), self._c_config()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with _on_device(dev):
-            _native.check(_native.lib().gs_forward(ctxh, C.byref(scene), C.byref(cam), C.byref(cfg), C.byref(out),
-                                                   1 if keep else 0, C.byref(frame_h), C.c_void_p(stream)), "gs_forward")
-        frame = _Frame(context, frame_h, dev, owned=keep)
+        out = _native.GsForwardOut.of(image, depth, acc_alpha, last, count)
+        frame = _Frame.of_call("gs_forward", self._ctxs.of(dev), dev, scene, cam, cfg, out, keep=keep)
         if keep:
             frame.marshalled = (scene, cam, cfg)       # the backward of this frame reads the same tensors (Kmat is kept alive below)
             frame._keepalive = Kmat
@@ -343,9 +178,9 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                           ms[1].q_pointcloud_camera, ms[1].t_pointcloud_camera) != (
                 pointcloud.data_ptr() or None, features.data_ptr() or None, mask.data_ptr() or None, obj.data_ptr() or None, pointcloud.shape[0],
                 q.data_ptr() or None, t.data_ptr() or None):
-            ms = self._marshal(pointcloud, features, mask, obj, q, t, camera_info)     # storage was swapped since the forward (p.data = ...)
-        scene, cam, _ = ms
-        cfg = self._c_config()          # read again: the grad factors (and bwd_reference_order) may have changed since the forward
+            ms = _marshal(self.config, pointcloud, features, mask, obj, q, t, camera_info)   # storage was swapped since the forward (p.data = ...)
+        scene, cam = ms[0], ms[1]       # (a re-marshalled ms[3], the intrinsics, lives in `ms` until this call returns)
+        cfg = _native.GsConfig.of(self.config)     # read again: the grad factors (and bwd_reference_order) may have changed since the forward
         if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (H, W, 3):
             raise ValueError("grad of rasterized_image must be float32 (H,W,3)")
         # one allocation for both gradients so that data-parallel training all-reduces ONE buffer; the 56-float rows
@@ -372,19 +207,20 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
             n_aff, h_ids, h_ntiles = parts[9].view(torch.int32), parts[10].view(torch.int32), parts[11].view(torch.int32)
         ctrl = None
         if self.controller_accumulators is not None and want_points:
-            ca = self.controller_accumulators
-            ca.validate(N, dev)
-            ctrl = _native.GsControllerAccumulators(
-                _ptr(ca.accumulated_num_in_camera), _ptr(ca.accumulated_num_pixels),
-                _ptr(ca.accumulated_view_space_position_gradients), _ptr(ca.accumulated_view_space_position_gradients_avg),
-                _ptr(ca.accumulated_position_gradients), _ptr(ca.accumulated_position_gradients_norm))
-        out = _native.GsBackwardOut(_ptr(grad_pc), _ptr(grad_feat), _ptr(grad_uv), _ptr(mag), _ptr(mag_img), _ptr(n_aff),
-                                    _ptr(h_pc), _ptr(h_feat), _ptr(h_uv), _ptr(h_mag),
-                                    C.pointer(ctrl) if ctrl is not None and N > 0 else None,
-                                    _ptr(h_ids), _ptr(h_ntiles), _ptr(h_depth), _ptr(h_puv), _ptr(grad_q), _ptr(grad_t))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        extra = None
-        if grad_depth is not None or grad_alpha is not None:
+            self.controller_accumulators.validate(N, dev)
+            if N > 0:
+                ctrl = _native.GsControllerAccumulators.of(self.controller_accumulators)
+        out = _native.GsBackwardOut.of(
+            controller=ctrl, grad_pointcloud=grad_pc, grad_pointcloud_features=grad_feat, grad_viewspace=grad_uv,
+            magnitude_grad_viewspace=mag, magnitude_grad_viewspace_on_image=mag_img, num_affected_pixels=n_aff,
+            hook_grad_point_in_camera=h_pc, hook_grad_pointfeatures_in_camera=h_feat, hook_grad_viewspace=h_uv,
+            hook_magnitude_grad_viewspace=h_mag, hook_point_id_in_camera_list=h_ids, hook_num_overlap_tiles=h_ntiles,
+            hook_point_depth=h_depth, hook_point_uv_in_camera=h_puv, grad_q_pointcloud_camera=grad_q, grad_t_pointcloud_camera=grad_t)
+        ptr, ctxh = _native.ptr, self._ctx_for(dev)
+        if grad_depth is None and grad_alpha is None:
+            _native.call("gs_backward", dev, ctxh, frame.handle, scene, cam, cfg, ptr(grad_image), ptr(acc_alpha), ptr(last),
+                         int(sh_band), out)
+        else:
             if grad_depth is not None and depth is None:
                 raise ValueError("a depth gradient needs the forward's rasterized_depth")
             for g, name in ((grad_depth, "rasterized_depth"), (grad_alpha, "accumulated_alpha")):
@@ -392,16 +228,10 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                     raise ValueError(f"grad of {name} must be float32 (H,W)")
             grad_depth = grad_depth.contiguous() if grad_depth is not None else None
             grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
-            extra = _native.GsBackwardExtra(_ptr(grad_depth), _ptr(depth) if grad_depth is not None else None, _ptr(grad_alpha))
-        with _on_device(dev):
-            if extra is None:
-                _native.check(_native.lib().gs_backward(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
-                                                        _ptr(grad_image), _ptr(acc_alpha), _ptr(last), int(sh_band),
-                                                        C.byref(out), C.c_void_p(stream)), "gs_backward")
-            else:
-                _native.check(_native.lib().gs_backward_ex(self._ctx_for(dev), frame.handle, C.byref(scene), C.byref(cam), C.byref(cfg),
-                                                           _ptr(grad_image), C.byref(extra), _ptr(acc_alpha), _ptr(last), int(sh_band),
-                                                           C.byref(out), C.c_void_p(stream)), "gs_backward_ex")
+            extra = _native.GsBackwardExtra(grad_rasterized_depth=ptr(grad_depth), rasterized_depth=ptr(depth) if grad_depth is not None else None,
+                                            grad_pixel_accumulated_alpha=ptr(grad_alpha))
+            _native.call("gs_backward_ex", dev, ctxh, frame.handle, scene, cam, cfg, ptr(grad_image), extra, ptr(acc_alpha), ptr(last),
+                         int(sh_band), out)
         self.last_backward_extras = dict(grad_viewspace=grad_uv, magnitude_grad_viewspace=mag,
                                          magnitude_grad_viewspace_on_image=mag_img, num_affected_pixels=n_aff)
         if want_hook:                                                                   # RAST:1127-1142

@@ -4,20 +4,16 @@ with the L1 + SSIM part (value and gradient) computed by libgsrast in three HIP 
 (gs_loss_l1_ssim_forward / _backward) instead of pytorch_msssim's conv2d chain + autograd.  SSIM follows
 pytorch_msssim.ssim(data_range=1, size_average=True): 11-tap Gaussian window (sigma 1.5), valid filtering,
 K1 = 0.01, K2 = 0.03.  The scale regulariser is fused as well (gs_scale_regulariser[_grad]): in torch its
-boolean-mask indexing and the sort-based index_put of its backward cost more than the rasteriser's backward."""
-import ctypes as C
+boolean-mask indexing and the sort-based index_put of its backward cost more than the rasteriser's backward.
+The library calls go through _native.call()."""
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
 from . import _native
-
-try:
-    from dataclass_wizard import YAMLWizard as _ConfigBase
-except Exception:  # pragma: no cover
-    class _ConfigBase:
-        pass
+from ._host import _ConfigBase
+from ._native import ptr as _ptr
 
 
 def check_loss_images(predicted, ground_truth):
@@ -64,16 +60,11 @@ class _L1SSIM(torch.autograd.Function):
         check_loss_images(predicted, ground_truth)
         dev = predicted.device
         H, W = int(predicted.shape[1]), int(predicted.shape[2])
-        L = _native.lib()
         terms = torch.empty(3, dtype=torch.float32, device=dev)
-        maps = torch.empty(L.gs_loss_maps_floats(H, W), dtype=torch.float32, device=dev)
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        x, y = _native.GsLossImage.of(predicted), _native.GsLossImage.of(ground_truth)
-        with torch.cuda.device(dev):
-            _native.check(L.gs_loss_l1_ssim_forward(
-                _native.shared_ctx(idx), C.byref(x), C.byref(y), H, W, int(bool(clamp_predicted)), float(lambda_value),
-                C.c_void_p(maps.data_ptr()), C.c_void_p(terms.data_ptr()),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gs_loss_l1_ssim_forward")
+        maps = torch.empty(_native.lib().gs_loss_maps_floats(H, W), dtype=torch.float32, device=dev)
+        _native.call("gs_loss_l1_ssim_forward", dev, _native.shared_ctx(dev),
+                     _native.GsLossImage.of(predicted), _native.GsLossImage.of(ground_truth), H, W, int(bool(clamp_predicted)),
+                     float(lambda_value), _ptr(maps), _ptr(terms))
         ctx.save_for_backward(predicted, ground_truth, maps)
         ctx.lambda_value, ctx.clamp_predicted = float(lambda_value), int(bool(clamp_predicted))
         ctx.mark_non_differentiable(terms)
@@ -90,13 +81,9 @@ class _L1SSIM(torch.autograd.Function):
         # (preserve_format: the input's strides when it is dense and non-overlapping, contiguous otherwise)
         grad = torch.empty_like(predicted, memory_format=torch.preserve_format)
         up = grad_loss.reshape(1).to(torch.float32).contiguous()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        x, y, g = _native.GsLossImage.of(predicted), _native.GsLossImage.of(ground_truth), _native.GsLossImage.of(grad)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().gs_loss_l1_ssim_backward(
-                _native.shared_ctx(idx), C.byref(x), C.byref(y), H, W, ctx.clamp_predicted, ctx.lambda_value,
-                C.c_void_p(maps.data_ptr()), C.c_void_p(up.data_ptr()), C.byref(g),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gs_loss_l1_ssim_backward")
+        _native.call("gs_loss_l1_ssim_backward", dev, _native.shared_ctx(dev),
+                     _native.GsLossImage.of(predicted), _native.GsLossImage.of(ground_truth), H, W, ctx.clamp_predicted,
+                     ctx.lambda_value, _ptr(maps), _ptr(up), _native.GsLossImage.of(grad))
         return grad, None, None, None
 
 
@@ -108,11 +95,8 @@ class _ScaleRegulariser(torch.autograd.Function):
         mask = check_regulariser_inputs(features, invalid_mask)
         dev = features.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().gs_scale_regulariser(
-                _native.shared_ctx(idx), C.c_void_p(features.data_ptr()), C.c_void_p(mask.data_ptr()), features.shape[0],
-                C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gs_scale_regulariser")
+        _native.call("gs_scale_regulariser", dev, _native.shared_ctx(dev), _ptr(features), _ptr(mask),
+                     features.shape[0], _ptr(out))
         ctx.save_for_backward(features, mask, out)
         return out[0]
 
@@ -122,12 +106,8 @@ class _ScaleRegulariser(torch.autograd.Function):
         dev = features.device
         grad = torch.empty_like(features)
         up = upstream.reshape(1).to(torch.float32).contiguous()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().gs_scale_regulariser_grad(
-                _native.shared_ctx(idx), C.c_void_p(features.data_ptr()), C.c_void_p(mask.data_ptr()), features.shape[0],
-                C.c_void_p(out.data_ptr()), C.c_void_p(up.data_ptr()), C.c_void_p(grad.data_ptr()),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gs_scale_regulariser_grad")
+        _native.call("gs_scale_regulariser_grad", dev, _native.shared_ctx(dev), _ptr(features), _ptr(mask),
+                     features.shape[0], _ptr(out), _ptr(up), _ptr(grad))
         return grad, None
 
 

@@ -2,11 +2,19 @@
 
 The library is hand-written HIP for gfx950; there is no CPU or PyTorch fallback.  If it
 is missing or does not load, every entry point of this package raises -- loudly.
+
+This is the only module of the package that knows ctypes.  Every status-returning library call goes through call(), which
+makes the device current, passes the current stream and raises on a non-zero status; every argument struct is filled by the
+`of` classmethod next to its fields, by field name.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
 import sys
+
+import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSRAST_LIB selects another build of the same library (e.g. the counter-instrumented `make stats` one); no other fallback
@@ -16,26 +24,55 @@ ABI_VERSION = 9
 _I64, _I32, _F32, _VP = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 
 
+def ptr(t):
+    """The device pointer of a tensor as a c_void_p field or argument takes it; None (NULL) for no tensor or an empty one."""
+    return t.data_ptr() if t is not None and t.numel() > 0 else None
+
+
 class GsConfig(C.Structure):
     _fields_ = [("near_plane", _F32), ("far_plane", _F32), ("depth_to_sort_key_scale", _F32),
                 ("rgb_only", _I32), ("grad_color_factor", _F32), ("grad_high_order_color_factor", _F32),
                 ("grad_s_factor", _F32), ("grad_q_factor", _F32), ("grad_alpha_factor", _F32),
                 ("allow_partial_tiles", _I32), ("bwd_reference_order", _I32)]
 
+    @classmethod
+    def of(cls, c):
+        """c: a GaussianPointCloudRasterisationConfig, whose float fields carry the names of this struct's"""
+        return cls(rgb_only=1 if c.rgb_only else 0, allow_partial_tiles=1 if getattr(c, "allow_partial_tiles", False) else 0,
+                   bwd_reference_order=1 if getattr(c, "backward_reference_order", False) else 0,
+                   **{name: getattr(c, name) for name, kind in cls._fields_ if kind is _F32})
+
 
 class GsScene(C.Structure):
+    """gs_scene, and gs_density_scene (the same layout, edited in place by gs_density_apply)"""
     _fields_ = [("point_cloud", _VP), ("point_cloud_features", _VP), ("point_invalid_mask", _VP),
                 ("point_object_id", _VP), ("n_points", _I64)]
+
+    @classmethod
+    def of(cls, point_cloud, features, invalid_mask, object_id):
+        return cls(point_cloud=ptr(point_cloud), point_cloud_features=ptr(features), point_invalid_mask=ptr(invalid_mask),
+                   point_object_id=ptr(object_id), n_points=point_cloud.shape[0])
 
 
 class GsCamera(C.Structure):
     _fields_ = [("q_pointcloud_camera", _VP), ("t_pointcloud_camera", _VP), ("n_objects", _I32),
                 ("camera_intrinsics", _VP), ("camera_height", _I32), ("camera_width", _I32)]
 
+    @classmethod
+    def of(cls, camera_info, q=None, t=None, intrinsics=None):
+        """Without poses and intrinsics: the image size alone, all that gs_forward_projected reads."""
+        return cls(q_pointcloud_camera=ptr(q), t_pointcloud_camera=ptr(t), n_objects=1 if q is None else q.shape[0],
+                   camera_intrinsics=ptr(intrinsics), camera_height=camera_info.camera_height, camera_width=camera_info.camera_width)
+
 
 class GsForwardOut(C.Structure):
     _fields_ = [("rasterized_image", _VP), ("rasterized_depth", _VP), ("pixel_accumulated_alpha", _VP),
                 ("pixel_offset_of_last_effective_point", _VP), ("pixel_valid_point_count", _VP)]
+
+    @classmethod
+    def of(cls, image, depth, accumulated_alpha, last, count):
+        return cls(rasterized_image=ptr(image), rasterized_depth=ptr(depth), pixel_accumulated_alpha=ptr(accumulated_alpha),
+                   pixel_offset_of_last_effective_point=ptr(last), pixel_valid_point_count=ptr(count))
 
 
 class GsFrameInfo(C.Structure):
@@ -63,6 +100,11 @@ class GsControllerAccumulators(C.Structure):
                 ("accumulated_view_space_position_gradients_avg", _VP),
                 ("accumulated_position_gradients", _VP), ("accumulated_position_gradients_norm", _VP)]
 
+    @classmethod
+    def of(cls, a):
+        """a: a ControllerAccumulators, whose six tensors carry the names of the fields"""
+        return cls(**{name: ptr(getattr(a, name)) for name, _ in cls._fields_})
+
 
 class GsBackwardOut(C.Structure):
     _fields_ = [("grad_pointcloud", _VP), ("grad_pointcloud_features", _VP), ("grad_viewspace", _VP),
@@ -72,6 +114,13 @@ class GsBackwardOut(C.Structure):
                 ("hook_magnitude_grad_viewspace", _VP), ("controller", C.POINTER(GsControllerAccumulators)),
                 ("hook_point_id_in_camera_list", _VP), ("hook_num_overlap_tiles", _VP), ("hook_point_depth", _VP),
                 ("hook_point_uv_in_camera", _VP), ("grad_q_pointcloud_camera", _VP), ("grad_t_pointcloud_camera", _VP)]
+
+    @classmethod
+    def of(cls, controller=None, **tensors):
+        """tensors: the output arrays by field name (None allowed); every field not named stays NULL.
+        controller: a GsControllerAccumulators or None."""
+        return cls(controller=C.pointer(controller) if controller is not None else None,
+                   **{name: ptr(t) for name, t in tensors.items()})
 
 
 class GsBackwardExtra(C.Structure):
@@ -90,16 +139,22 @@ class GsDensityConfig(C.Structure):
                 ("floater_depth_threshold", _F32), ("under_reconstructed_num_pixels_threshold", _I32),
                 ("under_reconstructed_move_factor", _F32), ("enable_ellipsoid_offset", _I32), ("enable_sample_from_point", _I32)]
 
+    @classmethod
+    def of(cls, c):
+        """c: a GaussianPointAdaptiveControllerConfig, whose float thresholds carry the names of this struct's.  The pixel
+        thresholds are integers on the device, and log(phi) is taken here and rounded once."""
+        floor_int = lambda v: int(max(min(np.floor(v), 2 ** 31 - 1), -2 ** 31))   # int32 > x  <=>  int32 > floor(x)
+        return cls(log_gaussian_split_factor_phi=float(np.float32(np.log(c.gaussian_split_factor_phi))),   # CTRL:255 np.log, then stored as f32
+                   floater_near_camrea_num_pixels_threshold=floor_int(c.floater_near_camrea_num_pixels_threshold),
+                   under_reconstructed_num_pixels_threshold=floor_int(c.under_reconstructed_num_pixels_threshold),
+                   enable_ellipsoid_offset=1 if c.enable_ellipsoid_offset else 0, enable_sample_from_point=1 if c.enable_sample_from_point else 0,
+                   **{name: getattr(c, name) for name, kind in cls._fields_ if kind is _F32 and name != "log_gaussian_split_factor_phi"})
+
 
 class GsDensityPlan(C.Structure):
     _fields_ = [("flags", _VP), ("densify_point_id", _VP), ("densify_point_position_before_optimization", _VP),
                 ("densify_point_grad_position", _VP), ("densify_size_reduction_factor", _VP), ("fill_point_id", _VP),
                 ("scratch", _VP), ("counts", _VP), ("n_points", _I64)]
-
-
-class GsDensityScene(C.Structure):
-    _fields_ = [("point_cloud", _VP), ("point_cloud_features", _VP), ("point_invalid_mask", _VP),
-                ("point_object_id", _VP), ("n_points", _I64)]
 
 
 # gs_density_plan.flags bits and gs_density_count indices (include/gs_rasterizer.h)
@@ -225,7 +280,7 @@ def lib():
     L.gs_density_scratch_bytes.restype = _I64
     L.gs_density_select.argtypes = [_VP, C.POINTER(GsScene), C.POINTER(GsControllerAccumulators), _VP, _VP, _VP, _VP, _I64, _I32,
                                     C.POINTER(GsDensityConfig), C.POINTER(GsDensityPlan), _VP]
-    L.gs_density_apply.argtypes = [_VP, C.POINTER(GsDensityScene), C.POINTER(GsDensityConfig), C.POINTER(GsDensityPlan), C.c_uint64,
+    L.gs_density_apply.argtypes = [_VP, C.POINTER(GsScene), C.POINTER(GsDensityConfig), C.POINTER(GsDensityPlan), C.c_uint64,
                                    C.c_uint32, _VP]
     L.gs_controller_accumulate.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _I64, C.POINTER(GsControllerAccumulators), _VP]
     if L.gs_abi_version() != ABI_VERSION:
@@ -240,6 +295,50 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
 
 
+def device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+_ALREADY_CURRENT = contextlib.nullcontext()
+
+
+def on_device(device):
+    """torch.cuda.device(device) only when it is not already current (the context manager costs microseconds per call).  The
+    library sets the HIP device of its context on entry and does not restore it: every call runs under this guard."""
+    if device.index is None or torch.cuda.current_device() == device.index:
+        return _ALREADY_CURRENT
+    return torch.cuda.device(device)
+
+
+# the status-returning calls that take no gs_stream (every other one takes it as its last argument)
+_STREAMLESS = frozenset(["gs_create", "gs_destroy", "gs_frame_get_info", "gs_frame_release", "gs_profile_enable", "gs_profile_read"])
+
+
+def call(name, device, *args, what=None):
+    """The library call `name`(*args[, current stream of device]) with `device` current; raises RuntimeError on a non-zero
+    status (`what` replaces the name in the message).  device None: for the calls that neither launch nor wait (gs_create,
+    gs_frame_release), which need no device and take no stream.  Structures are passed by reference, None is NULL."""
+    fn = getattr(lib(), name)
+    if device is None:
+        rc = fn(*args)
+    else:
+        if name not in _STREAMLESS:
+            args += (torch.cuda.current_stream(device).cuda_stream,)
+        with on_device(device):
+            rc = fn(*args)
+    check(rc, what or name)
+
+
+def frame_out():
+    """The gs_frame** argument of the forward-type calls: receives the ticket."""
+    return C.c_void_p()
+
+
+def int32_pair():
+    """The int32[2] argument of gs_frame_heavy_tiles."""
+    return (C.c_int32 * 2)(0, 0)
+
+
 class Context:
     """Owner of one gs_ctx.  Everything that can outlive the operator module -- above all the frame handles autograd keeps
     between forward and backward -- holds a strong reference to this object, and gs_destroy runs only from its finaliser,
@@ -248,7 +347,7 @@ class Context:
     def __init__(self, device_index: int):
         self.handle = C.c_void_p()
         self.device_index = device_index
-        check(lib().gs_create(device_index, C.byref(self.handle)), "gs_create")
+        call("gs_create", None, device_index, self.handle)
 
     def __del__(self):
         try:
@@ -262,8 +361,9 @@ class Context:
 _shared_ctx = {}
 
 
-def shared_ctx(device_index: int):
-    """A process-wide gs_ctx per device for the stateless helpers (loss, Adam)."""
-    if device_index not in _shared_ctx:
-        _shared_ctx[device_index] = Context(device_index)
-    return _shared_ctx[device_index].handle
+def shared_ctx(device):
+    """A process-wide gs_ctx per device (a torch.device or a device index) for the stateless helpers (loss, Adam)."""
+    idx = device if isinstance(device, int) else device_index(device)
+    if idx not in _shared_ctx:
+        _shared_ctx[idx] = Context(idx)
+    return _shared_ctx[idx].handle

@@ -1,13 +1,13 @@
 """FusedAdam -- torch.optim.Adam(params, lr, betas=(0.9, 0.999)) as the reference trainer uses it for the
 feature and position tensors (GaussianPointTrainer.py:131-134, 183-184), one HIP launch per tensor
 (gs_adam_step) instead of torch's multi-kernel foreach path.  `lr` is a plain attribute so an exponential
-decay (GaussianPointTrainer.py:136-137,191-192) is `opt.lr *= rate`."""
-import ctypes as C
+decay (GaussianPointTrainer.py:136-137,191-192) is `opt.lr *= rate`.  The library call goes through _native.call()."""
 from typing import Iterable
 
 import torch
 
 from . import _native
+from ._native import ptr as _ptr
 
 
 class FusedAdam:
@@ -28,16 +28,11 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self):
-        L = _native.lib()
         for p, st in zip(self.params, self.state):
             if p.grad is None:
                 continue
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             st["step"] += 1
-            dev = p.device
-            idx = dev.index if dev.index is not None else torch.cuda.current_device()
-            with torch.cuda.device(dev):
-                _native.check(L.gs_adam_step(_native.shared_ctx(idx), C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()),
-                                             C.c_void_p(st["exp_avg"].data_ptr()), C.c_void_p(st["exp_avg_sq"].data_ptr()),
-                                             p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, st["step"],
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gs_adam_step")
+            _native.call("gs_adam_step", p.device, _native.shared_ctx(p.device), _ptr(p), _ptr(g),
+                         _ptr(st["exp_avg"]), _ptr(st["exp_avg_sq"]), p.numel(), self.lr, self.betas[0], self.betas[1], self.eps,
+                         st["step"])

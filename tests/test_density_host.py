@@ -1,6 +1,5 @@
 """CPU: the pieces of the on-device adaptive density controller that need no GPU -- the Philox4x32-10 restatement
-the device stream is checked against, the ctypes mirrors of the new ABI structs, and the config defaults."""
-import ctypes as C
+the device stream is checked against and the config defaults (the ABI structs are probed in test_abi.py)."""
 import dataclasses
 import os
 import subprocess
@@ -13,7 +12,6 @@ import torch
 from density_ref import philox4x32_10_numpy, philox4x32_10_torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gs_rasterizer.h")
 
 # Random123's known-answer vectors for philox4x32 with 10 rounds (kat_vectors)
 KAT = [
@@ -36,40 +34,6 @@ def test_philox_torch_and_numpy_agree_on_many_counters():
     a = philox4x32_10_numpy(ctr, key)
     b = philox4x32_10_torch(torch.tensor(ctr.astype(np.int64)), key).numpy().astype(np.uint32)
     assert np.array_equal(a, b)
-
-
-def test_density_struct_layouts_match_the_header(tmp_path):
-    from taichi_3d_gaussian_splatting_amd import _native
-    structs = {"gs_density_config": _native.GsDensityConfig, "gs_density_plan": _native.GsDensityPlan,
-               "gs_density_scene": _native.GsDensityScene, "gs_controller_accumulators": _native.GsControllerAccumulators}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void){']
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    for name in ["GS_DENSITY_FLOATER", "GS_DENSITY_TRANSPARENT", "GS_DENSITY_DENSIFY", "GS_DENSITY_OVER", "GS_DENSITY_CAM_FLOATER",
-                 "GS_DENSITY_CAM_SINGLE", "GS_DENSITY_CAM_VIEWSPACE", "GS_DC_COUNT_", "GS_ABI_VERSION"]:
-        lines.append(f'printf("{name} %d\\n", (int){name});')
-    lines.append("return 0; }")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", str(src), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
-    for cname, cls in structs.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        # every field of the header struct is mirrored, in order
-        for fname, _ in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
-    assert int(got["GS_DENSITY_FLOATER"]) == _native.DENSITY_FLOATER
-    assert int(got["GS_DENSITY_TRANSPARENT"]) == _native.DENSITY_TRANSPARENT
-    assert int(got["GS_DENSITY_DENSIFY"]) == _native.DENSITY_DENSIFY
-    assert int(got["GS_DENSITY_OVER"]) == _native.DENSITY_OVER
-    assert int(got["GS_DENSITY_CAM_FLOATER"]) == _native.DENSITY_CAM_FLOATER
-    assert int(got["GS_DENSITY_CAM_SINGLE"]) == _native.DENSITY_CAM_SINGLE
-    assert int(got["GS_DENSITY_CAM_VIEWSPACE"]) == _native.DENSITY_CAM_VIEWSPACE
-    assert int(got["GS_DC_COUNT_"]) == len(_native.DENSITY_COUNTS)
-    assert int(got["GS_ABI_VERSION"]) == _native.ABI_VERSION == 9
 
 
 def test_density_symbols_are_bound_and_not_timed_kernels():
@@ -106,9 +70,9 @@ def test_config_defaults_equal_the_reference():
 
 def test_device_config_rounds_like_torch():
     """What the kernels compare against: f32 thresholds, log(phi) rounded once on the host, integer pixel thresholds."""
-    from taichi_3d_gaussian_splatting_amd import GaussianPointAdaptiveController as Ctl
+    from taichi_3d_gaussian_splatting_amd import GaussianPointAdaptiveController as Ctl, _native
     cfg = Ctl.GaussianPointAdaptiveControllerConfig(under_reconstructed_num_pixels_threshold=511.5)
-    c = Ctl._c_config(type("X", (), {"config": cfg})())
+    c = _native.GsDensityConfig.of(cfg)
     assert c.log_gaussian_split_factor_phi == float(np.float32(np.log(1.6)))
     assert c.densification_view_space_position_gradients_threshold == float(np.float32(6e-6))
     assert c.under_reconstructed_num_pixels_threshold == 511          # int > 511.5  <=>  int > 511

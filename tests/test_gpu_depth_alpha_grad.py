@@ -17,7 +17,7 @@ import torch
 import depth_alpha_ref as R
 import parity_util as P
 from oracle import oracle
-from taichi_3d_gaussian_splatting_amd import _native
+from taichi_3d_gaussian_splatting_amd import _host, _native
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, synth_clustered, view_pose
 from test_gpu_pose_grad import ELEM_FLOOR, ELEM_RTOL, SCENES, TENSOR_TOL, _scene, _tiny
 
@@ -327,8 +327,7 @@ def test_argument_errors():
     outs = module(inp)
     fr = module.last_frame
     dev = inp.point_cloud.device
-    scene, cam, cfg = module._marshal(inp.point_cloud, inp.point_cloud_features, inp.point_invalid_mask, inp.point_object_id,
-                                      inp.q_pointcloud_camera, inp.t_pointcloud_camera, inp.camera_info)
+    scene, cam, cfg, _intrinsics = _host._marshal_input(module.config, inp)
     N = s.point_cloud.shape[0]
     gpc, gfeat = torch.zeros(N, 3, device=dev), torch.zeros(N, 56, device=dev)
     img = torch.zeros(s.height, s.width, 3, device=dev)

@@ -491,8 +491,8 @@ def test_partial_tiles_switch_off_is_the_reference_contract(P):
     L = _native.lib()
     import ctypes as C
     ctx = _native.shared_ctx(0)
-    cfg = module._c_config()
-    scene = module._c_scene(inp.point_cloud, inp.point_cloud_features, inp.point_invalid_mask, inp.point_object_id)
+    cfg = _native.GsConfig.of(module.config)
+    scene = _native.GsScene.of(inp.point_cloud, inp.point_cloud_features, inp.point_invalid_mask, inp.point_object_id)
     out = torch.empty(5, 40, 40, 3, device=P.DEV)
     cam = _native.GsCamera(inp.q_pointcloud_camera.data_ptr(), inp.t_pointcloud_camera.data_ptr(), 1,
                            inp.camera_info.camera_intrinsics.data_ptr(), 40, 40)

@@ -10,7 +10,7 @@ import torch
 import parity_util as P
 import pose_ref
 from oracle import oracle
-from taichi_3d_gaussian_splatting_amd import _native
+from taichi_3d_gaussian_splatting_amd import _host, _native
 from taichi_3d_gaussian_splatting_amd.controller_stats import ControllerAccumulators
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
 
@@ -259,8 +259,7 @@ def test_staged_path_refuses_pose_gradients():
     module(inp)
     fr = module.last_frame
     dev = inp.point_cloud.device
-    scene, cam, cfg = module._marshal(inp.point_cloud, inp.point_cloud_features, inp.point_invalid_mask, inp.point_object_id,
-                                      inp.q_pointcloud_camera, inp.t_pointcloud_camera, inp.camera_info)
+    scene, cam, cfg, _intrinsics = _host._marshal_input(module.config, inp)
     N, M = s.point_cloud.shape[0], fr.n_points_in_camera
     gpc = torch.zeros(N, 3, device=dev)
     gfeat = torch.zeros(N, 56, device=dev)
