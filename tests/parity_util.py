@@ -1,13 +1,14 @@
-"""Shared helpers of the GPU parity tests: run the HIP operator (through the C ABI) and the
-CPU oracle on the same inputs and compare every product."""
+"""Shared helpers of the parity and gradient tests: the scenes, the operator and its input, the CPU oracle on the same
+inputs, the bars and the comparisons of every product.  Nothing here touches the GPU at import."""
+import os
+
 import numpy as np
 import torch
 
+import torch_ref
 from oracle import oracle
 from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
-
-import os
 
 Rast = GaussianPointCloudRasterisation
 DEV = "cuda:0"
@@ -19,7 +20,23 @@ FLOAT_EXPORTS = ["point_uv", "point_in_camera", "point_uv_conic_and_rescale", "p
                  "point_color", "point_radii"]
 
 
-def make_input(scene, q, t, band=3, requires_grad=True):
+UNIT_FACTORS = dict(grad_color_factor=1.0, grad_high_order_color_factor=1.0, grad_s_factor=1.0, grad_q_factor=1.0,
+                    grad_alpha_factor=1.0)
+
+
+def module(partial=False, strict=False, depth=False, hook=None, ctrl=None, **factors):
+    """The operator with allow_partial_tiles, backward_reference_order, differentiable_depth and any grad factors set"""
+    cfg = Rast.GaussianPointCloudRasterisationConfig()
+    cfg.allow_partial_tiles = bool(partial)
+    cfg.backward_reference_order = bool(strict)
+    cfg.differentiable_depth = bool(depth)
+    for k, v in factors.items():
+        setattr(cfg, k, v)
+    return Rast(cfg, backward_valid_point_hook=hook, controller_accumulators=ctrl)
+
+
+def make_input(scene, q, t, band=3, requires_grad=True, pose=False):
+    """requires_grad: of the points and their features; pose: of q_pointcloud_camera and t_pointcloud_camera"""
     pc = torch.tensor(scene.point_cloud, device=DEV, requires_grad=requires_grad)
     feat = torch.tensor(scene.point_cloud_features, device=DEV, requires_grad=requires_grad)
     inp = Rast.GaussianPointCloudRasterisationInput(
@@ -28,14 +45,30 @@ def make_input(scene, q, t, band=3, requires_grad=True):
         point_invalid_mask=torch.tensor(scene.point_invalid_mask, device=DEV),
         camera_info=CameraInfo(camera_intrinsics=torch.tensor(scene.camera_intrinsics, device=DEV),
                                camera_height=scene.height, camera_width=scene.width, camera_id=0),
-        q_pointcloud_camera=torch.tensor(q, device=DEV), t_pointcloud_camera=torch.tensor(t, device=DEV),
-        color_max_sh_band=band)
+        q_pointcloud_camera=torch.tensor(q, device=DEV, requires_grad=pose),
+        t_pointcloud_camera=torch.tensor(t, device=DEV, requires_grad=pose), color_max_sh_band=band)
     return inp
 
 
 def run_oracle(scene, q, t, cfg=None):
     return oracle.forward(scene.point_cloud, scene.point_cloud_features, scene.point_invalid_mask,
                           scene.point_object_id, q, t, scene.camera_intrinsics, scene.height, scene.width, cfg)
+
+
+def oracle_frame(scene, q, t, partial):
+    """-> (Forward, features_after) of the oracle with its default config, for a frame that blends something"""
+    f, feat_after = run_oracle(scene, q, t, oracle.default_config(allow_partial_tiles=int(partial)))
+    assert f.K > 0
+    return f, feat_after
+
+
+def bits(x):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return a.view(np.uint8) if a.dtype != np.bool_ else a
+
+
+def assert_same_bits(a, b, what=None):
+    assert np.array_equal(bits(a), bits(b)), what
 
 
 IMAGE_TOL = 2e-6      # max |a - ref| / max |ref| of the blended images (fused multiply-adds, shared weight alpha*T)
@@ -151,6 +184,67 @@ def assert_backward_parity(module, inp, g_image, f, band, extras=None, cfg=None,
     return b
 
 
+def assert_pose_gradient_parity(scene, q, t, partial, gq, gt, g_image=None, g_depth=None, g_alpha=None, per_element=True):
+    """grad_q (K,4) and grad_t (K,3) against torch_ref.pose_gradients for the given upstreams: GRAD_TOL of the tensor maximum;
+    per element within ELEM_RTOL of its value plus ELEM_FLOOR of the summed per-point magnitudes; rows no visible point depends
+    on exactly zero.  -> the reference's (grad_q, grad_t)"""
+    f, feat_after = oracle_frame(scene, q, t, partial)
+    rq, rt, sq, st = torch_ref.pose_gradients(scene, q, t, f, feat_after, g_image, g_depth, g_alpha)
+    for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
+        assert a.shape == ref.shape, name
+        scale = np.abs(ref).max()
+        assert scale > 0, name
+        err = np.abs(a.astype(np.float64) - ref)
+        assert err.max() / scale < GRAD_TOL, (name, err.max() / scale, a, ref)
+        if per_element:
+            bar = ELEM_RTOL * np.abs(ref) + ELEM_FLOOR * summed
+            assert np.all(err <= bar), (name, (err / np.maximum(bar, 1e-300)).max(), a, ref)
+        assert not a[summed == 0].any(), name          # rows no touched point depends on: exact zeros
+    return rq, rt
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------
+def tiny_case(seed, n, sigma0, width=32, height=None):
+    """A scene small enough for torch_ref, under a pose whose quaternion is deliberately not unit -> (scene, q, t, partial)"""
+    height = width if height is None else height
+    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
+    ang = 0.05
+    q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32)
+    t = np.array([[0.03, -0.02, 0.1]], np.float32)
+    return s, q, t, int(width % 16 != 0 or height % 16 != 0)
+
+
+# the scenes of the float64 gradient comparisons: the four of test_oracle_autograd and three of the soak
+SCENES = [("tiny", (0, 48, 0.25, 32, 32)), ("tiny", (1, 64, 0.6, 32, 32)), ("tiny", (2, 24, 1.2, 32, 32)),
+          ("tiny", (3, 56, 0.5, 41, 27)), ("soak", 29), ("soak", 54), ("soak", 182)]
+
+
+def scene_case(kind, arg):
+    """An entry of SCENES -> (scene, q, t, partial)"""
+    if kind == "tiny":
+        return tiny_case(*arg)
+    c = soak_case(arg)
+    return c["scene"], c["q"], c["t"], c["partial"]
+
+
+def dense_corner_scene():
+    """26000 splats at 208x160 with 6000 translucent ones piled on a corner region: lists of thousands of entries there, a few
+    hundred elsewhere"""
+    rng = np.random.default_rng(88)
+    s = synth(26000, 208, 160, 0.02, sh_deg=3, seed=88)
+    s.point_cloud[:6000, 0] = rng.uniform(-0.9, -0.4, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
+    s.point_cloud[:6000, 1] = rng.uniform(-0.7, -0.3, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
+    s.point_cloud_features[:6000, 4:7] = np.log(rng.uniform(0.05, 0.15, (6000, 3))).astype(np.float32)
+    s.point_cloud_features[:6000, 7] = rng.uniform(-5.0, -2.5, 6000).astype(np.float32)
+    return s
+
+
+def default_heavy_policy():
+    """False when the suite runs under one of the library's diagnostic switches, which replace the default policy of heavy
+    tiles and segments that some tests assert"""
+    return not any(k in os.environ for k in ("GS_BWD_SPLIT_HEAVY", "GS_BWD_SEGMENTS", "GS_BWD_HEAVY_X2"))
+
+
 # ---- the randomised scenes of tools/parity_soak.py (also the source of the two seeds kept in the suite) ------------
 def soak_case(seed):
     """Seeded scene + pose + config of the parity soak: image sizes 16..640 (half of them not multiples of 16),
@@ -169,14 +263,3 @@ def soak_case(seed):
     q = np.array([[ang[0], ang[1], ang[2], 1.0]], np.float32) * float(rng.uniform(0.5, 2.0))    # deliberately not unit
     t = rng.normal(0, 0.3, (1, 3)).astype(np.float32)
     return dict(scene=s, q=q, t=t, band=band, partial=partial, rng=rng, W=W, H=H, n=n, sigma0=sigma0)
-
-
-def float64_autograd_gradients(scene, q, t, f, feat_after, g_image):
-    """Gradients of tests/torch_ref.py (float64 torch.autograd restatement, CPU) for the oracle frame f: (xyz, features);
-    all grad factors 1, all SH bands."""
-    import torch_ref
-    pc = torch.tensor(scene.point_cloud, dtype=torch.float64, requires_grad=True)
-    ft = torch.tensor(feat_after, dtype=torch.float64, requires_grad=True)
-    img, _ = torch_ref.render(pc, ft, q, t, scene.camera_intrinsics, scene.height, scene.width, f)
-    img.backward(torch.as_tensor(g_image, dtype=torch.float64))
-    return pc.grad.numpy(), ft.grad.numpy()

@@ -1,5 +1,5 @@
 """GPU (-m gpu): differentiable depth (config.differentiable_depth) and accumulated alpha (forward(...,
-return_accumulated_alpha=True)), i.e. gs_backward_ex, against the float64 reference of tests/depth_alpha_ref.py; that the
+return_accumulated_alpha=True)), i.e. gs_backward_ex, against the float64 reference of tests/torch_ref.py; that the
 switch changes nothing while the depth is unused; determinism; the hook, controller and pose paths; heavy tiles.
 
 Bars.  Pose gradients: those of test_gpu_pose_grad (1e-4 of the tensor maximum; per element 2e-5 |ref| + 5e-6 of the summed
@@ -9,39 +9,20 @@ per-tile sum is not such a bound -- the CPU oracle itself misses it against this
 f32 keep / skip decisions of splats at the 1/255 edge can differ from float64 ones, so "no contribution" is not compared.)  The
 point-gradient references assume all grad factors 1 unless stated, and every SH band."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
-import depth_alpha_ref as R
 import parity_util as P
-from oracle import oracle
+import torch_ref
 from taichi_3d_gaussian_splatting_amd import _host, _native
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, synth_clustered, view_pose
-from test_gpu_pose_grad import ELEM_FLOOR, ELEM_RTOL, SCENES, TENSOR_TOL, _scene, _tiny
 
 pytestmark = pytest.mark.gpu
 
-UNIT = dict(grad_color_factor=1.0, grad_high_order_color_factor=1.0, grad_s_factor=1.0, grad_q_factor=1.0, grad_alpha_factor=1.0)
-GROUPS = [(0, 4, "q"), (4, 7, "s"), (7, 8, "opacity"), (8, 56, "sh")]
-
-
-def _module(partial=False, strict=False, depth=True, hook=None, ctrl=None, **factors):
-    cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-    cfg.allow_partial_tiles = bool(partial)
-    cfg.backward_reference_order = bool(strict)
-    cfg.differentiable_depth = bool(depth)
-    for k, v in factors.items():
-        setattr(cfg, k, v)
-    return P.Rast(cfg, backward_valid_point_hook=hook, controller_accumulators=ctrl)
-
-
-def _input(scene, q, t, points=True, pose=False, band=3):
-    inp = P.make_input(scene, q, t, band, requires_grad=points)
-    inp.q_pointcloud_camera.requires_grad_(pose)
-    inp.t_pointcloud_camera.requires_grad_(pose)
-    return inp
+_depth_module = functools.partial(P.module, depth=True)          # config.differentiable_depth on, unless a test says otherwise
 
 
 def _upstream(shape, seed, positive=False):
@@ -68,12 +49,6 @@ def _run(module, inp, which, seed=0, retain=False, positive=False):
     return ups, outs
 
 
-def _oracle_frame(scene, q, t, partial):
-    f, feat_after = P.run_oracle(scene, q, t, oracle.default_config(allow_partial_tiles=int(partial)))
-    assert f.K > 0
-    return f, feat_after
-
-
 def _scaled(gf, band, factors):
     """the reference's band mask and grad factors applied to a float64 feature gradient (RAST:1102-1125, 1167-1182)"""
     keep = {0: 1, 1: 4, 2: 9}.get(band, 16)
@@ -90,23 +65,23 @@ def _scaled(gf, band, factors):
 
 
 def _check_points(gp, gf, ref_p, ref_f, ids):
-    for name, a, ref in [("xyz", gp, ref_p)] + [(n, gf[:, lo:hi], ref_f[:, lo:hi]) for lo, hi, n in GROUPS]:
+    for name, a, ref in [("xyz", gp, ref_p)] + [(n, gf[:, lo:hi], ref_f[:, lo:hi]) for lo, hi, n in P.GROUPS]:
         scale = np.abs(ref).max()
         err = np.abs(a.astype(np.float64) - ref)
         if scale == 0:
             assert not a.any(), name
             continue
-        assert err.max() / scale < TENSOR_TOL, (name, err.max() / scale)
+        assert err.max() / scale < P.GRAD_TOL, (name, err.max() / scale)
     out = np.setdiff1d(np.arange(gp.shape[0]), ids)                # rows outside the frustum: exact zeros
     assert not gp[out].any() and not gf[out].any()
 
 
 def _reference(scene, q, t, partial, ups):
     """-> (grad_pointcloud, grad_features) of the float64 reference for the upstreams `ups`, and the in-camera ids"""
-    f, feat_after = _oracle_frame(scene, q, t, partial)
+    f, feat_after = P.oracle_frame(scene, q, t, partial)
     g = [ups.get(k) for k in ("image", "depth", "alpha")]
     g = [None if x is None else x.astype(np.float64) for x in g]
-    tp, tf = R.point_gradients(scene, q, t, f, feat_after, *g)
+    tp, tf = torch_ref.point_gradients(scene, q, t, f, feat_after, *g)
     return tp, tf, f.point_id_in_camera_list
 
 
@@ -123,15 +98,15 @@ def _waves_per_tile(monkeypatch, wpt):
 
 @pytest.mark.parametrize("wpt", WAVES_PER_TILE)
 @pytest.mark.parametrize("strict", [False, True])
-@pytest.mark.parametrize("kind,arg", SCENES)
+@pytest.mark.parametrize("kind,arg", P.SCENES)
 @pytest.mark.parametrize("which", ["depth", "alpha"])
 def test_single_output_gradient_matches_float64_reference(which, kind, arg, strict, wpt, monkeypatch):
     """A depth-only (differentiable_depth) or alpha-only loss.  Without this feature the first gives zeros, the second a
     TypeError.  (The colour gradient of both losses is zero: the SH columns are checked to be exactly so.)"""
     _waves_per_tile(monkeypatch, wpt)
-    s, q, t, partial = _scene(kind, arg)
-    module = _module(partial, strict, **UNIT)
-    inp = _input(s, q, t)
+    s, q, t, partial = P.scene_case(kind, arg)
+    module = _depth_module(partial, strict, **P.UNIT_FACTORS)
+    inp = P.make_input(s, q, t)
     ups, _ = _run(module, inp, [which])
     gp, gf = inp.point_cloud.grad.cpu().numpy(), inp.point_cloud_features.grad.cpu().numpy()
     assert np.abs(gp).max() > 0 and np.abs(gf[:, 7]).max() > 0
@@ -142,17 +117,17 @@ def test_single_output_gradient_matches_float64_reference(which, kind, arg, stri
 
 @pytest.mark.parametrize("wpt", WAVES_PER_TILE)
 @pytest.mark.parametrize("strict", [False, True])
-@pytest.mark.parametrize("kind,arg", SCENES[:4])
+@pytest.mark.parametrize("kind,arg", P.SCENES[:4])
 def test_image_depth_alpha_together_with_default_factors(kind, arg, strict, wpt, monkeypatch):
     """The tiny scenes only: the float64 colour gradient takes the ray origin of the forward, which the reference's backward
     replaces by t_pointcloud_camera (RAST:731-732); the two agree for the near-unit pose quaternions of these scenes."""
     _waves_per_tile(monkeypatch, wpt)
-    s, q, t, partial = _scene(kind, arg)
+    s, q, t, partial = P.scene_case(kind, arg)
     band = 1
     grads = {}
     for which in (["image", "depth", "alpha"], ["image"], ["depth"], ["alpha"]):
-        inp = _input(s, q, t, band=band)
-        ups, _ = _run(_module(partial, strict), inp, which)
+        inp = P.make_input(s, q, t, band)
+        ups, _ = _run(_depth_module(partial, strict), inp, which)
         grads[tuple(which)] = (inp.point_cloud.grad.cpu().numpy(), inp.point_cloud_features.grad.cpu().numpy(), ups)
     gp, gf, ups = grads[("image", "depth", "alpha")]
     tp, tf, ids = _reference(s, q, t, partial, ups)
@@ -163,23 +138,15 @@ def test_image_depth_alpha_together_with_default_factors(kind, arg, strict, wpt,
         assert np.abs(total - a).max() <= 1e-5 * np.abs(a).max(), k
 
 
-@pytest.mark.parametrize("kind,arg", SCENES)
+@pytest.mark.parametrize("kind,arg", P.SCENES)
 def test_pose_gradient_under_depth_loss(kind, arg):
     """A depth loss that pulls every pixel the same way (upstream in [0, 1]): the per-element floor sums |per-point terms|, and a
-    zero-mean random upstream cancels inside each point's term, below that floor (pose_ref's bar is set for image losses)."""
-    s, q, t, partial = _scene(kind, arg)
-    inp = _input(s, q, t, points=False, pose=True)
-    ups, _ = _run(_module(partial), inp, ["depth"], positive=True)
+    zero-mean random upstream cancels inside each point's term, below that floor (the pose bar is set for image losses)."""
+    s, q, t, partial = P.scene_case(kind, arg)
+    inp = P.make_input(s, q, t, requires_grad=False, pose=True)
+    ups, _ = _run(_depth_module(partial), inp, ["depth"], positive=True)
     gq, gt = inp.q_pointcloud_camera.grad.cpu().numpy(), inp.t_pointcloud_camera.grad.cpu().numpy()
-    f, feat_after = _oracle_frame(s, q, t, partial)
-    rq, rt, sq, st = R.pose_gradients(s, q, t, f, feat_after, None, ups["depth"].astype(np.float64), None)
-    for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
-        scale = np.abs(ref).max()
-        assert scale > 0, name
-        err = np.abs(a.astype(np.float64) - ref)
-        assert err.max() / scale < TENSOR_TOL, (name, err.max() / scale, a, ref)
-        bar = ELEM_RTOL * np.abs(ref) + ELEM_FLOOR * summed
-        assert np.all(err <= bar), (name, (err / np.maximum(bar, 1e-300)).max(), a, ref)
+    P.assert_pose_gradient_parity(s, q, t, partial, gq, gt, g_depth=ups["depth"])
 
 
 def test_pose_recovery_from_depth():
@@ -187,7 +154,7 @@ def test_pose_recovery_from_depth():
     true pose (lidar-style supervision: pixels the true render covers)."""
     s = synth(4000, 128, 128, 0.12, sh_deg=3, seed=21)
     q_true, t_true = view_pose()
-    module = _module()
+    module = _depth_module()
     with torch.no_grad():
         _, d_true, _, a_true = module(P.make_input(s, q_true, t_true, 3, requires_grad=False), return_accumulated_alpha=True)
         d_true, valid = d_true.clone(), (a_true > 0.5).clone()
@@ -219,8 +186,8 @@ def test_heavy_tiles_depth_and_alpha(wpt, monkeypatch):
     depth / alpha backward must not use.  Reference agreement, and an all-zero depth gradient against the image-only backward."""
     _waves_per_tile(monkeypatch, wpt)
     s, q, t = _clustered()
-    module = _module(**UNIT)
-    inp = _input(s, q, t)
+    module = _depth_module(**P.UNIT_FACTORS)
+    inp = P.make_input(s, q, t)
     ups, _ = _run(module, inp, ["image", "depth", "alpha"])
     fr = module.last_frame
     assert fr.heavy_tiles() > 0
@@ -230,13 +197,13 @@ def test_heavy_tiles_depth_and_alpha(wpt, monkeypatch):
     tp, tf, ids = _reference(s, q, t, False, ups)
     _check_points(gp, gf, tp, tf, ids)
     # image only, then image + an explicit all-zero depth gradient (the AUX walk, without segments)
-    base = _input(s, q, t)
-    m0 = _module(**UNIT)
+    base = P.make_input(s, q, t)
+    m0 = _depth_module(**P.UNIT_FACTORS)
     img = m0(base)[0]
     g = _upstream(img.shape, 0)
     img.backward(g)
-    aux = _input(s, q, t)
-    m1 = _module(**UNIT)
+    aux = P.make_input(s, q, t)
+    m1 = _depth_module(**P.UNIT_FACTORS)
     outs = m1(aux)
     torch.autograd.backward([outs[0], outs[1]], [g, torch.zeros_like(outs[1])])
     for a, b in ((base.point_cloud.grad, aux.point_cloud.grad), (base.point_cloud_features.grad, aux.point_cloud_features.grad)):
@@ -244,29 +211,24 @@ def test_heavy_tiles_depth_and_alpha(wpt, monkeypatch):
         assert np.abs(a - b).max() <= 1e-6 * np.abs(a).max()
 
 
-def _bits(x):
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    return a.view(np.uint8)
-
-
 def test_switch_without_depth_loss_changes_nothing():
     s = synth(6000, 256, 192, 0.05, sh_deg=3, seed=5)
     q, t = view_pose(1, 3)
     res = []
     for depth in (False, True):
-        inp = _input(s, q, t)
-        img = _module(depth=depth)(inp)[0]
+        inp = P.make_input(s, q, t)
+        img = _depth_module(depth=depth)(inp)[0]
         img.backward(_upstream(img.shape, 1))
         res.append((inp.point_cloud.grad, inp.point_cloud_features.grad))
     for a, b in zip(*res):
-        assert np.array_equal(_bits(a), _bits(b))
+        P.assert_same_bits(a, b)
 
 
 def test_depth_alpha_backward_is_deterministic():
     s = synth(40000, 512, 384, 0.02, sh_deg=3, seed=9)
     q, t = view_pose()
-    inp = _input(s, q, t, pose=True)
-    module = _module()
+    inp = P.make_input(s, q, t, pose=True)
+    module = _depth_module()
     outs = module(inp, return_accumulated_alpha=True)
     gs = [_upstream(outs[k].shape, k) for k in (0, 1, 3)]
     got = []
@@ -277,7 +239,7 @@ def test_depth_alpha_backward_is_deterministic():
         got.append([x.grad.clone() for x in (inp.point_cloud, inp.point_cloud_features, inp.q_pointcloud_camera, inp.t_pointcloud_camera)])
     assert got[0][0].abs().max() > 0
     for a, b in zip(*got):
-        assert np.array_equal(_bits(a), _bits(b))
+        P.assert_same_bits(a, b)
 
 
 def test_hook_and_controller_under_depth_loss():
@@ -301,9 +263,7 @@ def test_hook_and_controller_under_depth_loss():
             seen["ids"] = h.point_id_in_camera_list.clone()
             seen["gpc"] = h.grad_point_in_camera.clone()
             ctl.update(h)
-        cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-        cfg.differentiable_depth = True
-        module = P.Rast(cfg, backward_valid_point_hook=hook, controller_accumulators=ctl.accumulators if rasteriser_accumulates else None)
+        module = _depth_module(hook=hook, ctrl=ctl.accumulators if rasteriser_accumulates else None)
         cam = P.CameraInfo(torch.tensor(s.camera_intrinsics, device=P.DEV), s.height, s.width, 0)
         inp = P.Rast.GaussianPointCloudRasterisationInput(pc, ft, obj, mask, cam, torch.tensor(q, device=P.DEV),
                                                          torch.tensor(t, device=P.DEV), color_max_sh_band=3)
@@ -317,13 +277,13 @@ def test_hook_and_controller_under_depth_loss():
                       "accumulated_position_gradients", "accumulated_position_gradients_norm")})
     assert stats[0]["accumulated_position_gradients"].abs().max() > 0
     for k in stats[0]:
-        assert np.array_equal(_bits(stats[0][k]), _bits(stats[1][k])), k
+        P.assert_same_bits(stats[0][k], stats[1][k], k)
 
 
 def test_argument_errors():
-    s, q, t, partial = _tiny(0, 48, 0.25, 32, 32)
-    module = _module(partial)
-    inp = _input(s, q, t)
+    s, q, t, partial = P.tiny_case(0, 48, 0.25, 32, 32)
+    module = _depth_module(partial)
+    inp = P.make_input(s, q, t)
     outs = module(inp)
     fr = module.last_frame
     dev = inp.point_cloud.device

@@ -157,8 +157,8 @@ def test_backward_is_bitwise_reproducible(P):
         img = module(inp)[0]
         (img * img).sum().backward()
         grads.append((inp.point_cloud.grad.cpu().numpy().copy(), inp.point_cloud_features.grad.cpu().numpy().copy()))
-    assert np.array_equal(grads[0][0].view(np.uint32), grads[1][0].view(np.uint32))
-    assert np.array_equal(grads[0][1].view(np.uint32), grads[1][1].view(np.uint32))
+    P.assert_same_bits(grads[0][0], grads[1][0])
+    P.assert_same_bits(grads[0][1], grads[1][1])
 
 
 def test_dispatch_order_hint_from_an_earlier_frame_changes_nothing(P):
@@ -185,11 +185,11 @@ def test_dispatch_order_hint_from_an_earlier_frame_changes_nothing(P):
     img_small = module(inp)[0]
     (img_small * img_small).sum().backward()
     ref_small = P.Rast(P.Rast.GaussianPointCloudRasterisationConfig())(P.make_input(small, q, t, requires_grad=False))[0]
-    assert np.array_equal(img_small.detach().cpu().numpy().view(np.uint32), ref_small.cpu().numpy().view(np.uint32))
+    P.assert_same_bits(img_small.detach().cpu().numpy(), ref_small.cpu().numpy())
     back = run(module, q, t)                 # back to the first grid: no stale ordering either
     for got in (other, same, back):
         for a, b in zip(got, fresh):
-            assert np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b)
+            P.assert_same_bits(a, b)
 
 
 def test_not_a_number_stays_where_the_reference_puts_it(P):
@@ -340,7 +340,7 @@ def test_cfg5_inference_2e6_rgb_only(P):
             outs = module(inp)
         P.assert_forward_parity(module, inp, outs, f, feat_after, rgb_only=rgb_only)
         imgs[rgb_only] = outs[0].cpu().numpy()
-    assert np.array_equal(imgs[True].view(np.uint32), imgs[False].view(np.uint32))
+    P.assert_same_bits(imgs[True], imgs[False])
 
 
 def test_several_frames_in_flight_and_arena_is_stable(P):
@@ -552,19 +552,13 @@ def test_soak_seeds_with_ill_conditioned_splats(P, seed):
     hip_f64_tol, orc_f64_tol, closer = (1e-4, 3e-4, 2.5) if seed == 141447 else (2e-5, 2e-4, 5.0)
     c = P.soak_case(seed)
     s, q, t, partial, rng = c["scene"], c["q"], c["t"], c["partial"], c["rng"]
-    unit = dict(grad_color_factor=1.0, grad_high_order_color_factor=1.0, grad_s_factor=1.0, grad_q_factor=1.0, grad_alpha_factor=1.0)
-    ocfg = oracle.default_config(allow_partial_tiles=int(partial), **unit)
+    ocfg = oracle.default_config(allow_partial_tiles=int(partial), **P.UNIT_FACTORS)
     f, feat_after = P.run_oracle(s, q, t, ocfg)
     target = None
     report = {"seed": seed, "image": [c["W"], c["H"]], "points_in_camera": int(f.M), "metric": "max |a - b| / max |b| per column group"}
     grads = {}
     for form in ("fast", "reference_order"):
-        cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-        cfg.allow_partial_tiles = partial
-        cfg.backward_reference_order = form == "reference_order"
-        for k, v in unit.items():
-            setattr(cfg, k, v)
-        module = P.Rast(cfg)
+        module = P.module(partial, form == "reference_order", **P.UNIT_FACTORS)
         inp = P.make_input(s, q, t, 3)
         outs = module(inp)
         P.assert_forward_parity(module, inp, outs, f, feat_after)
@@ -576,7 +570,7 @@ def test_soak_seeds_with_ill_conditioned_splats(P, seed):
         # every element under the per-element bar in both forms; tensor level: 1e-5 in the reference's order, 2e-4 in the fast form
         b = P.assert_backward_parity(module, inp, g.cpu().numpy(), f, 3, None, ocfg, tensor_tol=1e-5 if form == "reference_order" else 2e-4)
         grads[form] = (inp.point_cloud.grad.cpu().numpy(), inp.point_cloud_features.grad.cpu().numpy(), b)
-    ref_pc, ref_ft = P.float64_autograd_gradients(s, q, t, f, feat_after, g.cpu().numpy())
+    ref_pc, ref_ft = P.torch_ref.point_gradients(s, q, t, f, feat_after, g.cpu().numpy())
     gp, gf, b = grads["fast"]
     sp, sf, _ = grads["reference_order"]
     op, of = b["grad_pointcloud"], b["grad_pointcloud_features"]
@@ -647,7 +641,7 @@ def test_predicted_sizing_and_its_redo_change_nothing(P):
 
     def same(a, b):
         for x, y in zip(a[1], b[1]):
-            assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, y.view(np.uint32) if y.dtype == np.float32 else y)
+            P.assert_same_bits(x, y)
         for n in a[2]:
             assert np.array_equal(a[2][n], b[2][n]), n
 
@@ -689,8 +683,7 @@ def test_heavy_tiles_shared_by_four_waves_clustered_scene(P):
         module, inp, f, b, _ = _fwd_bwd(P, s, q, t, band=3, hook=True, seed=9)
         lens = f.tile_points_end - f.tile_points_start
         assert lens.max() > 8 * lens.mean(), (lens.max(), lens.mean())
-        import os
-        if any(k in os.environ for k in ("GS_BWD_SPLIT_HEAVY", "GS_BWD_SEGMENTS", "GS_BWD_HEAVY_X2")):
+        if not P.default_heavy_policy():
             continue                # the suite is also run under the library's diagnostic switches: the policy below is then not the default one
         assert module.last_frame.heavy_tiles() > 0, waves
         tiles, items = module.last_frame.heavy_tiles(), module.last_frame.heavy_tiles(items=True)
@@ -707,20 +700,13 @@ def test_heavy_tiles_in_segments_very_long_lists(P):
     as one work item per segment, each starting from the record of its cut (k_backward.hip: BwdCoop.seg) -- including the pixels'
     sum |d uv| (magnitude_grad_viewspace_on_image), which the segments leave as partial sums.  Same bars against the oracle; the
     result must not depend on whether the list was cut (GS_BWD_SEGMENTS=0 is covered by the suite run under that switch)."""
-    rng = np.random.default_rng(88)
-    s = synth(26000, 208, 160, 0.02, sh_deg=3, seed=88)
-    # 6000 translucent splats piled on a corner region: lists of thousands of entries there, a few hundred elsewhere
-    s.point_cloud[:6000, 0] = rng.uniform(-0.9, -0.4, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
-    s.point_cloud[:6000, 1] = rng.uniform(-0.7, -0.3, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
-    s.point_cloud_features[:6000, 4:7] = np.log(rng.uniform(0.05, 0.15, (6000, 3))).astype(np.float32)
-    s.point_cloud_features[:6000, 7] = rng.uniform(-5.0, -2.5, 6000).astype(np.float32)
+    s = P.dense_corner_scene()
     q, t = view_pose()
     module, inp, f, b, got = _fwd_bwd(P, s, q, t, band=3, hook=True, seed=11)
     lens = f.tile_points_end - f.tile_points_start
     assert lens.max() > 3000, lens.max()
     fr = module.last_frame
-    import os
-    if not any(k in os.environ for k in ("GS_BWD_SPLIT_HEAVY", "GS_BWD_SEGMENTS", "GS_BWD_HEAVY_X2")):
+    if P.default_heavy_policy():
         assert fr.heavy_tiles() > 0 and fr.heavy_tiles(items=True) >= fr.heavy_tiles() + 4, (fr.heavy_tiles(), fr.heavy_tiles(items=True))
 
 
@@ -746,8 +732,8 @@ def test_flag_tags_wrap_round_after_255_backwards(P):
         else:
             got, ref = grads(a), ref_a
         if it in (253, 254, 255, 256, 257, 258, 509, 510, 511, 512) or it % 50 == 0:
-            assert np.array_equal(got[0].view(np.uint32), ref[0].view(np.uint32)), it
-            assert np.array_equal(got[1].view(np.uint32), ref[1].view(np.uint32)), it
+            P.assert_same_bits(got[0], ref[0], it)
+            P.assert_same_bits(got[1], ref[1], it)
 
 
 def test_heavy_set_and_cuts_do_not_depend_on_claim_order(P):
@@ -772,7 +758,7 @@ def test_heavy_set_and_cuts_do_not_depend_on_claim_order(P):
         assert [r[0] for r in runs] == ["exact", "predicted", "predicted"]
     for r in runs[1:]:
         for a, b in zip(r[1:], runs[0][1:]):
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+            P.assert_same_bits(a, b)
 
 
 def test_contributor_on_the_alpha_threshold_behind_a_cut(P):
@@ -785,8 +771,7 @@ def test_contributor_on_the_alpha_threshold_behind_a_cut(P):
     c = P.soak_case(800305)
     s, q, t = c["scene"], c["q"], c["t"]
     module, inp, f, b, _ = _fwd_bwd(P, s, q, t, band=c["band"], hook=True, cfg_kw=dict(allow_partial_tiles=bool(c["partial"])), seed=3)
-    import os
-    if not any(k in os.environ for k in ("GS_BWD_SPLIT_HEAVY", "GS_BWD_SEGMENTS", "GS_BWD_HEAVY_X2")):
+    if P.default_heavy_policy():
         fr = module.last_frame
         assert fr.heavy_tiles() > 0 and fr.heavy_tiles(items=True) > fr.heavy_tiles()
     assert max(m["bar_use_max"] for m in b["margins"].values()) < 0.6
@@ -796,12 +781,7 @@ def test_second_backward_through_a_frame_with_cut_lists(P):
     """backward(retain_graph=True) twice on a frame whose heavy tiles are walked in segments: the forward's cut records are read-only
     for the backward and the segments' partial sums are rewritten with the same values, so the second pass adds exactly the same
     gradient again (autograd accumulates: 2x, an exact doubling) and the hook's per-pixel magnitudes are the same bits."""
-    rng = np.random.default_rng(88)
-    s = synth(26000, 208, 160, 0.02, sh_deg=3, seed=88)
-    s.point_cloud[:6000, 0] = rng.uniform(-0.9, -0.4, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
-    s.point_cloud[:6000, 1] = rng.uniform(-0.7, -0.3, 6000).astype(np.float32) * s.point_cloud[:6000, 2] / 1.2
-    s.point_cloud_features[:6000, 4:7] = np.log(rng.uniform(0.05, 0.15, (6000, 3))).astype(np.float32)
-    s.point_cloud_features[:6000, 7] = rng.uniform(-5.0, -2.5, 6000).astype(np.float32)
+    s = P.dense_corner_scene()
     q, t = view_pose()
     mags = []
     module = P.Rast(P.Rast.GaussianPointCloudRasterisationConfig(), backward_valid_point_hook=lambda x: mags.append(x.magnitude_grad_viewspace_on_image.cpu().numpy().copy()))
@@ -813,5 +793,6 @@ def test_second_backward_through_a_frame_with_cut_lists(P):
     image.backward(g)
     second = (inp.point_cloud.grad.cpu().numpy(), inp.point_cloud_features.grad.cpu().numpy())
     for a, b in zip(first, second):
-        assert np.array_equal((2.0 * a).view(np.uint32), b.view(np.uint32))
-    assert len(mags) == 2 and np.array_equal(mags[0].view(np.uint32), mags[1].view(np.uint32))
+        P.assert_same_bits(2.0 * a, b)
+    assert len(mags) == 2
+    P.assert_same_bits(mags[0], mags[1])

@@ -1,5 +1,5 @@
 """GPU (-m gpu): gradients with respect to q_pointcloud_camera and t_pointcloud_camera (k_pose.hip), against the float64
-reference of tests/pose_ref.py; that requesting them changes nothing else; the pose-only backward; determinism; pose recovery;
+reference of tests/torch_ref.py; that requesting them changes nothing else; the pose-only backward; determinism; pose recovery;
 and the staged path's refusal."""
 import ctypes as C
 
@@ -8,40 +8,11 @@ import pytest
 import torch
 
 import parity_util as P
-import pose_ref
-from oracle import oracle
 from taichi_3d_gaussian_splatting_amd import _host, _native
 from taichi_3d_gaussian_splatting_amd.controller_stats import ControllerAccumulators
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
 
 pytestmark = pytest.mark.gpu
-
-ELEM_RTOL, ELEM_FLOOR, TENSOR_TOL = 2e-5, 5e-6, 1e-4
-
-
-def _tiny(seed, n, sigma0, width, height):
-    """The scenes of test_oracle_autograd (non-unit pose quaternion)."""
-    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
-    ang = 0.05
-    q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32)
-    t = np.array([[0.03, -0.02, 0.1]], np.float32)
-    return s, q, t, int(width % 16 != 0 or height % 16 != 0)
-
-
-def _module(partial=False, strict=False, hook=None, ctrl=None, **factors):
-    cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-    cfg.allow_partial_tiles = bool(partial)
-    cfg.backward_reference_order = bool(strict)
-    for k, v in factors.items():
-        setattr(cfg, k, v)
-    return P.Rast(cfg, backward_valid_point_hook=hook, controller_accumulators=ctrl)
-
-
-def _input(scene, q, t, points=True, pose=True, band=3):
-    inp = P.make_input(scene, q, t, band, requires_grad=points)
-    inp.q_pointcloud_camera.requires_grad_(pose)
-    inp.t_pointcloud_camera.requires_grad_(pose)
-    return inp
 
 
 def _target(shape, seed=0):
@@ -56,50 +27,21 @@ def _run(module, inp, seed=0, retain=False):
     return outs, g
 
 
-def _check_against_ref(scene, q, t, partial, gq, gt, g_image, per_element=True):
-    cfg = oracle.default_config(allow_partial_tiles=int(partial))
-    f, feat_after = P.run_oracle(scene, q, t, cfg)
-    assert f.K > 0
-    rq, rt, sq, st = pose_ref.pose_gradients(scene, q, t, f, feat_after, g_image)
-    for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
-        assert a.shape == ref.shape, name
-        scale = np.abs(ref).max()
-        assert scale > 0, name
-        err = np.abs(a.astype(np.float64) - ref)
-        assert err.max() / scale < TENSOR_TOL, (name, err.max() / scale, a, ref)
-        if per_element:
-            bar = ELEM_RTOL * np.abs(ref) + ELEM_FLOOR * summed
-            assert np.all(err <= bar), (name, (err / np.maximum(bar, 1e-300)).max(), a, ref)
-        assert not a[summed == 0].any(), name          # rows no touched point depends on: exact zeros
-    return rq, rt
-
-
-SCENES = [("tiny", (0, 48, 0.25, 32, 32)), ("tiny", (1, 64, 0.6, 32, 32)), ("tiny", (2, 24, 1.2, 32, 32)),
-          ("tiny", (3, 56, 0.5, 41, 27)), ("soak", 29), ("soak", 54), ("soak", 182)]
-
-
-def _scene(kind, arg):
-    if kind == "tiny":
-        return _tiny(*arg)
-    c = P.soak_case(arg)
-    return c["scene"], c["q"], c["t"], c["partial"]
-
-
 @pytest.mark.parametrize("strict", [False, True])
-@pytest.mark.parametrize("kind,arg", SCENES)
+@pytest.mark.parametrize("kind,arg", P.SCENES)
 def test_pose_gradient_matches_float64_reference(kind, arg, strict):
-    s, q, t, partial = _scene(kind, arg)
-    module = _module(partial, strict)
-    inp = _input(s, q, t)
+    s, q, t, partial = P.scene_case(kind, arg)
+    module = P.module(partial, strict)
+    inp = P.make_input(s, q, t, pose=True)
     outs, g = _run(module, inp)
     assert inp.q_pointcloud_camera.grad is not None and inp.t_pointcloud_camera.grad is not None
     assert inp.q_pointcloud_camera.grad.shape == (1, 4) and inp.t_pointcloud_camera.grad.shape == (1, 3)
-    _check_against_ref(s, q, t, partial, inp.q_pointcloud_camera.grad.cpu().numpy(), inp.t_pointcloud_camera.grad.cpu().numpy(),
-                       g.cpu().numpy())
+    P.assert_pose_gradient_parity(s, q, t, partial, inp.q_pointcloud_camera.grad.cpu().numpy(),
+                                  inp.t_pointcloud_camera.grad.cpu().numpy(), g.cpu().numpy())
 
 
 def _multi_object(seed, n_objects, n=64, width=32, height=32, empty_last=False):
-    s, q, t, partial = _tiny(seed, n, 0.5, width, height)
+    s, q, t, partial = P.tiny_case(seed, n, 0.5, width, height)
     rng = np.random.default_rng(seed + 7)
     s.point_object_id[:] = rng.integers(0, n_objects, n).astype(np.int32)
     q = np.repeat(q, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 4)).astype(np.float32)
@@ -116,12 +58,12 @@ def test_multi_object_rows(n_objects, empty_last):
     while the upstream that term is made from (loop 1's per-splat sums) is accurate relative to ITS summed per-pixel
     magnitude, which can be much larger (the floor of the point-gradient bar, parity_util.ELEM_FLOOR)."""
     s, q, t, partial = _multi_object(11, n_objects, empty_last=empty_last)
-    module = _module(partial)
-    inp = _input(s, q, t)
+    module = P.module(partial)
+    inp = P.make_input(s, q, t, pose=True)
     outs, g = _run(module, inp)
     gq, gt = inp.q_pointcloud_camera.grad.cpu().numpy(), inp.t_pointcloud_camera.grad.cpu().numpy()
     assert gq.shape == (n_objects, 4) and gt.shape == (n_objects, 3)
-    rq, rt = _check_against_ref(s, q, t, partial, gq, gt, g.cpu().numpy(), per_element=n_objects <= 3)
+    rq, rt = P.assert_pose_gradient_parity(s, q, t, partial, gq, gt, g.cpu().numpy(), per_element=n_objects <= 3)
     if empty_last:
         assert (s.point_object_id == n_objects - 1).any()
         assert np.all(gq[-1] == 0) and np.all(gt[-1] == 0)
@@ -133,16 +75,11 @@ HOOK_FIELDS = ["point_id_in_camera_list", "grad_point_in_camera", "grad_pointfea
                "point_depth", "point_uv_in_camera"]
 
 
-def _bits(x):
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    return a.view(np.uint8) if a.dtype != np.bool_ else a
-
-
 def _full_run(scene, q, t, pose):
     got = {}
     ctrl = ControllerAccumulators.zeros(scene.point_cloud.shape[0], P.DEV)
-    module = _module(hook=lambda h: got.setdefault("hook", {k: getattr(h, k).clone() for k in HOOK_FIELDS}), ctrl=ctrl)
-    inp = _input(scene, q, t, points=True, pose=pose)
+    module = P.module(hook=lambda h: got.setdefault("hook", {k: getattr(h, k).clone() for k in HOOK_FIELDS}), ctrl=ctrl)
+    inp = P.make_input(scene, q, t, pose=pose)
     outs, _ = _run(module, inp)
     torch.cuda.synchronize()
     res = {"image": outs[0], "depth": outs[1], "count": outs[2], "grad_pc": inp.point_cloud.grad,
@@ -162,18 +99,18 @@ def test_requesting_pose_gradients_changes_nothing_else():
     assert inp0.q_pointcloud_camera.grad is None and inp1.q_pointcloud_camera.grad is not None
     assert len(base) == 5 + 10 + 6
     for k in base:
-        assert np.array_equal(_bits(base[k]), _bits(with_pose[k])), k
+        P.assert_same_bits(base[k], with_pose[k], k)
 
 
 def test_pose_only_backward():
     s = synth(6000, 256, 192, 0.05, sh_deg=3, seed=6)
     q, t = view_pose(2, 3)
-    joint = _input(s, q, t, points=True, pose=True)
-    _run(_module(), joint)
+    joint = P.make_input(s, q, t, pose=True)
+    _run(P.module(), joint)
     calls = []
     ctrl = ControllerAccumulators.zeros(s.point_cloud.shape[0], P.DEV)
-    only = _input(s, q, t, points=False, pose=True)
-    _run(_module(hook=calls.append, ctrl=ctrl), only)
+    only = P.make_input(s, q, t, requires_grad=False, pose=True)
+    _run(P.module(hook=calls.append, ctrl=ctrl), only)
     torch.cuda.synchronize()
     assert not calls                                                            # the hook belongs to the point gradient (RAST:1028)
     for k in ("accumulated_num_in_camera", "accumulated_num_pixels", "accumulated_view_space_position_gradients",
@@ -181,14 +118,14 @@ def test_pose_only_backward():
         assert not getattr(ctrl, k).any(), k
     assert only.point_cloud.grad is None and only.point_cloud_features.grad is None
     for a, b in ((joint.q_pointcloud_camera, only.q_pointcloud_camera), (joint.t_pointcloud_camera, only.t_pointcloud_camera)):
-        assert np.array_equal(_bits(a.grad), _bits(b.grad))
+        P.assert_same_bits(a.grad, b.grad)
         assert b.grad.abs().max() > 0
     # grad factors and the SH band scale / mask feature gradients only
-    other = _input(s, q, t, points=False, pose=True, band=0)
-    _run(_module(grad_color_factor=3.0, grad_high_order_color_factor=0.25, grad_s_factor=7.0, grad_q_factor=2.0,
-                 grad_alpha_factor=0.1), other)
+    other = P.make_input(s, q, t, 0, requires_grad=False, pose=True)
+    _run(P.module(grad_color_factor=3.0, grad_high_order_color_factor=0.25, grad_s_factor=7.0, grad_q_factor=2.0,
+                  grad_alpha_factor=0.1), other)
     for a, b in ((only.q_pointcloud_camera, other.q_pointcloud_camera), (only.t_pointcloud_camera, other.t_pointcloud_camera)):
-        assert np.array_equal(_bits(a.grad), _bits(b.grad))
+        P.assert_same_bits(a.grad, b.grad)
 
 
 @pytest.mark.parametrize("n_objects", [1, 8])
@@ -198,8 +135,8 @@ def test_pose_gradient_is_deterministic(n_objects):
     s.point_object_id[:] = np.random.default_rng(3).integers(0, n_objects, s.point_object_id.shape[0]).astype(np.int32)
     q, t = np.repeat(q, n_objects, 0), np.repeat(t, n_objects, 0)
     grads = []
-    inp = _input(s, q, t, points=True, pose=True)
-    module = _module()
+    inp = P.make_input(s, q, t, pose=True)
+    module = P.module()
     outs = module(inp)
     g = 2.0 * (outs[0].detach() - _target(outs[0].shape))
     for _ in range(2):                                                          # the same frame twice (retain_graph)
@@ -207,12 +144,13 @@ def test_pose_gradient_is_deterministic(n_objects):
         outs[0].backward(g, retain_graph=True)
         grads.append((inp.q_pointcloud_camera.grad.clone(), inp.t_pointcloud_camera.grad.clone()))
     for _ in range(2):                                                          # fresh runs
-        inp = _input(s, q, t, points=True, pose=True)
-        _run(_module(), inp)
+        inp = P.make_input(s, q, t, pose=True)
+        _run(P.module(), inp)
         grads.append((inp.q_pointcloud_camera.grad.clone(), inp.t_pointcloud_camera.grad.clone()))
     assert grads[0][0].abs().max() > 0
     for gq, gt in grads[1:]:
-        assert np.array_equal(_bits(gq), _bits(grads[0][0])) and np.array_equal(_bits(gt), _bits(grads[0][1]))
+        P.assert_same_bits(gq, grads[0][0])
+        P.assert_same_bits(gt, grads[0][1])
 
 
 def _rotation_error(q, q_ref):
@@ -225,7 +163,7 @@ def test_pose_recovery():
     non-leaf pose), with Adam, against the image rendered at the true pose."""
     s = synth(4000, 128, 128, 0.12, sh_deg=3, seed=21)
     q_true, t_true = view_pose()
-    module = _module()
+    module = P.module()
     with torch.no_grad():
         target = module(P.make_input(s, q_true, t_true, 3, requires_grad=False))[0].clone()
     axis = np.array([1.0, 1.0, 0.3]) / np.linalg.norm([1.0, 1.0, 0.3])
@@ -253,9 +191,9 @@ def test_pose_recovery():
 
 
 def test_staged_path_refuses_pose_gradients():
-    s, q, t, partial = _tiny(0, 48, 0.25, 32, 32)
-    module = _module(partial)
-    inp = _input(s, q, t)
+    s, q, t, partial = P.tiny_case(0, 48, 0.25, 32, 32)
+    module = P.module(partial)
+    inp = P.make_input(s, q, t, pose=True)
     module(inp)
     fr = module.last_frame
     dev = inp.point_cloud.device

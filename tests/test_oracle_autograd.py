@@ -5,19 +5,15 @@ import numpy as np
 import pytest
 import torch
 
+import parity_util as P
 import torch_ref
 from oracle import oracle
-from taichi_3d_gaussian_splatting_amd.synthetic import synth
 
 
-def _tiny(seed, n, sigma0, size=32, height=None):
-    height = size if height is None else height
-    s = synth(n, size, height, sigma0, sh_deg=3, seed=seed)
-    rng = np.random.default_rng(seed + 100)
-    ang = 0.05
-    q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32)   # deliberately not unit
-    t = np.array([[0.03, -0.02, 0.1]], np.float32)
-    target = rng.uniform(0, 1, (height, size, 3)).astype(np.float32)
+def _case(seed, n, sigma0, width=32, height=None):
+    """P.tiny_case and a random target image -> (scene, q, t, target)"""
+    s, q, t, _ = P.tiny_case(seed, n, sigma0, width, height)
+    target = np.random.default_rng(seed + 100).uniform(0, 1, (s.height, s.width, 3)).astype(np.float32)
     return s, q, t, target
 
 
@@ -25,16 +21,15 @@ def _tiny(seed, n, sigma0, size=32, height=None):
                                                          (3, 56, 0.5, 41, 27)])
 def test_backward_matches_autograd(seed, n, sigma0, width, height):
     """The last case is the partial-tile extension (41x27: neither side a multiple of 16)."""
-    s, q, t, target = _tiny(seed, n, sigma0, width, height)
+    s, q, t, target = _case(seed, n, sigma0, width, height)
     partial = int(width % 16 != 0 or height % 16 != 0)
-    cfg = oracle.default_config(grad_color_factor=1.0, grad_high_order_color_factor=1.0, grad_s_factor=1.0,
-                                grad_q_factor=1.0, grad_alpha_factor=1.0, allow_partial_tiles=partial)
+    cfg = oracle.default_config(allow_partial_tiles=partial, **P.UNIT_FACTORS)
     f, feat_after = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask,
                                    s.point_object_id, q, t, s.camera_intrinsics, s.height, s.width, cfg)
     assert f.K > 0 and f.pixel_valid_point_count.max() >= 3
     pc = torch.tensor(s.point_cloud, dtype=torch.float64, requires_grad=True)
     ft = torch.tensor(feat_after, dtype=torch.float64, requires_grad=True)
-    img, aux = torch_ref.render(pc, ft, q, t, s.camera_intrinsics, s.height, s.width, f)
+    img, _, _, aux = torch_ref.render(pc, ft, q, t, s.camera_intrinsics, s.height, s.width, f)
     # forward agreement first (f32 oracle vs f64 restatement)
     assert np.allclose(img.detach().numpy(), f.rasterized_image, atol=2e-5)
     g_img = 2.0 * (f.rasterized_image.astype(np.float64) - target)
@@ -58,9 +53,8 @@ def test_backward_matches_autograd(seed, n, sigma0, width, height):
 
 def test_band_mask_and_factors():
     """RAST:1102-1125, 1167-1182: masked bands are zero, the rest scaled by 5 / 1 / 0.5 / 1 / 20."""
-    s, q, t, target = _tiny(3, 40, 0.5)
-    unit = oracle.default_config(grad_color_factor=1.0, grad_high_order_color_factor=1.0, grad_s_factor=1.0,
-                                 grad_q_factor=1.0, grad_alpha_factor=1.0)
+    s, q, t, target = _case(3, 40, 0.5)
+    unit = oracle.default_config(**P.UNIT_FACTORS)
     ref_cfg = oracle.default_config()
     f, _ = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask, s.point_object_id,
                           q, t, s.camera_intrinsics, s.height, s.width, unit)
@@ -80,7 +74,7 @@ def test_band_mask_and_factors():
 
 def test_hook_extras_consistency():
     """num_affected_pixels counts contributions; magnitude image is the per-pixel sum of |d uv|."""
-    s, q, t, target = _tiny(4, 32, 0.5)
+    s, q, t, target = _case(4, 32, 0.5)
     f, _ = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask, s.point_object_id,
                           q, t, s.camera_intrinsics, s.height, s.width)
     g = (2.0 * (f.rasterized_image - target)).astype(np.float32)
@@ -98,7 +92,7 @@ def test_summed_magnitudes_bound_the_gradients():
     """gso_backward_ex's "summed" outputs (the floor of the GPU tests' per-element bar): every gradient element is bounded by
     the magnitude summed to produce it (triangle inequality, up to rounding), is exactly zero where nothing was summed,
     and masked SH bands / rows outside the frustum have nothing summed."""
-    s, q, t, target = _tiny(5, 400, 0.3, 64, 48)
+    s, q, t, target = _case(5, 400, 0.3, 64, 48)
     f, _ = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask, s.point_object_id,
                           q, t, s.camera_intrinsics, s.height, s.width)
     g = (2.0 * (f.rasterized_image - target)).astype(np.float32)

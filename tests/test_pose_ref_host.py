@@ -1,20 +1,19 @@
-"""CPU: the float64 pose-gradient reference (tests/pose_ref.py) that the GPU pose tests compare against is the derivative of
-its own render: central finite differences for the oracle's fixed integer structure, with the gradient stops replayed."""
+"""CPU: the float64 pose-gradient reference (tests/torch_ref.py, wrt="pose") that the GPU pose tests compare against is the
+derivative of its own render: central finite differences for the oracle's fixed integer structure, with the gradient stops
+replayed."""
 import numpy as np
 import pytest
 import torch
 
-import pose_ref
+import parity_util as P
+import torch_ref
 from oracle import oracle
-from taichi_3d_gaussian_splatting_amd.synthetic import synth
 
 
 def _scene(seed, n, sigma0, width, height, n_objects):
-    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
+    s, q, t, _ = P.tiny_case(seed, n, sigma0, width, height)
     rng = np.random.default_rng(seed + 100)
-    ang = 0.05
-    q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32) * np.float32(1.3)   # not unit
-    t = np.array([[0.03, -0.02, 0.1]], np.float32)
+    q = q * np.float32(1.3)                                  # not unit
     if n_objects > 1:
         s.point_object_id[:] = (np.arange(n) % n_objects).astype(np.int32)
         q = np.repeat(q, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 4)).astype(np.float32)
@@ -30,21 +29,21 @@ def test_pose_gradient_matches_finite_differences(seed, n, sigma0, width, height
     f, feat_after = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask, s.point_object_id,
                                    q, t, s.camera_intrinsics, s.height, s.width, cfg)
     assert f.K > 0 and f.pixel_valid_point_count.max() >= 3
-    img, _ = pose_ref.render(s.point_cloud, feat_after, q, t, s.camera_intrinsics, s.height, s.width, f, s.point_object_id)
+    img, _, _, aux = torch_ref.render(s.point_cloud, feat_after, q, t, s.camera_intrinsics, s.height, s.width, f, s.point_object_id,
+                                      wrt="pose")
     assert np.allclose(img.detach().numpy(), f.rasterized_image, atol=2e-5)      # the same frame as the f32 oracle
     g_img = 2.0 * (f.rasterized_image.astype(np.float64) - target)
-    gq, gt, sq, st = pose_ref.pose_gradients(s, q, t, f, feat_after, g_img)
+    gq, gt, sq, st = torch_ref.pose_gradients(s, q, t, f, feat_after, g_img)
     assert np.all(np.abs(gq) <= sq * (1 + 1e-12)) and np.all(np.abs(gt) <= st * (1 + 1e-12))
     assert np.abs(gq).max() > 0 and np.abs(gt).max() > 0
 
-    _, aux = pose_ref.render(s.point_cloud, feat_after, q, t, s.camera_intrinsics, s.height, s.width, f, s.point_object_id)
     stops = aux["stops"]
     G = torch.as_tensor(g_img)
 
     def loss(qq, tt):
         with torch.no_grad():
-            im, _ = pose_ref.render(s.point_cloud, feat_after, qq, tt, s.camera_intrinsics, s.height, s.width, f,
-                                    s.point_object_id, stops=stops)
+            im = torch_ref.render(s.point_cloud, feat_after, qq, tt, s.camera_intrinsics, s.height, s.width, f,
+                                  s.point_object_id, stops=stops, wrt="pose")[0]
             return float((im * G).sum())
 
     h = 1e-6

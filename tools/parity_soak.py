@@ -16,20 +16,16 @@ import torch  # noqa: E402
 
 import parity_util as P  # noqa: E402
 from oracle import oracle  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import synth  # noqa: E402
 
 
 MODULES = {}     # one operator (one gs_ctx) per configuration for the whole soak: frames of many sizes share its arena, its tagged
                  # backward flags and its size predictions, as they would in a long-running trainer
 
 
-def _module(partial, strict):
+def soak_module(partial, strict):
     key = (partial, strict)
     if key not in MODULES:
-        cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-        cfg.allow_partial_tiles = partial
-        cfg.backward_reference_order = strict
-        MODULES[key] = P.Rast(cfg, backward_valid_point_hook=lambda x: None)
+        MODULES[key] = P.module(partial, strict, hook=lambda x: None)
     return MODULES[key]
 
 
@@ -55,7 +51,7 @@ def one(seed):
     s, q, t, band, partial, rng = c["scene"], c["q"], c["t"], c["band"], c["partial"], c["rng"]
     ocfg = oracle.default_config(allow_partial_tiles=int(partial))
     f, feat_after = P.run_oracle(s, q, t, ocfg)
-    module = _module(partial, False)
+    module = soak_module(partial, False)
     note = ""
     try:
         g, b, sizing, heavy, first = _run(module, s, q, t, band, f, feat_after, rng, ocfg, P.GRAD_TOL)
@@ -64,7 +60,7 @@ def one(seed):
         # (gs_config.bwd_reference_order), i.e. the gap is that one expression, and in the default
         # form the per-element bar still has to hold
         g, b, sizing, heavy, first = _run(module, s, q, t, band, f, feat_after, np.random.default_rng(seed + 7), ocfg, 2e-4)
-        _run(_module(partial, True), s, q, t, band, f, feat_after, g, ocfg, P.GRAD_TOL)
+        _run(soak_module(partial, True), s, q, t, band, f, feat_after, g, ocfg, P.GRAD_TOL)
         note = f" [default form over the tensor-level bar ({e.args[0] if e.args else e}); reference-order form within it]"
     # the same frame again on the same context: its sizes are now PREDICTED from the first pass; every bit must be the same
     _, _, sizing2, _, second = _run(module, s, q, t, band, f, feat_after, g, ocfg, 2e-4)
