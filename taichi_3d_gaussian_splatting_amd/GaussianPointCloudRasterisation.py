@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _native
+from . import _native, channels
 from ._host import _ConfigBase, _Contexts, _Frame, _marshal
 from .Camera import CameraInfo
 from .controller_stats import ControllerAccumulators
@@ -85,13 +85,15 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         class _module_function(torch.autograd.Function):
             @staticmethod
             def forward(ctx, pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
-                        q_pointcloud_camera, t_pointcloud_camera, camera_info, color_max_sh_band, grad_mode, return_alpha):
+                        q_pointcloud_camera, t_pointcloud_camera, camera_info, color_max_sh_band, grad_mode, return_alpha,
+                        keep_frame):
                 # ctx.needs_input_grad says whether the inputs require grad, not whether a graph is being recorded (it is True
                 # under torch.no_grad() too, and grad mode is always off inside forward): the caller passes the grad mode in
                 needs_grad = bool(grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or
                                                  ctx.needs_input_grad[4] or ctx.needs_input_grad[5]))
                 outs, frame = module._run_forward(pointcloud, pointcloud_features, point_invalid_mask, point_object_id,
-                                                  q_pointcloud_camera, t_pointcloud_camera, camera_info, keep=needs_grad)
+                                                  q_pointcloud_camera, t_pointcloud_camera, camera_info,
+                                                  keep=needs_grad or keep_frame)
                 image, depth, acc_alpha, last, count = outs
                 ctx.frame = frame if needs_grad else None
                 ctx.camera_info = camera_info
@@ -135,7 +137,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                     # node does, so backward(retain_graph=True) followed by another backward works; it goes back to the
                     # pool when autograd drops the node (_Frame.__del__)
                 return (grad_pointcloud, grad_pointcloud_features, None, None,
-                        grad_q if ctx.needs_input_grad[4] else None, grad_t if ctx.needs_input_grad[5] else None, None, None, None, None)
+                        grad_q if ctx.needs_input_grad[4] else None, grad_t if ctx.needs_input_grad[5] else None, None, None, None, None, None)
 
         self._module_function = _module_function
 
@@ -158,6 +160,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         if keep:
             frame.marshalled = (scene, cam, cfg)       # the backward of this frame reads the same tensors (Kmat is kept alive below)
             frame._keepalive = Kmat
+        frame.last = None if self.config.rgb_only else last      # what render_channels walks the frame with
         self.last_frame = frame
         self.last_forward_outputs = {"pixel_accumulated_alpha": acc_alpha, "pixel_offset_of_last_effective_point": last}
         return (image, depth, acc_alpha, last, count), frame
@@ -245,16 +248,25 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
 
     # ------------------------------------------------------------------ nn.Module
     def forward(self, input_data: "GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput",
-                return_accumulated_alpha: bool = False):
+                return_accumulated_alpha: bool = False, keep_frame: bool = False):
         """-> (rasterized_image, rasterized_depth, pixel_valid_point_count), as the reference; with return_accumulated_alpha
-        (extension) a fourth output, pixel_accumulated_alpha (H,W) = 1 - final transmittance, which is differentiable."""
+        (extension) a fourth output, pixel_accumulated_alpha (H,W) = 1 - final transmittance, which is differentiable.
+        keep_frame (extension): keep the frame (self.last_frame) even when no input requires grad or under torch.no_grad(),
+        so that render_channels can be differentiated on it with the geometry frozen."""
         camera_info = input_data.camera_info
         if not getattr(self.config, "allow_partial_tiles", False):
             assert camera_info.camera_width % TILE_WIDTH == 0        # RAST:1193-1194
             assert camera_info.camera_height % TILE_HEIGHT == 0
         if return_accumulated_alpha and self.config.rgb_only:
             raise ValueError("return_accumulated_alpha needs the full forward: rgb_only computes no accumulated alpha")
+        if keep_frame and self.config.rgb_only:
+            raise ValueError("keep_frame needs the full forward: an rgb_only frame cannot be kept")
         return self._module_function.apply(
             input_data.point_cloud, input_data.point_cloud_features, input_data.point_invalid_mask,
             input_data.point_object_id, input_data.q_pointcloud_camera, input_data.t_pointcloud_camera,
-            camera_info, input_data.color_max_sh_band, torch.is_grad_enabled(), bool(return_accumulated_alpha))
+            camera_info, input_data.color_max_sh_band, torch.is_grad_enabled(), bool(return_accumulated_alpha), bool(keep_frame))
+
+    def render_channels(self, values: torch.Tensor, frame: Optional[_Frame] = None) -> torch.Tensor:
+        """values (N,C) float32, C <= 64 -> (H,W,C): the per-Gaussian channels blended over `frame` (default: the frame of
+        the last forward) with the colour's own weights alpha_i T_i; differentiable in `values` only (channels.py)."""
+        return channels.render_channels(values, self.last_frame if frame is None else frame)

@@ -138,6 +138,8 @@ class _Frame:
         """Hands the ticket back.  Transient frames (forward without gradient tracking) belong to the context and are
         recycled by its next forward; their ticket then simply stops resolving."""
         h, self._h = self._h, None
+        if h is not None:
+            self._stale = h                 # the spent ticket: the library refuses it by itself (channels.py passes it on)
         if h is not None and self._owned and self._context.handle:
             _native.call("gs_frame_release", None, self._context.handle, h)
 

@@ -2,6 +2,7 @@
 // arena, frame pool and the forward / backward orchestration that replaces
 // _module_function.forward / .backward of the reference (RAST:830-1163).
 #include "../../include/gs_rasterizer.h"
+#include "../../include/gs_channels.h"
 #include "gs_common.h"
 
 #include <algorithm>
@@ -75,6 +76,7 @@ struct Frame {
     int cut_cap = 0;                    // list-cut records the forward of this frame could claim (0: it wrote none)
     int bwd_reference_order = 0;        // gs_config.bwd_reference_order of the forward that made the frame (gs_backward_projected has no config)
     int n_objects = 0;                  // pose rows of the forward that made the frame (the backward's pose gradient has as many)
+    bool rgb_only = false;              // gs_forward ran with gs_config.rgb_only: no `last` exists for the frame (gs_channels_* refuse it)
     bool max_tiles_known = false;       // k_project of this frame left the largest tile count of one point in the tile arrays (frames from records: no)
     uint32_t generation = 0;
     // gs_project_shard_begin: the hand-over of M (and the object-id check) has not been read yet; slot of the pinned counters
@@ -124,6 +126,7 @@ struct gs_ctx {
     // scratch shared by all frames (stream ordered)
     DevBuf block_counts, block_offsets, tile_block_sums, hist, scan_tmp, counters, partial, visited, zero_row, sums, loss_ws;
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
+    DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
@@ -182,7 +185,8 @@ extern "C" int gs_destroy(gs_ctx* c)
     (void)hipDeviceSynchronize();
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
-                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch };
+                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
+                      &c->ch_partial, &c->ch_flags };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : c->prof.spare) (void)hipEventDestroy(e);
@@ -669,6 +673,7 @@ extern "C" int gs_forward(gs_ctx* c, const gs_scene* sc, const gs_camera* cam, c
     if (rc == GS_OK) rc = run_forward_tail(c, f, pa, sc->n_points, -1, cfg, out, s, &M, &K);
     if (rc != GS_OK) { drop_frame(c, f); return rc; }
     f->bwd_reference_order = cfg->bwd_reference_order;
+    f->rgb_only = cfg->rgb_only != 0;
     finish_frame(c, f, slot, sc->n_points, M, K, GS_STAGE_PROJECT | GS_STAGE_RASTER, frame_out);
     return GS_OK;
 }
@@ -1044,6 +1049,76 @@ extern "C" int gs_backward_shard(gs_ctx* c, gs_frame* h, const gs_scene* sc, con
     a.prof = &c->prof;
     if ((rc = prepare_backward_points(f, sc, cam, cfg, sh_band, out, reinterpret_cast<const float4*>(splat_sums), &a)) != GS_OK) return rc;
     gs_launch_backward_points(a, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- feature channels (include/gs_channels.h, k_channels.hip) --------------------------------------------------------------
+// The checks both directions share (mutex held); on success the stream is entered and *f_out is the frame.
+static int channels_enter(gs_ctx* c, const gs_frame* h, int32_t n_channels, const char* who, gs_stream stream_, Frame** f_out, hipStream_t* s_out)
+{
+    if (n_channels < 1 || n_channels > GS_CHANNELS_MAX)
+        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_channels must be in 1.." + std::to_string(GS_CHANNELS_MAX));
+    Frame* f;
+    if (const int rc = lookup(c, h, who, true, &f)) return rc;
+    if (f->info.stages != (GS_STAGE_PROJECT | GS_STAGE_RASTER))
+        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": the frame must come from gs_forward (frames made from records or shards are not supported)");
+    if (f->rgb_only) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": an rgb_only frame has no pixel_offset_of_last_effective_point");
+    if (const int rc = enter_call(c, stream_, s_out)) return rc;
+    *f_out = f;
+    return GS_OK;
+}
+
+static GsChannelsArgs channels_args(const Frame* f, int32_t n_channels, const int32_t* last)
+{
+    GsChannelsArgs a{};
+    a.v = frame_view(*f);
+    a.M = (int)f->info.n_points_in_camera; a.K = (uint32_t)f->info.n_keys;
+    a.H = f->info.camera_height; a.W = f->info.camera_width; a.tiles_x = (a.W + GS_TILE - 1) / GS_TILE;
+    a.C = n_channels; a.last = last;
+    return a;
+}
+
+extern "C" int gs_channels_forward(gs_ctx* c, const gs_frame* h, const float* values, int32_t n_channels,
+                                   const int32_t* last, float* out, gs_stream stream_)
+{
+    if (!c || !h || !values || !last || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_channels_forward: NULL argument");
+    std::lock_guard<std::mutex> lock(c->mu);
+    Frame* f;
+    hipStream_t s;
+    if (const int rc = channels_enter(c, h, n_channels, "gs_channels_forward", stream_, &f, &s)) return rc;
+    GsChannelsArgs a = channels_args(f, n_channels, last);
+    a.values = values; a.out = out;
+    if (a.K == 0u || a.M <= 0) {                // nothing was blended: the tile ranges are all empty
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)a.H * (size_t)a.W * (size_t)n_channels * sizeof(float), s));
+        return GS_OK;
+    }
+    gs_launch_channels_fwd(a, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_channels_backward(gs_ctx* c, const gs_frame* h, const float* grad_out, int32_t n_channels,
+                                    const int32_t* last, float* grad_values, gs_stream stream_)
+{
+    if (!c || !h || !grad_out || !last || !grad_values) return fail(GS_ERR_INVALID_ARGUMENT, "gs_channels_backward: NULL argument");
+    std::lock_guard<std::mutex> lock(c->mu);
+    Frame* f;
+    hipStream_t s;
+    if (const int rc = channels_enter(c, h, n_channels, "gs_channels_backward", stream_, &f, &s)) return rc;
+    GsChannelsArgs a = channels_args(f, n_channels, last);
+    a.grad_out = grad_out; a.grad_values = grad_values;
+    // rows outside the camera are zero; k_channels_sum writes every in-camera row
+    if (f->info.n_points > 0) HIP_TRY(hipMemsetAsync(grad_values, 0, (size_t)f->info.n_points * (size_t)n_channels * sizeof(float), s));
+    if (a.K == 0u || a.M <= 0) return GS_OK;
+    // scratch of one channel chunk: four partial rows (one per quadrant) per (point, tile) pair, their flags, one byte per point
+    const size_t rows = (size_t)a.K * 4, row_flags = (rows + 15) / 16 * 16;
+    if (const int rc = grow(c, { NEED(c->ch_partial, rows * (size_t)gs_channels_chunk(n_channels) * sizeof(float)),
+                                 NEED(c->ch_flags, row_flags + (size_t)a.M) }))
+        return rc;
+    a.partial = c->ch_partial.as<float>(); a.flags = c->ch_flags.as<uint8_t>(); a.touched = a.flags + row_flags;
+    a.flag_bytes = row_flags + (size_t)a.M;
+    HIP_TRY(gs_launch_channels_bwd(a, s));
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

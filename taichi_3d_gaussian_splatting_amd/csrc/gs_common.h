@@ -400,6 +400,22 @@ void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s);    // a.
 size_t gs_pose_scratch_size(int M, int n_objects);
 void gs_launch_pose_grad(const GsBackwardArgs& a, int n_objects, void* scratch, float* grad_q, float* grad_t, hipStream_t s);
 
+// per-Gaussian feature channels over a frame (k_channels.hip; include/gs_channels.h).  Forward: values (N,C) -> out (H,W,C);
+// backward: grad_out (H,W,C) -> grad_values (N,C), whose rows outside the camera the caller has zeroed.
+struct GsChannelsArgs {
+    GsFrameView v;                              // read: sorted pairs, records, ids, tile ranges; the backward also box, offsets, ntiles
+    int M; uint32_t K; int H, W, tiles_x; int C;
+    const int32_t* last;                        // the forward's pixel_offset_of_last_effective_point
+    const float* values; float* out;
+    const float* grad_out; float* grad_values;
+    // backward scratch of one channel chunk: (4K, chunk) partial rows, one per (point, tile, quadrant) in slot order; 4K row flags
+    // with the M per-point `touched` bytes behind them (flag_bytes in all, cleared before every chunk)
+    float* partial; uint8_t* flags; uint8_t* touched; size_t flag_bytes;
+};
+int gs_channels_chunk(int C);                   // channels per pass: 4, 16 or 32
+void gs_launch_channels_fwd(const GsChannelsArgs& a, hipStream_t s);
+hipError_t gs_launch_channels_bwd(const GsChannelsArgs& a, hipStream_t s);
+
 // the argument of k_export, passed by value
 struct GsExportArgs { int what; int64_t N; int M; uint32_t K; int T; int depth_bits; int key64;
     const int32_t* ids; const float4 *PA, *PB, *PC, *PD; const int32_t* ntiles; const uint32_t* offsets;
