@@ -321,7 +321,7 @@ static void finish_frame(gs_ctx* c, Frame* f, int slot, int64_t N, int M, uint32
 }
 
 // The one description of a frame's device buffers.  Records: one 64-byte row per point.  Tile arrays (GS_TILE_INTS):
-// tile_start | tile_end | tile_work | tile_cut (T each) | cut_alloc, max tiles, two spare.  Tile order (GS_ORDER_INTS):
+// tile_start | tile_end | tile_work | tile_cut (T each) | spare, max tiles, two spare.  Tile order (GS_ORDER_INTS):
 // order (T) | n_heavy | n_items | pad pad | item_base.
 static GsFrameView frame_view(const Frame& f)
 {
@@ -335,7 +335,6 @@ static GsFrameView frame_view(const Frame& f)
     v.T = T;
     int32_t* tiles = B.tile_start.as<int32_t>();
     v.tile_start = tiles; v.tile_end = tiles + T; v.tile_work = tiles + 2 * (size_t)T; v.tile_cut = tiles + 3 * (size_t)T;
-    v.cut_alloc = tiles + 4 * (size_t)T;
     v.max_tiles = tiles + GS_TILE_INTS(T) - GS_TILE_SPARE_MAX_TILES;
     v.tile_ints = (int)GS_TILE_INTS(T);
     v.tile_order = B.tile_order.as<int32_t>(); v.n_heavy = v.tile_order + T;
@@ -457,7 +456,7 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     int rc = grow(c, { NEED(B.mask, Np), NEED(B.ids, 4 * Np), NEED(B.cam_index, 4 * Np),
                        NEED(B.rec, 64 * Np),
                        NEED(B.box, 8 * Np), NEED(B.ntiles, 4 * Np), NEED(B.depth_codes, 4 * Np), NEED(B.offsets, 4 * Np),
-                       NEED(B.tile_start, 4 * GS_TILE_INTS(T)),    // tile_start | tile_end | tile_work | tile_cut | cut_alloc, cleared together
+                       NEED(B.tile_start, 4 * GS_TILE_INTS(T)),    // tile_start | tile_end | tile_work | tile_cut | four ints, cleared together
                        NEED(B.tile_order, 4 * GS_ORDER_INTS(T)),   // + heavy-tile count, item count and item bases behind the order
                        NEED(B.pose, sizeof(GsPose) * (size_t)cam->n_objects),
                        NEED(c->block_counts, 4 * (nb + 1)), NEED(c->block_offsets, 4 * (nb + 1)),
@@ -559,13 +558,13 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     const size_t key_bytes = key64 ? 8 : 4;
     const size_t hist_elems = gs_sort_hist_elems(K_bound);
     if (const int rc = grow(c, { NEED(B.keys_a, key_bytes * Kp), NEED(B.keys_b, key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
-                                 NEED(c->hist, 4 * hist_elems), NEED(c->scan_tmp, 4 * gs_scan_tmp_elems(hist_elems)) }))
+                                 NEED(c->hist, 4 * hist_elems), NEED(c->scan_tmp, 4 * GS_SORT_DIGITS) }))
         return rc;
 
     GsBinArgs ba{};
     ba.prof = &c->prof;
     ba.N = n_rows; ba.M = M_bound; ba.K = K_bound; ba.counters = c->counters.as<GsCounters>();
-    ba.tiles_x = tiles_x; ba.depth_scale = cfg->depth_to_sort_key_scale;
+    ba.tiles_x = tiles_x;
     ba.depth_bits = depth_bits; ba.key_bits = depth_bits + tile_bits;
     ba.v = frame_view(*f);
     ba.tile_block_sums = pa.tile_block_sums;

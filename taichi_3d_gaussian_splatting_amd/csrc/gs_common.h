@@ -52,9 +52,9 @@ extern __device__ unsigned long long gs_stats_wave_times[2 * 65536];   // start,
 #define GS_CUT_MIN_LEN 512
 #endif
 #define GS_HEAVY_CAP 1024            // most tiles a backward treats as heavy
-// tile arrays of a frame, cleared by its first kernel: tile_start | tile_end | tile_work | tile_cut (first cut record + 1, 0 = none) | cut_alloc
+// tile arrays of a frame, cleared by its first kernel: tile_start | tile_end | tile_work | tile_cut (first cut record + 1, 0 = none) | four spare ints
 #define GS_TILE_INTS(T) (4 * (size_t)(T) + 4)
-// the four trailing ints: one unused (the cut records' claim counter until their positions became a closed form), then the largest tile count of one point of the frame (k_project -> k_sum_rows), two spare
+// the four trailing ints: one spare (the cut records' claim counter until their positions became a closed form), then the largest tile count of one point of the frame (k_project -> k_sum_rows), two spare
 #define GS_TILE_SPARE_MAX_TILES 3          // index from the END of the tile arrays
 // tile_order buffer: order (T) | n_heavy | n_items | pad pad | item_base (GS_HEAVY_CAP + 1)
 #define GS_ORDER_INTS(T) ((size_t)(T) + 4 + GS_HEAVY_CAP + 4 + GS_HEAVY_CAP)
@@ -282,6 +282,37 @@ __device__ __forceinline__ int gs_wave_max_i(int v)
     return v;
 }
 
+// inclusive scan over the 64 lanes (lane 63 holds the wave's total)
+__device__ __forceinline__ uint32_t gs_wave_scan_incl(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+    return v;
+}
+// Block reductions and scans over NW waves go through an NW-word LDS array in two halves, a deposit and a combine; the __syncthreads()
+// between them stays in the KERNEL, where one barrier often serves several of these (and other LDS) at once.
+//   reduction:  gs_block_put(ws, wave, lane, <the wave's total, in every lane>);  barrier;  gs_block_sum<NW>(ws) / gs_block_max<NW>(ws)
+//   scan:       incl = gs_wave_scan_incl(v, lane);  gs_block_scan_put(ws, wave, lane, incl);  barrier;
+//               gs_block_scan_excl(ws, wave, incl, v) = the waves before mine + the lanes before me;  total = gs_block_sum<NW>(ws)
+template <typename T> __device__ __forceinline__ void gs_block_put(T* ws, int wave, int lane, T v) { if (lane == 0) ws[wave] = v; }
+__device__ __forceinline__ void gs_block_scan_put(uint32_t* ws, int wave, int lane, uint32_t incl) { if (lane == 63) ws[wave] = incl; }
+template <int NW, typename T> __device__ __forceinline__ T gs_block_sum(const T* ws) { if constexpr (NW == 1) return ws[0]; else return gs_block_sum<NW - 1>(ws) + ws[NW - 1]; }
+template <int NW> __device__ __forceinline__ int gs_block_max(const int* ws) { if constexpr (NW == 1) return ws[0]; else return max(gs_block_max<NW / 2>(ws), gs_block_max<NW / 2>(ws + NW / 2)); }
+__device__ __forceinline__ uint32_t gs_block_scan_excl(const uint32_t* ws, int wave, uint32_t incl, uint32_t v)
+{
+    uint32_t woff = 0;
+    for (int w = 0; w < wave; ++w) woff += ws[w];
+    return woff + incl - v;
+}
+// counts[0 .. block) summed by a block of NT threads (a few thousand L2-resident words read by every block, instead of a scan launch in
+// between): every lane gets its WAVE's share, the caller folds the shares with a block sum
+template <int NT, typename T> __device__ __forceinline__ T gs_sum_of_blocks_before(const T* __restrict__ counts, int block)
+{
+    T pre = 0;
+    for (int j = threadIdx.x; j < block; j += NT) pre += counts[j];
+    return (T)gs_wave_sum_i((int)pre);
+}
+
 // ---- optional per-kernel timing with HIP events on the launch stream -------------
 // Kernel ids index the comma-separated list returned by gs_kernel_names().
 enum GsKernelId { KID_FILTER = 0, KID_PUBLISH, KID_PROJECT, KID_KEYGEN,
@@ -310,7 +341,7 @@ struct GsFrameView {
     // the tile arrays, cleared together by the frame's first kernel (tile_ints ints from tile_start on)
     int32_t *tile_start, *tile_end;             // written by the forward blend (each tile's block finds its range in the sorted keys)
     int32_t* tile_work;                         // (T) max over the tile's pixels of last - start (k_blend_fwd)
-    int32_t* tile_cut; int32_t* cut_alloc;      // (T) first cut record of each tile + 1, 0 = none; unused claim counter
+    int32_t* tile_cut;                          // (T) first cut record of each tile + 1, 0 = none
     int32_t* max_tiles;                         // the frame's largest tile count of one point (k_project -> k_sum_rows)
     int tile_ints;
     int32_t* tile_order;                        // (T) scheduling: heaviest tiles first (k_tile_order)
@@ -340,7 +371,7 @@ struct GsBinArgs {
     // M and K are BOUNDS here: the per-pixel half may be queued before the host has read the frame's counters (gs_api.hip,
     // "predicted sizing").  M bounds the in-camera offsets (N rows when unknown); K is the pair capacity the launch geometry and
     // the buffers were sized for -- every kernel works on min(counters->K, K) pairs, read on the device.
-    int64_t N; int M; uint32_t K; const GsCounters* counters; int tiles_x; float depth_scale; int depth_bits; int key_bits;
+    int64_t N; int M; uint32_t K; const GsCounters* counters; int tiles_x; int depth_bits; int key_bits;
     GsFrameView v;                              // read: box, ntiles, depth codes; written: offsets
     const uint32_t* tile_block_sums;
     GsCounters* counters_rw; GsCounters* host_mirror; int32_t ticket;   // host_mirror != NULL: the last k_keygen block publishes the frame counters
@@ -348,12 +379,12 @@ struct GsBinArgs {
     void *keys_a, *keys_b; int32_t *vals_a, *vals_b;       // ping-pong (K); keys are u32, or u64 when key64
     int key64;                                             // depth bits + tile bits > 32
     uint32_t* hist;                             // (256 * sort_blocks) + scratch
-    uint32_t* scan_tmp;                         // 256 digit totals of the current pass
+    uint32_t* scan_tmp;                         // GS_SORT_DIGITS digit totals of the current pass
     void** keys_sorted; int32_t** vals_sorted;       // out: which of a/b holds the result
 };
 void gs_launch_binning(const GsBinArgs& a, hipStream_t s);
 size_t gs_sort_hist_elems(uint32_t K);
-size_t gs_scan_tmp_elems(size_t n);
+#define GS_SORT_DIGITS 256          // words of scan_tmp: one row total per digit (k_binning.hip: k_sort_rowscan)
 
 struct GsBlendFwdArgs {
     GsProf* prof;

@@ -1,4 +1,5 @@
-// gs_cull.h -- conservative per-quadrant culling shared by the forward and backward blend kernels.
+// gs_cull.h -- what the kernels that walk a tile's list per 8x8 quadrant share (k_blend_fwd, k_channels, k_backward): the
+// quadrant's pixels (GsQuadPixel), one blend step's alpha (gs_splat_alpha, gs_alpha_clamp) and the conservative cull.
 //
 // A splat is dropped for an 8x8 pixel quadrant only when alpha = exp(e) * rescale * opacity is
 // certainly below 1/255 at every pixel centre of the quadrant, i.e. when the reference's own test
@@ -73,3 +74,38 @@ __device__ __forceinline__ bool gs_cull(const CullSplat& s, float rx0, float ry0
     return s.pd && (-0.5f * qmin + slack < s.cut);
 }
 
+// One lane's pixel of an 8x8 quadrant (quadrant bit 0 = right half of the 16x16 tile, bit 1 = lower half; lane = 8 * row + column).
+// A pixel of a partial edge tile that lies outside the image does not exist (extension; W, H % 16 == 0 in the reference): !inside.
+struct GsQuadPixel {
+    int tile_u, tile_v, qx, qy, pixel_u, pixel_v;   // the tile, the quadrant's first pixel, this lane's pixel
+    bool inside; size_t o;                          // o = pixel_v * W + pixel_u (an address only when inside)
+    float px, py, rx0, ry0;                         // pixel centre; centre of the quadrant's first pixel (origin of the cull rectangle)
+};
+__device__ __forceinline__ GsQuadPixel gs_quad_pixel(int tile, int quadrant, int lane, int tiles_x, int W, int H)
+{
+    GsQuadPixel q;
+    q.tile_u = tile % tiles_x; q.tile_v = tile / tiles_x;
+    q.qx = q.tile_u * 16 + (quadrant & 1) * 8; q.qy = q.tile_v * 16 + (quadrant >> 1) * 8;
+    q.pixel_u = q.qx + (lane & 7); q.pixel_v = q.qy + (lane >> 3);
+    q.inside = q.pixel_u < W && q.pixel_v < H; q.o = (size_t)q.pixel_v * (size_t)W + (size_t)q.pixel_u;
+    q.px = (float)q.pixel_u + 0.5f; q.py = (float)q.pixel_v + 0.5f; q.rx0 = (float)q.qx + 0.5f; q.ry0 = (float)q.qy + 0.5f;
+    return q;
+}
+// a pixel's pixel_offset_of_last_effective_point as the end of its walk: inside the tile's range whatever the caller passed
+__device__ __forceinline__ int gs_clamp_last(int last, int start, int end) { return last < start ? start : (last > end ? end : last); }
+
+// alpha of splat (a4 = {u, v, conic a, conic b}, b4 = {conic c, rescale, opacity, depth}) at pixel centre (px, py), before the clamp, in two
+// halves: the exponent, get_point_probability_density_from_conic_and_rescale UTIL:275-284 (same op order), and exp(e) * rescale * opacity
+// (RAST:449-450).  k_blend_fwd calls the halves itself, for two splats side by side as in its schedule; gs_splat_alpha is the two in a row.
+__device__ __forceinline__ float gs_splat_exponent(float px, float py, float4 a4, float4 b4)
+{
+    const float dx = px - a4.x, dy = py - a4.y;
+    return -0.5f * (dx * dx * a4.z + dy * dy * b4.x) - dx * dy * a4.w;
+}
+__device__ __forceinline__ float gs_alpha_of_exponent(float e, float4 b4) { return gs_exp_blend(e) * b4.y * b4.z; }
+__device__ __forceinline__ float gs_splat_alpha(float px, float py, float4 a4, float4 b4) { return gs_alpha_of_exponent(gs_splat_exponent(px, py, a4, b4), b4); }
+// min(alpha, 0.99), RAST:453, as the UNSIGNED minimum of the bit patterns: one instruction (the float form costs a canonicalising
+// v_max first).  Same value for every alpha >= 0; a NaN of either sign gives 0.99 like the compare-and-select of the oracle; a
+// negative alpha (never blended: it fails the 1/255 test) may come out as 0.99.
+// (gs_clamp_alpha of k_backward.hip is not this one: it clamps a product known to be positive, with the SIGNED minimum.)
+__device__ __forceinline__ float gs_alpha_clamp(float alpha) { return __uint_as_float(min(__float_as_uint(alpha), __float_as_uint(GS_ALPHA_MAX))); }

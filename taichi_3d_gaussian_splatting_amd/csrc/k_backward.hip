@@ -94,9 +94,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     __syncthreads();
     // exclusive scan of the 2048 bins (2 per thread)
     uint32_t a = bins[2 * t], b = bins[2 * t + 1];
-    uint32_t incl = a + b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+    const uint32_t incl = gs_wave_scan_incl(a + b, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     uint32_t woff = 0;
@@ -155,9 +153,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     // Segments are handed out heaviest tile first for as long as the grid's item capacity lasts (every later tile still needs one item):
     // inclusive scan of the wanted counts; a tile keeps its segments while (items up to and including it) + (tiles after it) fits.
     auto block_scan = [&](uint32_t x, uint32_t& excl, uint32_t& total_out) {
-        uint32_t inc = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(inc, o, 64); if (lane >= o) inc += y; }
+        const uint32_t inc = gs_wave_scan_incl(x, lane);
         __syncthreads();
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
@@ -305,6 +301,8 @@ __device__ __forceinline__ void gs_bwd_tile_body(const int tile, const int grp, 
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
         const int q = grp * NQ + qi;
+        // (gs_quad_pixel, written out here and at the end of this function: through the struct every instance of the two blend kernels
+        // comes out scheduled differently, and this one sits at a VGPR boundary -- see the note at the end)
         const int pu = tile_u * 16 + (q & 1) * 8 + lx, pv = tile_v * 16 + (q >> 1) * 8 + ly;
         // pixels of a partial edge tile outside the image do not exist: nothing is in range for them
         const bool inside = pu < W && pv < H;
@@ -736,13 +734,12 @@ __device__ __forceinline__ void gs_fold_mag(const GsMagFold& fold)
         if (fold.n_heavy[GS_ORDER_REDO_OFFSET + h] != 0) return;              // walked again in one piece (k_blend_bwd_repair): its pixels' sums are final
         const int tile = fold.tile_order[h];
         const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const int pu = (tile % fold.tiles_x) * 16 + (q & 1) * 8 + (lane & 7), pv = (tile / fold.tiles_x) * 16 + (q >> 1) * 8 + (lane >> 3);
-        if (pu >= fold.W || pv >= fold.H) return;
+        const GsQuadPixel qp = gs_quad_pixel(tile, q, lane, fold.tiles_x, fold.W, fold.H);
+        if (!qp.inside) return;
         const float2* part = fold.cut_mag + (size_t)(fold.tile_cut[tile] - 1) * 256 + threadIdx.x;
         float a = 0.0f, b = 0.0f;
         for (int sgm = nseg - 1; sgm >= 0; --sgm) { const float2 v = part[(size_t)sgm * 256]; a += v.x; b += v.y; }   // back to front, like the walk
-        const size_t o = (size_t)pv * (size_t)fold.W + (size_t)pu;
-        fold.mag_image[2 * o] = a; fold.mag_image[2 * o + 1] = b;
+        fold.mag_image[2 * qp.o] = a; fold.mag_image[2 * qp.o + 1] = b;
 }
 
 // AUX: also column 11 (d depth), in the same slot order; otherwise it is written as 0 (the staged path's sums keep it so)

@@ -31,13 +31,12 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
                                                 const uint32_t* __restrict__ tile_block_sums,
                                                 const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ block_counts,
                                                 int M, int tiles_x,
-                                                float depth_scale, int depth_bits, uint32_t K_cap,
+                                                int depth_bits, uint32_t K_cap,
                                                 uint32_t* __restrict__ offsets, KeyT* __restrict__ keys,
                                                 int32_t* __restrict__ vals,
                                                 GsCounters* __restrict__ counters, volatile GsCounters* host_mirror, int32_t ticket)
 {
-    __shared__ uint32_t ws[4];
-    __shared__ uint32_t wpre[4];
+    __shared__ uint32_t ws[4], wpre[4];
     __shared__ uint32_t sExcl[256 + 1];
     __shared__ ushort4 sBox[256];
     __shared__ KeyT sCode[256];
@@ -49,28 +48,20 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool valid = idx < M;
     const uint32_t n = valid ? (uint32_t)ntiles[idx] : 0u;
-    uint32_t incl = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    if (lane == 63) ws[wave] = incl;
+    const uint32_t incl = gs_wave_scan_incl(n, lane);
+    gs_block_scan_put(ws, wave, lane, incl);
     sBox[threadIdx.x] = valid ? boxes[idx] : make_ushort4(0, 1, 0, 1);
     sCode[threadIdx.x] = valid ? (KeyT)(uint32_t)depth_codes[idx] : (KeyT)0;     // i32(depth * scale), RAST:159-160, from k_project
-    // first pair of this block = the tile counts of all blocks before it (RAST:913-922 across blocks): a few thousand L2-resident
-    // counters summed by the block itself, instead of a scan launch in between
-    uint32_t pre = 0;
-    for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) pre += tile_block_sums[j];
-    pre = (uint32_t)gs_wave_sum_i((int)pre);
-    if (lane == 0) wpre[wave] = pre;
-    __syncthreads();
-    const uint32_t block_base = wpre[0] + wpre[1] + wpre[2] + wpre[3];
-    const uint32_t block_total = ws[0] + ws[1] + ws[2] + ws[3];
+    // first pair of this block = the tile counts of all blocks before it (RAST:913-922 across blocks)
+    gs_block_put(wpre, wave, lane, gs_sum_of_blocks_before<256>(tile_block_sums, (int)blockIdx.x));
+    __syncthreads();                                                              // the scan, wpre and the LDS table
+    const uint32_t block_base = gs_block_sum<4>(wpre);
+    const uint32_t block_total = gs_block_sum<4>(ws);
     // the last block knows K = its base + its own count: it hands the frame counters to the host when the launch was queued
     // before the host had them (predicted sizing; k_project.hip: gs_publish_counters)
     if (host_mirror && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
         gs_publish_counters(counters, block_base + block_total, host_mirror, ticket);
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += ws[w];
-    const uint32_t excl = woff + incl - n;                                        // first pair of this point inside the block
+    const uint32_t excl = gs_block_scan_excl(ws, wave, incl, n);                  // first pair of this point inside the block
     sExcl[threadIdx.x] = excl;
     if (threadIdx.x == 0) sExcl[256] = 0xffffffffu;
     if (valid) offsets[idx] = block_base + excl;                                  // RAST:913-922 (also the backward's row slots)
@@ -98,7 +89,6 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
             vals[slot] = first + j;
         }
     }
-    (void)depth_scale;
 }
 
 template <typename KeyT>
@@ -132,7 +122,7 @@ __global__ __launch_bounds__(256) void k_sort_hist(const KeyT* __restrict__ keys
 // the scatter's prologue: k_sort_rowscan (one block per digit) scans the digit's own row exclusively and leaves the
 // row's total in `totals`; every scatter block then adds, for each digit, the totals of all smaller digits (a
 // 256-element block scan).  No atomics, no cross-block waiting, fixed order.
-__global__ __launch_bounds__(1024) void k_sort_rowscan(const uint32_t* __restrict__ hist, uint32_t* __restrict__ totals,
+__global__ __launch_bounds__(1024) void k_sort_rowscan(const uint32_t* __restrict__ hist, uint32_t* __restrict__ totals /* GS_SORT_DIGITS */,
                                                        uint32_t* __restrict__ offsets_out, int nblocks)
 {
     __shared__ uint32_t wsum[16];
@@ -143,18 +133,13 @@ __global__ __launch_bounds__(1024) void k_sort_rowscan(const uint32_t* __restric
     for (int start = 0; start < nblocks; start += 1024) {
         const int i = start + t;
         const uint32_t x = i < nblocks ? row[i] : 0u;
-        uint32_t incl = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
+        const uint32_t incl = gs_wave_scan_incl(x, lane);
+        __syncthreads();                                            // the previous trip's reads of wsum
+        gs_block_scan_put(wsum, wave, lane, incl);
         __syncthreads();
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        if (i < nblocks) orow[i] = carry + woff + incl - x;
-        uint32_t tot = 0;
-        for (int w = 0; w < 16; ++w) tot += wsum[w];
-        carry += tot;
+        const uint32_t excl = gs_block_scan_excl(wsum, wave, incl, x);
+        if (i < nblocks) orow[i] = carry + excl;
+        carry += gs_block_sum<16>(wsum);
     }
     if (t == 0) totals[d] = carry;
 }
@@ -182,14 +167,10 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const KeyT* __restrict__ k
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     {   // global start of digit t = totals of all smaller digits (exclusive scan of the 256 row totals) + this block's offset in the row
         const uint32_t tot = totals[t];
-        uint32_t incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
-        if (lane == 63) wtot[wave] = incl;
+        const uint32_t incl = gs_wave_scan_incl(tot, lane);
+        gs_block_scan_put(wtot, wave, lane, incl);
         __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wtot[w];
-        gbase[t] = (woff + incl - tot) + hist_scanned[t * nblocks + blockIdx.x];
+        gbase[t] = gs_block_scan_excl(wtot, wave, incl, tot) + hist_scanned[t * nblocks + blockIdx.x];
         __syncthreads();
     }
     // one 4096-pair tile; FULL (every tile but the last of the array) drops all bounds predicates
@@ -232,14 +213,10 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const KeyT* __restrict__ k
         // thread t owns digit t: tile total, exclusive scan over digits, per-wave starts
         const uint32_t c0 = cnt[0][t], c1 = cnt[1][t], c2 = cnt[2][t], c3 = cnt[3][t];
         const uint32_t tot = c0 + c1 + c2 + c3;
-        uint32_t incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
-        if (lane == 63) wtot[wave] = incl;
+        const uint32_t incl = gs_wave_scan_incl(tot, lane);
+        gs_block_scan_put(wtot, wave, lane, incl);
         __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wtot[w];
-        const uint32_t ds = woff + incl - tot;
+        const uint32_t ds = gs_block_scan_excl(wtot, wave, incl, tot);
         dstart[t] = ds;
         cnt[0][t] = ds; cnt[1][t] = ds + c0; cnt[2][t] = ds + c0 + c1; cnt[3][t] = ds + c0 + c1 + c2;
         __syncthreads();
@@ -296,8 +273,6 @@ size_t gs_sort_hist_elems(uint32_t K)
     return (size_t)2 * 256 * nb;      // raw counts + scanned offsets
 }
 
-size_t gs_scan_tmp_elems(size_t) { return 256; }      // the 256 row totals of k_sort_rowscan
-
 template <typename KeyT>
 static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
 {
@@ -308,7 +283,7 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
     if (a.N == 0 || a.M == 0) return;
     const unsigned kg_blocks = a.block_offsets ? (unsigned)((a.N + 255) / 256) : (unsigned)((a.M + 255) / 256);
     GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT><<<kg_blocks, 256, 0, s>>>(
-        a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_scale, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
+        a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
         a.counters_rw, a.host_mirror, a.ticket));
     if (a.K == 0) return;
     int nb, tpb;
@@ -318,7 +293,7 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
     for (int shift = 0; shift < a.key_bits; shift += 8) {
         uint32_t* offs = a.hist + (size_t)256 * nb;                 // second half of the table: scanned offsets
         GS_TIMED(a.prof, KID_SORT_HIST, s, k_sort_hist<KeyT><<<nb, 256, 0, s>>>(kin, a.counters, a.K, shift, a.hist, nb, tpb));
-        GS_TIMED(a.prof, KID_SORT_ROWSCAN, s, k_sort_rowscan<<<256, 1024, 0, s>>>(a.hist, a.scan_tmp, offs, nb));
+        GS_TIMED(a.prof, KID_SORT_ROWSCAN, s, k_sort_rowscan<<<GS_SORT_DIGITS, 1024, 0, s>>>(a.hist, a.scan_tmp, offs, nb));
         GS_TIMED(a.prof, KID_SORT_SCATTER, s, k_sort_scatter<KeyT><<<nb, 256, 0, s>>>(kin, vin, kout, vout, a.counters, a.K, shift, offs, a.scan_tmp, nb, tpb));
         KeyT* tk = kin; kin = kout; kout = tk;
         int32_t* tv = vin; vin = vout; vout = tv;

@@ -14,9 +14,6 @@
 // Bound: FP32 VALU (exp polynomial + blend), not HBM: see DESIGN.md.
 #include "gs_common.h"
 #include "gs_cull.h"
-#ifndef GS_FWD_INT_MIN
-#define GS_FWD_INT_MIN 1
-#endif
 #ifndef GS_WORK_PER_BATCH
 #define GS_WORK_PER_BATCH 8      // a walked batch in units of (splat, quadrant) evaluations, for the tile ordering / heavy-tile choice
 #endif
@@ -53,7 +50,7 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
                                                    float* __restrict__ acc_alpha, int32_t* __restrict__ last_out,
                                                    int32_t* __restrict__ count_out, int32_t* __restrict__ tile_work,
                                                    const int32_t* __restrict__ order_hint,
-                                                   float4* __restrict__ cuts, int32_t* __restrict__ tile_cut, int32_t* __restrict__ cut_alloc, int cut_cap)
+                                                   float4* __restrict__ cuts, int32_t* __restrict__ tile_cut, int cut_cap)
 {
     __shared__ float4 sRec[4][64][3];          // the batch's splat records, one slab per wave
     const uint32_t K = min(ctr->K, K_cap);     // pairs of this frame, read on the device (gs_api.hip: predicted sizing)
@@ -62,11 +59,7 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
     const int tile = order_hint ? order_hint[blockIdx.x] : (int)blockIdx.x;
     // the wave index as a scalar: LDS addresses of the wave's slab are then SGPR arithmetic + one v_mov instead of a 64-bit VALU mad per splat
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int tile_u = tile % tiles_x, tile_v = tile / tiles_x;
-    const int qx = tile_u * 16 + (wave & 1) * 8, qy = tile_v * 16 + (wave >> 1) * 8;
-    const int pixel_u = qx + (lane & 7), pixel_v = qy + (lane >> 3);
-    const float px = (float)pixel_u + 0.5f, py = (float)pixel_v + 0.5f;
-    const float rx0 = (float)qx + 0.5f, ry0 = (float)qy + 0.5f;
+    const GsQuadPixel qp = gs_quad_pixel(tile, wave, lane, tiles_x, W, H);
     // the tile's range in the sorted list: wave 0 finds where the tile starts, wave 1 where the next one does; an empty
     // tile keeps the reference's zero-initialised 0, 0 (RAST:954-957).  The ranges are stored for the backward.
     __shared__ int sRange[2];
@@ -109,11 +102,9 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
     int last = start, count = 0;
     int evals = 0;                 // work the backward will repeat for this quadrant (wave-uniform): GS_WORK_PER_BATCH per 64-entry batch
                                    // walked (index load, record gather, cull: latency a lone wave pays in full) + 1 per splat that survived the cull
-    // a pixel of a partial edge tile that lies outside the image does not exist (extension; W,H % 16 == 0 in the reference)
-    const bool inside = pixel_u < W && pixel_v < H;
     // Lane predicates live as wave-uniform 64-bit masks in SGPRs (votes fold into the v_cmp that made them, and
     // inverse_ballot turns a mask back into exec without VALU work): `alive` = lanes that have not saturated yet.
-    unsigned long long alive = gs_ballot(inside);
+    unsigned long long alive = gs_ballot(qp.inside);
 
     for (int base = start; base < end; base += 64) {
         if (alive == 0ull) break;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
         const bool valid = i < end;
         const int p = valid ? sorted_vals[i] : 0;
         float4 A = GS_REC(PA, p), B = GS_REC(PB, p), C = GS_REC(PC, p);
-        const CullRect lr = gs_live_rect(alive, rx0, ry0);          // the pixels that have not saturated yet
+        const CullRect lr = gs_live_rect(alive, qp.rx0, qp.ry0);          // the pixels that have not saturated yet
         bool keep = valid && !gs_cull(gs_cull_prepare(A, B, C), lr.x0, lr.y0, lr.wx, lr.wy);
         unsigned long long mask = gs_ballot(keep);
         GS_STAT(0, 1); GS_STAT(1, __popcll(mask));
@@ -159,25 +150,17 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
             asm("s_bitset0_b64 %0, %1" : "+s"(mask) : "s"(j1));
             const float4 a40 = sRec[wave][j0][0], b40 = sRec[wave][j0][1], c40 = sRec[wave][j0][2];
             const float4 a41 = sRec[wave][j1][0], b41 = sRec[wave][j1][1], c41 = sRec[wave][j1][2];
-            // get_point_probability_density_from_conic_and_rescale, UTIL:275-284 (same op order)
-            const float dx0 = px - a40.x, dy0 = py - a40.y, dx1 = px - a41.x, dy1 = py - a41.y;
-            const float e0 = -0.5f * (dx0 * dx0 * a40.z + dy0 * dy0 * b40.x) - dx0 * dy0 * a40.w;
-            const float e1 = -0.5f * (dx1 * dx1 * a41.z + dy1 * dy1 * b41.x) - dx1 * dy1 * a41.w;
-            float alpha0 = gs_exp_blend(e0) * b40.y * b40.z;
-            float alpha1 = gs_exp_blend(e1) * b41.y * b41.z;
+            const float e0 = gs_splat_exponent(qp.px, qp.py, a40, b40), e1 = gs_splat_exponent(qp.px, qp.py, a41, b41);   // gs_splat_alpha, half by half
+            float alpha0 = gs_alpha_of_exponent(e0, b40);
+            float alpha1 = gs_alpha_of_exponent(e1, b41);
             // both alphas are complete HERE: without this the compiler sinks the second chain below the first blend step
             // (next to its only use) and the two run one after the other
             asm volatile("" : "+v"(alpha0), "+v"(alpha1));
 #define GS_FWD_STEP(ALPHA, A4, B4, C4, J, LIVE)                                                                                        \
             {                                                                                                                    \
                 GS_STAT(2, 1);                                                                                                   \
-                float alpha = (ALPHA);                                                                                           \
-                unsigned long long use_m = gs_ballot(!(alpha < GS_ALPHA_EPS)) & (LIVE);   /* RAST:451 */                          \
-                /* min(alpha, 0.99), RAST:453, as the UNSIGNED minimum of the bit patterns: one instruction (the float form costs a  */ \
-                /* canonicalising v_max first).  Same value for every alpha >= 0; a NaN of either sign gives 0.99 like the compare- */ \
-                /* and-select of the oracle; a negative alpha (never blended: it fails the 1/255 test) may come out as 0.99         */ \
-                alpha = GS_FWD_INT_MIN ? __uint_as_float(min(__float_as_uint(alpha), __float_as_uint(GS_ALPHA_MAX)))                \
-                                       : (alpha < GS_ALPHA_MAX ? alpha : GS_ALPHA_MAX);                                             \
+                unsigned long long use_m = gs_ballot(!((ALPHA) < GS_ALPHA_EPS)) & (LIVE); /* RAST:451 */                          \
+                const float alpha = gs_alpha_clamp(ALPHA);                                /* RAST:453 */                          \
                 const float next_T = T_i * (1.0f - alpha);                                /* RAST:457 */                          \
                 const unsigned long long sat_m = gs_ballot(next_T < GS_T_STOP) & use_m;   /* RAST:458-460 */                      \
                 alive &= ~sat_m;                                                                                                 \
@@ -214,8 +197,8 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
         cuts[(size_t)(cut_base + n_rec - 1) * 256 + threadIdx.x] = make_float4(T_i, cr, cg, cb);
     }
     cr += tot_r; cg += tot_g; cb += tot_b;          // (exact for a list without cuts: the totals are zero)
-    if (!inside) return;
-    const size_t o = (size_t)pixel_v * (size_t)W + (size_t)pixel_u;
+    if (!qp.inside) return;
+    const size_t o = qp.o;                          // (outside the image: no pixel, see GsQuadPixel)
     image[3 * o] = cr; image[3 * o + 1] = cg; image[3 * o + 2] = cb;
     if (!RGB_ONLY) {
         depth_out[o] = acc_d / (norm > 1e-6f ? norm : 1e-6f);                  // RAST:479-480
@@ -232,10 +215,10 @@ void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s)
 {
     const GsFrameView& v = a.v;
     if (v.T <= 0) return;
-    if (a.rgb_only)
-        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<true><<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
-                                                                             a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, v.cut_alloc, a.cut_cap));
-    else
-        GS_TIMED(a.prof, KID_BLEND_FWD, s, k_blend_fwd<false><<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
-                                                                              a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, v.cut_alloc, a.cut_cap));
+    auto launch = [&](auto kernel) {
+        GS_TIMED(a.prof, KID_BLEND_FWD, s, kernel<<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
+                                                                   a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, a.cut_cap));
+    };
+    if (a.rgb_only) launch(k_blend_fwd<true>);
+    else launch(k_blend_fwd<false>);
 }

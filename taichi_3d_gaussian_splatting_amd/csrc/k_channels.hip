@@ -8,8 +8,8 @@
 //
 // Both directions share ONE walk (gs_channel_walk): one wave per 8x8 quadrant, 64-entry batches, the gs_cull.h cull against the
 // rectangle of the pixels whose `last` lies beyond the batch, records through a wave-private LDS slab, and per surviving splat
-// the f32 operation sequence of k_blend_fwd for alpha, the 1/255 test, the 0.99 clamp, w and T -- so the contributor set, and
-// every w, is the forward's own, bit for bit.  No saturation test: `last` ends a pixel's list before the entry that saturated it.
+// the functions k_blend_fwd calls for alpha and the 0.99 clamp (gs_cull.h: gs_splat_alpha, gs_alpha_clamp), its 1/255 test, w and T -- so the
+// contributor set, and every w, is the forward's own, bit for bit.  No saturation test: `last` ends a pixel's list before the entry that saturated it.
 //
 // Channels are processed CH at a time (gs_channels_chunk: 4, 16 or 32).  The forward keeps CH accumulators per lane (pixel) and
 // reads the splat's value row, gathered by the lane that gathered its record, as LDS broadcasts; chunks are grid.y.
@@ -31,7 +31,7 @@
 // op.gather(keep, p): per batch, lane-wise, for the record this lane fetched; op.splat(j, use, w): per surviving splat, batch
 // position j (wave-uniform), use / w lane-wise (w = 0 where the pixel takes nothing).
 template <typename Op>
-__device__ __forceinline__ void gs_channel_walk(int start, int lim, float px, float py, float rx0, float ry0, int lane,
+__device__ __forceinline__ void gs_channel_walk(int start, int lim, const GsQuadPixel& qp, int lane,
                                                 const int32_t* __restrict__ sorted_vals, const float4* __restrict__ PA,
                                                 const float4* __restrict__ PB, const float4* __restrict__ PC,
                                                 float4 (*sRec)[2], Op& op)
@@ -44,7 +44,7 @@ __device__ __forceinline__ void gs_channel_walk(int start, int lim, float px, fl
         const bool valid = i < lim_max;
         const int p = valid ? sorted_vals[i] : 0;
         const float4 A = GS_REC(PA, p), B = GS_REC(PB, p), C = GS_REC(PC, p);
-        const CullRect lr = gs_live_rect(live, rx0, ry0);
+        const CullRect lr = gs_live_rect(live, qp.rx0, qp.ry0);
         const bool keep = valid && !gs_cull(gs_cull_prepare(A, B, C), lr.x0, lr.y0, lr.wx, lr.wy);
         unsigned long long mask = gs_ballot(keep);
         if (mask == 0ull) continue;
@@ -55,12 +55,10 @@ __device__ __forceinline__ void gs_channel_walk(int start, int lim, float px, fl
             const int j = __builtin_ctzll(mask);
             mask &= mask - 1ull;
             const float4 a4 = sRec[j][0], b4 = sRec[j][1];
-            // alpha, the 1/255 test, the clamp, w and T exactly as k_blend_fwd.hip (GS_FWD_STEP)
-            const float dx = px - a4.x, dy = py - a4.y;
-            const float e = -0.5f * (dx * dx * a4.z + dy * dy * b4.x) - dx * dy * a4.w;
-            float alpha = gs_exp_blend(e) * b4.y * b4.z;
+            // alpha and the clamp are the forward's own functions; the 1/255 test, w and T as in its GS_FWD_STEP
+            float alpha = gs_splat_alpha(qp.px, qp.py, a4, b4);
             const bool use = !(alpha < GS_ALPHA_EPS) && base + j < lim;
-            alpha = __uint_as_float(min(__float_as_uint(alpha), __float_as_uint(GS_ALPHA_MAX)));
+            alpha = gs_alpha_clamp(alpha);
             const float w = use ? alpha * T_i : 0.0f;
             T_i = use ? T_i * (1.0f - alpha) : T_i;
             op.splat(j, use, w);
@@ -103,22 +101,16 @@ __global__ __launch_bounds__(256) void k_channels_fwd(const int32_t* __restrict_
     __shared__ __attribute__((aligned(16))) float sVal[4][64][CH];
     const int tile = (int)blockIdx.x, c0 = (int)blockIdx.y * CH;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int tile_u = tile % tiles_x, tile_v = tile / tiles_x;
-    const int qx = tile_u * 16 + (wave & 1) * 8, qy = tile_v * 16 + (wave >> 1) * 8;
-    const int pixel_u = qx + (lane & 7), pixel_v = qy + (lane >> 3);
-    const bool inside = pixel_u < W && pixel_v < H;
-    const size_t o = (size_t)pixel_v * (size_t)W + (size_t)pixel_u;
+    const GsQuadPixel qp = gs_quad_pixel(tile, wave, lane, tiles_x, W, H);
     const int start = tile_start[tile], end = tile_end[tile];
-    int lim = inside ? last[o] : start;
-    lim = lim < start ? start : (lim > end ? end : lim);
+    const int lim = gs_clamp_last(qp.inside ? last[qp.o] : start, start, end);
     GsChannelFwdOp<CH> op;
     op.ids = ids; op.values = values; op.C = C; op.c0 = c0; op.lane = lane; op.sVal = sVal[wave];
 #pragma unroll
     for (int c = 0; c < CH; ++c) op.acc[c] = 0.0f;
-    gs_channel_walk(start, lim, (float)pixel_u + 0.5f, (float)pixel_v + 0.5f, (float)qx + 0.5f, (float)qy + 0.5f, lane,
-                    sorted_vals, PA, PB, PC, sRec[wave], op);
-    if (!inside) return;
-    float* dst = out + o * (size_t)C + c0;
+    gs_channel_walk(start, lim, qp, lane, sorted_vals, PA, PB, PC, sRec[wave], op);
+    if (!qp.inside) return;
+    float* dst = out + qp.o * (size_t)C + c0;
 #pragma unroll
     for (int c = 0; c < CH; ++c)
         if (c0 + c < C) dst[c] = op.acc[c];
@@ -193,24 +185,18 @@ __global__ __launch_bounds__(64) void k_channels_bwd(const int32_t* __restrict__
     __shared__ __attribute__((aligned(16))) float sG[64][CH];
     const int tile = (int)(blockIdx.x >> 2), quad = (int)(blockIdx.x & 3u);
     const int lane = threadIdx.x;
-    const int tile_u = tile % tiles_x, tile_v = tile / tiles_x;
-    const int qx = tile_u * 16 + (quad & 1) * 8, qy = tile_v * 16 + (quad >> 1) * 8;
-    const int pixel_u = qx + (lane & 7), pixel_v = qy + (lane >> 3);
-    const bool inside = pixel_u < W && pixel_v < H;
-    const size_t o = (size_t)pixel_v * (size_t)W + (size_t)pixel_u;
+    const GsQuadPixel qp = gs_quad_pixel(tile, quad, lane, tiles_x, W, H);
     const int start = tile_start[tile], end = tile_end[tile];
-    int lim = inside ? last[o] : start;
-    lim = lim < start ? start : (lim > end ? end : lim);
+    const int lim = gs_clamp_last(qp.inside ? last[qp.o] : start, start, end);
     if (gs_ballot(lim > start) == 0ull) return;             // nothing was blended into this quadrant
 #pragma unroll
-    for (int c = 0; c < CH; ++c) sG[lane][c] = (inside && c0 + c < C) ? grad_out[o * (size_t)C + c0 + c] : 0.0f;
+    for (int c = 0; c < CH; ++c) sG[lane][c] = (qp.inside && c0 + c < C) ? grad_out[qp.o * (size_t)C + c0 + c] : 0.0f;
     GsChannelBwdOp<CH> op;
     op.box = box; op.offsets = offsets; op.partial = partial; op.flags = flags; op.touched = touched;
-    op.K = K; op.tile_u = tile_u; op.tile_v = tile_v; op.quad = quad; op.lane = lane;
+    op.K = K; op.tile_u = qp.tile_u; op.tile_v = qp.tile_v; op.quad = quad; op.lane = lane;
     op.sW = sW; op.sG = sG; op.cnt = 0; op.slot = 0xffffffffu; op.point = 0; op.col_slot = 0xffffffffu; op.col_point = 0;
     __builtin_amdgcn_wave_barrier();
-    gs_channel_walk(start, lim, (float)pixel_u + 0.5f, (float)pixel_v + 0.5f, (float)qx + 0.5f, (float)qy + 0.5f, lane,
-                    sorted_vals, PA, PB, PC, sRec, op);
+    gs_channel_walk(start, lim, qp, lane, sorted_vals, PA, PB, PC, sRec, op);
     if (op.cnt > 0) op.flush();
 }
 

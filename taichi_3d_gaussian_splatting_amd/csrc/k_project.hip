@@ -103,16 +103,44 @@ __global__ __launch_bounds__(256) void k_filter(const float* __restrict__ pc, co
     if (i < N) mask[i] = in ? 1 : 0;
     unsigned long long b = gs_ballot(in);
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_cnt[wave] = __popcll(b);
+    gs_block_put(wave_cnt, wave, lane, (int)__popcll(b));
     __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = gs_block_sum<4>(wave_cnt);
+}
+
+// ---------------------------------------------------------------------------------
+// What the binning needs from one in-camera point, stated once for k_project and k_boxes_from_records: tile box and tile count
+// (RAST:81-128) and depth code (RAST:159-160) from (u, v, radius, depth), stored at in-camera offset idx ...
+__device__ __forceinline__ void gs_bin_point(float u, float v, float radius, float depth, int W, int H, float depth_scale, int idx, ushort4* __restrict__ boxes,
+                                             int32_t* __restrict__ ntiles, int32_t* __restrict__ depth_codes, int& count, int& depth_code)
+{
+    int box[4];
+    gs_tile_box(u, v, radius, (W + GS_TILE_SZ - 1) / GS_TILE_SZ, (H + GS_TILE_SZ - 1) / GS_TILE_SZ, box);   // = W/16, H/16 at the reference's sizes
+    count = (box[1] - box[0]) * (box[3] - box[2]);
+    depth_code = (int)(depth * depth_scale);
+    boxes[idx] = make_ushort4((unsigned short)box[0], (unsigned short)box[1], (unsigned short)box[2], (unsigned short)box[3]);
+    ntiles[idx] = count;
+    depth_codes[idx] = depth_code;          // for the key build: 4 bytes instead of a 64-byte record row per point
+}
+// ... and from a block of them: its tile-count sum (k_keygen's block offsets) and the frame's depth-code range, as the two halves of
+// a block reduction (gs_common.h) around the caller's barrier; thread 0 calls the second
+__device__ __forceinline__ void gs_bin_block_put(int* wave_sum, int* wave_max, int wave, int lane, int count, int depth_code)
+{
+    const int s = gs_wave_sum_i(count), mx = gs_wave_max_i(depth_code);      // both before the deposits: the two butterflies interleave
+    gs_block_put(wave_sum, wave, lane, s); gs_block_put(wave_max, wave, lane, mx);
+}
+__device__ __forceinline__ void gs_bin_block_publish(const int* wave_sum, const int* wave_max, uint32_t* __restrict__ tile_block_sums, GsCounters* counters)
+{
+    tile_block_sums[blockIdx.x] = (uint32_t)gs_block_sum<4>(wave_sum);
+    const int m = gs_block_max<4>(wave_max);
+    if (m > 0) atomicMax(&counters->max_depth_code, m);
 }
 
 // ---------------------------------------------------------------------------------
 // Compaction (point_id[mask], RAST:861-870, ascending ids) fused with the projection: a block takes 256 consecutive
-// rows of the point cloud, sums the in-camera counts of the blocks before it (a few thousand L2-resident ints, instead
-// of waiting for a scan launch), compacts its own in-camera rows through LDS and then projects them with its first
-// `cnt` threads -- dense within the block, and the records of block b start at in-camera offset block_offsets[b].
+// rows of the point cloud, sums the in-camera counts of the blocks before it (gs_sum_of_blocks_before), compacts its own in-camera
+// rows through LDS and then projects them with its first `cnt` threads -- dense within the block, and the records of block b start
+// at in-camera offset block_offsets[b].
 __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, float* __restrict__ feat,
                                                  const int32_t* __restrict__ obj, const float* __restrict__ Kmat,
                                                  const GsPose* __restrict__ pose, const int8_t* __restrict__ mask,
@@ -125,28 +153,23 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
                                                  int32_t* __restrict__ ntiles, uint32_t* __restrict__ tile_block_sums,
                                                  GsCounters* counters, int32_t* __restrict__ depth_codes, int32_t* __restrict__ max_tiles_hint)
 {
-    __shared__ int wave_sum[4];
-    __shared__ int wave_max[4];
-    __shared__ int wave_maxn[4];
+    __shared__ int wave_sum[4], wave_max[4], wave_maxn[4];
     // the four float4 of a record leave through LDS: a lane-per-record store writes 16 bytes out of every 64 per
     // instruction; staged, each of the wave's four store instructions writes 1 KB of consecutive bytes
     __shared__ float4 sOut[4][4 * 64];
     __shared__ int sIds[256];
-    __shared__ int wave_cnt[4];
-    __shared__ int wave_pre[4];
+    __shared__ int wave_cnt[4], wave_pre[4];
     int block_offset, cnt;
     {
         const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
         const bool in = i < N && mask[i] != 0;
         const unsigned long long b = gs_ballot(in);
         const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
-        int pre = 0;
-        for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) pre += block_counts[j];
-        pre = gs_wave_sum_i(pre);
-        if (lane_ == 0) { wave_cnt[wave_] = __popcll(b); wave_pre[wave_] = pre; }
-        __syncthreads();
-        block_offset = wave_pre[0] + wave_pre[1] + wave_pre[2] + wave_pre[3];
-        cnt = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        const int pre = gs_sum_of_blocks_before<256>(block_counts, (int)blockIdx.x);
+        gs_block_put(wave_cnt, wave_, lane_, (int)__popcll(b)); gs_block_put(wave_pre, wave_, lane_, pre);
+        __syncthreads();                                             // wave_cnt and wave_pre
+        block_offset = gs_block_sum<4>(wave_pre);
+        cnt = gs_block_sum<4>(wave_cnt);
         int woff = 0;
         for (int w = 0; w < wave_; ++w) woff += wave_cnt[w];
         const int r = woff + __popcll(b & ((1ull << lane_) - 1ull));
@@ -165,8 +188,8 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         int pid = sIds[threadIdx.x];
         float4* row4 = reinterpret_cast<float4*>(feat + (size_t)GS_NFEAT * pid);
         float row[GS_NFEAT];
-        // (gs_load_feat_row, written out: through the helper two VALU instructions of this kernel come out with their operands swapped,
-        // and this file's code is held to the parent's to the instruction; the row is also written back below through row4)
+        // (gs_load_feat_row, written out: through the helper two VALU instructions of this kernel come out with their operands swapped --
+        // still so after the forward refactor moved the code around it; the row is also written back below through row4)
 #pragma unroll
         for (int k = 0; k < GS_NFEAT / 4; ++k) {
             float4 v = row4[k];
@@ -239,11 +262,6 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
 #endif
         float large_eigen = (e00 + e11 + sqrtf((e00 - e11) * (e00 - e11) + 4.0f * c01 * c10)) / 2.0f;
         float radii = sqrtf(large_eigen) * 3.0f;
-        // ---- tile box + count, RAST:81-128 ----
-        int box[4];
-        gs_tile_box(uv[0], uv[1], radii, (W + GS_TILE_SZ - 1) / GS_TILE_SZ, (H + GS_TILE_SZ - 1) / GS_TILE_SZ, box);   // = W/16, H/16 at the reference's sizes
-        count = (box[1] - box[0]) * (box[3] - box[2]);
-        depth_code = (int)(pcam[2] * depth_scale);                            // RAST:159-160
         // Conservative log-domain cut for the blend kernels: alpha = exp(e)*rescale*opacity < 1/255
         // whenever e < cut (margins are applied where it is used).  Not an index-determining value.
         float ra = rescale * alpha;
@@ -252,9 +270,7 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         recB = make_float4(conic_c, rescale, alpha, pcam[2]);
         recC = make_float4(col[0], col[1], col[2], cut);
         recD = make_float4(pcam[0], pcam[1], pcam[2], radii);
-        boxes[idx] = make_ushort4((unsigned short)box[0], (unsigned short)box[1], (unsigned short)box[2], (unsigned short)box[3]);
-        ntiles[idx] = count;
-        depth_codes[idx] = depth_code;          // for the key build: 4 bytes instead of a 64-byte record row per point
+        gs_bin_point(uv[0], uv[1], radii, pcam[2], W, H, depth_scale, idx, boxes, ntiles, depth_codes, count, depth_code);
     }
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     {
@@ -270,56 +286,41 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
             if ((e >> 2) < n_rec) dst[e] = mine[(e & 3) * 64 + (e >> 2)];
         }
     }
-    int s = gs_wave_sum_i(count);
-    int mx = gs_wave_max_i(depth_code);
-    int mn = gs_wave_max_i(count);
-    if (lane == 0) { wave_sum[wave] = s; wave_max[wave] = mx; wave_maxn[wave] = mn; }
+    const int mn = gs_wave_max_i(count);
+    gs_bin_block_put(wave_sum, wave_max, wave, lane, count, depth_code);
+    gs_block_put(wave_maxn, wave, lane, mn);
     __syncthreads();
     if (threadIdx.x == 0) {
-        tile_block_sums[blockIdx.x] = (uint32_t)(wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3]);
-        int m = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
-        if (m > 0) atomicMax(&counters->max_depth_code, m);
+        gs_bin_block_publish(wave_sum, wave_max, tile_block_sums, counters);
         // the frame's largest tile count of one point (a word of the tile arrays, cleared by k_filter): the backward's row sum looks for
         // points with thousands of rows only in a frame that has any (k_backward.hip: SUM_ROWS_GIANT)
-        const int mt = max(max(wave_maxn[0], wave_maxn[1]), max(wave_maxn[2], wave_maxn[3]));
+        const int mt = gs_block_max<4>(wave_maxn);
         if (max_tiles_hint && mt > 64) atomicMax(max_tiles_hint, mt);
     }
 }
 
-
 // ---------------------------------------------------------------------------------
 // gs_forward_projected: the records arrive from elsewhere (another rank's k_project); what the binning needs besides
-// them -- tile box, tile count, per-block count sums, depth-code range -- is recomputed from u, v, radius and depth with
-// the same expressions k_project uses (RAST:81-128, 159-160), so the result is the one k_project would have stored.
+// them -- tile box, tile count, per-block count sums, depth-code range -- is recomputed from u, v, radius and depth by the
+// functions k_project calls (gs_bin_point, gs_bin_block_*), so the result is the one k_project would have stored.
 __global__ __launch_bounds__(256) void k_boxes_from_records(const float4* __restrict__ PA, const float4* __restrict__ PB,
                                                             const float4* __restrict__ PD, int M, int W, int H, float depth_scale,
                                                             ushort4* __restrict__ boxes, int32_t* __restrict__ ntiles,
                                                             uint32_t* __restrict__ tile_block_sums, GsCounters* counters,
                                                             int32_t* __restrict__ depth_codes, int32_t* __restrict__ tile_arrays, int tile_ints)
 {
-    __shared__ int wave_sum[4];
-    __shared__ int wave_max[4];
+    __shared__ int wave_sum[4], wave_max[4];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     for (int k = idx; k < tile_ints; k += (int)gridDim.x * 256) tile_arrays[k] = 0;       // as k_filter does
     int count = 0, depth_code = 0;
     if (idx < M) {
         const float4 A = GS_REC(PA, idx);
-        int box[4];
-        gs_tile_box(A.x, A.y, GS_REC(PD, idx).w, (W + GS_TILE_SZ - 1) / GS_TILE_SZ, (H + GS_TILE_SZ - 1) / GS_TILE_SZ, box);
-        count = (box[1] - box[0]) * (box[3] - box[2]);
-        depth_code = (int)(GS_REC(PB, idx).w * depth_scale);
-        boxes[idx] = make_ushort4((unsigned short)box[0], (unsigned short)box[1], (unsigned short)box[2], (unsigned short)box[3]);
-        ntiles[idx] = count;
-        depth_codes[idx] = depth_code;
+        gs_bin_point(A.x, A.y, GS_REC(PD, idx).w, GS_REC(PB, idx).w, W, H, depth_scale, idx, boxes, ntiles, depth_codes, count, depth_code);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int sm = gs_wave_sum_i(count), mx = gs_wave_max_i(depth_code);
-    if (lane == 0) { wave_sum[wave] = sm; wave_max[wave] = mx; }
+    gs_bin_block_put(wave_sum, wave_max, (int)(threadIdx.x >> 6), threadIdx.x & 63, count, depth_code);
     __syncthreads();
     if (threadIdx.x == 0) {
-        tile_block_sums[blockIdx.x] = (uint32_t)(wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3]);
-        const int m = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
-        if (m > 0) atomicMax(&counters->max_depth_code, m);
+        gs_bin_block_publish(wave_sum, wave_max, tile_block_sums, counters);
         if (blockIdx.x == 0) counters->M = M;
     }
 }
@@ -335,17 +336,9 @@ __global__ __launch_bounds__(1024) void k_scan_tiles_publish(const uint32_t* __r
                                                              volatile GsCounters* host_mirror, int32_t ticket)
 {
     __shared__ uint32_t wave_tot[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t v = 0;
-    for (int i = threadIdx.x; i < n; i += 1024) v += in[i];
-    v = (uint32_t)gs_wave_sum_i((int)v);
-    if (lane == 0) wave_tot[wave] = v;
+    gs_block_put(wave_tot, (int)(threadIdx.x >> 6), threadIdx.x & 63, gs_sum_of_blocks_before<1024>(in, n));
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t K = 0;
-        for (int w = 0; w < 16; ++w) K += wave_tot[w];
-        gs_publish_counters(counters, K, host_mirror, ticket);
-    }
+    if (threadIdx.x == 0) gs_publish_counters(counters, gs_block_sum<16>(wave_tot), host_mirror, ticket);
 }
 
 void gs_launch_publish(const GsProjectArgs& a, int n_blocks, hipStream_t s)
@@ -358,10 +351,7 @@ void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish)
 {
     const GsFrameView& v = a.v;
     const int nb = (int)((a.N + 255) / 256);
-    if (nb == 0) {
-        (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s);     // empty scene: nothing else clears them
-        return;
-    }
+    if (nb == 0) { (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s); return; }     // empty scene: nothing else clears them
     GS_TIMED(a.prof, KID_FILTER, s, k_filter<<<nb, 256, 0, s>>>(a.point_cloud, a.invalid, a.object_id, a.Kmat, a.q_pc, a.t_pc, a.n_objects,
                                                             v.pose, a.counters, a.N, a.W, a.H, a.near_plane, a.far_plane, v.mask,
                                                             a.block_counts, v.tile_start, v.tile_ints));
@@ -376,10 +366,7 @@ void gs_launch_boxes_from_records(const GsProjectArgs& a, int M, hipStream_t s, 
 {
     const GsFrameView& v = a.v;
     const int nb = (M + 255) / 256;
-    if (nb == 0) {
-        (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s);
-        return;
-    }
+    if (nb == 0) { (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s); return; }
     GS_TIMED(a.prof, KID_PROJECT, s, k_boxes_from_records<<<nb, 256, 0, s>>>(v.PA, v.PB, v.PD, M, a.W, a.H, a.depth_scale, v.box, v.ntiles,
                                                                           a.tile_block_sums, a.counters, v.depth_codes, v.tile_start, v.tile_ints));
     if (publish) gs_launch_publish(a, nb, s);

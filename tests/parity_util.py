@@ -239,6 +239,19 @@ def dense_corner_scene():
     return s
 
 
+def block_edges_scene(width, height, sigma0):
+    """3 * 256 + 1 rows for the edges of the binning's block scans and reductions: rows 256..511 lie behind the camera, so a
+    block with no in-camera point sits between two populated ones (and the last block holds one row); row 600 is one faint
+    splat far larger than the image, whose box is every tile; the image size is no multiple of 16 (partial edge tiles)"""
+    n = 3 * 256 + 1
+    s = synth(n, width, height, sigma0, sh_deg=3, seed=n)
+    s.point_cloud[256:512, 2] *= -1.0
+    s.point_cloud[600, :2] *= 0.1                              # near the optical axis
+    s.point_cloud_features[600, 4:7] = np.log(3.0)
+    s.point_cloud_features[600, 7] = -3.0                      # faint: everything behind it still counts
+    return s
+
+
 def default_heavy_policy():
     """False when the suite runs under one of the library's diagnostic switches, which replace the default policy of heavy
     tiles and segments that some tests assert"""

@@ -513,6 +513,28 @@ def test_point_counts_that_are_not_multiples_of_four(P, n):
     assert inp.point_cloud_features.grad.data_ptr() % 16 == 0
 
 
+def test_block_scans_and_reductions_at_their_edges(P):
+    """The forward's block primitives (gs_common.h: wave scan, block scan / sum / max over 4 and 16 waves, sum of the blocks before)
+    where no other scene takes them together: 3 * 256 + 1 rows, the middle block of k_project / k_keygen with a count of zero
+    between two populated ones, one splat whose pairs span several trips of k_keygen's pair loop and several waves of its scan,
+    partial edge tiles, and a pair count between one and two sort tiles (4096), so that k_sort_scatter runs one FULL and one
+    partial tile.  Each property is asserted on the oracle's frame first.
+    Two image sizes, because one cannot show everything: 250 x 203 is 16 x 13 = 208 tiles, and a tile box is clamped to the
+    image's tiles (RAST:81-103), so no splat covers more than 208 there -- the giant covers them all, which still spans two
+    trips of the pair loop; 410 x 203 (26 x 13 tiles) is the smallest step up at which one splat covers more than 256.
+    Splat scales chosen with the oracle: K = 5748 at 250 x 203 with sigma0 0.15, K = 6587 at 410 x 203 with sigma0 0.1."""
+    q, t = view_pose()
+    for width, height, sigma0 in [(250, 203, 0.15), (410, 203, 0.1)]:
+        s = P.block_edges_scene(width, height, sigma0)
+        f, _ = P.run_oracle(s, q, t, oracle.default_config(allow_partial_tiles=1))
+        assert 4096 < f.K < 8192, f.K
+        tiles = ((width + 15) // 16) * ((height + 15) // 16)
+        assert f.num_overlap_tiles.max() > min(256, tiles - 1), f.num_overlap_tiles.max()      # more than 256; all 208 at 250 x 203
+        ids = f.point_id_in_camera_list
+        assert not ((ids >= 256) & (ids < 512)).any() and (ids < 256).any() and (ids >= 512).any()
+        _fwd_bwd(P, s, q, t, cfg_kw={"allow_partial_tiles": True})
+
+
 def test_backward_through_depth_only_gives_zero_gradients(P):
     """The reference ignores the depth gradient (RAST:1157-1163); with unmaterialised grads the image gradient is None then."""
     s = synth(500, 64, 64, 0.1, seed=3)
