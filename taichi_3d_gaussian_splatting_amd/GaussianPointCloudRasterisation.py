@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _native, channels
+from . import _native, channels, sparse
 from ._host import _ConfigBase, _Contexts, _Frame, _marshal
 from .Camera import CameraInfo
 from .controller_stats import ControllerAccumulators
@@ -67,6 +67,11 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         point_depth: torch.Tensor  # M
         point_uv_in_camera: torch.Tensor  # Mx2
 
+    # extension (a plain attribute, not a config field: the config's field order mirrors the reference): True makes every
+    # backward leave the rows it touched in last_touched_rows (sparse.TouchedRows, for FusedAdam.step(rows=...)); None
+    # after a backward that computed no point gradients
+    track_touched_rows = False
+
     def __init__(self, config: "GaussianPointCloudRasterisation.GaussianPointCloudRasterisationConfig",
                  backward_valid_point_hook: Optional[Callable[["GaussianPointCloudRasterisation.BackwardValidPointHookInput"], None]] = None,
                  controller_accumulators: Optional[ControllerAccumulators] = None):
@@ -80,6 +85,7 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
         self._ctxs = _Contexts()            # device index -> _native.Context (owner of the gs_ctx)
         self.last_frame: Optional[_Frame] = None   # inspection aid (tests / profiling); replaced every call
         self.last_forward_outputs = {}
+        self.last_touched_rows: Optional[sparse.TouchedRows] = None
         module = self
 
         class _module_function(torch.autograd.Function):
@@ -235,6 +241,8 @@ class GaussianPointCloudRasterisation(torch.nn.Module):
                                             grad_pixel_accumulated_alpha=ptr(grad_alpha))
             _native.call("gs_backward_ex", dev, ctxh, frame.handle, scene, cam, cfg, ptr(grad_image), extra, ptr(acc_alpha), ptr(last),
                          int(sh_band), out)
+        if self.track_touched_rows:             # same stream, directly behind the backward whose tags it reads; one allocation
+            self.last_touched_rows = sparse.touched_rows(frame) if want_points else None
         self.last_backward_extras = dict(grad_viewspace=grad_uv, magnitude_grad_viewspace=mag,
                                          magnitude_grad_viewspace_on_image=mag_img, num_affected_pixels=n_aff)
         if want_hook:                                                                   # RAST:1127-1142

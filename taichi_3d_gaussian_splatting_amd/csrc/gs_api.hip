@@ -3,6 +3,7 @@
 // _module_function.forward / .backward of the reference (RAST:830-1163).
 #include "../../include/gs_rasterizer.h"
 #include "../../include/gs_channels.h"
+#include "../../include/gs_sparse.h"
 #include "gs_common.h"
 
 #include <algorithm>
@@ -79,6 +80,7 @@ struct Frame {
     bool rgb_only = false;              // gs_forward ran with gs_config.rgb_only: no `last` exists for the frame (gs_channels_* refuse it)
     bool max_tiles_known = false;       // k_project of this frame left the largest tile count of one point in the tile arrays (frames from records: no)
     uint32_t generation = 0;
+    uint64_t bwd_serial = 0;            // gs_ctx::bwd_serial of the last backward blend on this frame (0: none has run)
     // gs_project_shard_begin: the hand-over of M (and the object-id check) has not been read yet; slot of the pinned counters
     // the frame's publish kernel writes, its ticket and the stream to fall back on
     int pending_slot = -1;
@@ -128,6 +130,11 @@ struct gs_ctx {
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
+    // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
+    // begin in `visited`.  A frame whose bwd_serial is not this one no longer owns the tags (gs_touched_rows).
+    uint64_t bwd_serial = 0;
+    size_t touched_offset = 0;
+    DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
     uint64_t slots_busy = 1ull;            // slot 0 serves the calls that wait at once; the others belong to frames begun and not yet read
@@ -186,7 +193,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
-                      &c->ch_partial, &c->ch_flags };
+                      &c->ch_partial, &c->ch_flags, &c->row_block_totals };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : c->prof.spare) (void)hipEventDestroy(e);
@@ -306,6 +313,7 @@ static Frame* begin_frame(gs_ctx* c, const gs_camera* cam, int T, int keep, int*
     if (c->transient >= 0) drop_frame(c, c->frames[c->transient]);
     Frame* f = acquire_frame(c, slot);
     f->info = gs_frame_info{};
+    f->bwd_serial = 0;
     // (known before the stages run: a kept frame gets list cuts for its backward, and the tile count lays out the tile arrays)
     f->info.kept_for_backward = keep ? 1 : 0;
     f->info.n_tiles = T; f->info.camera_height = cam->camera_height; f->info.camera_width = cam->camera_width;
@@ -835,7 +843,7 @@ static int waves_per_tile(int n_tiles)
 }
 
 // fills the blend half of the arguments; sums_out = where the per-splat sums go
-static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_image, const float* acc_alpha, const int32_t* last,
+static int prepare_backward_blend(gs_ctx* c, Frame* f, const float* grad_image, const float* acc_alpha, const int32_t* last,
                                   float* mag_image, float4* sums_out, int strict, hipStream_t stream, GsBackwardArgs* a_out)
 {
     const uint32_t K = (uint32_t)f->info.n_keys;
@@ -857,6 +865,9 @@ static int prepare_backward_blend(gs_ctx* c, const Frame* f, const float* grad_i
         c->visit_gen = 0;
     }
     c->visit_gen += 1;
+    c->bwd_serial += 1;                               // this backward owns the tags from here on
+    c->touched_offset = flag_bytes;
+    f->bwd_serial = c->bwd_serial;
     if (!c->zero_row.p) {
         if (c->zero_row.ensure(64, &c->device_bytes) != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "backward: zero row");
         HIP_TRY(hipMemsetAsync(c->zero_row.p, 0, c->zero_row.cap, stream));
@@ -1232,6 +1243,51 @@ extern "C" int gs_adam_step(gs_ctx* c, float* param, const float* grad, float* e
     return GS_OK;
 }
 
+// ---- touched rows and the row-selective Adam step (include/gs_sparse.h, k_sparse.hip) ------------------------------------
+// No host synchronisation and no device-to-host copy in either: the count stays on the device.
+extern "C" int gs_touched_rows(gs_ctx* c, const gs_frame* h, int32_t* ids_out, int64_t capacity, int32_t* count_out, gs_stream stream_)
+{
+    if (!c || !h || !ids_out || !count_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_touched_rows: NULL argument");
+    std::lock_guard<std::mutex> lock(c->mu);
+    Frame* f;
+    int rc;
+    if ((rc = lookup(c, h, "gs_touched_rows", false, &f)) != GS_OK) return rc;      // (a frame only begun has had no backward: nothing to wait for)
+    if (!(f->info.stages & GS_STAGE_PROJECT))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_touched_rows: the frame holds no projection stage (frames made from records are not supported)");
+    if (capacity < f->info.n_points_in_camera) return fail(GS_ERR_INVALID_ARGUMENT, "gs_touched_rows: capacity is below the frame's n_points_in_camera");
+    if (f->bwd_serial == 0) return fail(GS_ERR_STATE, "gs_touched_rows: no backward has run on this frame");
+    if (f->bwd_serial != c->bwd_serial)
+        return fail(GS_ERR_STATE, "gs_touched_rows: another backward has run on this context since the frame's (the list describes the latest one only)");
+    const int M = (int)f->info.n_points_in_camera;
+    // no pair: the blend did not run and wrote no tag (stale bytes never equal this backward's tag, but nothing needs reading)
+    const int M_eff = (f->info.n_keys > 0 && f->info.n_tiles > 0) ? M : 0;
+    HIP_TRY(hipSetDevice(c->device));           // the scratch grows before the stream enters: a call that fails here leaves it alone
+    if ((rc = grow(c, { NEED(c->row_block_totals, (size_t)(gs_rows_blocks(M_eff) + 1) * sizeof(uint32_t)) })) != GS_OK) return rc;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    gs_launch_touched_rows(c->visited.as<uint8_t>() + c->touched_offset, c->visit_gen, frame_view(*f).ids, M_eff,
+                           c->row_block_totals.as<uint32_t>(), ids_out, capacity, count_out, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_adam_step_rows(gs_ctx* c, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_rows,
+                                 int32_t row_len, const int32_t* ids, const int32_t* count, int64_t max_count,
+                                 float lr, float beta1, float beta2, float eps, int64_t step, gs_stream stream_)
+{
+    if (!c || (n_rows > 0 && max_count > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !ids || !count)))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step_rows: NULL argument");
+    if (row_len < 1 || step < 1 || n_rows < 0 || max_count < 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step_rows: row_len and step must be >= 1, n_rows and max_count >= 0");
+    if (n_rows == 0 || max_count == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_adam_rows(param, grad, exp_avg, exp_avg_sq, n_rows, row_len, ids, count, max_count, lr, beta1, beta2, eps, step, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
 extern "C" int gs_frame_heavy_tiles(gs_ctx* c, const gs_frame* h, int32_t* n_out, gs_stream stream_)
 {
     if (!c || !n_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_heavy_tiles: NULL argument");
@@ -1239,6 +1295,8 @@ extern "C" int gs_frame_heavy_tiles(gs_ctx* c, const gs_frame* h, int32_t* n_out
     Frame* f;
     int rc;
     if ((rc = lookup(c, h, "gs_frame_heavy_tiles", false, &f)) != GS_OK) return rc;
+    // the counts are the frame's own (k_tile_order writes them into its tile-order buffer), but only a backward writes them
+    if (f->bwd_serial == 0) return fail(GS_ERR_STATE, "gs_frame_heavy_tiles: no backward has run on this frame");
     if (!(f->info.stages & GS_STAGE_RASTER) || f->info.n_tiles <= 0 || f->info.n_keys <= 0 || !f->bufs.tile_order.p) { n_out[0] = n_out[1] = 0; return GS_OK; }
     hipStream_t s;
     if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;

@@ -464,6 +464,29 @@ void gs_launch_loss_backward(const GsLossImage& X, const GsLossImage& Y, int H, 
                              const GsLossImage& G, hipStream_t s);
 void gs_launch_adam(float* param, const float* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     int64_t step, hipStream_t s);
+// torch.optim.Adam's update of ONE element (no weight decay, no amsgrad): the arithmetic of k_adam (k_loss.hip) and of
+// k_adam_rows (k_sparse.hip), stated once.  bias1 = 1 - beta1^t, bias2_sqrt = sqrt(1 - beta2^t), rounded to f32 by the launcher.
+__device__ __forceinline__ void gs_adam_update(float& p, const float g, float& m_io, float& v_io, const float lr, const float beta1,
+                                               const float beta2, const float eps, const float bias1, const float bias2_sqrt)
+{
+    const float m = beta1 * m_io + (1.0f - beta1) * g;                // exp_avg.lerp_(grad, 1 - beta1)
+    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2); g * g first, as torch's GPU addcmul: a gradient whose square
+    // overflows f32 makes v infinite (and the step zero) there too, rather than finite through (1 - beta2) g first
+    const float v = beta2 * v_io + (1.0f - beta2) * (g * g);
+    m_io = m; v_io = v;
+    const float denom = sqrtf(v) / bias2_sqrt + eps;
+    p = p - (lr / bias1) * (m / denom);
+}
+// the two bias corrections of step t as the kernels take them
+void gs_adam_bias(float beta1, float beta2, int64_t step, float* bias1, float* bias2_sqrt);
+// k_sparse.hip (include/gs_sparse.h).  Compaction: ids_in[m] of the M in-camera points whose tag is `gen`, in m order ->
+// ids_out[0 .. *count_out); block_totals: gs_rows_blocks(M) words of scratch.  touched must be 4-byte aligned with M rounded
+// up to 4 readable bytes.
+int gs_rows_blocks(int M);
+void gs_launch_touched_rows(const uint8_t* touched, uint8_t gen, const int32_t* ids_in, int M, uint32_t* block_totals,
+                            int32_t* ids_out, int64_t capacity, int32_t* count_out, hipStream_t s);
+void gs_launch_adam_rows(float* param, const float* grad, float* m, float* v, int64_t n_rows, int row_len, const int32_t* ids,
+                         const int32_t* count, int64_t max_count, float lr, float beta1, float beta2, float eps, int64_t step, hipStream_t s);
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s);
 void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, const float* value_and_count, const float* upstream,
                         float* grad, hipStream_t s);

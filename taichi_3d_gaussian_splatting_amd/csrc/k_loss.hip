@@ -455,19 +455,23 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ param, const f
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float g = grad[i];
-    const float m = beta1 * exp_avg[i] + (1.0f - beta1) * g;          // exp_avg.lerp_(grad, 1 - beta1)
-    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2); g * g first, as torch's GPU addcmul: a gradient whose square
-    // overflows f32 makes v infinite (and the step zero) there too, rather than finite through (1 - beta2) g first
-    const float v = beta2 * exp_avg_sq[i] + (1.0f - beta2) * (g * g);
+    float m = exp_avg[i], v = exp_avg_sq[i], p = param[i];
+    gs_adam_update(p, g, m, v, lr, beta1, beta2, eps, bias1, bias2_sqrt);
     exp_avg[i] = m; exp_avg_sq[i] = v;
-    const float denom = sqrtf(v) / bias2_sqrt + eps;
-    param[i] = param[i] - (lr / bias1) * (m / denom);
+    param[i] = p;
+}
+
+void gs_adam_bias(float beta1, float beta2, int64_t step, float* bias1, float* bias2_sqrt)
+{
+    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
+    *bias1 = (float)b1; *bias2_sqrt = (float)sqrt(b2);
 }
 
 void gs_launch_adam(float* param, const float* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     int64_t step, hipStream_t s)
 {
     if (n <= 0) return;
-    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
-    k_adam<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(param, grad, m, v, n, lr, beta1, beta2, eps, (float)b1, (float)sqrt(b2));
+    float bias1, bias2_sqrt;
+    gs_adam_bias(beta1, beta2, step, &bias1, &bias2_sqrt);
+    k_adam<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(param, grad, m, v, n, lr, beta1, beta2, eps, bias1, bias2_sqrt);
 }
