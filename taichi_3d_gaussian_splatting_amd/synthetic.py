@@ -134,5 +134,22 @@ def make_scene(name):
     return synth(**CONFIGS[name])
 
 
+def scene_input(scene, q, t, device, band=3, requires_grad=False, pose=False):
+    """The operator's input for a scene under pose (q, t), on `device`.  requires_grad: of the points and their features;
+    pose: of q_pointcloud_camera and t_pointcloud_camera.  torch and the package are imported here: the module stays numpy-only."""
+    import torch
+
+    from . import CameraInfo, GaussianPointCloudRasterisation as Rast
+    return Rast.GaussianPointCloudRasterisationInput(
+        point_cloud=torch.tensor(scene.point_cloud, device=device, requires_grad=requires_grad),
+        point_cloud_features=torch.tensor(scene.point_cloud_features, device=device, requires_grad=requires_grad),
+        point_object_id=torch.tensor(scene.point_object_id, device=device),
+        point_invalid_mask=torch.tensor(scene.point_invalid_mask, device=device),
+        camera_info=CameraInfo(camera_intrinsics=torch.tensor(scene.camera_intrinsics, device=device),
+                               camera_height=scene.height, camera_width=scene.width, camera_id=0),
+        q_pointcloud_camera=torch.tensor(q, device=device, requires_grad=pose),
+        t_pointcloud_camera=torch.tensor(t, device=device, requires_grad=pose), color_max_sh_band=band)
+
+
 def workload_args(name):
     return CLUSTERED.get(name) or SMALL.get(name) or CONFIGS[name]

@@ -8,7 +8,7 @@ import torch
 import torch_ref
 from oracle import oracle
 from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation
-from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
+from taichi_3d_gaussian_splatting_amd.synthetic import scene_input, synth, view_pose
 
 Rast = GaussianPointCloudRasterisation
 DEV = "cuda:0"
@@ -37,17 +37,7 @@ def module(partial=False, strict=False, depth=False, hook=None, ctrl=None, **fac
 
 def make_input(scene, q, t, band=3, requires_grad=True, pose=False):
     """requires_grad: of the points and their features; pose: of q_pointcloud_camera and t_pointcloud_camera"""
-    pc = torch.tensor(scene.point_cloud, device=DEV, requires_grad=requires_grad)
-    feat = torch.tensor(scene.point_cloud_features, device=DEV, requires_grad=requires_grad)
-    inp = Rast.GaussianPointCloudRasterisationInput(
-        point_cloud=pc, point_cloud_features=feat,
-        point_object_id=torch.tensor(scene.point_object_id, device=DEV),
-        point_invalid_mask=torch.tensor(scene.point_invalid_mask, device=DEV),
-        camera_info=CameraInfo(camera_intrinsics=torch.tensor(scene.camera_intrinsics, device=DEV),
-                               camera_height=scene.height, camera_width=scene.width, camera_id=0),
-        q_pointcloud_camera=torch.tensor(q, device=DEV, requires_grad=pose),
-        t_pointcloud_camera=torch.tensor(t, device=DEV, requires_grad=pose), color_max_sh_band=band)
-    return inp
+    return scene_input(scene, q, t, DEV, band, requires_grad, pose)
 
 
 def run_oracle(scene, q, t, cfg=None):

@@ -5,28 +5,27 @@ in place of its Taichi sampling kernel), both timed with device events around th
 
 Scene: 1e6 rows, 5e5 of them valid (scene_io.preallocate(..., 2.0)); the hook of one view with 2e5 in-camera points;
 thresholds chosen from the data so that about 5 % of the valid rows densify and about 1 % are pruned.
-Prints one JSON line and writes it to profiles/density_bench.json (or the path given as the first argument)."""
-import json
+The timer is this tool's own: the scene is restored and the device drained before every repetition, so each event pair
+brackets one step on an idle GPU.  Prints one JSON line and writes it to profiles/density_bench.json (or the path given
+as the first argument or as --out).
+
+    python tools/bench_densify.py [PATH] [--rows 500000] [--in-camera 200000] [--steps 20] [--warmup 3] [--out PATH]
+"""
+import argparse
 import os
-import sys
 import types
 
+import harness as H
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from density_ref import add_densify_points, find_densify_points  # noqa: E402
-from taichi_3d_gaussian_splatting_amd import GaussianPointAdaptiveController as Ctl  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.scene_io import preallocate  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import synth  # noqa: E402
-
-DEV = torch.device("cuda:0")
-N_VALID, M, REPS = 500_000, 200_000, 20
+from density_ref import add_densify_points, find_densify_points
+from taichi_3d_gaussian_splatting_amd import GaussianPointAdaptiveController as Ctl
+from taichi_3d_gaussian_splatting_amd.scene_io import preallocate
+from taichi_3d_gaussian_splatting_amd.synthetic import synth
 
 
-def make_workload():
+def make_workload(N_VALID, M):
     s = synth(N_VALID, 1920, 1080, 0.02, sh_deg=3, seed=0)
     pc, ft, mask, obj = preallocate(s.point_cloud, s.point_cloud_features, 2.0)
     N = pc.shape[0]
@@ -60,9 +59,9 @@ def make_workload():
     return scene, acc, hook, cfg
 
 
-def timed(fn, restore):
+def timed(fn, restore, reps, warmup):
     times = []
-    for r in range(REPS + 3):
+    for r in range(reps + warmup):
         restore()
         torch.cuda.synchronize()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -70,14 +69,24 @@ def timed(fn, restore):
         fn()
         b.record()
         torch.cuda.synchronize()
-        if r >= 3:
+        if r >= warmup:
             times.append(a.elapsed_time(b))
     return float(np.median(times)), float(np.min(times))
 
 
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "density_bench.json")
-    scene, acc, hook, cfg = make_workload()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("path", nargs="?", help="where to write the result (same as --out)")
+    ap.add_argument("--rows", type=int, default=500_000, help="valid rows (the arrays hold twice as many)")
+    ap.add_argument("--in-camera", type=int, default=200_000, help="points of the view's hook")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(H.ROOT, "profiles", "density_bench.json"))
+    a = ap.parse_args()
+    H.require_gpu("bench_densify.py")
+    DEV = torch.device("cuda:0")
+    N_VALID, M, REPS = a.rows, a.in_camera, a.steps
+    scene, acc, hook, cfg = make_workload(N_VALID, M)
     N = scene["pc"].shape[0]
     orig = {k: torch.tensor(v, device=DEV) for k, v in scene.items()}
     live = {k: v.clone() for k, v in orig.items()}
@@ -107,21 +116,17 @@ def main():
                                    hook_d["mag"], True, cfg)
         add_densify_points(live["pc"], live["feat"], live["mask"], live["obj"], info, cfg, 0, 0)
 
-    hip_med, hip_min = timed(hip_step, restore)
-    sel_med, _ = timed(hip_select, restore)
+    hip_med, hip_min = timed(hip_step, restore, REPS, a.warmup)
+    sel_med, _ = timed(hip_select, restore, REPS, a.warmup)
     counts = ctl.last_refinement_counts()
-    torch_med, torch_min = timed(torch_step, restore)
+    torch_med, torch_min = timed(torch_step, restore, REPS, a.warmup)
     res = dict(what="one densification: select + apply (device events, host syncs of the torch path included)",
                n_rows=N, n_valid=N_VALID, n_in_camera=M, reps=REPS, device=torch.cuda.get_device_name(0),
                counts=counts, densify_fraction_of_valid=counts["densify"] / N_VALID,
                pruned_fraction_of_valid=(counts["floaters"] + counts["transparent"]) / N_VALID,
                hip_select_apply_ms_median=hip_med, hip_select_apply_ms_min=hip_min, hip_select_ms_median=sel_med,
                torch_reference_ms_median=torch_med, torch_reference_ms_min=torch_min, speedup_median=torch_med / hip_med)
-    line = json.dumps(res)
-    print(line)
-    os.makedirs(os.path.dirname(out_path), exist_ok=True)
-    with open(out_path, "w") as fh:
-        fh.write(line + "\n")
+    H.write_json(res, a.path or a.out, indent=None)
 
 
 if __name__ == "__main__":

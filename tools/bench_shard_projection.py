@@ -1,32 +1,35 @@
 """Owner side of the Gaussian-parallel scheme on ONE GPU: a shard of N/W Gaussians projected for W views, once with a host
 wait per view (gs_project_shard) and once begun back to back and read afterwards (gs_project_shard_begin): milliseconds per
-step of that stage alone, GPU otherwise idle.  `python tools/bench_shard_projection.py [W]` (GPU)."""
-import json
-import os
-import sys
-import time
+step of that stage alone, GPU otherwise idle, by a host clock around the loop (harness.wall_ms).
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+    python tools/bench_shard_projection.py [W] [--workload cfg3_headline] [--steps 200] [--warmup 20] [--out PATH]   (GPU)
+"""
+import argparse
+import dataclasses
 
-from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation as Rast  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.stages import StagedRasteriser  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import CONFIGS, synth, view_pose  # noqa: E402
+import harness as H
+import torch
+
+from taichi_3d_gaussian_splatting_amd.stages import StagedRasteriser
+from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, scene_input, view_pose
 
 
 def main():
-    W = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+    ap = argparse.ArgumentParser()
+    ap.add_argument("views", nargs="?", type=int, default=8, help="W: views per step, and the shard is 1/W of the scene")
+    ap.add_argument("--workload", default="cfg3_headline")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", help="also write the line there")
+    a = ap.parse_args()
+    H.require_gpu("bench_shard_projection.py")
+    W = a.views
     dev = torch.device("cuda", 0)
-    s = synth(**CONFIGS["cfg3_headline"])
+    s = make_scene(a.workload)
     n = s.point_cloud.shape[0] // W
-    inputs = []
-    for v in range(W):
-        q, t = view_pose(v, W)
-        inputs.append(Rast.GaussianPointCloudRasterisationInput(
-            point_cloud=torch.tensor(s.point_cloud[:n], device=dev), point_cloud_features=torch.tensor(s.point_cloud_features[:n], device=dev),
-            point_object_id=torch.tensor(s.point_object_id[:n], device=dev), point_invalid_mask=torch.tensor(s.point_invalid_mask[:n], device=dev),
-            camera_info=CameraInfo(torch.tensor(s.camera_intrinsics, device=dev), s.height, s.width, 0),
-            q_pointcloud_camera=torch.tensor(q, device=dev), t_pointcloud_camera=torch.tensor(t, device=dev), color_max_sh_band=3))
+    shard = dataclasses.replace(s, point_cloud=s.point_cloud[:n], point_cloud_features=s.point_cloud_features[:n],
+                                point_object_id=s.point_object_id[:n], point_invalid_mask=s.point_invalid_mask[:n])
+    inputs = [scene_input(shard, *view_pose(v, W), dev) for v in range(W)]
     st = StagedRasteriser()
 
     def waiting():
@@ -36,17 +39,10 @@ def main():
         frames = [st.project_shard_begin(i) for i in inputs]
         return [st.project_shard_finish(f, want_ids=False)[0] for f in frames]
 
-    out = {"workload": f"cfg3_headline shard of {n} Gaussians (1/{W}) projected for {W} views", "steps": 200}
+    out = {"workload": f"{a.workload} shard of {n} Gaussians (1/{W}) projected for {W} views", "steps": a.steps}
     for name, fn in (("wait_per_view_ms", waiting), ("begun_back_to_back_ms", begun)):
-        for _ in range(20):
-            fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(200):
-            fn()
-        torch.cuda.synchronize()
-        out[name] = round((time.perf_counter() - t0) / 200 * 1e3, 4)
-    print(json.dumps(out))
+        out[name] = round(H.wall_ms(fn, a.steps, a.warmup), 4)
+    H.write_json(out, a.out, indent=None)
 
 
 if __name__ == "__main__":

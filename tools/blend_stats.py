@@ -5,32 +5,25 @@
 Prints how many 64-entry batches, culled-in entries, evaluated (splat, 8x8 quadrant) pairs and contributing lanes
 each kernel went through, next to the per-pixel evaluation count E of the reference algorithm.
 """
+import argparse
 import ctypes as C
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GSRAST_LIB", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                 "taichi_3d_gaussian_splatting_amd", "lib", "libgsrast_stats.so"))
-import torch  # noqa: E402
-
-from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation as Rast, _native  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, view_pose  # noqa: E402
+import harness as H
+import torch
 
 
 def main():
-    wl = sys.argv[1] if len(sys.argv) > 1 else "cfg3_headline"
+    ap = argparse.ArgumentParser()
+    ap.add_argument("workload", nargs="?", default="cfg3_headline")
+    wl = ap.parse_args().workload
+    H.require_gpu("blend_stats.py")
+    H.use_library("libgsrast_stats.so")
+    from taichi_3d_gaussian_splatting_amd import GaussianPointCloudRasterisation as Rast, _native
+    from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, scene_input, view_pose
     dev = torch.device("cuda", 0)
     s = make_scene(wl)
-    q, t = view_pose()
-    pc = torch.tensor(s.point_cloud, device=dev, requires_grad=True)
-    feat = torch.tensor(s.point_cloud_features, device=dev, requires_grad=True)
-    inp = Rast.GaussianPointCloudRasterisationInput(
-        point_cloud=pc, point_cloud_features=feat, point_object_id=torch.tensor(s.point_object_id, device=dev),
-        point_invalid_mask=torch.tensor(s.point_invalid_mask, device=dev),
-        camera_info=CameraInfo(torch.tensor(s.camera_intrinsics, device=dev), s.height, s.width, 0),
-        q_pointcloud_camera=torch.tensor(q, device=dev), t_pointcloud_camera=torch.tensor(t, device=dev), color_max_sh_band=3)
+    inp = scene_input(s, *view_pose(), dev, requires_grad=True)
     module = Rast(Rast.GaussianPointCloudRasterisationConfig())
     L = _native.lib()
     buf = (C.c_ulonglong * 32)()
@@ -45,9 +38,8 @@ def main():
     with torch.no_grad():
         module(inp)
     fr = module.last_frame
-    H, W = s.height, s.width
-    tx = (W + 15) // 16
-    tile_of_pixel = (torch.arange(H, device=dev) // 16)[:, None] * tx + (torch.arange(W, device=dev) // 16)[None, :]
+    tx = (s.width + 15) // 16
+    tile_of_pixel = (torch.arange(s.height, device=dev) // 16)[:, None] * tx + (torch.arange(s.width, device=dev) // 16)[None, :]
     E = int((fr_last - fr.export("tile_points_start").to(torch.int64)[tile_of_pixel]).clamp_(min=0).sum().item())
     out = {
         "workload": wl, "sort_pairs": fr.n_keys, "tiles": fr.n_tiles, "pixel_entry_evaluations_E": E,

@@ -4,35 +4,30 @@ The forward hands M and K to the host once per frame.  With predicted sizing (de
 the whole forward, so the wait costs the GPU nothing; with GS_PREDICT_SIZES=0 it waits in the middle of the frame with the GPU
 idle behind it.  Prints, per step: host time inside forward / loss / backward, the time spent waiting for the counters
 (gs_ctx_counter_wait_ns) and how each frame was sized.  Run it once with and once without GS_PREDICT_SIZES=0."""
+import argparse
 import os
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import harness as H
+import torch
 
-from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation as Rast  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import CONFIGS, synth, view_pose  # noqa: E402
+from taichi_3d_gaussian_splatting_amd import GaussianPointCloudRasterisation as Rast, _native
+from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, scene_input, view_pose
 
 
 def main():
-    wl = sys.argv[1] if len(sys.argv) > 1 else "cfg3_headline"
+    ap = argparse.ArgumentParser()
+    ap.add_argument("workload", nargs="?", default="cfg3_headline")
+    wl = ap.parse_args().workload
+    H.require_gpu("host_timeline.py")
     dev = torch.device("cuda", 0)
-    s = synth(**CONFIGS[wl])
-    q, t = view_pose()
-    pc = torch.tensor(s.point_cloud, device=dev, requires_grad=True)
-    feat = torch.tensor(s.point_cloud_features, device=dev, requires_grad=True)
-    inp = Rast.GaussianPointCloudRasterisationInput(
-        point_cloud=pc, point_cloud_features=feat, point_object_id=torch.tensor(s.point_object_id, device=dev),
-        point_invalid_mask=torch.tensor(s.point_invalid_mask, device=dev),
-        camera_info=CameraInfo(torch.tensor(s.camera_intrinsics, device=dev), s.height, s.width, 0),
-        q_pointcloud_camera=torch.tensor(q, device=dev), t_pointcloud_camera=torch.tensor(t, device=dev), color_max_sh_band=3)
+    inp = scene_input(make_scene(wl), *view_pose(), dev, requires_grad=True)
     module = Rast(Rast.GaussianPointCloudRasterisationConfig(), backward_valid_point_hook=lambda p: None)
     marks = {"fwd": 0.0, "loss": 0.0, "bwd": 0.0}
 
     def step():
-        pc.grad = None
-        feat.grad = None
+        inp.point_cloud.grad = None
+        inp.point_cloud_features.grad = None
         a = time.perf_counter()
         image, _, _ = module(inp)
         b = time.perf_counter()
@@ -42,7 +37,6 @@ def main():
         d = time.perf_counter()
         marks["fwd"] += b - a; marks["loss"] += c - b; marks["bwd"] += d - c
 
-    from taichi_3d_gaussian_splatting_amd import _native
     for _ in range(30):
         step()
     torch.cuda.synchronize()

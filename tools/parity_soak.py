@@ -4,18 +4,15 @@ shape (including partial edge tiles) through the C ABI against the CPU oracle, w
 
     python tools/parity_soak.py [n_cases] [first_seed]
 """
-import os
-import sys
+import argparse
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import harness as H
+import numpy as np
+import torch
 
-import parity_util as P  # noqa: E402
-from oracle import oracle  # noqa: E402
+import parity_util as P
+from oracle import oracle
 
 
 MODULES = {}     # one operator (one gs_ctx) per configuration for the whole soak: frames of many sizes share its arena, its tagged
@@ -72,8 +69,12 @@ def one(seed):
 
 
 def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
-    first = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n_cases", nargs="?", type=int, default=60)
+    ap.add_argument("first_seed", nargs="?", type=int, default=1000)
+    a = ap.parse_args()
+    H.require_gpu("parity_soak.py")
+    n_cases, first = a.n_cases, a.first_seed
     t0 = time.time()
     for i in range(n_cases):
         info = one(first + i)

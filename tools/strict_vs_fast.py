@@ -5,40 +5,16 @@ tests/parity_util.py, the launch time of k_blend_bwd_tile; and the distribution 
 
     python tools/strict_vs_fast.py [out.json]        (the judged copy: profiles/r03_strict_vs_fast.json)
 """
-import ctypes as C
+import argparse
 import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import harness as H
+import numpy as np
 
-import parity_util as P  # noqa: E402
-from oracle import oracle  # noqa: E402
-from taichi_3d_gaussian_splatting_amd import _native  # noqa: E402
-from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, view_pose  # noqa: E402
-
-
-def kernel_ms(module, dev, fn, reps=20):
-    L = _native.lib()
-    names = L.gs_kernel_names().decode().split(",")
-    kid = names.index("k_blend_bwd_tile")
-    ctx = module._ctx_for(dev)
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    _native.check(L.gs_profile_enable(ctx, C.c_uint64(1 << kid)), "gs_profile_enable")
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    ms = (C.c_double * len(names))()
-    cnt = (C.c_int64 * len(names))()
-    _native.check(L.gs_profile_read(ctx, ms, cnt, len(names), 1), "gs_profile_read")
-    _native.check(L.gs_profile_enable(ctx, C.c_uint64(0)), "gs_profile_enable")
-    return ms[kid] / max(cnt[kid], 1)
+import parity_util as P
+from oracle import oracle
+from taichi_3d_gaussian_splatting_amd.synthetic import make_scene, view_pose
 
 
 def run(name):
@@ -49,15 +25,9 @@ def run(name):
     grads = {}
     g_np = None
     for form in ("fast", "reference_order"):
-        cfg = P.Rast.GaussianPointCloudRasterisationConfig()
-        cfg.backward_reference_order = form == "reference_order"
-        module = P.Rast(cfg)
+        module = P.module(strict=form == "reference_order")
         inp = P.make_input(scene, q, t, 3)
-        image = module(inp)[0]
-        rng = np.random.default_rng(0)
-        target = torch.tensor(rng.uniform(0, 1, image.shape).astype(np.float32), device=image.device)
-        g = 2.0 * (image.detach() - target)
-        image.backward(g, retain_graph=True)
+        image, g = H.seeded_backward(module, inp, retain_graph=True)
         gp, gf = inp.point_cloud.grad.cpu().numpy().copy(), inp.point_cloud_features.grad.cpu().numpy().copy()
         if g_np is None:
             g_np = g.cpu().numpy()
@@ -72,7 +42,7 @@ def run(name):
             inp.point_cloud.grad = None
             inp.point_cloud_features.grad = None
             image.backward(g, retain_graph=True)
-        row["k_blend_bwd_tile_ms"] = round(kernel_ms(module, image.device, again), 4)
+        row["k_blend_bwd_tile_ms"] = round(H.library_kernel_ms(module, image.device, "k_blend_bwd_tile", again, warm=3, reps=20), 4)
         res["forms"][form] = row
         grads[form] = (gp, gf)
     d = {}
@@ -89,12 +59,15 @@ def run(name):
 
 
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "strict_vs_fast.json")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default="strict_vs_fast.json")
+    out_path = ap.parse_args().out
+    H.require_gpu("strict_vs_fast.py")
     res = {"what": __doc__.split("\n\n")[0], "cases": []}
     for name in ("cfg2_truck7k", "cfg3_headline", "cfg2_clustered", "cfg3_clustered"):
         res["cases"].append(run(name))
         print(json.dumps(res["cases"][-1]), flush=True)
-    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as fh:
         json.dump(res, fh, indent=1)
 

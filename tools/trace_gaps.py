@@ -4,15 +4,18 @@
 
 Takes the steady-state part of the trace (after the first third), splits it into steps at every launch of the
 first kernel of a step (k_filter) and reports busy time, idle time and the largest gaps by predecessor kernel."""
+import argparse
 import csv
 import glob
-import sys
 from collections import defaultdict
 
 
 def main():
-    d = sys.argv[1]
-    first = sys.argv[2] if len(sys.argv) > 2 else "k_filter"
+    ap = argparse.ArgumentParser()
+    ap.add_argument("trace_dir", help="directory with *_kernel_trace.csv")
+    ap.add_argument("first_kernel", nargs="?", default="k_filter", help="first kernel of a step")
+    a = ap.parse_args()
+    d, first = a.trace_dir, a.first_kernel
     path = sorted(glob.glob(d + "/**/*kernel_trace.csv", recursive=True))[0]
     rows = []
     with open(path) as f:
