@@ -842,6 +842,12 @@ static int waves_per_tile(int n_tiles)
     return G;
 }
 
+static bool bwd_prefill_enabled()
+{
+    const char* e = getenv("GS_BWD_PREFILL");
+    return !(e && e[0] == '0');
+}
+
 // fills the blend half of the arguments; sums_out = where the per-splat sums go
 static int prepare_backward_blend(gs_ctx* c, Frame* f, const float* grad_image, const float* acc_alpha, const int32_t* last,
                                   float* mag_image, float4* sums_out, int strict, hipStream_t stream, GsBackwardArgs* a_out)
@@ -991,6 +997,10 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
         a.aux = 1;
         a.v.cuts = nullptr;
     }
+    // The feature-gradient rows (grad_pointcloud_features, the hook's gather) are zeroed by fill blocks of the blend's launch and the
+    // points stage stores the touched rows only -- when both run in this call and the blend is launched at all.  GS_BWD_PREFILL=0:
+    // the points stage writes every row itself.  Read per call (not cached), so that one process can compare the two forms.
+    a.prefill = points && a.grad_feat && a.v.T > 0 && a.K > 0 && bwd_prefill_enabled();
     launch_backward_blend(c, a, s);
     if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics
     if (pose) gs_launch_pose_grad(a, f->n_objects, c->pose_scratch.p, out->grad_q_pointcloud_camera, out->grad_t_pointcloud_camera, s);

@@ -420,6 +420,10 @@ struct GsBackwardArgs {
     const float* point_cloud; const float* features; const int32_t* object_id; const float* Kmat;
     int sh_band; float f_color, f_high, f_s, f_q, f_alpha;
     float* grad_pc; float* grad_feat; float* grad_uv; float* mag; float* mag_image; int32_t* n_affected;
+    // 1: gs_launch_backward_blend zeroes grad_feat and hook_gfeat (fill blocks of k_blend_bwd_tile's launch) and gs_launch_backward_points
+    // stores the touched rows only.  The host decides once per call (gs_api.hip: backward_impl); 0 wherever the two halves do not
+    // run in one call or the blend is not launched.
+    int prefill;
     float* hook_gpc; float* hook_gfeat; float* hook_guv; float* hook_mag;
     int32_t* hook_ids; int32_t* hook_ntiles; float* hook_depth; float* hook_uv;
     // adaptive-controller accumulators (CTRL:114-141), all nullable together

@@ -15,6 +15,8 @@
 //                 applies band masks and grad factors (RAST:1102-1125, 1167-1182) and writes
 //                 every output row exactly once (zero for rows outside the frustum), including
 //                 the BackwardValidPointHookInput gathers (RAST:1128-1140).
+//                 In gs_backward the all-zero 56-float rows are stored by fill blocks of k_blend_bwd_tile's launch instead
+//                 (GsZeroFill) and this kernel stores the touched rows only (PREZEROED).
 // k_blend_bwd_tile is VALU/latency bound, k_bwd_points HBM bound: see DESIGN.md.
 // Stated once, used by every form of these kernels: one contribution of loop 1 (gs_bwd_contribution), the LDS of a blend workgroup
 // (gs_bwd_lds), a row of sums by column (GsRow, gs_row_add, gs_row_store: gs_point_math.h) and the per-point math loop 2 shares with
@@ -57,6 +59,31 @@
 #endif
 #define HEAVY_CAP GS_HEAVY_CAP
 __host__ __device__ inline int gs_heavy_cap(int T) { return T / 8 < HEAVY_CAP ? T / 8 : HEAVY_CAP; }
+// ZERO FILL of the dense feature-gradient outputs, as extra workgroups of k_blend_bwd_tile's launch (behind the tile ones, as the fold
+// blocks of k_sum_rows are behind the summing ones).  Nine rows in ten of grad_pointcloud_features and of the hook's gather are
+// all-zero at the headline config; written here, while the blend leaves four fifths of HBM unused and empties out over its last
+// third, they cost k_bwd_points<.., PREZEROED> nothing: it stores the touched rows only.  dst[0 .. n) in float4, two ranges
+// (features, hook; the second empty without a hook), grid-stride over the fill blocks so that the blocks in flight write one
+// contiguous run.  Empty (no block is a fill block) unless the host fills it in.
+struct GsZeroFill { unsigned first_block = ~0u, n_blocks = 0; float4* dst0 = nullptr; float4* dst1 = nullptr; unsigned long long n0 = 0, n1 = 0; };
+// bytes per fill block: 25 float4 stores per thread, about 2100 blocks for the 212 MB of the headline config.  50 KB and 200 KB
+// measured the same within the run-to-run spread (profiles/bwd_prefill_ab.json).
+#define GS_FILL_BLOCK_BYTES (100u << 10)
+__device__ __forceinline__ void gs_store_zero(float4* p)
+{
+    // nontemporal: as plain stores the 212 MB push the rows and flags k_sum_rows reads next out of the caches (that kernel
+    // 43 -> 50 us, k_bwd_points 41 -> 46: DESIGN.md section 5)
+    typedef float gs_v4f __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(gs_v4f{0.0f, 0.0f, 0.0f, 0.0f}, reinterpret_cast<gs_v4f*>(p));
+}
+// fill blocks of k_blend_bwd_tile (behind the tile ones)
+__device__ __forceinline__ void gs_zero_fill(const GsZeroFill& z)
+{
+    const unsigned long long stride = (unsigned long long)z.n_blocks * 256;
+    const unsigned long long first = (unsigned long long)(blockIdx.x - z.first_block) * 256 + threadIdx.x;
+    for (unsigned long long i = first; i < z.n0; i += stride) gs_store_zero(z.dst0 + i);
+    for (unsigned long long i = first; i < z.n1; i += stride) gs_store_zero(z.dst1 + i);
+}
 // A heavy tile whose list the forward CUT (k_blend_fwd: every GS_SEG entries each pixel's T and the colour since the last cut) is handed out
 // as one work item per segment: item_base[h] .. item_base[h + 1] are the items of heavy tile h (n_heavy_out[1] = their number,
 // n_heavy_out[4 ..] = item_base).  A heavy tile without cuts is one item.
@@ -631,8 +658,9 @@ __global__ __launch_bounds__(256, GS_BWD_MIN_WAVES) void k_blend_bwd_tile(const 
                                                         float* __restrict__ partial, uint8_t* __restrict__ visited, uint8_t* __restrict__ touched,
                                                         const uint8_t gen, float* __restrict__ mag_image,
                                                         const float4* __restrict__ cuts, float2* __restrict__ cut_mag, const int32_t* __restrict__ tile_cut,
-                                                        const BwdAux aux)
+                                                        const BwdAux aux, const GsZeroFill fill)
 {
+    if (blockIdx.x >= fill.first_block) { gs_zero_fill(fill); return; }
     BwdLds lds = gs_bwd_lds();
     BwdCoop& coop = lds.coop;
     constexpr int G = 4 / NQ;
@@ -870,7 +898,9 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
 // ---------------------------------------------------------------------------------
 #define ROW_LDS 60
 // AUX: the sums carry d depth in column 11 (gs_backward_ex); it joins the camera-space z gradient of the position
-template <bool AUX>
+// PREZEROED: the fill blocks of this call's k_blend_bwd_tile launch (GsZeroFill) have zeroed grad_feat and hook_gfeat: only a touched
+// point stores its feature row (and its hook row), straight from its lane; no row is staged.
+template <bool AUX, bool PREZEROED>
 __global__ __launch_bounds__(256) void k_bwd_points(
     int64_t N, const int32_t* __restrict__ cam_index, const float4* __restrict__ sums, const float4* __restrict__ PD,
     const float* __restrict__ pc, const float* __restrict__ feat, const int32_t* __restrict__ obj,
@@ -884,14 +914,9 @@ __global__ __launch_bounds__(256) void k_bwd_points(
     int32_t* __restrict__ c_num_in_camera, int32_t* __restrict__ c_num_pixels, float* __restrict__ c_vs_grad,
     float* __restrict__ c_vs_grad_avg, float* __restrict__ c_pos_grad, float* __restrict__ c_pos_grad_norm)
 {
-    // The 56-float gradient rows leave through LDS: a lane-per-row store reaches ~3.2 TB/s, the same rows written
-    // as one contiguous 14 KB run per wave ~6.2 TB/s (tools/ubench_rows.hip).  Row stride 60 floats keeps both the
-    // lane-wise float4 staging writes and the row-wise reads spread over the banks.
-    __shared__ __attribute__((aligned(16))) float sRows[4][64 * ROW_LDS + 64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = n < N;
-    const int m = valid ? cam_index[n] : -1;
+    int m = valid ? cam_index[n] : -1;
     float out[GS_NFEAT];
 #pragma unroll
     for (int k = 0; k < GS_NFEAT; ++k) out[k] = 0.0f;               // RAST:1051-1058 zero rows
@@ -912,7 +937,7 @@ __global__ __launch_bounds__(256) void k_bwd_points(
     // nine in ten at the headline config) has all-zero sums, hence all-zero gradients: its 224-byte feature row is not
     // read and the Jacobian chain is not evaluated.  (The reference multiplies those zeros through the chain, which
     // gives the same zeros unless a Jacobian entry is not finite.)
-    const bool touched = m >= 0 && __float_as_int(s[10]) != 0;
+    bool touched = m >= 0 && __float_as_int(s[10]) != 0;
     if (m >= 0 && !touched) {
         grad_pc[3 * n] = 0.0f; grad_pc[3 * n + 1] = 0.0f; grad_pc[3 * n + 2] = 0.0f;
         if (grad_uv) { grad_uv[2 * n] = 0.0f; grad_uv[2 * n + 1] = 0.0f; }
@@ -926,6 +951,29 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         if (hook_depth) hook_depth[m] = GS_REC(PB, m).w;
         if (hook_uv) { const float4 pa = GS_REC(PA, m); hook_uv[2 * (size_t)m] = pa.x; hook_uv[2 * (size_t)m + 1] = pa.y; }
         if (c_num_in_camera) c_num_in_camera[n] += 1;                   // CTRL:133; the other five accumulators get += 0
+    }
+    if constexpr (PREZEROED) {
+        // Nothing is left to do for a lane without a touched point, and nearly every wave holds one (one lane in ten at the headline
+        // config): the block's touched points move up to its first threads, so that one wave -- not four at a tenth of their lanes --
+        // runs the chain below and the others leave.  A point's arithmetic does not depend on the lane that does it.
+        __shared__ int sCount[4];
+        __shared__ int sTouched[256];
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const unsigned long long tb = gs_ballot(touched);
+        if (lane == 0) sCount[wave] = __popcll(tb);
+        __syncthreads();
+        int first = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int c = sCount[w]; first += w < wave ? c : 0; total += c; }
+        if (touched) sTouched[first + __popcll(tb & ((1ull << lane) - 1ull))] = (int)threadIdx.x;
+        __syncthreads();
+        touched = (int)threadIdx.x < total;
+        if (!touched) return;
+        n = (int64_t)blockIdx.x * 256 + sTouched[threadIdx.x];
+        m = cam_index[n];
+        const float4 r0 = sums[3 * (size_t)m], r1 = sums[3 * (size_t)m + 1], r2 = sums[3 * (size_t)m + 2];
+        s[0] = r0.x; s[1] = r0.y; s[2] = r0.z; s[3] = r0.w; s[4] = r1.x; s[5] = r1.y; s[6] = r1.z; s[7] = r1.w;
+        s[8] = r2.x; s[9] = r2.y; s[10] = r2.z; s[11] = r2.w;
     }
     if (touched) {
         {   // the per-splat factors k_blend_bwd_tile left out (see there): opacity, 0.5, (1 - opacity) * opacity
@@ -1080,7 +1128,25 @@ __global__ __launch_bounds__(256) void k_bwd_points(
                               c_num_in_camera, c_num_pixels, c_vs_grad, c_vs_grad_avg, c_pos_grad, c_pos_grad_norm);
     }   // m >= 0
 
+    if constexpr (PREZEROED) {
+        // ---- rows out: the touched rows only, a row per lane (every other row is zero already) ----
+        if (touched) {
+            float4* dst = reinterpret_cast<float4*>(grad_feat + (size_t)GS_NFEAT * n);
+#pragma unroll
+            for (int k = 0; k < GS_NFEAT / 4; ++k) dst[k] = make_float4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
+            if (hook_gfeat) {
+                float4* hdst = reinterpret_cast<float4*>(hook_gfeat + (size_t)GS_NFEAT * m);
+#pragma unroll
+                for (int k = 0; k < GS_NFEAT / 4; ++k) hdst[k] = make_float4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
+            }
+        }
+    } else {
     // ---- rows out: stage, then the wave writes its 64 consecutive rows of grad_feat as one contiguous run ----
+    // The 56-float gradient rows leave through LDS: a lane-per-row store reaches ~3.2 TB/s, the same rows written
+    // as one contiguous 14 KB run per wave ~6.2 TB/s (tools/ubench_rows.hip).  Row stride 60 floats keeps both the
+    // lane-wise float4 staging writes and the row-wise reads spread over the banks.
+    __shared__ __attribute__((aligned(16))) float sRows[4][64 * ROW_LDS + 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* mine = sRows[wave] + lane * ROW_LDS;
 #pragma unroll
     for (int k = 0; k < GS_NFEAT / 4; ++k)
@@ -1108,6 +1174,7 @@ __global__ __launch_bounds__(256) void k_bwd_points(
             dst[e] = *reinterpret_cast<const float4*>(sRows[wave] + rank_to_lane[r] * ROW_LDS + 4 * c);
         }
     }
+    }   // !PREZEROED
 }
 
 void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
@@ -1116,15 +1183,23 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
     // (a.aux: the caller has set v.cuts = NULL -- the depth / alpha backward walks every heavy tile whole, see k_blend_bwd_tile)
     const BwdAux aux{a.grad_depth, a.depth, a.grad_alpha};
     if (v.T > 0 && a.K > 0) {
+        // workgroups: room for every segment of every heavy tile (no cuts: one item per heavy tile) + the ordinary work items four to a workgroup
+        const unsigned groups = (unsigned)(v.cuts ? a.item_cap : gs_heavy_cap(v.T)) + (unsigned)(((size_t)v.T * (size_t)a.G + 3) / 4);
+        // ... + the fill blocks behind them (a.prefill: the caller runs gs_launch_backward_points<PREZEROED> next)
+        GsZeroFill fill{};
+        if (a.prefill) {
+            fill.dst0 = reinterpret_cast<float4*>(a.grad_feat); fill.n0 = (unsigned long long)(GS_NFEAT / 4) * (unsigned long long)a.N;
+            if (a.hook_gfeat) { fill.dst1 = reinterpret_cast<float4*>(a.hook_gfeat); fill.n1 = (unsigned long long)(GS_NFEAT / 4) * (unsigned long long)a.M; }
+            fill.first_block = groups;
+            fill.n_blocks = (unsigned)(((fill.n0 + fill.n1) * sizeof(float4) + GS_FILL_BLOCK_BYTES - 1) / GS_FILL_BLOCK_BYTES);
+        }
         // (the `visited` / `touched` flags are not cleared per backward: a flag counts only if it holds THIS backward's tag, a.gen)
         GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(v.tile_work, v.T, v.tile_order, a.order_hint, v.n_heavy, a.heavy_factor_x2,
                                                                               v.tile_start, v.tile_end, v.cuts ? v.tile_cut : nullptr, v.cuts ? a.item_cap : gs_heavy_cap(v.T)));
-        // workgroups: room for every segment of every heavy tile (no cuts: one item per heavy tile) + the ordinary work items four to a workgroup
-        const unsigned groups = (unsigned)(v.cuts ? a.item_cap : gs_heavy_cap(v.T)) + (unsigned)(((size_t)v.T * (size_t)a.G + 3) / 4);
 #define GS_BWD_LAUNCH_(NQ_, STRICT_, AUX_)                                                                                             \
-        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups, 256, 0, s>>>(v.tile_order, v.n_heavy, v.T,      \
+        GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups + fill.n_blocks, 256, 0, s>>>(v.tile_order, v.n_heavy, v.T,      \
                  v.tile_start, v.tile_end, v.vals_sorted, v.PA, v.PB, v.PC, v.box, v.offsets, a.grad_image, a.acc_alpha, a.last, a.W,     \
-                 a.H, a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image, v.cuts, v.cut_mag, v.tile_cut, aux))
+                 a.H, a.tiles_x, a.partial, a.visited, a.touched, a.gen, a.mag_image, v.cuts, v.cut_mag, v.tile_cut, aux, fill))
 #define GS_BWD_LAUNCH(NQ_, STRICT_) { if (a.aux) GS_BWD_LAUNCH_(NQ_, STRICT_, true); else GS_BWD_LAUNCH_(NQ_, STRICT_, false); }
         if (a.G == 1) { if (a.strict) GS_BWD_LAUNCH(4, true) else GS_BWD_LAUNCH(4, false) }
         else if (a.G == 2) { if (a.strict) GS_BWD_LAUNCH(2, true) else GS_BWD_LAUNCH(2, false) }
@@ -1165,13 +1240,14 @@ void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s)
     const int nb = (int)((a.N + 255) / 256);
     if (nb == 0) return;
     int keep = a.sh_band <= 0 ? 1 : a.sh_band == 1 ? 4 : a.sh_band == 2 ? 9 : 16;
-#define GS_BWD_POINTS(AUX_)                                                                                                             \
-    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<AUX_><<<nb, 256, 0, s>>>(a.N, v.cam_index, a.sums, v.PD, a.point_cloud, a.features,   \
+#define GS_BWD_POINTS(AUX_, PRE_)                                                                                                       \
+    GS_TIMED(a.prof, KID_BWD_POINTS, s, k_bwd_points<AUX_, PRE_><<<nb, 256, 0, s>>>(a.N, v.cam_index, a.sums, v.PD, a.point_cloud, a.features,   \
                                                                     a.object_id, a.Kmat, v.pose, keep, a.f_color, a.f_high, a.f_s, a.f_q, a.f_alpha, \
                                                                     a.grad_pc, a.grad_feat, a.grad_uv, a.mag, a.n_affected,                \
                                                                     a.hook_gpc, a.hook_gfeat, a.hook_guv, a.hook_mag,                      \
                                                                     a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, v.PA, v.PB, v.ntiles, \
                                                                     a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm))
-    if (a.aux) GS_BWD_POINTS(true); else GS_BWD_POINTS(false);
+    if (a.prefill) { if (a.aux) GS_BWD_POINTS(true, true); else GS_BWD_POINTS(false, true); }
+    else { if (a.aux) GS_BWD_POINTS(true, false); else GS_BWD_POINTS(false, false); }
 #undef GS_BWD_POINTS
 }
