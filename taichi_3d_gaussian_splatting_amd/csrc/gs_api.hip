@@ -908,6 +908,7 @@ static int prepare_backward_blend(gs_ctx* c, Frame* f, const float* grad_image, 
     a.max_tiles_hint = f->max_tiles_known ? a.v.max_tiles : nullptr;
     a.sums = sums_out;
     a.mag_image = mag_image;
+    a.live_sums = bwd_prefill_enabled() ? 1 : 0;
     *a_out = a;
     return GS_OK;
 }
@@ -997,9 +998,10 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
         a.aux = 1;
         a.v.cuts = nullptr;
     }
-    // The feature-gradient rows (grad_pointcloud_features, the hook's gather) are zeroed by fill blocks of the blend's launch and the
-    // points stage stores the touched rows only -- when both run in this call and the blend is launched at all.  GS_BWD_PREFILL=0:
-    // the points stage writes every row itself.  Read per call (not cached), so that one process can compare the two forms.
+    // What an untouched point receives (zeros in every per-point output, the hook's copies of forward data, the controller's in-camera
+    // count) is written by fill blocks of the blend's launch and the points stage visits the touched points only -- when both run in
+    // this call and the blend is launched at all.  GS_BWD_PREFILL=0: the points stage writes everything itself (and k_sum_rows runs
+    // in its previous mapping: prepare_backward_blend).  Read per call (not cached), so that one process can compare the two forms.
     a.prefill = points && a.grad_feat && a.v.T > 0 && a.K > 0 && bwd_prefill_enabled();
     launch_backward_blend(c, a, s);
     if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics

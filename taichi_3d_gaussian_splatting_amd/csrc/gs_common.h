@@ -420,10 +420,14 @@ struct GsBackwardArgs {
     const float* point_cloud; const float* features; const int32_t* object_id; const float* Kmat;
     int sh_band; float f_color, f_high, f_s, f_q, f_alpha;
     float* grad_pc; float* grad_feat; float* grad_uv; float* mag; float* mag_image; int32_t* n_affected;
-    // 1: gs_launch_backward_blend zeroes grad_feat and hook_gfeat (fill blocks of k_blend_bwd_tile's launch) and gs_launch_backward_points
-    // stores the touched rows only.  The host decides once per call (gs_api.hip: backward_impl); 0 wherever the two halves do not
+    // 1: gs_launch_backward_blend writes what an untouched point receives into every per-point output, the hook's copies of forward data
+    // and the controller's in-camera count (fill blocks of k_blend_bwd_tile's launch), and gs_launch_backward_points visits the touched
+    // points only.  The host decides once per call (gs_api.hip: backward_impl); 0 wherever the two halves do not
     // run in one call or the blend is not launched.
     int prefill;
+    // 1: k_sum_rows in its mapping over compacted live points, 0: four lanes per point over all M (the same sums, bit for bit).
+    // Set with the blend half of the arguments (gs_api.hip: prepare_backward_blend); GS_BWD_PREFILL=0 selects 0.
+    int live_sums;
     float* hook_gpc; float* hook_gfeat; float* hook_guv; float* hook_mag;
     int32_t* hook_ids; int32_t* hook_ntiles; float* hook_depth; float* hook_uv;
     // adaptive-controller accumulators (CTRL:114-141), all nullable together
@@ -500,11 +504,13 @@ void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, con
 // one operation order both k_bwd_points (from its per-splat sums) and k_controller_accumulate (from the hook payload) use,
 // so that the two wirings give the same bits.  npix / mag / g: the point's num_affected_pixels, magnitude_grad_viewspace
 // and grad_point_in_camera row.
+// IN_CAMERA = false: without num_in_camera -- in a gs_backward whose fill blocks count it (k_backward.hip: GsZeroFill).
+template <bool IN_CAMERA = true>
 __device__ __forceinline__ void gs_controller_add(int64_t n, int32_t npix, float mag, float g0, float g1, float g2,
                                                   int32_t* num_in_camera, int32_t* num_pixels, float* vs_grad, float* vs_grad_avg,
                                                   float* pos_grad, float* pos_grad_norm)
 {
-    num_in_camera[n] += 1;
+    if constexpr (IN_CAMERA) num_in_camera[n] += 1;
     num_pixels[n] += npix;
     vs_grad[n] += mag;
     const float avg = mag / (float)npix;                            // 0/0 -> NaN -> 0 (CTRL:138-139); x/0 -> inf is kept

@@ -10,13 +10,16 @@
 //                 in p's tile box), so all rows of a point are contiguous; a byte of `visited`
 //                 tags the rows this backward wrote.  Factors that are constant per splat (opacity,
 //                 0.5, (1 - opacity) * opacity) are left out of the rows and applied once per point.
-//   k_sum_rows    sums a point's visited rows in slot order (deterministic).
+//   k_sum_rows    sums a point's visited rows in slot order (deterministic): a block's live points compacted into LDS lists and
+//                 summed by class of row count (quads, a wave, the block); the untouched points get their zero row.  (Previous
+//                 mapping, four lanes per point over all points, under GS_BWD_PREFILL=0: the same per-point functions, the same bits.)
 //   k_bwd_points  loop 2 (RAST:708-772) over all N rows: chains the Jacobians (GP3D:132-159, 237-331, 351-373),
 //                 applies band masks and grad factors (RAST:1102-1125, 1167-1182) and writes
 //                 every output row exactly once (zero for rows outside the frustum), including
 //                 the BackwardValidPointHookInput gathers (RAST:1128-1140).
-//                 In gs_backward the all-zero 56-float rows are stored by fill blocks of k_blend_bwd_tile's launch instead
-//                 (GsZeroFill) and this kernel stores the touched rows only (PREZEROED).
+//                 In gs_backward everything a point WITHOUT a contribution receives -- zeros in every per-point output, the hook's
+//                 copies of forward data, the controller's in-camera count -- is written by fill blocks of k_blend_bwd_tile's
+//                 launch instead (GsZeroFill), and this kernel visits the touched points only, found by their tag bytes (PREZEROED).
 // k_blend_bwd_tile is VALU/latency bound, k_bwd_points HBM bound: see DESIGN.md.
 // Stated once, used by every form of these kernels: one contribution of loop 1 (gs_bwd_contribution), the LDS of a blend workgroup
 // (gs_bwd_lds), a row of sums by column (GsRow, gs_row_add, gs_row_store: gs_point_math.h) and the per-point math loop 2 shares with
@@ -59,30 +62,65 @@
 #endif
 #define HEAVY_CAP GS_HEAVY_CAP
 __host__ __device__ inline int gs_heavy_cap(int T) { return T / 8 < HEAVY_CAP ? T / 8 : HEAVY_CAP; }
-// ZERO FILL of the dense feature-gradient outputs, as extra workgroups of k_blend_bwd_tile's launch (behind the tile ones, as the fold
-// blocks of k_sum_rows are behind the summing ones).  Nine rows in ten of grad_pointcloud_features and of the hook's gather are
-// all-zero at the headline config; written here, while the blend leaves four fifths of HBM unused and empties out over its last
-// third, they cost k_bwd_points<.., PREZEROED> nothing: it stores the touched rows only.  dst[0 .. n) in float4, two ranges
-// (features, hook; the second empty without a hook), grid-stride over the fill blocks so that the blocks in flight write one
-// contiguous run.  Empty (no block is a fill block) unless the host fills it in.
-struct GsZeroFill { unsigned first_block = ~0u, n_blocks = 0; float4* dst0 = nullptr; float4* dst1 = nullptr; unsigned long long n0 = 0, n1 = 0; };
+// FILL: everything a point WITHOUT a contribution receives from a backward, written by extra workgroups of k_blend_bwd_tile's launch
+// (behind the tile ones, as the fold blocks of k_sum_rows are behind the summing ones).  None of it depends on the incoming gradient,
+// nine in-camera points in ten are such points at the headline config, and the blend leaves four fifths of HBM unused and empties out
+// over its last third: written here these values cost k_bwd_points<.., PREZEROED> nothing -- it visits the touched points only and
+// overwrites what they got here.
+//   zero ranges   dst[0 .. n) floats: the feature rows (grad_pointcloud_features, the hook's gather: 212 MB at the headline config),
+//                 then grad_pc, grad_uv, mag over N and n_affected, hook_gpc, hook_guv, hook_mag over M.  float4 stores; a range whose
+//                 base is not 16-byte aligned or whose length is no multiple of four floats gets scalar head and tail stores.  A null
+//                 pointer is an empty range.
+//   copy ranges   over the M in-camera points, from forward data that lies in in-camera order already: hook_ids[m] = ids[m],
+//                 hook_ntiles[m] = ntiles[m], hook_depth[m] = PB[m].w, hook_uv[m] = PA[m].xy -- four coalesced streams.
+//   controller    c_num_in_camera[ids[m]] += 1 for every in-camera point, touched or not (CTRL:133): the fill blocks are the only
+//                 place of such a call that touches that accumulator.
+// Every range is walked grid-stride over the fill blocks, so that the blocks in flight write one contiguous run.  Empty (no block is
+// a fill block) unless the host fills it in.
+#define GS_FILL_ZERO_RANGES 9
+struct GsFillRange { float* dst = nullptr; unsigned long long n = 0; };
+struct GsZeroFill { unsigned first_block = ~0u, n_blocks = 0; GsFillRange zero[GS_FILL_ZERO_RANGES];
+                    unsigned M = 0;                  // points the copy ranges run over (0: none of the five below is wanted)
+                    const int32_t* ids = nullptr; const int32_t* ntiles = nullptr; const float4* PA = nullptr; const float4* PB = nullptr;
+                    int32_t* hook_ids = nullptr; int32_t* hook_ntiles = nullptr; float* hook_depth = nullptr; float* hook_uv = nullptr;
+                    int32_t* c_num_in_camera = nullptr; };
 // bytes per fill block: 25 float4 stores per thread, about 2100 blocks for the 212 MB of the headline config.  50 KB and 200 KB
 // measured the same within the run-to-run spread (profiles/bwd_prefill_ab.json).
 #define GS_FILL_BLOCK_BYTES (100u << 10)
+// nontemporal: as plain stores the 212 MB push the rows and flags k_sum_rows reads next out of the caches (that kernel
+// 43 -> 50 us, k_bwd_points 41 -> 46: DESIGN.md section 5)
 __device__ __forceinline__ void gs_store_zero(float4* p)
 {
-    // nontemporal: as plain stores the 212 MB push the rows and flags k_sum_rows reads next out of the caches (that kernel
-    // 43 -> 50 us, k_bwd_points 41 -> 46: DESIGN.md section 5)
     typedef float gs_v4f __attribute__((ext_vector_type(4)));
     __builtin_nontemporal_store(gs_v4f{0.0f, 0.0f, 0.0f, 0.0f}, reinterpret_cast<gs_v4f*>(p));
 }
+template <typename T> __device__ __forceinline__ void gs_store_nt(T* p, const T v) { __builtin_nontemporal_store(v, p); }
 // fill blocks of k_blend_bwd_tile (behind the tile ones)
 __device__ __forceinline__ void gs_zero_fill(const GsZeroFill& z)
 {
     const unsigned long long stride = (unsigned long long)z.n_blocks * 256;
     const unsigned long long first = (unsigned long long)(blockIdx.x - z.first_block) * 256 + threadIdx.x;
-    for (unsigned long long i = first; i < z.n0; i += stride) gs_store_zero(z.dst0 + i);
-    for (unsigned long long i = first; i < z.n1; i += stride) gs_store_zero(z.dst1 + i);
+#pragma unroll
+    for (int r = 0; r < GS_FILL_ZERO_RANGES; ++r) {
+        float* dst = z.zero[r].dst;
+        const unsigned long long n = z.zero[r].n;
+        if (n == 0ull) continue;
+        unsigned long long head = ((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) / 4u;    // floats in front of the first aligned float4
+        head = head < n ? head : n;
+        const unsigned long long n4 = (n - head) / 4ull, tail = (n - head) & 3ull;
+        float4* body = reinterpret_cast<float4*>(dst + head);
+        for (unsigned long long i = first; i < n4; i += stride) gs_store_zero(body + i);
+        if (first < head) gs_store_nt(dst + first, 0.0f);
+        if (first < tail) gs_store_nt(dst + head + 4ull * n4 + first, 0.0f);
+    }
+    for (unsigned long long m = first; m < z.M; m += stride) {
+        const int32_t n = z.ids[m];
+        if (z.hook_ids) gs_store_nt(z.hook_ids + m, n);
+        if (z.hook_ntiles) gs_store_nt(z.hook_ntiles + m, z.ntiles[m]);
+        if (z.hook_depth) gs_store_nt(z.hook_depth + m, GS_REC(z.PB, m).w);
+        if (z.hook_uv) { const float4 pa = GS_REC(z.PA, m); gs_store_nt(z.hook_uv + 2 * m, pa.x); gs_store_nt(z.hook_uv + 2 * m + 1, pa.y); }
+        if (z.c_num_in_camera) z.c_num_in_camera[n] += 1;
+    }
 }
 // A heavy tile whose list the forward CUT (k_blend_fwd: every GS_SEG entries each pixel's T and the colour since the last cut) is handed out
 // as one work item per segment: item_base[h] .. item_base[h + 1] are the items of heavy tile h (n_heavy_out[1] = their number,
@@ -747,6 +785,111 @@ __device__ __forceinline__ void gs_sum_rows_strided(const float4* __restrict__ r
         for (int k = 0; k < 4; ++k) gs_row_add<AUX>(w, wpix, a[k], b[k], c[k]);
     }
 }
+// The summation of ONE point, by the class its row count puts it in: stated once, called by both mappings of k_sum_rows.  The order
+// of additions within a point is a function of its row count alone, so which mapping summed it does not show in the bits.
+// QUAD (at most SUM_ROWS_SMALL rows): lane q of a quad adds rows q, q + 4, ... (all loads in flight at once), then two quad DPP folds.
+template <bool AUX>
+__device__ __forceinline__ void gs_sum_point_quad(const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t gen,
+                                                  const float4* __restrict__ zero_row, const uint32_t off, const int cnt, const int q,
+                                                  float (&v)[11], int& npix)
+{
+    const float4* rows = reinterpret_cast<const float4*>(partial + (size_t)off * PW);
+    const uint8_t* vis = visited + off;
+    // the lane's eight flags first, as one mask (eight row pointers held across the loads would be sixteen registers, and k_sum_rows sits
+    // at the 72 VGPRs of seven waves per SIMD); an unvisited row reads the shared zero row
+    uint32_t on = 0u;
+#pragma unroll
+    for (int k = 0; k < SUM_ROWS_SMALL / 4; ++k) {
+        const int i = q + 4 * k;
+        on |= (i < cnt && vis[i] == gen) ? 1u << k : 0u;
+    }
+    // sixteen rows at a time, the second half only for a point that has it (wave-divergent but cheap: most points have few rows).
+    static_assert(SUM_ROWS_SMALL == 32, "two groups of sixteen rows");
+    auto sixteen = [&](const int h) {
+        float4 a[4], b[4], c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4* r = (on >> (h + k)) & 1u ? rows + 3 * (q + 4 * (h + k)) : zero_row;
+            a[k] = r[0]; b[k] = r[1]; c[k] = r[2];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gs_row_add<AUX>(v, npix, a[k], b[k], c[k]);
+    };
+    if (cnt > 0) {
+        sixteen(0);
+        if (cnt > 16) sixteen(4);
+    }
+}
+// (the folds: run by whole quads, whether or not their point took the path above)
+__device__ __forceinline__ void gs_sum_quad_fold(float (&v)[11], int& npix)
+{
+    GS_DPP11("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
+    GS_DPP11("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
+    asm volatile("s_nop 1");
+    npix += __builtin_amdgcn_update_dpp(0, npix, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+    npix += __builtin_amdgcn_update_dpp(0, npix, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
+}
+// WAVE (more rows, at most SUM_ROWS_GIANT or any number where no point of the frame can be a giant): lanes stride 64 over the rows,
+// then gs_wave_sum11_row3; lane 63 holds the sums.  Up to 256 rows the four flags of a lane travel in `flags` (gs_wave_flags), which
+// the caller may have requested while it was busy with another point.
+__device__ __forceinline__ uint32_t gs_wave_flags(const uint8_t* __restrict__ vis, const int lane, const int bcnt)
+{
+    uint32_t f = 0u;                                              // (0 beyond the end: no backward's tag is 0)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int i = lane + 64 * k; if (i < bcnt) f |= (uint32_t)vis[i] << (8 * k); }
+    return f;
+}
+template <bool AUX>
+__device__ __forceinline__ void gs_sum_point_wave(const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t gen,
+                                                  const float4* __restrict__ zero_row, const uint32_t boff, const int bcnt, const uint32_t flags,
+                                                  const int lane, float (&w)[11], int& wpix)
+{
+    const float4* rows = reinterpret_cast<const float4*>(partial + (size_t)boff * PW);
+    if (bcnt <= 256) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = lane + 64 * k;
+            if (((flags >> (8 * k)) & 255u) == (uint32_t)gen) gs_row_add<AUX>(w, wpix, rows[3 * i], rows[3 * i + 1], rows[3 * i + 2]);
+        }
+    } else {
+        gs_sum_rows_strided<64, AUX>(rows, visited + boff, gen, zero_row, lane, bcnt, w, wpix);
+    }
+    gs_wave_sum11_row3(w);
+    wpix = gs_wave_sum_i(wpix);
+}
+// BLOCK (a giant: a background splat over the whole image, thousands of rows, 350 KB): the 256 threads stride over the rows, four
+// per thread in flight; the four waves' sums are added in wave order and thread 0 stores the row.  Two barriers: every thread of
+// the block calls it.
+template <bool AUX>
+__device__ __forceinline__ void gs_sum_point_block(const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t gen,
+                                                   const float4* __restrict__ zero_row, const uint32_t boff, const int bcnt,
+                                                   float (*sPart)[12], float4* __restrict__ dst)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float w[11];
+    int wpix = 0;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) w[k] = 0.0f;
+    gs_sum_rows_strided<256, AUX>(reinterpret_cast<const float4*>(partial + (size_t)boff * PW), visited + boff, gen, zero_row, (int)threadIdx.x, bcnt, w, wpix);
+    gs_wave_sum11_row3(w);
+    wpix = gs_wave_sum_i(wpix);
+    if (lane == 63) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) sPart[wave][k] = w[k];
+        sPart[wave][10] = __int_as_float(wpix);
+        if constexpr (AUX) sPart[wave][11] = w[10];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float r[11];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) r[k] = ((sPart[0][k] + sPart[1][k]) + sPart[2][k]) + sPart[3][k];
+        const int np = (__float_as_int(sPart[0][10]) + __float_as_int(sPart[1][10])) + (__float_as_int(sPart[2][10]) + __float_as_int(sPart[3][10]));
+        r[10] = AUX ? ((sPart[0][11] + sPart[1][11]) + sPart[2][11]) + sPart[3][11] : 0.0f;
+        gs_row_store<AUX>(dst, r, np);
+    }
+    __syncthreads();
+}
 struct GsMagFold { unsigned first_block; const int32_t* n_heavy; const int32_t* tile_order; const int32_t* tile_cut; const float2* cut_mag;
                    float* mag_image; int W, H, tiles_x; };
 // fold blocks of k_sum_rows (behind the summing ones)
@@ -770,14 +913,13 @@ __device__ __forceinline__ void gs_fold_mag(const GsMagFold& fold)
         fold.mag_image[2 * qp.o] = a; fold.mag_image[2 * qp.o + 1] = b;
 }
 
-// AUX: also column 11 (d depth), in the same slot order; otherwise it is written as 0 (the staged path's sums keep it so)
+// The parent mapping (GS_BWD_PREFILL=0): FOUR lanes per in-camera point over all M points, live or not.
 template <bool AUX>
-__global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_t* __restrict__ offsets, const int32_t* __restrict__ ntiles,
-                                                  const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ touched,
-                                                  const uint8_t gen, const float4* __restrict__ zero_row, float4* __restrict__ sums, const GsMagFold fold,
-                                                  const int32_t* __restrict__ max_tiles_hint)
+__device__ __forceinline__ void gs_sum_rows_all(int M, int G, const uint32_t* __restrict__ offsets, const int32_t* __restrict__ ntiles,
+                                                const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ touched,
+                                                const uint8_t gen, const float4* __restrict__ zero_row, float4* __restrict__ sums,
+                                                const int32_t* __restrict__ max_tiles_hint)
 {
-    if (blockIdx.x >= fold.first_block) { gs_fold_mag(fold); return; }
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int m = t >> 2, q = t & 3;
     const int lane = threadIdx.x & 63;
@@ -801,34 +943,10 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
     int npix = 0;                                                     // column 10 is an integer count: summed as one
 #pragma unroll
     for (int k = 0; k < 11; ++k) v[k] = 0.0f;
-    if (cnt <= SUM_ROWS_SMALL) {
-        const float4* rows = reinterpret_cast<const float4*>(partial + (size_t)off * PW);
-        const uint8_t* vis = visited + off;
-        const float4* r[SUM_ROWS_SMALL / 4];
-#pragma unroll
-        for (int k = 0; k < SUM_ROWS_SMALL / 4; ++k) {
-            const int i = q + 4 * k;
-            const bool on = i < cnt && vis[i] == gen;
-            r[k] = on ? rows + 3 * i : zero_row;
-        }
-#pragma unroll
-        for (int h = 0; h < SUM_ROWS_SMALL / 4; h += 4) {
-            if (4 * h >= cnt) break;                                  // wave-divergent but cheap: most points have few rows
-            float4 a[4], b[4], c[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { a[k] = r[h + k][0]; b[k] = r[h + k][1]; c[k] = r[h + k][2]; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gs_row_add<AUX>(v, npix, a[k], b[k], c[k]);
-        }
-    }
-    GS_DPP11("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
-    GS_DPP11("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
-    asm volatile("s_nop 1");
-    npix += __builtin_amdgcn_update_dpp(0, npix, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
-    npix += __builtin_amdgcn_update_dpp(0, npix, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
+    if (cnt <= SUM_ROWS_SMALL) gs_sum_point_quad<AUX>(partial, visited, gen, zero_row, off, cnt, q, v, npix);
+    gs_sum_quad_fold(v, npix);
     if (valid && q == 0 && cnt <= SUM_ROWS_SMALL) gs_row_store<AUX>(sums + 3 * (size_t)m, v, npix);
-    // wave-cooperative pass over the large points of this wave (one vote per quad leader); the GIANT ones (a background splat over
-    // the whole image: thousands of rows, 350 KB) are left to the whole block below
+    // wave-cooperative pass over the large points of this wave (one vote per quad leader); the GIANT ones are left to the whole block below
     const bool leader = valid && q == 0;
     unsigned long long big = gs_ballot(leader && cnt > SUM_ROWS_SMALL && cnt <= giant_rows);
     while (big) {
@@ -837,69 +955,147 @@ __global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_
         const uint32_t boff = (uint32_t)__builtin_amdgcn_readlane((int)off, j);
         const int bcnt = __builtin_amdgcn_readlane(cnt, j);
         const int bm = __builtin_amdgcn_readlane(m, j);
-        const float4* rows = reinterpret_cast<const float4*>(partial + (size_t)boff * PW);
-        const uint8_t* vis = visited + boff;
         float w[11];
         int wpix = 0;
 #pragma unroll
         for (int k = 0; k < 11; ++k) w[k] = 0.0f;
-        if (bcnt <= 256) {
-            for (int i = lane; i < bcnt; i += 64) {
-                if (vis[i] == gen) gs_row_add<AUX>(w, wpix, rows[3 * i], rows[3 * i + 1], rows[3 * i + 2]);
-            }
-        } else {
-            gs_sum_rows_strided<64, AUX>(rows, vis, gen, zero_row, lane, bcnt, w, wpix);
-        }
-        gs_wave_sum11_row3(w);
-        wpix = gs_wave_sum_i(wpix);
+        const uint32_t flags = bcnt <= 256 ? gs_wave_flags(visited + boff, lane, bcnt) : 0u;
+        gs_sum_point_wave<AUX>(partial, visited, gen, zero_row, boff, bcnt, flags, lane, w, wpix);
         if (lane == 63) gs_row_store<AUX>(sums + 3 * (size_t)bm, w, wpix);
     }
-    // block-cooperative pass over the giant points of this block: its 256 threads stride over the rows, four per thread in flight; the
-    // four waves' sums are added in wave order.  Which points are giant is a function of their tile counts alone: fixed order, fixed bits.
-    // Every wave looks at all 64 points of the block itself (one more coalesced load), so a block without giants -- nearly all of
-    // them -- leaves without a barrier (waiting for the slowest wave there cost 3 us of the launch at the headline config).
+    // block-cooperative pass over the giant points of this block.  Which points are giant is a function of their tile counts alone:
+    // fixed order, fixed bits.  Every wave looks at all 64 points of the block itself (one more coalesced load), so a block without
+    // giants -- nearly all of them -- leaves without a barrier (waiting for the slowest wave there cost 3 us of the launch at the
+    // headline config).
     __shared__ float sPart[4][12];
-    const int wave = threadIdx.x >> 6;
     unsigned long long gm = giants;
+    while (gm) {
+        const int j = __builtin_ctzll(gm);
+        gm &= gm - 1ull;
+        const int bm = (int)blockIdx.x * 64 + j;
+        gs_sum_point_block<AUX>(partial, visited, gen, zero_row, offsets[bm] * (uint32_t)G, ntiles[bm] * G, sPart, sums + 3 * (size_t)bm);
+    }
+}
+
+// The default mapping: a block owns 256 consecutive in-camera points, a thread each for the prologue.  At the headline config nine
+// points in ten are untouched: their thread stores the all-zero row (`sums` stays complete: k_pose_points and the callers of
+// gs_backward_projected read every row) and is done.  The live points are compacted into LDS lists by class -- a ballot per class,
+// the four waves' counts, the idiom of k_bwd_points<.., PREZEROED> -- and summed from there, so that a wave holds sixteen live points
+// and not 1.6: quads over the small ones, the block's four waves in turn over the larger ones (the flags of a wave's next point
+// requested before the current one is reduced), the whole block on each giant.  ceil(M / 256) blocks: one round of the chip's wave
+// slots at the headline config, not four.
+template <bool AUX>
+__device__ __forceinline__ void gs_sum_rows_live(int M, int G, const uint32_t* __restrict__ offsets, const int32_t* __restrict__ ntiles,
+                                                 const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ touched,
+                                                 const uint8_t gen, const float4* __restrict__ zero_row, float4* __restrict__ sums,
+                                                 const int32_t* __restrict__ max_tiles_hint)
+{
+    __shared__ uint32_t sOff[256];
+    __shared__ int32_t sCnt[256];
+    __shared__ uint16_t sList[3][256];               // local indices of the block's live points by class: quad, wave, block
+    __shared__ int32_t sN[3][4];
+    __shared__ float sPart[4][12];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int m0 = (int)blockIdx.x * 256, m = m0 + t;
+    const bool valid = m < M;
+    const bool live = valid && touched[m] == gen;
+    const int giant_rows = (!max_tiles_hint || max_tiles_hint[0] * G > SUM_ROWS_GIANT) ? SUM_ROWS_GIANT : 0x7fffffff;   // as gs_sum_rows_all
+    uint32_t off = 0u;
+    int cnt = 0;
+    if (live) { off = offsets[m] * (uint32_t)G; cnt = ntiles[m] * G; }
+    else if (valid) { float4* z = sums + 3 * (size_t)m; z[0] = z[1] = z[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    sOff[t] = off; sCnt[t] = cnt;
+    const int cls = cnt <= SUM_ROWS_SMALL ? 0 : cnt <= giant_rows ? 1 : 2;
+    const unsigned long long b0 = gs_ballot(live && cls == 0), b1 = gs_ballot(live && cls == 1), b2 = gs_ballot(live && cls == 2);
+    if (lane == 0) { sN[0][wave] = __popcll(b0); sN[1][wave] = __popcll(b1); sN[2][wave] = __popcll(b2); }
+    __syncthreads();
+    if (live) {
+        int at = __popcll((cls == 0 ? b0 : cls == 1 ? b1 : b2) & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) at += sN[cls][w];
+        sList[cls][at] = (uint16_t)t;
+    }
+    __syncthreads();
+    // a list's length: the same number in every thread, kept in a scalar register (this kernel sits at its register budget)
+    auto total_of = [&](const int c) { return __builtin_amdgcn_readfirstlane((sN[c][0] + sN[c][1]) + (sN[c][2] + sN[c][3])); };
+    // quads: sixteen points per wave
+    const int n_quad = total_of(0);
+    for (int base = 0; base < n_quad; base += 64) {
+        // (derived afresh in every pass, the asm hides that it is the same: hoisted out of the loop, the row offsets that depend on q
+        // hold eight registers across it, and the kernel sits exactly at the 72 VGPRs of seven waves per SIMD)
+        int q = t & 3;
+        asm volatile("" : "+v"(q));
+        const int e = base + (t >> 2);
+        const bool on = e < n_quad;
+        const int li = on ? (int)sList[0][e] : 0;
+        const int c = on ? sCnt[li] : 0;
+        float v[11];
+        int npix = 0;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) v[k] = 0.0f;
+        gs_sum_point_quad<AUX>(partial, visited, gen, zero_row, sOff[li], c, q, v, npix);
+        gs_sum_quad_fold(v, npix);
+        if (on && q == 0) gs_row_store<AUX>(sums + 3 * (size_t)(m0 + (int)sList[0][e]), v, npix);      // (read again: one register fewer across the loads)
+    }
+    // waves: entry wave, wave + 4, ... of the list
     {
-        while (gm) {
-            const int j = __builtin_ctzll(gm);
-            gm &= gm - 1ull;
-            const int bm = (int)blockIdx.x * 64 + j;
-            const uint32_t boff = offsets[bm] * (uint32_t)G;
-            const int bcnt = ntiles[bm] * G;
+        const int n_wave = total_of(1);
+        int e = __builtin_amdgcn_readfirstlane(wave);
+        uint32_t next_flags = 0u;
+        if (e < n_wave) {
+            const int li = (int)sList[1][e];
+            const int c = sCnt[li];
+            if (c <= 256) next_flags = gs_wave_flags(visited + sOff[li], lane, c);
+        }
+        while (e < n_wave) {
+            const int li = __builtin_amdgcn_readfirstlane((int)sList[1][e]);
+            const uint32_t boff = (uint32_t)__builtin_amdgcn_readfirstlane((int)sOff[li]);
+            const int bcnt = __builtin_amdgcn_readfirstlane(sCnt[li]);
+            const uint32_t flags = next_flags;
+            e += 4;
+            if (e < n_wave) {
+                const int ln = (int)sList[1][e];
+                const int cn = sCnt[ln];
+                if (cn <= 256) next_flags = gs_wave_flags(visited + sOff[ln], lane, cn);
+            }
             float w[11];
             int wpix = 0;
 #pragma unroll
             for (int k = 0; k < 11; ++k) w[k] = 0.0f;
-            gs_sum_rows_strided<256, AUX>(reinterpret_cast<const float4*>(partial + (size_t)boff * PW), visited + boff, gen, zero_row, (int)threadIdx.x, bcnt, w, wpix);
-            gs_wave_sum11_row3(w);
-            wpix = gs_wave_sum_i(wpix);
-            if (lane == 63) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) sPart[wave][k] = w[k];
-                sPart[wave][10] = __int_as_float(wpix);
-                if constexpr (AUX) sPart[wave][11] = w[10];
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                float r[11];
-#pragma unroll
-                for (int k = 0; k < 10; ++k) r[k] = ((sPart[0][k] + sPart[1][k]) + sPart[2][k]) + sPart[3][k];
-                const int np = (__float_as_int(sPart[0][10]) + __float_as_int(sPart[1][10])) + (__float_as_int(sPart[2][10]) + __float_as_int(sPart[3][10]));
-                r[10] = AUX ? ((sPart[0][11] + sPart[1][11]) + sPart[2][11]) + sPart[3][11] : 0.0f;
-                gs_row_store<AUX>(sums + 3 * (size_t)bm, r, np);
-            }
-            __syncthreads();
+            gs_sum_point_wave<AUX>(partial, visited, gen, zero_row, boff, bcnt, flags, lane, w, wpix);
+            if (lane == 63) gs_row_store<AUX>(sums + 3 * (size_t)(m0 + li), w, wpix);
         }
     }
+    // giants: the whole block, one after the other (n_block is the same number in every thread: the barriers inside are met by all)
+    const int n_block = total_of(2);
+    for (int e = 0; e < n_block; ++e) {
+        const int li = (int)sList[2][e];
+        gs_sum_point_block<AUX>(partial, visited, gen, zero_row, sOff[li], sCnt[li], sPart, sums + 3 * (size_t)(m0 + li));
+    }
+}
+
+// AUX: also column 11 (d depth), in the same slot order; otherwise it is written as 0 (the staged path's sums keep it so)
+// LIVE: the mapping over compacted live points (256 points per block) instead of four lanes per point (64 points per block)
+template <bool AUX, bool LIVE>
+__global__ __launch_bounds__(256, 7) void k_sum_rows(int M, int G, const uint32_t* __restrict__ offsets, const int32_t* __restrict__ ntiles,
+                                                  const float* __restrict__ partial, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ touched,
+                                                  const uint8_t gen, const float4* __restrict__ zero_row, float4* __restrict__ sums, const GsMagFold fold,
+                                                  const int32_t* __restrict__ max_tiles_hint)
+{
+    if (blockIdx.x >= fold.first_block) { gs_fold_mag(fold); return; }
+    if constexpr (LIVE) gs_sum_rows_live<AUX>(M, G, offsets, ntiles, partial, visited, touched, gen, zero_row, sums, max_tiles_hint);
+    else gs_sum_rows_all<AUX>(M, G, offsets, ntiles, partial, visited, touched, gen, zero_row, sums, max_tiles_hint);
 }
 
 // ---------------------------------------------------------------------------------
 #define ROW_LDS 60
 // AUX: the sums carry d depth in column 11 (gs_backward_ex); it joins the camera-space z gradient of the position
-// PREZEROED: the fill blocks of this call's k_blend_bwd_tile launch (GsZeroFill) have zeroed grad_feat and hook_gfeat: only a touched
-// point stores its feature row (and its hook row), straight from its lane; no row is staged.
+// PREZEROED: the fill blocks of this call's k_blend_bwd_tile launch (GsZeroFill) have written what a point without a contribution
+// receives into EVERY per-point output, copied the four hook arrays that repeat forward data and counted c_num_in_camera.  This form
+// has no out-of-camera and no untouched branch: a block takes 256 consecutive in-camera points m, finds the touched ones from their
+// tag bytes (touched_tag[m] == gen), and only those read their sums and their ids[m], run the chain and store their values, a
+// feature row straight from its lane; no row is staged.  The tag is the same predicate as column 10 of the sums != 0, the test of
+// the other form: k_sum_rows stores an all-zero row for a point without the tag, and a tagged point has a row with a contribution
+// count of at least one (k_blend_bwd_tile tags a point only behind `n_use != 0`).
 template <bool AUX, bool PREZEROED>
 __global__ __launch_bounds__(256) void k_bwd_points(
     int64_t N, const int32_t* __restrict__ cam_index, const float4* __restrict__ sums, const float4* __restrict__ PD,
@@ -912,20 +1108,26 @@ __global__ __launch_bounds__(256) void k_bwd_points(
     int32_t* __restrict__ hook_ids, int32_t* __restrict__ hook_ntiles, float* __restrict__ hook_depth, float* __restrict__ hook_uv,
     const float4* __restrict__ PA, const float4* __restrict__ PB, const int32_t* __restrict__ ntiles,
     int32_t* __restrict__ c_num_in_camera, int32_t* __restrict__ c_num_pixels, float* __restrict__ c_vs_grad,
-    float* __restrict__ c_vs_grad_avg, float* __restrict__ c_pos_grad, float* __restrict__ c_pos_grad_norm)
+    float* __restrict__ c_vs_grad_avg, float* __restrict__ c_pos_grad, float* __restrict__ c_pos_grad_norm,
+    int M, const int32_t* __restrict__ ids, const uint8_t* __restrict__ touched_tag, const uint8_t gen)      // (PREZEROED only)
 {
-    int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = n < N;
-    int m = valid ? cam_index[n] : -1;
+    int64_t n;
+    int m;
+    bool touched;
     float out[GS_NFEAT];
 #pragma unroll
     for (int k = 0; k < GS_NFEAT; ++k) out[k] = 0.0f;               // RAST:1051-1058 zero rows
+    float s[PW];
+    if constexpr (!PREZEROED) {
+    // the point domain: a thread per point n, in camera (m = cam_index[n] >= 0) or not
+    n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = n < N;
+    m = valid ? cam_index[n] : -1;
     if (valid && m < 0) {
         grad_pc[3 * n] = 0.0f; grad_pc[3 * n + 1] = 0.0f; grad_pc[3 * n + 2] = 0.0f;
         if (grad_uv) { grad_uv[2 * n] = 0.0f; grad_uv[2 * n + 1] = 0.0f; }
         if (mag) mag[n] = 0.0f;
     }
-    float s[PW];
 #pragma unroll
     for (int k = 0; k < PW; ++k) s[k] = 0.0f;
     if (m >= 0) {
@@ -937,7 +1139,7 @@ __global__ __launch_bounds__(256) void k_bwd_points(
     // nine in ten at the headline config) has all-zero sums, hence all-zero gradients: its 224-byte feature row is not
     // read and the Jacobian chain is not evaluated.  (The reference multiplies those zeros through the chain, which
     // gives the same zeros unless a Jacobian entry is not finite.)
-    bool touched = m >= 0 && __float_as_int(s[10]) != 0;
+    touched = m >= 0 && __float_as_int(s[10]) != 0;
     if (m >= 0 && !touched) {
         grad_pc[3 * n] = 0.0f; grad_pc[3 * n + 1] = 0.0f; grad_pc[3 * n + 2] = 0.0f;
         if (grad_uv) { grad_uv[2 * n] = 0.0f; grad_uv[2 * n + 1] = 0.0f; }
@@ -952,10 +1154,13 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         if (hook_uv) { const float4 pa = GS_REC(PA, m); hook_uv[2 * (size_t)m] = pa.x; hook_uv[2 * (size_t)m + 1] = pa.y; }
         if (c_num_in_camera) c_num_in_camera[n] += 1;                   // CTRL:133; the other five accumulators get += 0
     }
-    if constexpr (PREZEROED) {
+    } else {
         // Nothing is left to do for a lane without a touched point, and nearly every wave holds one (one lane in ten at the headline
         // config): the block's touched points move up to its first threads, so that one wave -- not four at a tenth of their lanes --
         // runs the chain below and the others leave.  A point's arithmetic does not depend on the lane that does it.
+        // The in-camera domain: a thread per in-camera point m; N and cam_index are not used.
+        const int mt = (int)blockIdx.x * 256 + (int)threadIdx.x;
+        touched = mt < M && touched_tag[mt] == gen;
         __shared__ int sCount[4];
         __shared__ int sTouched[256];
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -969,8 +1174,8 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         __syncthreads();
         touched = (int)threadIdx.x < total;
         if (!touched) return;
-        n = (int64_t)blockIdx.x * 256 + sTouched[threadIdx.x];
-        m = cam_index[n];
+        m = (int)blockIdx.x * 256 + sTouched[threadIdx.x];
+        n = ids[m];
         const float4 r0 = sums[3 * (size_t)m], r1 = sums[3 * (size_t)m + 1], r2 = sums[3 * (size_t)m + 2];
         s[0] = r0.x; s[1] = r0.y; s[2] = r0.z; s[3] = r0.w; s[4] = r1.x; s[5] = r1.y; s[6] = r1.z; s[7] = r1.w;
         s[8] = r2.x; s[9] = r2.y; s[10] = r2.z; s[11] = r2.w;
@@ -1119,13 +1324,15 @@ __global__ __launch_bounds__(256) void k_bwd_points(
         if (hook_gpc) { hook_gpc[3 * (size_t)m] = gt[0]; hook_gpc[3 * (size_t)m + 1] = gt[1]; hook_gpc[3 * (size_t)m + 2] = gt[2]; }
         if (hook_guv) { hook_guv[2 * (size_t)m] = guv0; hook_guv[2 * (size_t)m + 1] = guv1; }
         if (hook_mag) hook_mag[m] = s[9];
-        if (hook_ids) hook_ids[m] = (int32_t)n;                         // RAST:1129, 1136-1139
-        if (hook_ntiles) hook_ntiles[m] = ntiles[m];
-        if (hook_depth) hook_depth[m] = GS_REC(PB, m).w;
-        if (hook_uv) { const float4 pa = GS_REC(PA, m); hook_uv[2 * (size_t)m] = pa.x; hook_uv[2 * (size_t)m + 1] = pa.y; }
+        if constexpr (!PREZEROED) {                                     // (PREZEROED: copied by the fill blocks)
+            if (hook_ids) hook_ids[m] = (int32_t)n;                     // RAST:1129, 1136-1139
+            if (hook_ntiles) hook_ntiles[m] = ntiles[m];
+            if (hook_depth) hook_depth[m] = GS_REC(PB, m).w;
+            if (hook_uv) { const float4 pa = GS_REC(PA, m); hook_uv[2 * (size_t)m] = pa.x; hook_uv[2 * (size_t)m + 1] = pa.y; }
+        }
         if (c_num_in_camera)                                            // GaussianPointAdaptiveController.update, CTRL:133-141
-            gs_controller_add(n, __float_as_int(s[10]), s[9], gt[0], gt[1], gt[2],
-                              c_num_in_camera, c_num_pixels, c_vs_grad, c_vs_grad_avg, c_pos_grad, c_pos_grad_norm);
+            gs_controller_add<!PREZEROED>(n, __float_as_int(s[10]), s[9], gt[0], gt[1], gt[2],           // (PREZEROED: counted by the fill blocks)
+                                          c_num_in_camera, c_num_pixels, c_vs_grad, c_vs_grad_avg, c_pos_grad, c_pos_grad_norm);
     }   // m >= 0
 
     if constexpr (PREZEROED) {
@@ -1188,10 +1395,23 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
         // ... + the fill blocks behind them (a.prefill: the caller runs gs_launch_backward_points<PREZEROED> next)
         GsZeroFill fill{};
         if (a.prefill) {
-            fill.dst0 = reinterpret_cast<float4*>(a.grad_feat); fill.n0 = (unsigned long long)(GS_NFEAT / 4) * (unsigned long long)a.N;
-            if (a.hook_gfeat) { fill.dst1 = reinterpret_cast<float4*>(a.hook_gfeat); fill.n1 = (unsigned long long)(GS_NFEAT / 4) * (unsigned long long)a.M; }
+            const unsigned long long N = (unsigned long long)a.N, M = (unsigned long long)a.M;
+            int r = 0;
+            unsigned long long bytes = 0;
+            auto zero = [&](void* p, unsigned long long n) { if (p && n) { fill.zero[r].dst = static_cast<float*>(p); fill.zero[r].n = n; ++r; bytes += 4 * n; } };
+            zero(a.grad_feat, GS_NFEAT * N); zero(a.hook_gfeat, GS_NFEAT * M);
+            zero(a.grad_pc, 3 * N); zero(a.grad_uv, 2 * N); zero(a.mag, N);
+            zero(a.n_affected, M); zero(a.hook_gpc, 3 * M); zero(a.hook_guv, 2 * M); zero(a.hook_mag, M);      // (GS_FILL_ZERO_RANGES of them)
+            if (a.hook_ids || a.hook_ntiles || a.hook_depth || a.hook_uv || a.c_num_in_camera) {
+                fill.M = (unsigned)a.M;
+                fill.ids = v.ids; fill.ntiles = v.ntiles; fill.PA = v.PA; fill.PB = v.PB;
+                fill.hook_ids = a.hook_ids; fill.hook_ntiles = a.hook_ntiles; fill.hook_depth = a.hook_depth; fill.hook_uv = a.hook_uv;
+                fill.c_num_in_camera = a.c_num_in_camera;
+                bytes += 4 * M * ((a.hook_ids != nullptr) + (a.hook_ntiles != nullptr) + (a.hook_depth != nullptr) + 2 * (a.hook_uv != nullptr) +
+                                  (a.c_num_in_camera != nullptr));
+            }
             fill.first_block = groups;
-            fill.n_blocks = (unsigned)(((fill.n0 + fill.n1) * sizeof(float4) + GS_FILL_BLOCK_BYTES - 1) / GS_FILL_BLOCK_BYTES);
+            fill.n_blocks = (unsigned)((bytes + GS_FILL_BLOCK_BYTES - 1) / GS_FILL_BLOCK_BYTES);
         }
         // (the `visited` / `touched` flags are not cleared per backward: a flag counts only if it holds THIS backward's tag, a.gen)
         GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(v.tile_work, v.T, v.tile_order, a.order_hint, v.n_heavy, a.heavy_factor_x2,
@@ -1219,16 +1439,16 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
         (void)hipMemsetAsync(a.mag_image, 0, sizeof(float) * 2 * (size_t)a.H * (size_t)a.W, s);
     if (a.M > 0 && v.T > 0 && a.K > 0) {
         GsMagFold fold{};
-        fold.first_block = (unsigned)(((size_t)a.M * 4 + 255) / 256);
+        fold.first_block = a.live_sums ? (unsigned)((a.M + 255) / 256) : (unsigned)(((size_t)a.M * 4 + 255) / 256);
         fold.n_heavy = v.n_heavy; fold.tile_order = v.tile_order; fold.tile_cut = v.tile_cut; fold.cut_mag = v.cut_mag;
         fold.mag_image = v.cuts ? a.mag_image : nullptr; fold.W = a.W; fold.H = a.H; fold.tiles_x = a.tiles_x;
         const unsigned fold_blocks = fold.mag_image ? (unsigned)gs_heavy_cap(v.T) : 0u;
-        if (a.aux)
-            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<true><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, v.offsets, v.ntiles, a.partial, a.visited,
-                                                                                  a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
-        else
-            GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<false><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, v.offsets, v.ntiles, a.partial, a.visited,
-                                                                                  a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint));
+#define GS_SUM_ROWS(AUX_, LIVE_)                                                                                                        \
+        GS_TIMED(a.prof, KID_SUM_ROWS, s, k_sum_rows<AUX_, LIVE_><<<fold.first_block + fold_blocks, 256, 0, s>>>(a.M, a.G, v.offsets, v.ntiles, a.partial, \
+                                                                                  a.visited, a.touched, a.gen, a.zero_row, a.sums, fold, a.max_tiles_hint))
+        if (a.live_sums) { if (a.aux) GS_SUM_ROWS(true, true); else GS_SUM_ROWS(false, true); }
+        else { if (a.aux) GS_SUM_ROWS(true, false); else GS_SUM_ROWS(false, false); }
+#undef GS_SUM_ROWS
     }
     else if (a.M > 0)
         (void)hipMemsetAsync(a.sums, 0, sizeof(float) * PW * (size_t)a.M, s);          // no pairs at all: every sum is zero
@@ -1237,7 +1457,7 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
 void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s)
 {
     const GsFrameView& v = a.v;
-    const int nb = (int)((a.N + 255) / 256);
+    const int nb = a.prefill ? (a.M + 255) / 256 : (int)((a.N + 255) / 256);      // (prefill: over the in-camera points, M > 0)
     if (nb == 0) return;
     int keep = a.sh_band <= 0 ? 1 : a.sh_band == 1 ? 4 : a.sh_band == 2 ? 9 : 16;
 #define GS_BWD_POINTS(AUX_, PRE_)                                                                                                       \
@@ -1246,7 +1466,8 @@ void gs_launch_backward_points(const GsBackwardArgs& a, hipStream_t s)
                                                                     a.grad_pc, a.grad_feat, a.grad_uv, a.mag, a.n_affected,                \
                                                                     a.hook_gpc, a.hook_gfeat, a.hook_guv, a.hook_mag,                      \
                                                                     a.hook_ids, a.hook_ntiles, a.hook_depth, a.hook_uv, v.PA, v.PB, v.ntiles, \
-                                                                    a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm))
+                                                                    a.c_num_in_camera, a.c_num_pixels, a.c_vs_grad, a.c_vs_grad_avg, a.c_pos_grad, a.c_pos_grad_norm, \
+                                                                    a.M, v.ids, a.touched, a.gen))
     if (a.prefill) { if (a.aux) GS_BWD_POINTS(true, true); else GS_BWD_POINTS(false, true); }
     else { if (a.aux) GS_BWD_POINTS(true, false); else GS_BWD_POINTS(false, false); }
 #undef GS_BWD_POINTS
