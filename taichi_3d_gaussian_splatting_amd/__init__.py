@@ -5,3 +5,4 @@ from .Camera import CameraInfo  # noqa: F401
 from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation  # noqa: F401
 from .controller_stats import ControllerAccumulators  # noqa: F401
 from .GaussianPointAdaptiveController import GaussianPointAdaptiveController  # noqa: F401
+from .GaussianPointCloudScene import GaussianPointCloudScene  # noqa: F401

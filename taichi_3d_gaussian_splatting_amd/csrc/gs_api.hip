@@ -4,6 +4,7 @@
 #include "../../include/gs_rasterizer.h"
 #include "../../include/gs_channels.h"
 #include "../../include/gs_sparse.h"
+#include "../../include/gs_knn.h"
 #include "gs_common.h"
 
 #include <algorithm>
@@ -135,6 +136,7 @@ struct gs_ctx {
     uint64_t bwd_serial = 0;
     size_t touched_offset = 0;
     DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
+    DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
     uint64_t slots_busy = 1ull;            // slot 0 serves the calls that wait at once; the others belong to frames begun and not yet read
@@ -193,7 +195,8 @@ extern "C" int gs_destroy(gs_ctx* c)
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
-                      &c->ch_partial, &c->ch_flags, &c->row_block_totals };
+                      &c->ch_partial, &c->ch_flags, &c->row_block_totals,
+                      &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : c->prof.spare) (void)hipEventDestroy(e);
@@ -1296,6 +1299,29 @@ extern "C" int gs_adam_step_rows(gs_ctx* c, float* param, const float* grad, flo
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_adam_rows(param, grad, exp_avg, exp_avg_sq, n_rows, row_len, ids, count, max_count, lr, beta1, beta2, eps, step, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- exact k nearest neighbours (include/gs_knn.h, k_knn.hip) --------------------------------------------------------------
+// Everything is queued on the call's stream; nothing is read back.
+extern "C" int gs_knn(gs_ctx* c, const float* xyz, const int8_t* invalid_mask, int64_t n_points, int32_t k, float* d2_out,
+                      int32_t* idx_out, gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: ctx is NULL");
+    if (k < 1 || k > 8) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: k must be in [1, 8]");
+    if (n_points < 0 || n_points > (int64_t)GS_KNN_MAX_POINTS)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: n_points must be in [0, 2^30]");
+    if (n_points > 0 && (!xyz || !d2_out)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: NULL xyz or d2_out with n_points > 0");
+    if (n_points == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
+    int rc;
+    if ((rc = grow(c, { NEED(c->knn_sort, gs_knn_sort_bytes(n_points)), NEED(c->knn_hist, gs_knn_hist_bytes(n_points)),
+                        NEED(c->knn_points, gs_knn_points_bytes(n_points)), NEED(c->knn_tree, gs_knn_tree_bytes(n_points)) })) != GS_OK) return rc;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    gs_launch_knn(xyz, invalid_mask, n_points, k, d2_out, idx_out, c->knn_sort.p, c->knn_hist.p, c->knn_points.p, c->knn_tree.p, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -495,6 +495,13 @@ void gs_launch_touched_rows(const uint8_t* touched, uint8_t gen, const int32_t* 
                             int32_t* ids_out, int64_t capacity, int32_t* count_out, hipStream_t s);
 void gs_launch_adam_rows(float* param, const float* grad, float* m, float* v, int64_t n_rows, int row_len, const int32_t* ids,
                          const int32_t* count, int64_t max_count, float lr, float beta1, float beta2, float eps, int64_t step, hipStream_t s);
+// k_knn.hip (include/gs_knn.h): exact k nearest neighbours of the n rows of xyz; the four work buffers hold gs_knn_*_bytes(n)
+size_t gs_knn_sort_bytes(int64_t n);
+size_t gs_knn_hist_bytes(int64_t n);
+size_t gs_knn_points_bytes(int64_t n);
+size_t gs_knn_tree_bytes(int64_t n);
+void gs_launch_knn(const float* xyz, const int8_t* invalid, int64_t n, int k, float* d2_out, int32_t* idx_out,
+                   void* sort_ws, void* hist_ws, void* pts_ws, void* tree_ws, hipStream_t s);
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s);
 void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, const float* value_and_count, const float* upstream,
                         float* grad, hipStream_t s);

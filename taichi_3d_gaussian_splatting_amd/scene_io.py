@@ -34,13 +34,26 @@ def save_parquet(path: str, point_cloud: np.ndarray, point_cloud_features: np.nd
 
 def load_parquet(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """Returns (point_cloud (N,3), point_cloud_features (N,56)); raises if the file has no feature columns
-    (a bare x,y,z[,r,g,b] initialisation cloud needs the reference's KD-tree initialiser, which is out of scope)."""
+    (a bare x,y,z[,r,g,b] initialisation cloud has none yet: GaussianPointCloudScene.from_parquet reads it through
+    load_parquet_columns and initialises it on the GPU)."""
     import pandas as pd
     df = pd.read_parquet(path)
     if not set(FEATURE_COLUMNS).issubset(df.columns):
         raise ValueError(f"{path} holds no trained features (columns {FEATURE_COLUMNS[0]}..{FEATURE_COLUMNS[-1]} missing)")
     return (np.ascontiguousarray(df[["x", "y", "z"]].to_numpy(dtype=np.float32)),
             np.ascontiguousarray(df[FEATURE_COLUMNS].to_numpy(dtype=np.float32)))
+
+
+def load_parquet_columns(path: str):
+    """Whatever the file holds: (point_cloud (N,3) f32, point_cloud_features (N,56) f32 or None, rgb (N,3) f32 in 0..255 or
+    None).  A bare x,y,z[,r,g,b] cloud comes back without features; the colours are read only then."""
+    import pandas as pd
+    df = pd.read_parquet(path)
+    point_cloud = np.ascontiguousarray(df[["x", "y", "z"]].to_numpy(dtype=np.float32))
+    if set(FEATURE_COLUMNS).issubset(df.columns):
+        return point_cloud, np.ascontiguousarray(df[FEATURE_COLUMNS].to_numpy(dtype=np.float32)), None
+    rgb = np.ascontiguousarray(df[["r", "g", "b"]].to_numpy(dtype=np.float32)) if {"r", "g", "b"}.issubset(df.columns) else None
+    return point_cloud, None, rgb
 
 
 def features_to_ply_columns(point_cloud: np.ndarray, features: np.ndarray) -> np.ndarray:
