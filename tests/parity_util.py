@@ -204,6 +204,73 @@ def tiny_case(seed, n, sigma0, width=32, height=None):
     return s, q, t, int(width % 16 != 0 or height % 16 != 0)
 
 
+def multi_object_case(seed, n_objects, n=64, sigma0=0.5, width=32, height=32, ids=None, empty_last=False):
+    """tiny_case with n_objects poses, each the tiny_case pose perturbed by N(0, 0.01) -> (scene, q, t, partial).  ids: the
+    object of every point (default: drawn uniformly).  empty_last: the last object's points lie behind the camera, so no
+    visible point depends on its row"""
+    s, q, t, partial = tiny_case(seed, n, sigma0, width, height)
+    rng = np.random.default_rng(seed + 7)
+    drawn = rng.integers(0, n_objects, n).astype(np.int32)
+    s.point_object_id[:] = drawn if ids is None else np.asarray(ids, np.int32)
+    q = np.repeat(q, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 4)).astype(np.float32)
+    t = np.repeat(t, n_objects, 0) + rng.normal(0, 0.01, (n_objects, 3)).astype(np.float32)
+    if empty_last:
+        t[-1] = [0.0, 0.0, 50.0]
+    return s, q.astype(np.float32), t.astype(np.float32), partial
+
+
+# Multi-object frames past one wave (64 in-camera points) and one block (256) of k_pose_points, still small enough for the
+# pixel-loop reference: 700 points at 48x48 (3 blocks) and 1200 at 64x64 (5 blocks), every point in camera unless empty_last.
+# k_pose_points counts touched points only (a point hidden everywhere takes no slot), so the two layouts that must fill a wave's
+# 64 and a block's 256 record slots put the rows that cover most pixels under the unperturbed pose first: the same scene in another row order.
+# name -> (frame, n_objects, ids(n) or None for random, empty_last, touched rows first)
+POSE_FRAMES = {700: (700, 0.15, 48), 1200: (1200, 0.1, 64)}
+POSE_LAYOUTS = {
+    "random3_empty_last": (700, 3, None, True, False),                        # several waves and blocks per object; a zero row
+    "random3": (1200, 3, None, False, False),
+    "random300": (700, 300, None, False, False),                              # more than 256 objects: records at stride 256
+    "one_point_per_object": (700, 700, lambda n: np.arange(n), False, True),  # block 0 holds 256 distinct ids: every record slot
+    "modulo64": (1200, 64, lambda n: np.arange(n) % 64, False, True),         # a wave holds 64 distinct ids: its last slot
+    "contiguous100": (1200, 12, lambda n: np.arange(n) // 100, False, False), # an object straddles every block edge
+}
+
+
+def affected_pixels(f):
+    """(M) int: num_affected_pixels of the in-camera entries of an oracle Forward (it does not depend on the upstream)"""
+    cfg = oracle.default_config(allow_partial_tiles=int(f.W % 16 != 0 or f.H % 16 != 0))
+    return oracle.backward(f, np.ones((f.H, f.W, 3), np.float32), 3, cfg)["num_affected_pixels"]
+
+
+def pose_layout_case(name):
+    """An entry of POSE_LAYOUTS -> (scene, q, t, partial)"""
+    n, n_objects, ids, empty_last, touched_first = POSE_LAYOUTS[name]
+    _, sigma0, width = POSE_FRAMES[n]
+    s, q, t, partial = multi_object_case(n, n_objects, n, sigma0, width, width, None if ids is None else ids(n), empty_last)
+    if touched_first:       # rows by falling pixel count under the unperturbed pose: the first ones stay touched under any of the poses
+        f, _ = oracle_frame(*tiny_case(n, n, sigma0, width))
+        pixels = np.zeros(n, np.int64)
+        pixels[f.point_id_in_camera_list] = affected_pixels(f)
+        order = np.argsort(-pixels, kind="stable")
+        s.point_cloud[:], s.point_cloud_features[:] = s.point_cloud[order], s.point_cloud_features[order]
+    return s, q, t, partial
+
+
+def pose_reduction_shape(object_of_entry, touched):
+    """How k_pose_points sees a frame: object_of_entry (M) the object id of every in-camera entry, touched (M) bool (its per-splat
+    count is not zero) -> blocks, the largest number of distinct touched ids in a wave (64 entries) and in a block (256), the
+    number of objects with a touched point, and of objects with touched points in more than one block."""
+    o = np.where(touched, object_of_entry, -1)
+    distinct = lambda size: [np.unique(c[c >= 0]) for c in (o[i:i + size] for i in range(0, o.size, size))]
+    per_block = distinct(256)
+    blocks_of = np.bincount(np.concatenate(per_block).astype(np.int64)) if o.size else np.zeros(0, np.int64)
+    return dict(blocks=len(per_block), per_wave=max(len(u) for u in distinct(64)), per_block=max(len(u) for u in per_block),
+                objects=int((blocks_of > 0).sum()), objects_in_several_blocks=int((blocks_of > 1).sum()))
+
+
+LARGE_FRAME = (1, 300000, 0.01, 256, 256)    # tiny_case arguments: more than 262 144 points in camera, past the second trip
+                                              # of k_pose_reduce's block loop (1024 x 256) and of k_rows_scatter's (256 x 1024)
+
+
 # the scenes of the float64 gradient comparisons: the four of test_oracle_autograd and three of the soak
 SCENES = [("tiny", (0, 48, 0.25, 32, 32)), ("tiny", (1, 64, 0.6, 32, 32)), ("tiny", (2, 24, 1.2, 32, 32)),
           ("tiny", (3, 56, 0.5, 41, 27)), ("soak", 29), ("soak", 54), ("soak", 182)]

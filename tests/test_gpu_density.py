@@ -344,6 +344,49 @@ def test_edges():
     assert all(v == 0 for v in counts.values())
 
 
+# ---- past the thresholds of the scan and the fill --------------------------------------------------------------------------
+# k_density_scan: one workgroup of 1024 threads, ceil(nb / 1024) per-block counts per thread (nb = ceil(N / 256) blocks);
+# k_density_fill: min(nb, 1024) blocks of 256 pairs that stride over the fillable pairs.  Every case above has nb <= 157.
+SCAN_THREADS, ROWS_PER_BLOCK, FILL_BLOCKS = 1024, 256, 1024
+ALL_MULTI_FRAME = dict(densification_multi_frame_view_space_position_gradients_threshold=-1.0)    # every valid row a candidate
+
+
+def _scan_shape(N):
+    nb = -(-N // ROWS_PER_BLOCK)
+    return nb, -(-nb // SCAN_THREADS)
+
+
+def test_scan_with_two_block_counts_per_thread():
+    """1025 blocks, the last one of a single row: threads 0..511 sum two counts each, thread 512 one, the rest none"""
+    N = SCAN_THREADS * ROWS_PER_BLOCK + 1
+    scene, acc, hook = make_case(N=N, n_valid=200000, M=100000, seed=21)
+    nb, per = _scan_shape(N)
+    assert nb == 1025 > SCAN_THREADS and per == 2 and N % ROWS_PER_BLOCK == 1
+    counts, _ = assert_same_as_reference(scene, acc, hook, low_config(True))
+    print(counts)
+    assert counts["densify"] == counts["fillable"] > 0 and counts["floaters"] > 0 and counts["transparent"] > 0
+    assert counts["over"] > 0 and counts["under"] > 0
+
+
+@pytest.mark.parametrize("n_valid,truncated", [(360000, False), (450000, True)], ids=["every_candidate_filled", "more_candidates_than_free_rows"])
+def test_fill_past_one_trip_of_its_grid(n_valid, truncated):
+    """2735 blocks (three counts per scan thread) and more than 1024 x 256 fillable pairs: the fill grid strides a second time.
+    With 450 000 valid rows the candidates outnumber the free rows and the scene ends full."""
+    N = 700000
+    scene, acc, hook = make_case(N=N, n_valid=n_valid, M=150000, seed=21)
+    nb, per = _scan_shape(N)
+    assert nb == 2735 > SCAN_THREADS and per == 3
+    counts, _ = assert_same_as_reference(scene, acc, hook, low_config(True, **ALL_MULTI_FRAME))
+    print(counts)
+    assert counts["fillable"] > FILL_BLOCKS * ROWS_PER_BLOCK, counts
+    assert counts["floaters"] > 0 and counts["transparent"] > 0 and counts["over"] > 0 and counts["under"] > 0
+    assert counts["over"] + counts["under"] == counts["fillable"]
+    if truncated:
+        assert counts["densify"] > counts["fillable"] and counts["valid_after"] == N
+    else:
+        assert counts["densify"] == counts["fillable"] and counts["valid_after"] < N
+
+
 def test_reference_controller_test_basic():
     """T_CTRL:15-95 (GaussianPointAdaptiveControllerTest.test_basic) shortened: 32x32 image, 10 000 rows of which 1 000
     valid, the reference's wiring (backward_valid_point_hook=controller.update), FusedAdam, ~400 iterations."""

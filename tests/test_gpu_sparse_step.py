@@ -4,7 +4,9 @@ kernel, and the two wired together behind the operator (track_touched_rows).
 
 The compaction has one level: a single workgroup and one launch up to sparse.COMPACT_BLOCK in-camera points, a count launch
 and a scatter launch (every workgroup adds up the totals before it) beyond.  The 32x32 scenes and block_edges take the first
-shape, tiny-3000 (three workgroups, the last one partial) and dense_corner (26) the second; there is no further threshold."""
+shape, tiny-3000 (three workgroups, the last one partial) and dense_corner (26) the second.  Every scatter workgroup adds up the
+totals before it with a 256-thread strided loop, which takes a second trip beyond 256 workgroups: the large frame of
+parity_util (293), checked against the hook payload of the same backward because no CPU backward is needed for it."""
 import functools
 
 import numpy as np
@@ -127,6 +129,36 @@ def test_list_equals_the_oracles(name):
     assert np.array_equal(deep.last_touched_rows.tensor().cpu().numpy(), want)
     got = _raw_list(deep.last_frame)
     assert got[1] == count and np.array_equal(got[0], ids)
+
+
+def test_list_past_one_trip_of_the_sum_of_earlier_blocks():
+    s, q, t, partial = P.tiny_case(*P.LARGE_FRAME)
+    N = s.point_cloud.shape[0]
+    got = {}
+    module = P.module(partial, hook=lambda h: got.update(ids=h.point_id_in_camera_list.clone(), npix=h.num_affected_pixels.clone()))
+    module.track_touched_rows = True
+    inp = _fwd_bwd(module, s, q, t)
+    frame = module.last_frame
+    M = frame.n_points_in_camera
+    blocks = -(-M // sparse.COMPACT_BLOCK)
+    assert M > 262144 and blocks > 256, (M, blocks)
+    assert got["ids"].shape[0] == got["npix"].shape[0] == M
+    want = got["ids"][got["npix"] > 0].cpu().numpy()
+    print(f"N {N}, M {M}, touched {want.size}, compaction workgroups {blocks}")
+    assert 0 < want.size < M
+    assert bool((got["npix"][256 * sparse.COMPACT_BLOCK:] > 0).any())      # workgroups past the 256th own entries of the list
+    rows = module.last_touched_rows
+    assert rows.n_points == N and rows.max_count == M
+    assert np.array_equal(rows.tensor().cpu().numpy(), want)
+    ids, count = _raw_list(frame)
+    assert count == want.size
+    assert np.array_equal(ids[:count], want)
+    assert (ids[count:] == -1).all()                                     # nothing at or beyond the count is written
+    assert (np.diff(ids[:count]) > 0).all()                               # strictly ascending
+    out = np.setdiff1d(np.arange(N), want)
+    gp, gf = inp.point_cloud.grad.cpu().numpy(), inp.point_cloud_features.grad.cpu().numpy()
+    assert not gp[out].view(np.uint32).any() and not gf[out].view(np.uint32).any()
+    assert gf[want].any(axis=1).all()
 
 
 def _one_visible():

@@ -116,8 +116,8 @@ def blend(uv, conic_a, conic_b, conic_c, rescale, opacity, color, z, H, W, fwd, 
 
 
 def per_point(xyz, f, q_pts, t_pts, Kmat, live, stops):
-    """Everything the blend needs of each visible point (M rows): -> uv, (conic_a, conic_b, conic_c), opacity, colour, z and
-    the stops {"pc", "dir", "rescale"}.  live: J(p) and the SH view direction are differentiated (the pose mode); otherwise
+    """Everything the blend needs of each visible point (M rows): -> uv, (conic_a, conic_b, conic_c), opacity, colour, z,
+    the stops {"pc", "dir", "rescale"} and Sigma' = J W Sigma W^T J^T (M,2,2), the covariance before + 0.3 I.  live: J(p) and the SH view direction are differentiated (the pose mode); otherwise
     they are constants, recorded in the stops.  stops: None (record), or those of an earlier call (replay)."""
     # pose: inverse of (q_pc, t_pc), UTIL:426-432 (the conjugate is NOT renormalised for W, the rotation the kernels use)
     q_cp = torch.cat([-q_pts[:, :3], q_pts[:, 3:]], -1)
@@ -148,7 +148,7 @@ def per_point(xyz, f, q_pts, t_pts, Kmat, live, stops):
     origin = -(Wm.transpose(-1, -2) @ t_cp[..., None])[..., 0]
     Y = sh16(xyz - origin if live else rec.setdefault("dir", (xyz - origin).detach()))
     color = torch.sigmoid(torch.stack([(f[:, 8:24] * Y).sum(-1), (f[:, 24:40] * Y).sum(-1), (f[:, 40:56] * Y).sum(-1)], -1))
-    return uv, conics, torch.sigmoid(f[:, 7]), color, pcam[:, 2], rec
+    return uv, conics, torch.sigmoid(f[:, 7]), color, pcam[:, 2], rec, cov
 
 
 def _t(x):
@@ -168,7 +168,7 @@ def render(point_cloud, features, q_pc, t_pc, Kmat, H, W, fwd, object_id=None, s
     pose = wrt == "pose"
     q_pts = _t(np.asarray(q_pc, np.float64).reshape(-1, 4))[oid].clone().requires_grad_(pose)
     t_pts = _t(np.asarray(t_pc, np.float64).reshape(-1, 3))[oid].clone().requires_grad_(pose)
-    uv, conics, opacity, color, z, rec = per_point(point_cloud[ids], features[ids], q_pts, t_pts, _t(Kmat), pose, stops)
+    uv, conics, opacity, color, z, rec, _ = per_point(point_cloud[ids], features[ids], q_pts, t_pts, _t(Kmat), pose, stops)
     if uv.requires_grad:
         uv.retain_grad()
     image, depth, alpha, rec["blend"] = blend(uv, *conics, rec["rescale"], opacity, color, z, H, W, fwd, rec.get("blend"))
@@ -192,14 +192,41 @@ def point_gradients(scene, q, t, fwd, feat_after, g_image=None, g_depth=None, g_
     return grad(pc), grad(ft)
 
 
-def pose_gradients(scene, q, t, fwd, feat_after, g_image=None, g_depth=None, g_alpha=None):
-    """(grad_q (K,4), grad_t (K,3), summed_q (K,4), summed_t (K,3)) of the same loss, float64 numpy"""
-    K = np.asarray(q).reshape(-1, 4).shape[0]
-    aux = _backward(scene, q, t, fwd, feat_after, (g_image, g_depth, g_alpha), wrt="pose")
-    oid = aux["obj"]
+def _by_object(K, oid, leaves):
+    """per-point leaf gradients (q (M,4), t (M,3)) -> (grad_q, grad_t, summed_q, summed_t): their index_add by object and that of
+    their absolute values"""
     res = []
-    for leaf, w in ((aux["q_pts"], 4), (aux["t_pts"], 3)):
+    for leaf, w in zip(leaves, (4, 3)):
         g = leaf.grad if leaf.grad is not None else torch.zeros(oid.shape[0], w, dtype=F64)
         res.append(torch.zeros(K, w, dtype=F64).index_add_(0, oid, g).numpy())
         res.append(torch.zeros(K, w, dtype=F64).index_add_(0, oid, g.abs()).numpy())
     return res[0], res[2], res[1], res[3]
+
+
+def pose_gradients(scene, q, t, fwd, feat_after, g_image=None, g_depth=None, g_alpha=None):
+    """(grad_q (K,4), grad_t (K,3), summed_q (K,4), summed_t (K,3)) of the same loss, float64 numpy"""
+    aux = _backward(scene, q, t, fwd, feat_after, (g_image, g_depth, g_alpha), wrt="pose")
+    return _by_object(np.asarray(q).reshape(-1, 4).shape[0], aux["obj"], (aux["q_pts"], aux["t_pts"]))
+
+
+def pose_gradients_from_sums(scene, q, t, ids, feat_after, sums):
+    """The same four arrays from loop 1's per-splat sums instead of a blend: the float64 restatement of what k_pose.hip computes
+    from them, vectorised over the M in-camera points `ids` (no pixel loop, so any M).  sums (M,12) in the reference's scaling
+    (oracle.backward_sums): columns 0-1 dL/duv, 2-4 dL/dSigma' xx, xy, yy, 5-7 dL/dcolour, 11 dL/d depth (zero without a depth
+    upstream); they are constants of the surrogate
+        sum_m [ s0 u + s1 v + s2 Sigma'00 + 2 s3 Sigma'01 + s4 Sigma'11 + s5..7 . colour + s11 p_z ]
+    whose derivative with respect to the per-point pose leaves is each point's contribution.  A point whose sums are all zero
+    contributes exact zeros."""
+    ids = torch.as_tensor(np.asarray(ids).astype(np.int64))
+    s = _t(np.asarray(sums, np.float64).reshape(-1, 12))
+    assert s.shape[0] == ids.shape[0]
+    oid = torch.as_tensor(np.asarray(scene.point_object_id)).long()[ids]
+    q = np.asarray(q, np.float64).reshape(-1, 4)
+    q_pts = _t(q)[oid].clone().requires_grad_(True)
+    t_pts = _t(np.asarray(t, np.float64).reshape(-1, 3))[oid].clone().requires_grad_(True)
+    uv, _, _, color, z, _, cov = per_point(_t(scene.point_cloud)[ids], _t(feat_after)[ids], q_pts, t_pts,
+                                           _t(scene.camera_intrinsics), True, None)
+    surrogate = (s[:, 0:2] * uv).sum() + (s[:, 2] * cov[:, 0, 0] + 2.0 * s[:, 3] * cov[:, 0, 1] + s[:, 4] * cov[:, 1, 1]).sum() \
+        + (s[:, 5:8] * color).sum() + (s[:, 11] * z).sum()
+    surrogate.backward()
+    return _by_object(q.shape[0], oid, (q_pts, t_pts))
