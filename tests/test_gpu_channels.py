@@ -15,7 +15,8 @@ from taichi_3d_gaussian_splatting_amd.synthetic import CONFIGS, synth, view_pose
 
 pytestmark = pytest.mark.gpu
 
-CHANNELS = [1, 3, 4, 7, 16, 17, 64]
+# 17: a partial chunk at c0 = 0; 64: two full 32-wide chunks; 33 and 63: a partial chunk at c0 = 32
+CHANNELS = [1, 3, 4, 7, 16, 17, 33, 63, 64]
 
 
 def _scenes():
@@ -98,6 +99,53 @@ def test_backward_matches_the_reference(name):
         assert g.shape == (f.N, C)
         _assert_elementwise(g, d["ref"]["grad"][:, :C], d["ref"]["grad_abs"][:, :C], f"{name} backward C={C}")
         assert not g[outside].any()
+
+
+@functools.lru_cache(maxsize=None)
+def _kept(name):
+    s, q, t, partial, module, inp, outs = _frozen(name)
+    rng = np.random.default_rng(13)
+    V = rng.normal(0, 1, (s.point_cloud.shape[0], 64)).astype(np.float32)
+    G = rng.normal(0, 1, (s.height, s.width, 64)).astype(np.float32)
+    return s, module, module.last_frame, V, G
+
+
+@pytest.mark.parametrize("C", [3, 17, 33, 63])
+@pytest.mark.parametrize("name", ["tiny-3", "soak-54"])
+def test_raw_calls_write_their_outputs_and_nothing_around_them(name, C):
+    """`out` and `grad_values` inside larger sentinel-filled allocations, 67 floats of band on each side (so the outputs are
+    4-byte aligned and no more): the bands keep the sentinel, no element inside does, and the inside is render_channels' result
+    bit for bit.  tiny-3 is 41 x 27: its edge tiles hold pixels outside the image.
+
+    gs_channels_backward clears all of grad_values before its kernels run, so a chunk that was never summed leaves zeros, not
+    the sentinel, and render_channels would leave the same zeros.  Hence the second yardstick: the same columns rendered with
+    whole chunks only (4 channels for C = 3, 64 for the others, which share C's chunk width): a channel's arithmetic does not
+    depend on the channels beside it, so the first C columns of both directions are the same bits."""
+    from taichi_3d_gaussian_splatting_amd import _native
+    s, module, frame, V, G = _kept(name)
+    band, sentinel = 67, -1.2345678e30
+    v = _dev(V[:, :C]).requires_grad_(True)
+    g = _dev(G[..., :C])
+    want_out = module.render_channels(v, frame)
+    want_out.backward(g)
+    want = {"gs_channels_forward": want_out.detach(), "gs_channels_backward": v.grad}
+    assert want_out.abs().max() > 0 and v.grad.abs().max() > 0
+    whole = 4 if C <= 4 else 64
+    vw = _dev(V[:, :whole]).requires_grad_(True)
+    out_w = module.render_channels(vw, frame)
+    out_w.backward(_dev(G[..., :whole]))
+    P.assert_same_bits(want_out.detach(), out_w.detach()[..., :C].contiguous(), "forward against whole chunks")
+    P.assert_same_bits(v.grad, vw.grad[:, :C].contiguous(), "backward against whole chunks")
+    assert (v.grad != 0).any(dim=0).all(), "a channel without any gradient"
+    for entry, src in (("gs_channels_forward", v.detach()), ("gs_channels_backward", g)):
+        size = want[entry].numel()
+        buf = torch.full((size + 2 * band,), sentinel, dtype=torch.float32, device=P.DEV)
+        _native.call(entry, buf.device, frame._context.handle, frame.handle, src.data_ptr(), C, frame.last.data_ptr(),
+                     buf.data_ptr() + 4 * band)
+        assert (buf[:band] == sentinel).all() and (buf[-band:] == sentinel).all(), (entry, "wrote outside its output")
+        inside = buf[band:-band]
+        assert not (inside == sentinel).any(), (entry, int((inside == sentinel).sum()), "elements were not written")
+        P.assert_same_bits(inside.reshape(want[entry].shape), want[entry], entry)
 
 
 @pytest.mark.parametrize("name", ["tiny-3", "soak-54", "dense_corner", "cfg1"])

@@ -5,13 +5,16 @@ The mean 3-NN distance in f32 is within 1e-6 relative of float64 on the same f32
 three squares, the two sums, the square root, the two sums of the mean and the division is about 6 * 2^-24 = 3.6e-7, and
 picking another neighbour among near-ties moves the value by no more than that.  Where the k + 1 smallest float64 distances
 of a row (itself and its k neighbours) are distinct beyond 1e-6 relative, and the k-th neighbour's from the one behind it,
-the neighbours are cKDTree's."""
+the neighbours are cKDTree's.
+
+Without scipy: what the reference says about pairs at +inf, on a case small enough to read; torch_knn, the same brute force in
+torch (the yardstick of the GPU tests at sizes numpy cannot cover row by row), equal to it bit for bit on every cloud and mask
+the k-NN tests use; and the rows= form equal to the same rows of the full result."""
 import numpy as np
 import pytest
+import torch
 
 import knn_ref
-
-scipy_spatial = pytest.importorskip("scipy.spatial", reason="scipy is the yardstick here")
 
 CLOUDS = knn_ref.clouds()
 K = 3
@@ -19,6 +22,7 @@ K = 3
 
 @pytest.fixture(scope="module")
 def results():
+    scipy_spatial = pytest.importorskip("scipy.spatial", reason="scipy is the yardstick here")
     out = {}
     for name, x in CLOUDS.items():
         x64 = x.astype(np.float64)
@@ -71,3 +75,68 @@ def test_reference_semantics_on_a_case_small_enough_to_read():
     assert idx.tolist() == [[2, 1, 3, -1], [0, 2, 3, -1], [0, 1, 3, -1], [0, 2, 1, -1], [-1] * 4, [-1] * 4]
     assert d2[0].tolist() == [0.0, 1.0, 4.0, np.inf] and d2[3].tolist() == [4.0, 4.0, 5.0, np.inf]
     assert np.isinf(d2[4:]).all()
+
+
+def test_pairs_at_infinity_on_a_case_small_enough_to_read():
+    """Row 0 has two finite pairs, then two at +inf that come with their rows, the smaller row first, then the -1 tail: five
+    rows take part, so four others answer and k = 6 leaves two places empty.  Rows 3 and 4 are at +inf from everything,
+    each other included (their difference overflows before it is squared)."""
+    inf, big = np.inf, 3e38
+    x = np.array([[0, 0, 0], [1, 0, 0], [0, 2, 0], [big, 0, 0], [-big, big, 0], [7, 7, 7], [0, np.inf, 0]], np.float32)
+    mask = np.array([0, 0, 0, 0, 0, 1, 0], np.int8)
+    d2, idx = knn_ref.knn(x, 6, mask)
+    assert not np.isnan(d2).any()
+    assert idx.tolist() == [[1, 2, 3, 4, -1, -1], [0, 2, 3, 4, -1, -1], [0, 1, 3, 4, -1, -1], [0, 1, 2, 4, -1, -1],
+                            [0, 1, 2, 3, -1, -1], [-1] * 6, [-1] * 6]
+    assert d2.tolist() == [[1, 4, inf, inf, inf, inf], [1, 5, inf, inf, inf, inf], [4, 5, inf, inf, inf, inf], [inf] * 6, [inf] * 6,
+                           [inf] * 6, [inf] * 6]
+    # k below the number of pairs: a pair at +inf is the last one chosen, never NaN, never the row itself
+    d2, idx = knn_ref.knn(x, 3, mask)
+    assert idx[:5].tolist() == [[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2], [0, 1, 2]] and d2[0].tolist() == [1, 4, inf]
+
+
+def _cases():
+    named = {**{n: (lambda c=c: c) for n, c in CLOUDS.items()}, **knn_ref.EXTRA}
+    del named["big_clusters"]                    # 65 537 rows: on the GPU only, against a sample of numpy rows
+    out = [(n, None) for n in named]
+    return out + [("overflow", "fifth")] + [("uniform", m) for m in ("third", "all", "garbage", "nan_row")], named
+
+
+CASES, NAMED = _cases()
+
+
+@pytest.fixture(scope="module")
+def full():
+    """k = 8 by numpy, once per (cloud, mask)"""
+    cache = {}
+
+    def get(name, mask_name):
+        if (name, mask_name) not in cache:
+            x, mask = knn_ref.masked(NAMED[name](), mask_name)
+            cache[name, mask_name] = (x, mask, knn_ref.knn(x, 8, mask))
+        return cache[name, mask_name]
+    return get
+
+
+@pytest.mark.parametrize("name,mask_name", CASES)
+def test_torch_knn_equals_the_numpy_reference_bit_for_bit(full, name, mask_name):
+    x, mask, (d2, idx) = full(name, mask_name)
+    assert not np.isnan(d2).any()
+    for k in (8, 3):
+        td2, tidx = knn_ref.torch_knn(torch.from_numpy(x), k, None if mask is None else torch.from_numpy(mask),
+                                      chunk=2048 if k == 8 else 1000)
+        assert td2.dtype == torch.float32 and tidx.dtype == torch.int32 and td2.shape == tidx.shape == (len(x), k)
+        assert np.array_equal(td2.numpy().view(np.uint32), d2[:, :k].view(np.uint32)), (name, mask_name, k)
+        assert np.array_equal(tidx.numpy(), idx[:, :k]), (name, mask_name, k)
+
+
+@pytest.mark.parametrize("name,mask_name", [("uniform", "garbage"), ("overflow", "fifth"), ("copies", None), ("clusters", None)])
+def test_chosen_rows_equal_the_same_rows_of_the_full_result(full, name, mask_name):
+    x, mask, (d2, idx) = full(name, mask_name)
+    rows = np.random.default_rng(3).permutation(len(x))[:97]             # unordered, masked rows among them
+    rows = np.concatenate([rows, rows[:2], [0, len(x) - 1]])             # ... and a row may be asked for twice
+    rd2, ridx = knn_ref.knn(x, 8, mask, rows=rows, chunk=40)
+    assert rd2.shape == ridx.shape == (len(rows), 8)
+    assert np.array_equal(rd2.view(np.uint32), d2[rows].view(np.uint32)) and np.array_equal(ridx, idx[rows])
+    empty = knn_ref.knn(x, 8, mask, rows=np.zeros(0, np.int64))
+    assert empty[0].shape == empty[1].shape == (0, 8)
