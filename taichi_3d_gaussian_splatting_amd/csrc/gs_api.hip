@@ -612,8 +612,8 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
 //
 // The reference stops twice per forward to learn M and K on the host (RAST:870, 916-931).  Here the host needs them only to
 // size buffers and grids, so in steady state it does not stop in the middle at all: binning, sort and blend are queued at
-// once on PREDICTED sizes -- pair capacity = what the last frame of this ctx needed + 25 %, key width from the last frame's
-// depth-code range + 25 % -- and the hand-over is read AFTER the last launch,
+// once on PREDICTED sizes -- pair capacity = what the last frame of this ctx needed + 25 %, key width from the depth-code range
+// + 25 % of the last frame that had a point in camera -- and the hand-over is read AFTER the last launch,
 // when the GPU has the whole forward in its queue instead of nothing.  The kernels read the real pair count on the device and
 // never leave the predicted capacity, so a wrong prediction is harmless: the host sees it in the counters (K beyond the
 // capacity, or depth codes wider than the key field), grows the buffers and queues the per-pixel half again with the exact
@@ -659,7 +659,10 @@ static int run_forward_tail(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
         }
         if ((rc = run_raster_stage(c, f, pa, n_rows, hc.M, hc.K, bits, cfg, out, s, false)) != GS_OK) return rc;
     }
-    c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = hc.K; c->seen.max_code = hc.max_depth_code;
+    // (a frame with no point in camera says nothing about the depth range: the key width of the last frame that had one stays
+    // the prediction, or the frame after an empty view would always be rendered twice)
+    if (!(c->seen.valid && c->seen.H == H && c->seen.W == W && hc.M == 0)) c->seen.max_code = hc.max_depth_code;
+    c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = hc.K;
     *M_out = hc.M; *K_out = hc.K;
     return GS_OK;
 }

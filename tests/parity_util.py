@@ -333,3 +333,216 @@ def soak_case(seed):
     q = np.array([[ang[0], ang[1], ang[2], 1.0]], np.float32) * float(rng.uniform(0.5, 2.0))    # deliberately not unit
     t = rng.normal(0, 0.3, (1, 3)).astype(np.float32)
     return dict(scene=s, q=q, t=t, band=band, partial=partial, rng=rng, W=W, H=H, n=n, sigma0=sigma0)
+
+
+# ---- frames built from projected records, and frames whose predicted sizes did not hold -----------------------------------
+# (tests/test_oracle_stages_host.py, test_gpu_records_frames.py, test_gpu_sizing_redo.py)
+RECORD_COUNTS = (1, 255, 256, 257, 513)      # one record; a block of k_boxes_from_records / records-mode k_keygen less one, full, plus one; two blocks plus one
+SHARD_CUTS = (0, 1, 300, 300, 1500)          # a single-row shard, an empty shard in the middle
+RASTER_EXPORTS = ("sort_key", "point_offset_with_sort_key", "tile_points_start", "tile_points_end", "num_overlap_tiles")
+
+
+def records_scene():
+    """1500 points at 96x64, all in camera under view_pose(): the scene of the block-tail and shard cases"""
+    return synth(1500, 96, 64, 0.08, seed=7)
+
+
+def clustered_cut_scene():
+    """3000 clustered points at 64x64: the oracle gives 4 lists over 512 entries, the longest 1030 (cut records, heavy tiles)"""
+    from taichi_3d_gaussian_splatting_amd.synthetic import synth_clustered
+    return synth_clustered(3000, 64, 64, 0.05, sh_deg=3, seed=4)
+
+
+def giant_scene(n, width, height, giants=4):
+    """synth(n, width, height, 0.05, seed=3) whose first `giants` splats are faint and far larger than the image: the box of each
+    is every tile"""
+    s = synth(n, width, height, 0.05, seed=3)
+    s.point_cloud_features[:giants, 4:7] = np.log(3.0)
+    s.point_cloud_features[:giants, 7] = -3.0                  # faint: everything behind them still counts
+    return s
+
+
+def shard_of(scene, lo, hi):
+    """Rows lo..hi of a scene (views of its arrays)"""
+    import copy
+    sub = copy.copy(scene)
+    sub.point_cloud, sub.point_cloud_features = scene.point_cloud[lo:hi], scene.point_cloud_features[lo:hi]
+    sub.point_invalid_mask, sub.point_object_id = scene.point_invalid_mask[lo:hi], scene.point_object_id[lo:hi]
+    return sub
+
+
+def only_points(scene, ids):
+    """The scene with every row but `ids` marked invalid (a copy of the mask; the other arrays are shared)"""
+    import copy
+    sub = copy.copy(scene)
+    sub.point_invalid_mask = np.ones_like(scene.point_invalid_mask)
+    sub.point_invalid_mask[np.asarray(ids, np.int64)] = 0
+    return sub
+
+
+def oracle_config(partial=False, **kw):
+    return oracle.default_config(allow_partial_tiles=int(bool(partial)), **kw)
+
+
+FORWARD_PRODUCTS = ("rasterized_image", "rasterized_depth", "pixel_accumulated_alpha", "pixel_offset_of_last_effective_point",
+                    "pixel_valid_point_count")
+
+
+class Run(dict):
+    """The products of one forward + backward, by name, as attributes"""
+    __getattr__ = dict.__getitem__
+
+
+def run_monolithic(mod, scene, q, t, band, g_fn):
+    """Forward and backward of the operator `mod` -> Run: the five forward products, the raster exports, both gradients, the
+    frame's sizing; all numpy but `inp`, `outs`, `g` and `frame`"""
+    inp = make_input(scene, q, t, band)
+    image, depth, count = mod(inp)
+    fr = mod.last_frame
+    r = Run(inp=inp, frame=fr, sizing=fr.sizing, outs=(image, depth, count), sort_key_bits=fr.sort_key_bits, n_keys=fr.n_keys,
+            n_points_in_camera=fr.n_points_in_camera)
+    lo = mod.last_forward_outputs
+    for name, x in zip(FORWARD_PRODUCTS, (image, depth, lo["pixel_accumulated_alpha"], lo["pixel_offset_of_last_effective_point"], count)):
+        r[name] = x.detach().cpu().numpy().copy()
+    for name in RASTER_EXPORTS:
+        r[name] = fr.export(name).cpu().numpy()
+    r["g"] = g_fn(image.detach())
+    image.backward(r["g"])
+    r["grad_pointcloud"] = inp.point_cloud.grad.cpu().numpy().copy()
+    r["grad_pointcloud_features"] = inp.point_cloud_features.grad.cpu().numpy().copy()
+    return r
+
+
+def run_staged(st, scene, cuts, q, t, band, g_fn, records_prefix=None, second_backward=False):
+    """project_shard of every shard lo..hi of `cuts` -> forward_projected of the concatenated records -> backward_projected ->
+    backward_shard of every shard, on the StagedRasteriser `st` -> Run with run_monolithic's names plus the staged path's own:
+    the magnitude image, the (N,2) / (N) / (M) extras put side by side in shard order, the global ids of the records, the (M,12)
+    sums as the library scales them and the opacity of every record.
+    records_prefix = (whole_scene, m): forward_projected gets the first m records of whole_scene's projection instead, which
+    must be the bits of `scene`'s own records (scene = whole_scene with every other point invalid)."""
+    shards, ids_all = [], []
+    if records_prefix is not None:                                    # (first, and kept: a frame slot of its own to the end)
+        rec_whole, _, fr_whole = st.project_shard(make_input(records_prefix[0], q, t, band, requires_grad=False))
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        sinp = make_input(shard_of(scene, lo, hi), q, t, band, requires_grad=False)
+        rec, ids, frame = st.project_shard(sinp)
+        assert rec.shape == (frame.n_points_in_camera, 16) and ids.shape == (frame.n_points_in_camera,)
+        assert bool((ids[1:] > ids[:-1]).all())
+        shards.append((sinp, rec, frame))
+        ids_all.append(ids.cpu().numpy().astype(np.int64) + lo)
+    records = torch.cat([sh[1] for sh in shards]).contiguous()        # shard-major = ascending global point id
+    if records_prefix is not None:
+        m = records_prefix[1]
+        assert records.shape[0] == m
+        assert_same_bits(rec_whole[:m], records, "the first m records of the whole scene")
+        records = rec_whole[:m].contiguous()
+    outs, rframe = st.forward_projected(records, shards[0][0].camera_info)
+    r = Run(frame=rframe, sizing=rframe.sizing, sort_key_bits=rframe.sort_key_bits, n_keys=rframe.n_keys,
+            n_points_in_camera=rframe.n_points_in_camera, ids=np.concatenate(ids_all), records=records.cpu().numpy())
+    assert rframe.n_points_in_camera == records.shape[0]
+    for name in FORWARD_PRODUCTS:
+        r[name] = getattr(outs, name).cpu().numpy().copy()
+    for name in RASTER_EXPORTS:
+        r[name] = rframe.export(name).cpu().numpy()
+    r["point_alpha_after_activation"] = rframe.export("point_alpha_after_activation").cpu().numpy()
+    r["g"] = g_fn(outs.rasterized_image)
+    sums, mag_img = st.backward_projected(rframe, outs, r["g"], want_magnitude_image=True)
+    assert sums.shape == (records.shape[0], 12)
+    r["heavy_tiles"] = rframe.heavy_tiles()
+    if second_backward:                                               # through the same kept frame: the same bits again
+        sums2, mag2 = st.backward_projected(rframe, outs, r["g"], want_magnitude_image=True)
+        assert_same_bits(sums2, sums, "sums of a second backward")
+        assert_same_bits(mag2, mag_img, "magnitude image of a second backward")
+    r["sums"], r["magnitude_grad_viewspace_on_image"] = sums.cpu().numpy(), mag_img.cpu().numpy()
+    parts, off = [], 0
+    for sinp, rec, frame in shards:
+        m = rec.shape[0]
+        parts.append(st.backward_shard(frame, sinp, sums[off:off + m].contiguous(), want_extras=True))
+        off += m
+    assert off == records.shape[0]
+    cat = lambda name: torch.cat([getattr(p, name) for p in parts]).cpu().numpy()
+    for name in ("grad_pointcloud", "grad_pointcloud_features", "grad_viewspace", "magnitude_grad_viewspace", "num_affected_pixels"):
+        r[name] = cat(name)
+    r["shard_frames"] = [sh[2] for sh in shards] + ([fr_whole] if records_prefix is not None else [])
+    return r
+
+
+FRAME_PRODUCTS = FORWARD_PRODUCTS + RASTER_EXPORTS + ("grad_pointcloud", "grad_pointcloud_features")
+
+
+def assert_same_frame(a, b, what=""):
+    """Two Runs agree bit for bit in the forward products, the raster exports and both gradients"""
+    for name in FRAME_PRODUCTS:
+        assert a[name].shape == b[name].shape, (what, name, a[name].shape, b[name].shape)
+        assert_same_bits(a[name], b[name], (what, name))
+
+
+def assert_staged_equals_monolithic(staged, mono, hook, extras):
+    """run_staged against run_monolithic on the same points, bit for bit: assert_same_frame, and the staged path's magnitude image
+    and extras against what the operator's hook delivered (`hook`: the BackwardValidPointHookInput, per in-camera point) and
+    against the operator's last_backward_extras (`extras`: per point of the scene)"""
+    assert staged.n_keys == mono.n_keys and staged.n_points_in_camera == mono.n_points_in_camera
+    assert_same_frame(staged, mono, "staged against monolithic")
+    ids = staged.ids
+    assert np.array_equal(ids, hook.point_id_in_camera_list.cpu().numpy())
+    assert_same_bits(staged.magnitude_grad_viewspace_on_image, hook.magnitude_grad_viewspace_on_image, "magnitude image")
+    assert_same_bits(staged.grad_viewspace[ids], hook.grad_viewspace, "hook grad_viewspace")
+    assert_same_bits(staged.magnitude_grad_viewspace[ids], hook.magnitude_grad_viewspace, "hook magnitude_grad_viewspace")
+    assert_same_bits(staged.num_affected_pixels, hook.num_affected_pixels, "hook num_affected_pixels")
+    assert_same_bits(staged.num_overlap_tiles, hook.num_overlap_tiles, "hook num_overlap_tiles")
+    assert_same_bits(staged.grad_viewspace, extras["grad_viewspace"], "grad_viewspace of every point")
+    assert_same_bits(staged.magnitude_grad_viewspace, extras["magnitude_grad_viewspace"], "magnitude_grad_viewspace of every point")
+    assert_same_bits(staged.num_affected_pixels, extras["num_affected_pixels"], "num_affected_pixels")
+
+
+def leave_stale_frames(st, scene, q, t, n_frames, band=3):
+    """What a StagedRasteriser's frame slots hold after other work: the dense `scene` projected, rendered from its records and
+    back-propagated in n_frames kept raster frames, then everything released -- the next n_frames + 1 frames of `st` get buffers
+    whose tile arrays, cut records and flags are that scene's, not fresh zeros"""
+    sinp = make_input(scene, q, t, band, requires_grad=False)
+    rec, ids, pframe = st.project_shard(sinp)
+    assert rec.shape[0] > 0
+    kept = []
+    for _ in range(n_frames):
+        outs, rframe = st.forward_projected(rec.contiguous(), sinp.camera_info)
+        assert rframe.n_keys > 0
+        sums, _ = st.backward_projected(rframe, outs, 2.0 * (outs.rasterized_image - 0.5), want_magnitude_image=True)
+        kept.append(rframe)
+    st.backward_shard(pframe, sinp, sums)
+    torch.cuda.synchronize()
+    for fr in kept + [pframe]:
+        fr.release()
+
+
+SUM_GROUPS = [(0, 2, "uv"), (2, 5, "cov"), (5, 8, "colour"), (8, 9, "opacity"), (9, 10, "magnitude")]
+
+
+def sums_in_reference_scaling(sums, alpha):
+    """(M,12) sums of backward_projected -> float64 in the scaling of oracle.backward_sums: loop 1 of the library leaves the
+    per-splat factors to the per-point kernel (k_backward.hip: opacity on columns 0, 1 and 9, opacity / 2 on 2..4,
+    (1 - opacity) opacity on 8).  Column 10 (the pixel count, integer bits) and 11 (the depth column, not written without a depth
+    upstream) are left out: zeros"""
+    s = np.asarray(sums).astype(np.float64)
+    a = np.asarray(alpha).astype(np.float64)[:, None]
+    s[:, [0, 1, 9]] *= a
+    s[:, 2:5] *= 0.5 * a
+    s[:, 8:9] *= (1.0 - a) * a
+    s[:, 10:12] = 0.0
+    return s
+
+
+def assert_sums_parity(sums, alpha, f, g_image):
+    """backward_projected's (M,12) sums against oracle.backward_sums of the oracle frame `f` (of the same records): GRAD_TOL on
+    rel_err per column group, the pixel counts exactly -> the worst rel_err"""
+    ref, _ = oracle.backward_sums(f, g_image)
+    assert ref.shape == np.asarray(sums).shape
+    got = sums_in_reference_scaling(sums, alpha)
+    assert np.array_equal(np.ascontiguousarray(sums[:, 10]).view(np.int32), np.ascontiguousarray(ref[:, 10]).view(np.int32)), "pixel counts"
+    worst = 0.0
+    for lo, hi, name in SUM_GROUPS:
+        e = rel_err(got[:, lo:hi], ref[:, lo:hi].astype(np.float64))
+        print(f"sums against oracle.backward_sums, {name}: max |a - ref| / max |ref| = {e:.3g} (bar {GRAD_TOL})")
+        assert np.abs(ref[:, lo:hi]).max() > 0, name
+        assert e < GRAD_TOL, (name, e)
+        worst = max(worst, e)
+    return worst

@@ -49,8 +49,13 @@ def test_staged_path_equals_monolithic_bit_for_bit(P, n_shards):
     s.point_invalid_mask[np.random.default_rng(2).random(9001) < 0.05] = 1
     q, t = view_pose(1, 4)
     g_fn = lambda img: 2.0 * (img - 0.3)
-    module, inp, (image, depth, count), g = _monolithic(P, s, q, t, 2, g_fn)
+    hooked = []
+    module = P.module(hook=hooked.append)                                 # the hook's payload is what the staged extras must equal
+    inp = P.make_input(s, q, t, 2)
+    image, depth, count = module(inp)
+    image.backward(g_fn(image.detach()))
     ref_pc, ref_ft = inp.point_cloud.grad, inp.point_cloud_features.grad
+    hook, extras = hooked[0], module.last_backward_extras
 
     st = StagedRasteriser()
     bounds = np.linspace(0, 9001, n_shards + 1).astype(int)
@@ -69,13 +74,24 @@ def test_staged_path_equals_monolithic_bit_for_bit(P, n_shards):
     assert rframe.n_keys == module.last_frame.n_keys
     sums, mag_img = st.backward_projected(rframe, outs, g_fn(outs.rasterized_image), want_magnitude_image=True)
     assert sums.shape == (records.shape[0], 12)
+    assert mag_img.shape == (192, 320, 2) and bool(mag_img.any())
+    assert np.array_equal(_bits(mag_img), _bits(hook.magnitude_grad_viewspace_on_image))
     off = 0
     for (sinp, rec, ids, frame), lo, hi in zip(shards, bounds[:-1], bounds[1:]):
         m = rec.shape[0]
         gr = st.backward_shard(frame, sinp, sums[off:off + m], want_extras=True)
-        off += m
         assert np.array_equal(_bits(gr.grad_pointcloud), _bits(ref_pc[lo:hi]))
         assert np.array_equal(_bits(gr.grad_pointcloud_features), _bits(ref_ft[lo:hi]))
+        # the three extras: per point of the shard against the operator's arrays, per in-camera point against the hook's payload
+        assert gr.grad_viewspace.shape == (hi - lo, 2) and gr.magnitude_grad_viewspace.shape == (hi - lo,) and gr.num_affected_pixels.shape == (m,)
+        assert np.array_equal(_bits(gr.grad_viewspace), _bits(extras["grad_viewspace"][lo:hi]))
+        assert np.array_equal(_bits(gr.magnitude_grad_viewspace), _bits(extras["magnitude_grad_viewspace"][lo:hi]))
+        assert np.array_equal(_bits(gr.grad_viewspace[ids.long()]), _bits(hook.grad_viewspace[off:off + m]))
+        assert np.array_equal(_bits(gr.magnitude_grad_viewspace[ids.long()]), _bits(hook.magnitude_grad_viewspace[off:off + m]))
+        assert np.array_equal(gr.num_affected_pixels.cpu().numpy(), hook.num_affected_pixels[off:off + m].cpu().numpy())
+        assert np.array_equal(ids.cpu().numpy() + lo, hook.point_id_in_camera_list[off:off + m].cpu().numpy())
+        off += m
+    assert off == records.shape[0] and bool(hook.num_affected_pixels.any()) and bool(hook.magnitude_grad_viewspace.any())
     # a projection-only frame exports the per-point arrays, but not the raster stage
     assert shards[0][3].export("point_uv").shape[1] == 2
     with pytest.raises(RuntimeError):
