@@ -128,6 +128,10 @@ struct gs_ctx {
     int transient = -1;                 // slot of the frame of the last keep_for_backward == 0 call
     // scratch shared by all frames (stream ordered)
     DevBuf block_counts, block_offsets, tile_block_sums, hist, scan_tmp, counters, partial, visited, zero_row, sums, loss_ws;
+    // the per-point stage's [digit][block] pair counts + their row scans (k_project.hip: gs_bin_digits_*; k_binning.hip: k_keygen's first
+    // pass).  Written by the frame's per-point kernel, read by every binning of the SAME call (the second one of a re-sized frame too):
+    // nothing else touches it, and the K-sized hist of the later passes is a buffer of its own
+    DevBuf first_hist;
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
@@ -193,7 +197,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
-    DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp,
+    DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp, &c->first_hist,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree };
@@ -448,6 +452,22 @@ static int check_forward_out(const gs_forward_out* out, const gs_config* cfg, in
     return GS_OK;
 }
 
+// The sort's first radix pass inside k_keygen (k_binning.hip), for a per-point stage over `rows` rows: the default up to
+// GS_FIRST_PASS_MAX_BLOCKS blocks of 256 rows.  Measured on both sides of the cap (profiles/sort_first_pass_ab.json):
+// at 1954 blocks (cfg3_headline, 12.9 pairs per point) the pass saves 30 us of a 640 us step; at 7813 blocks (cfg5_infer2e6, two
+// million small splats, 3 to 4 pairs per point, a 16 MB table) k_keygen's short runs, k_project's strided stores and the longer row
+// scan cost what the pass saves, and the frame lost 4.7 fps at a parent spread of 3.4: above the cap the three-kernel pass runs.
+// Nothing was measured between the two sizes; the cap is the power of two between them.  GS_SORT_FIRST_PASS=0 keeps the three-kernel
+// pass everywhere; read on every call, so that one process can compare both.  The table (2 KB per 256 rows) is written whether or
+// not the frame's keys turn out to have the 8 depth bits the pass needs (the width is known only afterwards).
+#define GS_FIRST_PASS_MAX_BLOCKS 4096
+static bool sort_first_pass_enabled(int64_t rows)
+{
+    if ((rows + 255) / 256 > GS_FIRST_PASS_MAX_BLOCKS) return false;
+    const char* e = getenv("GS_SORT_FIRST_PASS");
+    return !(e && e[0] == '0');
+}
+
 // ---- per-point half: filter, compaction, projection (+ tile counts, scan, publication) ----------------------------
 // On success the frame's buffers hold mask / ids / cam_index / records / box / ntiles.  The counters (M, K, depth-code range,
 // bad object ids) are handed over through pinned memory; `wait` says when the host reads them:
@@ -473,6 +493,10 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
                        NEED(c->block_counts, 4 * (nb + 1)), NEED(c->block_offsets, 4 * (nb + 1)),
                        NEED(c->tile_block_sums, 4 * (nb + 1)) });
     if (rc != GS_OK) return rc;
+    // the digit table only for a call that goes on to bin these points (gs_forward, the one caller that waits later): the shard entry
+    // points hand records out, and whoever renders them has k_boxes_from_records build the table over ITS blocks
+    const bool first_pass = wait == WAIT_LATER && sort_first_pass_enabled(N);
+    if (first_pass && (rc = grow(c, { NEED(c->first_hist, 4 * gs_first_hist_elems(N)) })) != GS_OK) return rc;
     f->n_objects = cam->n_objects;
 
     GsProjectArgs pa{};
@@ -484,6 +508,7 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     pa.v = frame_view(*f);
     pa.block_counts = c->block_counts.as<int32_t>(); pa.block_offsets = c->block_offsets.as<int32_t>();
     pa.tile_block_sums = c->tile_block_sums.as<uint32_t>();
+    pa.first_hist = first_pass ? c->first_hist.as<uint32_t>() : nullptr;
     pa.counters = c->counters.as<GsCounters>();
     int slot = 0;
     if (wait == WAIT_FRAME && N > 0) {
@@ -522,11 +547,14 @@ static int run_records_stage(gs_ctx* c, Frame* f, const float* records, int64_t 
                              NEED(B.tile_start, 4 * GS_TILE_INTS(T)), NEED(B.tile_order, 4 * GS_ORDER_INTS(T)),
                              NEED(c->tile_block_sums, 4 * (nb + 1)) });
     if (rc != GS_OK) return rc;
+    const bool first_pass = sort_first_pass_enabled(m);
+    if (first_pass) if (const int rc2 = grow(c, { NEED(c->first_hist, 4 * gs_first_hist_elems(m)) })) return rc2;
     if (m > 0) HIP_TRY(hipMemcpyAsync(B.rec.p, records, (size_t)m * 64, hipMemcpyDeviceToDevice, s));
     GsProjectArgs pa{};
     pa.prof = &c->prof; pa.N = m; pa.H = f->info.camera_height; pa.W = f->info.camera_width; pa.depth_scale = cfg->depth_to_sort_key_scale;
     pa.v = frame_view(*f);
     pa.tile_block_sums = c->tile_block_sums.as<uint32_t>();
+    pa.first_hist = first_pass ? c->first_hist.as<uint32_t>() : nullptr;
     pa.counters = c->counters.as<GsCounters>();
     pa.host_mirror = c->host_counters_dev; pa.ticket = ++c->ticket;
     if (c->ticket == 0x7fffffff) c->ticket = 0;
@@ -584,6 +612,7 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     ba.keys_a = B.keys_a.p; ba.keys_b = B.keys_b.p; ba.key64 = key64;
     ba.vals_a = B.vals_a.as<int32_t>(); ba.vals_b = B.vals_b.as<int32_t>();
     ba.hist = c->hist.as<uint32_t>(); ba.scan_tmp = c->scan_tmp.as<uint32_t>();
+    ba.first_hist = depth_bits >= 8 ? pa.first_hist : nullptr;      // below 8 depth bits digit 0 holds tile bits: the full-pass loop
     ba.keys_sorted = &f->keys_sorted; ba.vals_sorted = &f->vals_sorted;
     gs_launch_binning(ba, s);
     HIP_TRY(hipGetLastError());

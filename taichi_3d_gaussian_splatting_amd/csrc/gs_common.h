@@ -357,6 +357,9 @@ struct GsProjectArgs {
     int H, W; float near_plane, far_plane, depth_scale;
     GsFrameView v;                              // written: pose, mask, ids, cam_index, records, box, ntiles, depth codes; tile arrays cleared before the binning
     int32_t* block_counts; int32_t* block_offsets; uint32_t* tile_block_sums;
+    // (256, blocks) pair counts per low byte of the depth code and block of this stage, with room for the scanned table behind it
+    // (gs_first_hist_elems), or NULL: the sort's first radix pass as k_keygen does it (k_binning.hip)
+    uint32_t* first_hist;
     GsCounters* counters;
     GsCounters* host_mirror; int32_t ticket;    // pinned host copy of the counters; .reserved = ticket once they are valid
 };
@@ -379,11 +382,15 @@ struct GsBinArgs {
     void *keys_a, *keys_b; int32_t *vals_a, *vals_b;       // ping-pong (K); keys are u32, or u64 when key64
     int key64;                                             // depth bits + tile bits > 32
     uint32_t* hist;                             // (256 * sort_blocks) + scratch
+    // the per-point stage's digit table (GsProjectArgs::first_hist) when k_keygen is to do the first radix pass itself, or NULL: the
+    // host's decision (gs_api.hip: run_raster_stage); taken only where depth_bits >= 8
+    uint32_t* first_hist;
     uint32_t* scan_tmp;                         // GS_SORT_DIGITS digit totals of the current pass
     void** keys_sorted; int32_t** vals_sorted;       // out: which of a/b holds the result
 };
 void gs_launch_binning(const GsBinArgs& a, hipStream_t s);
 size_t gs_sort_hist_elems(uint32_t K);
+size_t gs_first_hist_elems(int64_t rows);        // words of first_hist for a per-point stage over `rows` rows: raw + scanned
 #define GS_SORT_DIGITS 256          // words of scan_tmp: one row total per digit (k_binning.hip: k_sort_rowscan)
 
 struct GsBlendFwdArgs {

@@ -17,6 +17,25 @@
 #endif
 #define SORT_TILE (256 * SORT_ROUNDS)          // keys per tile: 256 threads x SORT_ROUNDS
 
+// The lanes of a wave that hold the same 8-bit digit as this one, among those of `among`, as two 32-bit halves per lane: per bit one
+// vote, then same &= ~(vote ^ m) with m = all ones where the lane's bit is set (v_bfe_i32, v_xnor_b32, v_and_b32 per half).  A lane's
+// rank among its equals is the population count of the halves below it (k_sort_scatter per round; k_keygen's first pass once).
+__device__ __forceinline__ void gs_match_digit(uint32_t d, unsigned long long among, uint32_t& slo, uint32_t& shi)
+{
+    slo = (uint32_t)among; shi = (uint32_t)(among >> 32);
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+        const int32_t mb = (int32_t)(d << (31 - bit)) >> 31;
+        const unsigned long long bal = gs_ballot(mb < 0);
+        slo &= ~((uint32_t)bal ^ (uint32_t)mb);
+        shi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)mb);
+    }
+}
+__device__ __forceinline__ uint32_t gs_match_rank(uint32_t slo, uint32_t shi, unsigned long long lt_mask)
+{
+    return (uint32_t)__popc(slo & (uint32_t)lt_mask) + (uint32_t)__popc(shi & (uint32_t)(lt_mask >> 32));
+}
+
 // One lane per PAIR, not per point: a block scans its 256 points' tile counts, keeps {first pair, tile box, depth code} of
 // every point in a small LDS table, and then walks the BLOCK's pairs e = 0, 1, 2 ... 256 at a time -- a thread finds the
 // point that owns pair e (binary search over the 256 scanned counts), derives the tile from the pair's position in that
@@ -25,7 +44,17 @@
 // are; a splat covering thousands of tiles is simply many iterations in which all threads find the same owner -- shared by the
 // block's four waves (walked by its own wave alone, one background splat over the whole image was 120 iterations of one wave
 // against 8 for the others: k_keygen 51 us on the clustered workload with fewer pairs than the uniform one's 22 us).
-template <typename KeyT>
+//
+// FIRST_PASS: the sort's pass over digit 0 of the key, done here.  With depth_bits >= 8 that digit is the low byte of the depth code, the
+// same for all pairs of a point, and a stable pass over it moves whole per-point runs: the pairs of point j of this block, in their order,
+// to   (pairs of smaller digits in the frame) + (pairs of digit d_j in earlier blocks) + (pairs of earlier points of this block with
+// digit d_j) + t.   The first two terms come from the [digit][block] pair counts the per-point stage left (k_project.hip:
+// gs_bin_digits_*), scanned along each row by k_sort_rowscan and across the 256 row totals here, as k_sort_scatter's prologue does; the
+// third from ranking the block's 256 points by digit (the ballot matching of k_sort_scatter, one round per wave) into a second LDS
+// table in (digit, point) order and scanning the tile counts in THAT order.  The pair loop then walks the block's pairs in that order
+// too, so consecutive lanes write consecutive slots across all points of one digit.  What is left in keys / vals is byte for byte what
+// k_sort_scatter leaves after shift 0; `offsets` (the scan in point order) is unchanged.
+template <typename KeyT, bool FIRST_PASS>
 __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ depth_codes, const ushort4* __restrict__ boxes,
                                                 const int32_t* __restrict__ ntiles,
                                                 const uint32_t* __restrict__ tile_block_sums,
@@ -34,12 +63,15 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
                                                 int depth_bits, uint32_t K_cap,
                                                 uint32_t* __restrict__ offsets, KeyT* __restrict__ keys,
                                                 int32_t* __restrict__ vals,
-                                                GsCounters* __restrict__ counters, volatile GsCounters* host_mirror, int32_t ticket)
+                                                GsCounters* __restrict__ counters, volatile GsCounters* host_mirror, int32_t ticket,
+                                                const uint32_t* __restrict__ first_offs, const uint32_t* __restrict__ first_totals)
 {
     __shared__ uint32_t ws[4], wpre[4];
     __shared__ uint32_t sExcl[256 + 1];
     __shared__ ushort4 sBox[256];
     __shared__ KeyT sCode[256];
+    __shared__ uint32_t sBase[FIRST_PASS ? 256 : 1];        // FIRST_PASS: slot of a row's pair e, minus e
+    __shared__ unsigned short sOrig[FIRST_PASS ? 256 : 1];  // FIRST_PASS: the row's thread (its point is first + that)
     // same blocks as the kernel that produced ntiles / tile_block_offsets: k_project's (256 rows of the point cloud each, in-camera
     // points dense from block_offsets[b]) or, for records that arrived from elsewhere, 256 consecutive records
     const int first = block_offsets ? block_offsets[blockIdx.x] : (int)blockIdx.x * 256;
@@ -50,8 +82,9 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
     const uint32_t n = valid ? (uint32_t)ntiles[idx] : 0u;
     const uint32_t incl = gs_wave_scan_incl(n, lane);
     gs_block_scan_put(ws, wave, lane, incl);
-    sBox[threadIdx.x] = valid ? boxes[idx] : make_ushort4(0, 1, 0, 1);
-    sCode[threadIdx.x] = valid ? (KeyT)(uint32_t)depth_codes[idx] : (KeyT)0;     // i32(depth * scale), RAST:159-160, from k_project
+    const ushort4 my_box = valid ? boxes[idx] : make_ushort4(0, 1, 0, 1);
+    const KeyT my_code = valid ? (KeyT)(uint32_t)depth_codes[idx] : (KeyT)0;     // i32(depth * scale), RAST:159-160, from k_project
+    if constexpr (!FIRST_PASS) { sBox[threadIdx.x] = my_box; sCode[threadIdx.x] = my_code; }
     // first pair of this block = the tile counts of all blocks before it (RAST:913-922 across blocks)
     gs_block_put(wpre, wave, lane, gs_sum_of_blocks_before<256>(tile_block_sums, (int)blockIdx.x));
     __syncthreads();                                                              // the scan, wpre and the LDS table
@@ -62,9 +95,52 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
     if (host_mirror && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
         gs_publish_counters(counters, block_base + block_total, host_mirror, ticket);
     const uint32_t excl = gs_block_scan_excl(ws, wave, incl, n);                  // first pair of this point inside the block
-    sExcl[threadIdx.x] = excl;
-    if (threadIdx.x == 0) sExcl[256] = 0xffffffffu;
     if (valid) offsets[idx] = block_base + excl;                                  // RAST:913-922 (also the backward's row slots)
+    // slot of the block's pair e: block_base + e, or with FIRST_PASS sBase[owner] + e
+    if constexpr (!FIRST_PASS) {
+        sExcl[threadIdx.x] = excl;
+    } else {
+        __shared__ uint32_t cnt[4][256];      // points per (wave, digit), then each wave's first position of the digit in the second table
+        __shared__ uint32_t gbase[256];       // the block's first slot of each digit
+        __shared__ uint32_t sN[256];
+        __shared__ uint32_t wtot[4], wdig[4], wsec[4];
+        const int t = threadIdx.x;
+        const uint32_t d = (uint32_t)my_code & 255u;
+        // (a thread past the block's points has digit 0 and no pairs: it ranks behind the block's own points of that digit)
+        cnt[0][t] = 0; cnt[1][t] = 0; cnt[2][t] = 0; cnt[3][t] = 0;
+        const uint32_t tot = first_totals[t];
+        const uint32_t tincl = gs_wave_scan_incl(tot, lane);
+        gs_block_scan_put(wtot, wave, lane, tincl);
+        // lanes of this wave with the same digit: rank among them = the lower ones
+        uint32_t slo, shi;
+        gs_match_digit(d, ~0ull, slo, shi);
+        const uint32_t in_wave = gs_match_rank(slo, shi, (1ull << lane) - 1ull);
+        __syncthreads();                                                          // cnt cleared, wtot
+        gbase[t] = gs_block_scan_excl(wtot, wave, tincl, tot) + first_offs[(size_t)t * gridDim.x + blockIdx.x];
+        if (in_wave == 0) cnt[wave][d] = (uint32_t)__popc(slo) + (uint32_t)__popc(shi);
+        __syncthreads();
+        // thread t owns digit t: its points in the block, exclusive scan over digits, per-wave starts
+        const uint32_t c0 = cnt[0][t], c1 = cnt[1][t], c2 = cnt[2][t], c3 = cnt[3][t];
+        const uint32_t dtot = c0 + c1 + c2 + c3;
+        const uint32_t dincl = gs_wave_scan_incl(dtot, lane);
+        gs_block_scan_put(wdig, wave, lane, dincl);
+        __syncthreads();
+        const uint32_t ds = gs_block_scan_excl(wdig, wave, dincl, dtot);
+        cnt[0][t] = ds; cnt[1][t] = ds + c0; cnt[2][t] = ds + c0 + c1; cnt[3][t] = ds + c0 + c1 + c2;
+        __syncthreads();
+        const uint32_t pos = cnt[wave][d] + in_wave;                              // this point's row of the second table
+        sN[pos] = n; sBox[pos] = my_box; sCode[pos] = my_code; sOrig[pos] = (unsigned short)t;
+        __syncthreads();
+        const uint32_t m = sN[t];
+        const uint32_t sincl = gs_wave_scan_incl(m, lane);
+        gs_block_scan_put(wsec, wave, lane, sincl);
+        __syncthreads();
+        sExcl[t] = gs_block_scan_excl(wsec, wave, sincl, m);                      // first pair of row t in (digit, point) order
+        __syncthreads();
+        const uint32_t dt = (uint32_t)sCode[t] & 255u;
+        sBase[t] = gbase[dt] - sExcl[cnt[0][dt]];                                 // (cnt[0][dt]: the digit's first row)
+    }
+    if (threadIdx.x == 0) sExcl[256] = 0xffffffffu;
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < block_total; e += 256u) {
         int j = 0;                                                                // owner: the last point whose first pair is <= e
@@ -83,10 +159,12 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
             tr = (uint32_t)r;
         } else { tq = t / dv; tr = t - tq * dv; }
         const KeyT tile_id = (KeyT)(((uint32_t)bx.x + tq) + ((uint32_t)bx.z + tr) * (uint32_t)tiles_x);   // RAST:163-168
-        const uint32_t slot = block_base + e;
+        uint32_t slot; int point;
+        if constexpr (FIRST_PASS) { slot = sBase[j] + e; point = first + (int)sOrig[j]; }
+        else { slot = block_base + e; point = first + j; }
         if (slot < K_cap) {
             keys[slot] = (tile_id << depth_bits) | sCode[j];                     // RAST:169-170, compact form
-            vals[slot] = first + j;
+            vals[slot] = point;
         }
     }
 }
@@ -193,18 +271,9 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const KeyT* __restrict__ k
             const uint32_t li = (uint32_t)wave * (SORT_ROUNDS * 64) + r * 64 + lane;
             const bool valid = FULL || li < tile_n;
             const uint32_t d = (uint32_t)(k[r] >> shift) & 255u;
-            // lanes with the same digit, as two 32-bit halves per lane: per bit one vote, then same &= ~(vote ^ m) with m = all
-            // ones where the lane's bit is set (v_bfe_i32, v_xnor_b32, v_and_b32 per half)
-            const unsigned long long vm = gs_ballot(valid);
-            uint32_t slo = (uint32_t)vm, shi = (uint32_t)(vm >> 32);
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const int32_t mb = (int32_t)(d << (31 - bit)) >> 31;
-                const unsigned long long bal = gs_ballot(mb < 0);
-                slo &= ~((uint32_t)bal ^ (uint32_t)mb);
-                shi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)mb);
-            }
-            const uint32_t in_round = (uint32_t)__popc(slo & (uint32_t)lt_mask) + (uint32_t)__popc(shi & (uint32_t)(lt_mask >> 32));
+            uint32_t slo, shi;
+            gs_match_digit(d, gs_ballot(valid), slo, shi);                       // the valid lanes with the same digit
+            const uint32_t in_round = gs_match_rank(slo, shi, lt_mask);
             const uint32_t before = valid ? cnt[wave][d] : 0u;
             if (valid && in_round == 0) cnt[wave][d] = before + (uint32_t)__popc(slo) + (uint32_t)__popc(shi);
             rank[r] = before + in_round;
@@ -266,6 +335,12 @@ static void sort_geometry(uint32_t K, int* nblocks, int* tiles_per_block)
     if (*nblocks < 1) *nblocks = 1;
 }
 
+size_t gs_first_hist_elems(int64_t rows)
+{
+    const size_t nb = (size_t)((rows + 255) / 256);
+    return (size_t)2 * 256 * (nb > 0 ? nb : 1);      // raw counts + scanned offsets
+}
+
 size_t gs_sort_hist_elems(uint32_t K)
 {
     int nb, tpb;
@@ -282,15 +357,26 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
     *a.vals_sorted = a.vals_a;
     if (a.N == 0 || a.M == 0) return;
     const unsigned kg_blocks = a.block_offsets ? (unsigned)((a.N + 255) / 256) : (unsigned)((a.M + 255) / 256);
-    GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT><<<kg_blocks, 256, 0, s>>>(
-        a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
-        a.counters_rw, a.host_mirror, a.ticket));
+    // digit 0 of the key is the low byte of the depth code, the same for all pairs of a point, once the depth field has 8 bits: then
+    // k_keygen stores every pair where the first pass would have put it, from the per-point stage's digit table, and the loop starts at 8
+    const bool first_pass = a.first_hist != nullptr && a.depth_bits >= 8;
+    if (first_pass) {
+        uint32_t* first_offs = a.first_hist + (size_t)256 * kg_blocks;
+        GS_TIMED(a.prof, KID_SORT_ROWSCAN, s, k_sort_rowscan<<<GS_SORT_DIGITS, 1024, 0, s>>>(a.first_hist, a.scan_tmp, first_offs, (int)kg_blocks));
+        GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT, true><<<kg_blocks, 256, 0, s>>>(
+            a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
+            a.counters_rw, a.host_mirror, a.ticket, first_offs, a.scan_tmp));
+    } else {
+        GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT, false><<<kg_blocks, 256, 0, s>>>(
+            a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
+            a.counters_rw, a.host_mirror, a.ticket, nullptr, nullptr));
+    }
     if (a.K == 0) return;
     int nb, tpb;
     sort_geometry(a.K, &nb, &tpb);
     KeyT *kin = keys_a, *kout = keys_b;
     int32_t *vin = a.vals_a, *vout = a.vals_b;
-    for (int shift = 0; shift < a.key_bits; shift += 8) {
+    for (int shift = first_pass ? 8 : 0; shift < a.key_bits; shift += 8) {
         uint32_t* offs = a.hist + (size_t)256 * nb;                 // second half of the table: scanned offsets
         GS_TIMED(a.prof, KID_SORT_HIST, s, k_sort_hist<KeyT><<<nb, 256, 0, s>>>(kin, a.counters, a.K, shift, a.hist, nb, tpb));
         GS_TIMED(a.prof, KID_SORT_ROWSCAN, s, k_sort_rowscan<<<GS_SORT_DIGITS, 1024, 0, s>>>(a.hist, a.scan_tmp, offs, nb));

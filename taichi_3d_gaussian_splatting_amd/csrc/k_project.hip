@@ -135,6 +135,20 @@ __device__ __forceinline__ void gs_bin_block_publish(const int* wave_sum, const 
     const int m = gs_block_max<4>(wave_max);
     if (m > 0) atomicMax(&counters->max_depth_code, m);
 }
+// ... and, for the sort's first radix pass (k_binning.hip: k_keygen places every pair where a pass over digit 0 of its key would have put
+// it): the block's PAIR count per low byte of the depth code -- all pairs of a point share it when the key's depth field has 8 bits or
+// more.  Three steps around the caller's barriers: every thread clears its word of dig[256]; barrier; every in-camera thread adds its
+// tile count (LDS integer atomics: the order does not matter); barrier; thread t stores word t of column blockIdx.x of the [digit][block]
+// table k_sort_rowscan reads.  Every block writes all 256 words, so nothing has to be cleared.
+__device__ __forceinline__ void gs_bin_digits_clear(uint32_t* dig) { dig[threadIdx.x] = 0u; }
+__device__ __forceinline__ void gs_bin_digits_add(uint32_t* dig, int count, int depth_code)
+{
+    if (count > 0) atomicAdd(&dig[(uint32_t)depth_code & 255u], (uint32_t)count);
+}
+__device__ __forceinline__ void gs_bin_digits_store(const uint32_t* dig, uint32_t* __restrict__ first_hist)
+{
+    if (first_hist) first_hist[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = dig[threadIdx.x];
+}
 
 // ---------------------------------------------------------------------------------
 // Compaction (point_id[mask], RAST:861-870, ascending ids) fused with the projection: a block takes 256 consecutive
@@ -151,9 +165,12 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
                                                  float4* __restrict__ PA, float4* __restrict__ PB, float4* __restrict__ PC,
                                                  float4* __restrict__ PD, ushort4* __restrict__ boxes,
                                                  int32_t* __restrict__ ntiles, uint32_t* __restrict__ tile_block_sums,
-                                                 GsCounters* counters, int32_t* __restrict__ depth_codes, int32_t* __restrict__ max_tiles_hint)
+                                                 GsCounters* counters, int32_t* __restrict__ depth_codes, int32_t* __restrict__ max_tiles_hint,
+                                                 uint32_t* __restrict__ first_hist)
 {
     __shared__ int wave_sum[4], wave_max[4], wave_maxn[4];
+    __shared__ uint32_t dig[256];
+    gs_bin_digits_clear(dig);                                        // (the two barriers of the compaction lie before the first add)
     // the four float4 of a record leave through LDS: a lane-per-record store writes 16 bytes out of every 64 per
     // instruction; staged, each of the wave's four store instructions writes 1 KB of consecutive bytes
     __shared__ float4 sOut[4][4 * 64];
@@ -271,6 +288,7 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
         recC = make_float4(col[0], col[1], col[2], cut);
         recD = make_float4(pcam[0], pcam[1], pcam[2], radii);
         gs_bin_point(uv[0], uv[1], radii, pcam[2], W, H, depth_scale, idx, boxes, ntiles, depth_codes, count, depth_code);
+        gs_bin_digits_add(dig, count, depth_code);
     }
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     {
@@ -290,6 +308,7 @@ __global__ __launch_bounds__(256) void k_project(const float* __restrict__ pc, f
     gs_bin_block_put(wave_sum, wave_max, wave, lane, count, depth_code);
     gs_block_put(wave_maxn, wave, lane, mn);
     __syncthreads();
+    gs_bin_digits_store(dig, first_hist);
     if (threadIdx.x == 0) {
         gs_bin_block_publish(wave_sum, wave_max, tile_block_sums, counters);
         // the frame's largest tile count of one point (a word of the tile arrays, cleared by k_filter): the backward's row sum looks for
@@ -307,18 +326,24 @@ __global__ __launch_bounds__(256) void k_boxes_from_records(const float4* __rest
                                                             const float4* __restrict__ PD, int M, int W, int H, float depth_scale,
                                                             ushort4* __restrict__ boxes, int32_t* __restrict__ ntiles,
                                                             uint32_t* __restrict__ tile_block_sums, GsCounters* counters,
-                                                            int32_t* __restrict__ depth_codes, int32_t* __restrict__ tile_arrays, int tile_ints)
+                                                            int32_t* __restrict__ depth_codes, int32_t* __restrict__ tile_arrays, int tile_ints,
+                                                            uint32_t* __restrict__ first_hist)
 {
     __shared__ int wave_sum[4], wave_max[4];
+    __shared__ uint32_t dig[256];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     for (int k = idx; k < tile_ints; k += (int)gridDim.x * 256) tile_arrays[k] = 0;       // as k_filter does
+    gs_bin_digits_clear(dig);
+    __syncthreads();
     int count = 0, depth_code = 0;
     if (idx < M) {
         const float4 A = GS_REC(PA, idx);
         gs_bin_point(A.x, A.y, GS_REC(PD, idx).w, GS_REC(PB, idx).w, W, H, depth_scale, idx, boxes, ntiles, depth_codes, count, depth_code);
+        gs_bin_digits_add(dig, count, depth_code);
     }
     gs_bin_block_put(wave_sum, wave_max, (int)(threadIdx.x >> 6), threadIdx.x & 63, count, depth_code);
     __syncthreads();
+    gs_bin_digits_store(dig, first_hist);
     if (threadIdx.x == 0) {
         gs_bin_block_publish(wave_sum, wave_max, tile_block_sums, counters);
         if (blockIdx.x == 0) counters->M = M;
@@ -358,7 +383,7 @@ void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish)
     GS_TIMED(a.prof, KID_PROJECT, s, k_project<<<nb, 256, 0, s>>>(a.point_cloud, a.features, a.object_id, a.Kmat, v.pose, v.mask, a.block_counts, a.N,
                                                               v.ids, v.cam_index, a.block_offsets, a.W, a.H,
                                                               a.depth_scale, v.PA, v.PB, v.PC, v.PD, v.box, v.ntiles,
-                                                              a.tile_block_sums, a.counters, v.depth_codes, v.max_tiles));
+                                                              a.tile_block_sums, a.counters, v.depth_codes, v.max_tiles, a.first_hist));
     if (publish) gs_launch_publish(a, nb, s);
 }
 
@@ -368,6 +393,6 @@ void gs_launch_boxes_from_records(const GsProjectArgs& a, int M, hipStream_t s, 
     const int nb = (M + 255) / 256;
     if (nb == 0) { (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s); return; }
     GS_TIMED(a.prof, KID_PROJECT, s, k_boxes_from_records<<<nb, 256, 0, s>>>(v.PA, v.PB, v.PD, M, a.W, a.H, a.depth_scale, v.box, v.ntiles,
-                                                                          a.tile_block_sums, a.counters, v.depth_codes, v.tile_start, v.tile_ints));
+                                                                          a.tile_block_sums, a.counters, v.depth_codes, v.tile_start, v.tile_ints, a.first_hist));
     if (publish) gs_launch_publish(a, nb, s);
 }
