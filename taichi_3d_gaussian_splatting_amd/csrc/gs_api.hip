@@ -5,6 +5,7 @@
 #include "../../include/gs_channels.h"
 #include "../../include/gs_sparse.h"
 #include "../../include/gs_knn.h"
+#include "../../include/gs_exchange.h"
 #include "gs_common.h"
 
 #include <algorithm>
@@ -140,6 +141,7 @@ struct gs_ctx {
     uint64_t bwd_serial = 0;
     size_t touched_offset = 0;
     DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
+    DevBuf merge_tags, merge_ids;          // gs_merge_rows: one tag byte per point-cloud row, the id words of all lists (block totals: row_block_totals)
     DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
@@ -199,7 +201,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp, &c->first_hist,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
-                      &c->ch_partial, &c->ch_flags, &c->row_block_totals,
+                      &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1331,6 +1333,60 @@ extern "C" int gs_adam_step_rows(gs_ctx* c, float* param, const float* grad, flo
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_adam_rows(param, grad, exp_avg, exp_avg_sq, n_rows, row_len, ids, count, max_count, lr, beta1, beta2, eps, step, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- packed rows and their merge (include/gs_exchange.h, k_exchange.hip) -----------------------------------------------------
+// No host synchronisation and no device-to-host copy in either: every count stays on the device.
+extern "C" int gs_pack_rows(gs_ctx* c, const float* grad_features, const float* grad_pointcloud, int64_t n_rows, const int32_t* ids,
+                            const int32_t* count, int64_t max_count, float* packed_out, gs_stream stream_)
+{
+    if (!c || (n_rows > 0 && max_count > 0 && (!grad_features || !grad_pointcloud || !ids || !count || !packed_out)))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: NULL argument");
+    if (n_rows < 0 || max_count < 0 || n_rows > 0x7fffffffll)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: n_rows and max_count must be >= 0, n_rows <= 2^31 - 1");
+    if (n_rows == 0 || max_count == 0) return GS_OK;
+    if ((uintptr_t)packed_out & 15u) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: packed_out must be 16-byte aligned");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_pack_rows(grad_features, grad_pointcloud, n_rows, ids, count, max_count, packed_out, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_merge_rows(gs_ctx* c, const float* packed, const int32_t* counts, int32_t n_lists, int64_t list_stride, int64_t n_rows,
+                             float* grad_features_out, float* grad_pointcloud_out, int32_t* union_ids_out, int64_t union_capacity,
+                             int32_t* union_count_out, gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: NULL argument");
+    if (n_lists < 1 || n_lists > GS_MERGE_MAX_LISTS) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: n_lists must be >= 1 and <= 64");
+    if (list_stride < 0 || n_rows < 0 || n_rows > 0x7fffffffll - 4096 || list_stride > (int64_t)1 << 40)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: list_stride and n_rows must be >= 0, n_rows <= 2^31 - 2^12");
+    const int64_t entries = (int64_t)n_lists * list_stride, max_union = n_rows < entries ? n_rows : entries;
+    if (union_capacity < max_union)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: union_capacity must be >= min(n_rows, n_lists * list_stride)");
+    if (max_union == 0) {                       // nothing to merge: an empty union
+        if (!union_count_out) return GS_OK;
+        std::lock_guard<std::mutex> lock(c->mu);
+        hipStream_t s;
+        if (const int rc = enter_call(c, stream_, &s)) return rc;
+        HIP_TRY(hipMemsetAsync(union_count_out, 0, sizeof(int32_t), s));
+        return GS_OK;
+    }
+    if (!packed || !counts || !grad_features_out || !grad_pointcloud_out || !union_ids_out || !union_count_out)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: NULL argument");
+    if ((uintptr_t)packed & 15u) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: packed must be 16-byte aligned");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the scratch grows before the stream enters: a call that fails here leaves it alone
+    int rc;
+    if ((rc = grow(c, { NEED(c->merge_tags, gs_merge_tag_bytes(n_rows)), NEED(c->merge_ids, (size_t)entries * sizeof(int32_t)),
+                        NEED(c->row_block_totals, (size_t)(gs_rows_blocks((int)n_rows) + 1) * sizeof(uint32_t)) })) != GS_OK) return rc;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    gs_launch_merge_rows(packed, counts, n_lists, list_stride, n_rows, grad_features_out, grad_pointcloud_out, union_ids_out, union_capacity,
+                         union_count_out, c->merge_tags.as<uint8_t>(), c->merge_ids.as<int32_t>(), c->row_block_totals.as<uint32_t>(), s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -502,6 +502,16 @@ void gs_launch_touched_rows(const uint8_t* touched, uint8_t gen, const int32_t* 
                             int32_t* ids_out, int64_t capacity, int32_t* count_out, hipStream_t s);
 void gs_launch_adam_rows(float* param, const float* grad, float* m, float* v, int64_t n_rows, int row_len, const int32_t* ids,
                          const int32_t* count, int64_t max_count, float lr, float beta1, float beta2, float eps, int64_t step, hipStream_t s);
+// k_exchange.hip (include/gs_exchange.h): rows ids[0 .. *count) of the two dense gradients as packed rows of 60 words, and the merge of
+// n_lists packed lists (list l at packed + l * list_stride rows) into the union list and the summed dense rows.  tag:
+// gs_merge_tag_bytes(n_rows) bytes, ids_all: n_lists * list_stride words, block_totals: gs_rows_blocks(n_rows) words of scratch.
+// gs_launch_touched_rows with ids_in == NULL lists the tagged positions themselves.
+void gs_launch_pack_rows(const float* grad_features, const float* grad_pointcloud, int64_t n_rows, const int32_t* ids, const int32_t* count,
+                         int64_t max_count, float* packed_out, hipStream_t s);
+size_t gs_merge_tag_bytes(int64_t n_rows);
+void gs_launch_merge_rows(const float* packed, const int32_t* counts, int n_lists, int64_t list_stride, int64_t n_rows, float* grad_features_out,
+                          float* grad_pointcloud_out, int32_t* union_ids_out, int64_t union_capacity, int32_t* union_count_out, uint8_t* tag,
+                          int32_t* ids_all, uint32_t* block_totals, hipStream_t s);
 // k_knn.hip (include/gs_knn.h): exact k nearest neighbours of the n rows of xyz; the four work buffers hold gs_knn_*_bytes(n)
 size_t gs_knn_sort_bytes(int64_t n);
 size_t gs_knn_hist_bytes(int64_t n);

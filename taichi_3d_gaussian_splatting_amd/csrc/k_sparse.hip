@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void k_rows_scatter(const uint8_t* __restrict_
     while (mask) {
         const int k = __builtin_ctz(mask);
         mask &= mask - 1u;
-        sOut[at++] = ids_in[first + k];
+        sOut[at++] = ids_in ? ids_in[first + k] : first + k;    // (NULL: the identity, the tags are indexed by row -- gs_merge_rows)
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count_out = (int32_t)(base + total);      // the block that owns the end
     __syncthreads();

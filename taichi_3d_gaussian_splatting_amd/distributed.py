@@ -6,6 +6,8 @@ Backend "nccl" is RCCL on ROCm (xGMI inside a node); "gloo" is used by the CPU t
   59*N float buffer, so the all-reduce is a single RCCL call on 236*N bytes (all_reduce_point_gradients).  With several
   views per rank per step the collective is either issued once per step on the locally accumulated gradient, or once
   per view asynchronously so that it runs beside the next view's forward + backward (OverlappedGradientReducer).
+  Nine gradient rows in ten are exact zeros at a training view: sparse_reduce_point_gradients moves only the touched rows
+  (packed by exchange.pack_rows, all-gathered, merged in rank order by exchange.merge_rows).
 
 * Gaussian-parallel: every rank OWNS a contiguous shard of the Gaussians (parameters, gradients, optimiser state) and
   RENDERS one view.  Owners project their shard for every view, an all-to-all hands each renderer the projected splat
@@ -69,6 +71,49 @@ def all_reduce_point_gradients(grad_pc: torch.Tensor, grad_feat: torch.Tensor, g
         if average:
             b.div_(dist.get_world_size(group))
     return len(bufs)
+
+
+def sparse_reduce_point_gradients(grad_pc: torch.Tensor, grad_feat: torch.Tensor, rows, group=None, zero: bool = False):
+    """The view-parallel reduction on the rows that carry a gradient: every rank packs the rows its backward touched
+    (`rows`, the sparse.TouchedRows of that backward; exchange.pack_rows), the packed lists are all-gathered, and every rank
+    merges them in rank order (exchange.merge_rows).
+    -> (grad_pointcloud, grad_pointcloud_features, union_rows, stats): on every row of union_rows, the ascending union of
+    all ranks' lists, the two gradients equal the rank-ordered sum ((g0 + g1) + g2) ... over the ranks that list the row, the
+    same bits on every rank; the other rows are undefined (zeros with zero=True).  FusedAdam.step(rows=union_rows) consumes
+    them.  RCCL's dense all-reduce promises no order of summation, so bit-equality with all_reduce_point_gradients is not
+    claimed beyond two ranks (where a + b is commutative).
+
+    Two collectives: an all-gather of the counts, then an all-gather of equal-sized buffers padded to the largest count (gloo
+    has no uneven all-gather; the padding rows are never read).  Between them the count table is read on the host -- the one
+    host read of the call, the trade gaussian_parallel_step makes too.  The packed rows travel as int32 words, never as
+    float32: no backend arithmetic or NaN canonicalisation can touch the id word.
+    stats: rows_local, bytes_sent (the padded buffer and the count this rank contributes), bytes_dense (236 * N, what the
+    dense all-reduce moves), collectives (2) and rows_union, which stays a 0-dim int32 DEVICE tensor (reading it
+    synchronises).  With one process or world_size == 1 the inputs and `rows` come back unchanged, collectives = 0, and rows_local is
+    None (the local count is not read on the host then)."""
+    from . import exchange
+    n = grad_pc.shape[0]
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return grad_pc, grad_feat, rows, {"rows_local": None, "rows_union": rows.count, "bytes_sent": 0, "bytes_dense": 236 * n,
+                                          "collectives": 0}
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    packed = exchange.pack_rows(grad_pc, grad_feat, rows)
+    counts = torch.empty(world, dtype=torch.int32, device=grad_pc.device)
+    dist.all_gather(list(counts.view(world, 1).unbind(0)), packed.count.reshape(1), group=group)
+    table = [min(max(int(c), 0), 2 ** 31 - 1) for c in counts.tolist()]       # ONE device->host read: the count table
+    stride = max(max(table), 1)
+    words = packed.data.view(torch.int32)
+    if stride <= words.shape[0]:
+        send = words[:stride]
+    else:                                                                     # another rank lists more rows than this one's bound
+        send = words.new_empty((stride, exchange.ROW_WORDS))
+        send[:table[rank]] = words[:table[rank]]
+    gathered = torch.empty((world, stride, exchange.ROW_WORDS), dtype=torch.int32, device=grad_pc.device)
+    dist.all_gather(list(gathered.unbind(0)), send, group=group)
+    gpc, gft, union = exchange.merge_rows(gathered.view(torch.float32), counts, n, zero=zero)
+    stats = {"rows_local": table[rank], "rows_union": union.count, "bytes_sent": stride * exchange.ROW_BYTES + 4,
+             "bytes_dense": 236 * n, "collectives": 2}
+    return gpc, gft, union, stats
 
 
 class OverlappedGradientReducer:
