@@ -1,0 +1,422 @@
+"""GaussianPointCloudTrainer -- the reference's training loop (taichi_3d_gaussian_splatting/GaussianPointTrainer.py, TRAIN
+below) over this package's pieces: GaussianPointCloudScene, the rasteriser with the adaptive controller's update as its
+backward hook, the fused LossFunction and FusedAdam.  Same class and config names, fields, defaults, schedules, log tags and
+checkpoint files, so the reference's YAMLs and dataset JSONs work unchanged.
+
+What differs from the reference
+  - Targets come from targets.TargetStore by default (targets_on_device=True): images resident on the device as uint8, one
+    kernel per step.  targets_on_device=False is the reference's path, kept for comparison: ImagePoseDataset through a
+    DataLoader (num_workers=0) and the antialiased resize on the CPU.
+  - The view order is a seeded torch.randperm per epoch (trainer.view_order), not a shuffling DataLoader.
+  - The clamp of the predicted image runs inside the loss kernels (clamp_predicted=True), and SSIM for the logged metrics is
+    1 - the loss's third term instead of pytorch_msssim.
+  - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
+  - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
+    produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
+    for the device only at the logging intervals.  The FTGMM scene grab (TRAIN:188-189) and the Taichi kernel profiler are
+    left out.
+"""
+import dataclasses
+import json
+import os
+import typing
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import torch
+
+from ._host import _ConfigBase
+from .Camera import CameraInfo
+from .GaussianPointAdaptiveController import GaussianPointAdaptiveController
+from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
+from .GaussianPointCloudScene import GaussianPointCloudScene
+from .ImagePoseDataset import ImagePoseDataset, resize_antialias
+from .LossFunction import LossFunction
+from .optim import FusedAdam
+from .targets import TargetStore, downsampled_geometry, downsampled_intrinsics
+
+
+# ---- the three schedules of TRAIN:143-192 as pure functions of the iteration ----------------------------------------------
+def downsample_factor_at(iteration: int, initial_downsample_factor: int, half_downsample_factor_interval: int) -> int:
+    """The factor iteration `iteration` trains at: halved at every iteration > 0 that is a multiple of the interval, down to 1
+    (TRAIN:144-145)"""
+    factor = int(initial_downsample_factor)
+    for _ in range(int(iteration) // int(half_downsample_factor_interval)):
+        if factor > 1:
+            factor //= 2
+    return factor
+
+
+def color_max_sh_band_at(iteration: int, increase_color_max_sh_band_interval) -> int:
+    """TRAIN:168 (the interval's default is the float 1000.)"""
+    return int(iteration // increase_color_max_sh_band_interval)
+
+
+def position_learning_rate_at(iteration: int, position_learning_rate: float, decay_rate: float, decay_interval: int) -> float:
+    """The position learning rate iteration `iteration` steps with: multiplied by the rate after every earlier iteration that
+    is a multiple of the interval -- iteration 0 included, as the reference's scheduler.step() at TRAIN:191-192 has it"""
+    lr = float(position_learning_rate)
+    for _ in range((int(iteration) + int(decay_interval) - 1) // int(decay_interval)):
+        lr *= decay_rate
+    return lr
+
+
+class JsonlSummaryWriter:
+    """What the trainer needs of torch.utils.tensorboard.SummaryWriter when tensorboard is not installed: add_scalar appends
+    {"tag", "value", "step"} to <log_dir>/metrics.jsonl; images, figures and histograms are accepted and dropped."""
+
+    def __init__(self, log_dir: str):
+        os.makedirs(log_dir, exist_ok=True)
+        self.log_dir = log_dir
+        self.path = os.path.join(log_dir, "metrics.jsonl")
+        self._fh = open(self.path, "a")
+
+    def add_scalar(self, tag, scalar_value, global_step=None, walltime=None, **_):
+        value = scalar_value.item() if hasattr(scalar_value, "item") else scalar_value
+        self._fh.write(json.dumps({"tag": str(tag), "value": float(value), "step": None if global_step is None else int(global_step)}) + "\n")
+
+    def add_image(self, *args, **kwargs):
+        pass
+
+    def add_figure(self, *args, **kwargs):
+        pass
+
+    def add_histogram(self, *args, **kwargs):
+        pass
+
+    def flush(self):
+        self._fh.flush()
+
+    def close(self):
+        if not self._fh.closed:
+            self._fh.close()
+
+    @staticmethod
+    def read(path: str) -> List[dict]:
+        with open(path) as fh:
+            return [json.loads(line) for line in fh if line.strip()]
+
+
+def make_summary_writer(log_dir: str):
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+    except Exception:
+        return JsonlSummaryWriter(log_dir)
+    return SummaryWriter(log_dir=log_dir)
+
+
+def _coerce(value, annotation):
+    """A YAML scalar as the field's annotation wants it: PyYAML reads 3e-6 and 1e3 (no dot) as strings, and a float field may
+    be written as an integer.  Optional[T] is T unless the value is None; anything else passes as it is."""
+    if getattr(annotation, "__origin__", None) is typing.Union:
+        inner = [a for a in annotation.__args__ if a is not type(None)]
+        annotation = inner[0] if len(inner) == 1 else None
+    if value is None or isinstance(value, bool) or annotation not in (int, float, bool):
+        return value
+    if annotation is bool:
+        return {"true": True, "false": False}.get(value.strip().lower(), value) if isinstance(value, str) else value
+    if isinstance(value, str):
+        number = float(value)
+        return int(number) if annotation is int and number == int(number) else number
+    return float(value) if annotation is float and isinstance(value, int) else value
+
+
+def _config_from_dict(cls, data: dict, prefix: str, unknown: List[str]):
+    """cls(**data) with keys normalised ('-' -> '_'), nested config dataclasses recursed into and unknown keys collected"""
+    fields = {f.name: f for f in dataclasses.fields(cls)}
+    hints = {name: f.type for name, f in fields.items() if not isinstance(f.type, str)}
+    kwargs = {}
+    for key, value in (data or {}).items():
+        name = str(key).replace("-", "_")
+        if name not in fields:
+            unknown.append(prefix + name)
+            continue
+        default = fields[name].default_factory() if fields[name].default_factory is not dataclasses.MISSING else None
+        if dataclasses.is_dataclass(default) and isinstance(value, dict):
+            value = _config_from_dict(type(default), value, prefix + name + ".", unknown)
+        else:
+            value = _coerce(value, hints.get(name))
+        kwargs[name] = value
+    return cls(**kwargs)
+
+
+class GaussianPointCloudTrainer:
+    @dataclass
+    class TrainConfig(_ConfigBase):
+        """The reference's fields and defaults (TRAIN:35-63), then three of this package.  enable_taichi_kernel_profiler and
+        log_taichi_kernel_profile_interval are accepted and ignored: there is no Taichi here."""
+        train_dataset_json_path: str = ""
+        val_dataset_json_path: str = ""
+        pointcloud_parquet_path: str = ""
+        num_iterations: int = 300000
+        val_interval: int = 1000
+        feature_learning_rate: float = 1e-3
+        position_learning_rate: float = 1e-5
+        position_learning_rate_decay_rate: float = 0.97
+        position_learning_rate_decay_interval: int = 100
+        increase_color_max_sh_band_interval: int = 1000.
+        log_loss_interval: int = 10
+        log_metrics_interval: int = 100
+        print_metrics_to_console: bool = False
+        log_image_interval: int = 1000
+        enable_taichi_kernel_profiler: bool = False
+        log_taichi_kernel_profile_interval: int = 1000
+        log_validation_image: bool = True
+        initial_downsample_factor: int = 4
+        half_downsample_factor_interval: int = 250
+        summary_writer_log_dir: str = "logs"
+        output_model_dir: Optional[str] = None
+        rasterisation_config: GaussianPointCloudRasterisation.GaussianPointCloudRasterisationConfig = field(
+            default_factory=GaussianPointCloudRasterisation.GaussianPointCloudRasterisationConfig)
+        adaptive_controller_config: GaussianPointAdaptiveController.GaussianPointAdaptiveControllerConfig = field(
+            default_factory=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerConfig)
+        gaussian_point_cloud_scene_config: GaussianPointCloudScene.PointCloudSceneConfig = field(
+            default_factory=GaussianPointCloudScene.PointCloudSceneConfig)
+        loss_function_config: LossFunction.LossFunctionConfig = field(
+            default_factory=LossFunction.LossFunctionConfig)
+        # extensions over the reference
+        targets_on_device: bool = True      # targets.TargetStore; False: ImagePoseDataset + the CPU resize (the reference's path)
+        sparse_adam: bool = False           # FusedAdam.step(rows=rast.last_touched_rows)
+        seed: int = 0                       # of the view order and of the controller's split samples
+
+        @classmethod
+        def from_yaml_file(cls, path: str) -> "GaussianPointCloudTrainer.TrainConfig":
+            """The config of a YAML file in the reference's format, with or without dataclass_wizard: keys in lisp-case or
+            snake_case (a file may mix them), the four nested configs as mappings.  A key no field answers to is ignored and
+            listed in config.unknown_keys (nested ones as "adaptive_controller_config.name")."""
+            import yaml
+            with open(path) as fh:
+                data = yaml.safe_load(fh) or {}
+            unknown: List[str] = []
+            config = _config_from_dict(cls, data, "", unknown)
+            config.unknown_keys = unknown
+            return config
+
+    def __init__(self, config: TrainConfig, device="cuda", writer=None):
+        """device and writer are extensions: the GPU to train on, and a summary writer to use instead of the one
+        make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter otherwise)"""
+        self.config = config
+        self.device = torch.device(device)
+        os.makedirs(self.config.summary_writer_log_dir, exist_ok=True)
+        if self.config.output_model_dir is None:
+            self.config.output_model_dir = self.config.summary_writer_log_dir
+        os.makedirs(self.config.output_model_dir, exist_ok=True)
+        self.writer = writer if writer is not None else make_summary_writer(self.config.summary_writer_log_dir)
+        self.last_validation = None             # (iteration, means) of the last validation()
+
+        self.train_dataset = ImagePoseDataset(dataset_json_path=self.config.train_dataset_json_path)
+        self.val_dataset = ImagePoseDataset(dataset_json_path=self.config.val_dataset_json_path)
+        self.scene = GaussianPointCloudScene.from_parquet(
+            self.config.pointcloud_parquet_path, config=self.config.gaussian_point_cloud_scene_config, device=self.device)
+        self.adaptive_controller = GaussianPointAdaptiveController(
+            config=self.config.adaptive_controller_config,
+            maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
+                pointcloud=self.scene.point_cloud,
+                pointcloud_features=self.scene.point_cloud_features,
+                point_invalid_mask=self.scene.point_invalid_mask,
+                point_object_id=self.scene.point_object_id,
+            ), seed=self.config.seed)
+        self.rasterisation = GaussianPointCloudRasterisation(
+            config=self.config.rasterisation_config,
+            backward_valid_point_hook=self.adaptive_controller.update,
+        )
+        self.rasterisation.track_touched_rows = bool(self.config.sparse_adam)
+        self.loss_function = LossFunction(config=self.config.loss_function_config)
+        self.best_psnr_score = 0.
+
+        self.train_targets = self.val_targets = None
+        if self.config.targets_on_device:
+            self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device)
+            self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device)
+        else:
+            # batch_size=None: the dataset's items as they are; num_workers=0: no process is started behind an initialised GPU
+            self._val_loader = torch.utils.data.DataLoader(self.val_dataset, batch_size=None, shuffle=False, num_workers=0)
+        # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
+        self._order_generator = torch.Generator().manual_seed(int(self.config.seed))
+        self.view_order: List[int] = []
+
+    # ---- targets ----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _downsample_image_and_camera_info(image: torch.Tensor, camera_info: CameraInfo, downsample_factor: int):
+        """TRAIN:103-121 on whichever device the image is: the antialiased resize to (H // f, W // f), its crop to multiples of
+        16 and the intrinsics divided by f"""
+        h_full, w_full, camera_height, camera_width = downsampled_geometry(camera_info.camera_height, camera_info.camera_width,
+                                                                           downsample_factor)
+        image = resize_antialias(image, (h_full, w_full))
+        image = image[:3, :camera_height, :camera_width].contiguous()
+        return image, CameraInfo(camera_intrinsics=downsampled_intrinsics(camera_info.camera_intrinsics, downsample_factor),
+                                 camera_height=camera_height, camera_width=camera_width, camera_id=camera_info.camera_id)
+
+    def _view_at(self, iteration: int) -> int:
+        n = len(self.train_dataset)
+        while len(self.view_order) <= iteration:
+            self.view_order.extend(torch.randperm(n, generator=self._order_generator).tolist())
+        return self.view_order[iteration]
+
+    def _host_target(self, item, downsample_factor: int):
+        """the reference's path (TRAIN:149-159): a dataset item, resized on the CPU, then copied to the device"""
+        image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = item
+        if downsample_factor > 1:
+            image_gt, camera_info = self._downsample_image_and_camera_info(image_gt, camera_info, downsample_factor)
+        camera_info = CameraInfo(camera_intrinsics=camera_info.camera_intrinsics.to(self.device), camera_height=int(camera_info.camera_height),
+                                 camera_width=int(camera_info.camera_width), camera_id=camera_info.camera_id)
+        return image_gt.to(self.device), q_pointcloud_camera.to(self.device), t_pointcloud_camera.to(self.device), camera_info
+
+    def training_target(self, view: int, downsample_factor: int):
+        """-> (image (3,h,w) f32, q (1,4), t (1,3), CameraInfo) of one training view on the device, by the configured path"""
+        if self.train_targets is not None:
+            return self.train_targets.target(view, downsample_factor)
+        return self._host_target(self.train_dataset[view], downsample_factor)
+
+    def _views_from(self, iteration: int):
+        """the sampler of the host path's DataLoader: the view of every iteration from `iteration` on, without end"""
+        while True:
+            yield self._view_at(iteration)
+            iteration += 1
+
+    def _validation_targets(self):
+        if self.val_targets is not None:
+            for i in range(len(self.val_targets)):
+                yield self.val_targets.target(i, 1)
+        else:
+            for item in self._val_loader:
+                yield self._host_target(item, 1)
+
+    def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band):
+        return GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput(
+            point_cloud=self.scene.point_cloud,
+            point_cloud_features=self.scene.point_cloud_features,
+            point_object_id=self.scene.point_object_id,
+            point_invalid_mask=self.scene.point_invalid_mask,
+            camera_info=camera_info,
+            q_pointcloud_camera=q_pointcloud_camera,
+            t_pointcloud_camera=t_pointcloud_camera,
+            color_max_sh_band=color_max_sh_band,
+        )
+
+    # ---- the loop ---------------------------------------------------------------------------------------------------------
+    def train(self):
+        config = self.config
+        if self.train_targets is None:
+            train_items = iter(torch.utils.data.DataLoader(self.train_dataset, batch_size=None, sampler=self._views_from(0), num_workers=0))
+        optimizer = FusedAdam([self.scene.point_cloud_features], lr=config.feature_learning_rate, betas=(0.9, 0.999))
+        position_optimizer = FusedAdam([self.scene.point_cloud], lr=config.position_learning_rate, betas=(0.9, 0.999))
+        self.optimizer, self.position_optimizer = optimizer, position_optimizer
+        downsample_factor = config.initial_downsample_factor
+        try:
+            from tqdm import tqdm
+            iterations = tqdm(range(config.num_iterations), disable=None)
+        except Exception:
+            iterations = range(config.num_iterations)
+        for iteration in iterations:
+            if iteration % config.half_downsample_factor_interval == 0 and iteration > 0 and downsample_factor > 1:
+                downsample_factor = downsample_factor // 2
+            optimizer.zero_grad()
+            position_optimizer.zero_grad()
+
+            if self.train_targets is not None:
+                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self.train_targets.target(
+                    self._view_at(iteration), downsample_factor)
+            else:
+                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self._host_target(next(train_items), downsample_factor)
+            rasterisation_input = self._rasterisation_input(
+                camera_info, q_pointcloud_camera, t_pointcloud_camera,
+                color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval))
+            image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
+            # hxwx3->3xhxw, read where it lies; the clamp to [0, 1] runs inside the loss kernels
+            image_pred = image_pred.permute(2, 0, 1)
+            loss, l1_loss, ssim_loss = self.loss_function(
+                image_pred,
+                image_gt,
+                point_invalid_mask=self.scene.point_invalid_mask,
+                pointcloud_features=self.scene.point_cloud_features,
+                clamp_predicted=True)
+            loss.backward()
+            rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
+            optimizer.step(rows=rows)
+            position_optimizer.step(rows=rows)
+
+            if iteration % config.position_learning_rate_decay_interval == 0:
+                position_optimizer.lr *= config.position_learning_rate_decay_rate
+            self.adaptive_controller.refinement()
+
+            # (the reference reads loss.item() every iteration to pick "problematic" images for its image log; there is no
+            # image log here, so the loss is read -- and the host waits for the device -- only where it is logged)
+            if iteration % config.log_loss_interval == 0:
+                loss_value = loss.item()
+                self.writer.add_scalar("train/loss", loss_value, iteration)
+                self.writer.add_scalar("train/l1 loss", l1_loss.item(), iteration)
+                self.writer.add_scalar("train/ssim loss", ssim_loss.item(), iteration)
+                if config.print_metrics_to_console:
+                    print(f"train_iteration={iteration};")
+                    print(f"train_loss={loss_value};")
+                    print(f"train_l1_loss={l1_loss.item()};")
+                    print(f"train_ssim_loss={ssim_loss.item()};")
+            if iteration % config.log_metrics_interval == 0:
+                with torch.no_grad():
+                    psnr_score, ssim_score = self._compute_pnsr_and_ssim(torch.clamp(image_pred.detach(), 0, 1), image_gt)
+                    self.writer.add_scalar("value/num_valid_points", int((self.scene.point_invalid_mask == 0).sum().item()), iteration)
+                self.writer.add_scalar("train/psnr", psnr_score.item(), iteration)
+                self.writer.add_scalar("train/ssim", ssim_score.item(), iteration)
+                if config.print_metrics_to_console:
+                    print(f"train_psnr={psnr_score.item()};")
+                    print(f"train_psnr_{iteration}={psnr_score.item()};")
+                    print(f"train_ssim={ssim_score.item()};")
+                    print(f"train_ssim_{iteration}={ssim_score.item()};")
+            del image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, rasterisation_input, image_pred, loss, l1_loss, ssim_loss
+            # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
+            if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
+                self.validation(iteration)
+        if hasattr(self.writer, "flush"):
+            self.writer.flush()
+
+    def _compute_pnsr_and_ssim(self, image_pred, image_gt):
+        """PSNR = 10 log10(1 / mse); SSIM = 1 - the third term of the loss (pytorch_msssim.ssim's definition, in its kernels)"""
+        with torch.no_grad():
+            psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+            _, _, ssim_loss = self.loss_function(image_pred, image_gt)
+            return psnr_score, 1.0 - ssim_loss
+
+    def validation(self, iteration):
+        """TRAIN:342-423: every validation view at band 3 and full resolution; the means of loss, PSNR, SSIM and of the
+        rasteriser's time by device events are logged, the scene written as scene_<iteration>.parquet and, when the mean PSNR is
+        the best so far, as best_scene.parquet.  -> the means, as a dict"""
+        with torch.no_grad():
+            total_loss = total_psnr_score = total_ssim_score = total_inference_time = 0.0
+            count = 0
+            for image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info in self._validation_targets():
+                start_event = torch.cuda.Event(enable_timing=True)
+                end_event = torch.cuda.Event(enable_timing=True)
+                rasterisation_input = self._rasterisation_input(camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band=3)
+                start_event.record()
+                image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
+                end_event.record()
+                torch.cuda.synchronize()
+                total_inference_time += start_event.elapsed_time(end_event)
+                image_pred = torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
+                loss, _, ssim_loss = self.loss_function(image_pred, image_gt)
+                psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+                total_loss += loss.item()
+                total_psnr_score += psnr_score.item()
+                total_ssim_score += 1.0 - ssim_loss.item()
+                count += 1
+            count = max(count, 1)
+            means = dict(loss=total_loss / count, psnr=total_psnr_score / count, ssim=total_ssim_score / count,
+                         inference_time=total_inference_time / count)
+            for name, value in means.items():
+                self.writer.add_scalar(f"val/{name}", value, iteration)
+            if self.config.print_metrics_to_console:
+                print(f"val_loss={means['loss']};")
+                print(f"val_psnr={means['psnr']};")
+                print(f"val_psnr_{iteration}={means['psnr']};")
+                print(f"val_ssim={means['ssim']};")
+                print(f"val_ssim_{iteration}={means['ssim']};")
+                print(f"val_inference_time={means['inference_time']};")
+            self.scene.to_parquet(os.path.join(self.config.output_model_dir, f"scene_{iteration}.parquet"))
+            if means["psnr"] > self.best_psnr_score:
+                self.best_psnr_score = means["psnr"]
+                self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
+            if hasattr(self.writer, "flush"):
+                self.writer.flush()
+            self.last_validation = (iteration, means)
+            return means

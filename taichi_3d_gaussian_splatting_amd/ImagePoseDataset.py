@@ -1,0 +1,79 @@
+"""ImagePoseDataset -- the reference's dataset (taichi_3d_gaussian_splatting/ImagePoseDataset.py) without torchvision:
+the same JSON (pandas, orient="records"), the same item (image (3,H,W) f32 on the CPU, q (1,4), t (1,3), CameraInfo), the
+intrinsics rescaled to the real image size, the crop to multiples of 16 and the autoscale of images over 1600 pixels.
+to_tensor is uint8 / 255 and the antialiased resize is F.interpolate(mode="bilinear", antialias=True): the operator
+torchvision's resize calls.  load_raw() is the decoded image before any of that, for targets.TargetStore."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+import torch.utils.data
+
+from .Camera import CameraInfo
+from .targets import MAX_RESOLUTION_TRAIN, autoscaled_camera_info  # noqa: F401
+from .utils import SE3_to_quaternion_and_translation_torch
+
+TILE_WIDTH = TILE_HEIGHT = 16
+
+
+def resize_antialias(image: torch.Tensor, size) -> torch.Tensor:
+    """torchvision.transforms.functional.resize(image, size=(h, w), antialias=True) of a float (C,H,W) tensor"""
+    return F.interpolate(image.unsqueeze(0), size=(int(size[0]), int(size[1])), mode="bilinear", antialias=True,
+                         align_corners=False).squeeze(0)
+
+
+REQUIRED_COLUMNS = ("image_path", "T_pointcloud_camera", "camera_intrinsics", "camera_height", "camera_width", "camera_id")
+
+
+def _f32(field) -> torch.Tensor:
+    """a JSON field (nested lists, an array or a tensor) as a float32 tensor of its own"""
+    if isinstance(field, torch.Tensor):
+        return field.to(torch.float32).clone()
+    return torch.from_numpy(np.array(field, dtype=np.float32))
+
+
+class ImagePoseDataset(torch.utils.data.Dataset):
+    """Images, poses and camera intrinsics of one dataset JSON: a list of records with REQUIRED_COLUMNS."""
+
+    def __init__(self, dataset_json_path: str):
+        super().__init__()
+        import pandas as pd         # here and not at the top: importing the package needs neither pandas nor PIL
+        self.df = pd.read_json(dataset_json_path, orient="records")
+        missing = [c for c in REQUIRED_COLUMNS if c not in self.df.columns]
+        assert not missing, f"column {missing[0]} is not in the dataset"
+
+    def __len__(self):
+        return len(self.df)
+
+    @staticmethod
+    def _autoscale_image_and_camera_info(image: torch.Tensor, camera_info: CameraInfo):
+        """an image over MAX_RESOLUTION_TRAIN on either side: resize(size=1024, max_size=1600, antialias=True), the crop to
+        multiples of 16 and the intrinsics scaled with it (ImagePoseDataset.py:41-62); anything else passes unchanged"""
+        size_full, resized_info = autoscaled_camera_info(camera_info)
+        if size_full is None:
+            return image, camera_info
+        image = resize_antialias(image, size_full)
+        return image[:3, :resized_info.camera_height, :resized_info.camera_width].contiguous(), resized_info
+
+    def load_raw(self, idx):
+        """-> (image uint8 (H,W,3|4) CPU tensor as decoded, uncropped; q (1,4); t (1,3); CameraInfo of the cropped image:
+        intrinsics rescaled to the real image size, height and width cut to multiples of 16, before any autoscale)"""
+        import PIL.Image
+        row = self.df.iloc[idx]
+        q, t = SE3_to_quaternion_and_translation_torch(_f32(row["T_pointcloud_camera"]).unsqueeze(0))
+        with PIL.Image.open(row["image_path"]) as pil:
+            image = torch.from_numpy(np.array(pil if pil.mode in ("RGB", "RGBA") else pil.convert("RGB"), dtype=np.uint8))
+        height, width = image.shape[0], image.shape[1]
+        # the JSON's size is COLMAP's; the intrinsics follow the size the file really has
+        k = _f32(row["camera_intrinsics"])
+        k[0, :] = k[0, :] * width / row["camera_width"]
+        k[1, :] = k[1, :] * height / row["camera_height"]
+        info = CameraInfo(camera_intrinsics=k, camera_height=height - height % TILE_HEIGHT, camera_width=width - width % TILE_WIDTH,
+                          camera_id=row["camera_id"])
+        return image, q, t, info
+
+    def __getitem__(self, idx):
+        image, q, t, info = self.load_raw(idx)
+        image = image.permute(2, 0, 1).to(torch.float32).div(255)               # torchvision's to_tensor
+        image = image[:3, :info.camera_height, :info.camera_width].contiguous()
+        image, info = ImagePoseDataset._autoscale_image_and_camera_info(image, info)
+        return image, q, t, info

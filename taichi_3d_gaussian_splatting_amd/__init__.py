@@ -6,3 +6,7 @@ from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation  # 
 from .controller_stats import ControllerAccumulators  # noqa: F401
 from .GaussianPointAdaptiveController import GaussianPointAdaptiveController  # noqa: F401
 from .GaussianPointCloudScene import GaussianPointCloudScene  # noqa: F401
+from .LossFunction import LossFunction  # noqa: F401
+from .ImagePoseDataset import ImagePoseDataset  # noqa: F401
+from .targets import TargetStore, image_resample  # noqa: F401
+from .GaussianPointTrainer import GaussianPointCloudTrainer  # noqa: F401

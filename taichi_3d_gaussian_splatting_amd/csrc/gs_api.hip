@@ -6,11 +6,13 @@
 #include "../../include/gs_sparse.h"
 #include "../../include/gs_knn.h"
 #include "../../include/gs_exchange.h"
+#include "../../include/gs_targets.h"
 #include "gs_common.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -119,6 +121,14 @@ void gs_prof_end(GsProf* p, int rec, hipStream_t s)
     (void)hipEventRecord(p->recs[rec].b, s);
 }
 
+// gs_image_resample: both axes of one geometry on the device (start, count, weight of x, then of y, in one buffer)
+struct ResampleTable {
+    int H_in = 0, W_in = 0, h_full = 0, w_full = 0;
+    DevBuf buf;
+    GsResampleAxis ax{}, ay{};
+    std::vector<unsigned char> host;    // what the upload reads: lives as long as the table
+};
+
 #define GS_COUNTER_SLOTS 64
 struct gs_ctx {
     int device = 0;
@@ -143,6 +153,7 @@ struct gs_ctx {
     DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
     DevBuf merge_tags, merge_ids;          // gs_merge_rows: one tag byte per point-cloud row, the id words of all lists (block totals: row_block_totals)
     DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
+    std::vector<struct ResampleTable*> resample_tables;   // gs_image_resample: the tables of the geometries seen, oldest first
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
     uint64_t slots_busy = 1ull;            // slot 0 serves the calls that wait at once; the others belong to frames begun and not yet read
@@ -204,6 +215,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree };
     for (DevBuf* b : all) b->release(&c->device_bytes);
+    for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : c->prof.spare) (void)hipEventDestroy(e);
     if (c->switch_event) (void)hipEventDestroy(c->switch_event);
@@ -1410,6 +1422,120 @@ extern "C" int gs_knn(gs_ctx* c, const float* xyz, const int8_t* invalid_mask, i
     hipStream_t s;
     if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     gs_launch_knn(xyz, invalid_mask, n_points, k, d2_out, idx_out, c->knn_sort.p, c->knn_hist.p, c->knn_points.p, c->knn_tree.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- training targets (include/gs_targets.h, k_targets.hip) -------------------------------------------------------------------
+// One axis of ATen's _upsample_bilinear2d_aa (align_corners = false) for in >= out, in float64: window and normalised weights of
+// every output, the zero weights at either end of a window dropped.  -> the largest tap count.
+static int resample_axis(int in, int out, std::vector<int32_t>& start, std::vector<int32_t>& count, std::vector<std::vector<double>>& weights)
+{
+    const double scale = (double)in / (double)out, support = scale;
+    int taps = 0;
+    start.resize(out); count.resize(out); weights.resize(out);
+    for (int i = 0; i < out; ++i) {
+        const double center = scale * (i + 0.5);
+        const int64_t lo = std::max<int64_t>((int64_t)(center - support + 0.5), 0);
+        const int64_t hi = std::min<int64_t>((int64_t)(center + support + 0.5), in);
+        std::vector<double> w;
+        double sum = 0.0;
+        for (int64_t j = lo; j < hi; ++j) {
+            const double x = ((double)j - center + 0.5) / scale;
+            w.push_back(std::max(0.0, 1.0 - std::fabs(x)));
+            sum += w.back();
+        }
+        for (double& v : w) v /= sum;
+        size_t a = 0, b = w.size();
+        while (b - a > 1 && w[b - 1] == 0.0) --b;
+        while (b - a > 1 && w[a] == 0.0) ++a;
+        start[i] = (int32_t)(lo + (int64_t)a); count[i] = (int32_t)(b - a);
+        weights[i].assign(w.begin() + a, w.begin() + b);
+        taps = std::max(taps, count[i]);
+    }
+    return taps;
+}
+
+// what k_image_resample relies on: windows inside the input, moving right, at most GS_RS_MAX_TAPS wide, and a tile's span bounded
+static bool resample_axis_ok(int in, const std::vector<int32_t>& start, const std::vector<int32_t>& count, int tile)
+{
+    const int out = (int)start.size();
+    for (int i = 0; i < out; ++i) {
+        if (count[i] < 1 || count[i] > GS_RS_MAX_TAPS || start[i] < 0 || start[i] + count[i] > in) return false;
+        if (i > 0 && (start[i] < start[i - 1] || start[i] + count[i] < start[i - 1] + count[i - 1])) return false;
+    }
+    for (int i0 = 0; i0 < out; i0 += tile) {
+        const int i1 = std::min(out, i0 + tile) - 1;
+        if (start[i1] + count[i1] - start[i0] > GS_RS_MAX_SPAN) return false;
+    }
+    return true;
+}
+
+// the cached tables of a geometry, or new ones: made, allocated and queued for upload on s (mutex held, device current)
+static int resample_tables(gs_ctx* c, int H_in, int W_in, int h_full, int w_full, hipStream_t s, ResampleTable** out)
+{
+    for (ResampleTable* rt : c->resample_tables)
+        if (rt->H_in == H_in && rt->W_in == W_in && rt->h_full == h_full && rt->w_full == w_full) { *out = rt; return GS_OK; }
+    std::vector<int32_t> xs, xc, ys, yc;
+    std::vector<std::vector<double>> xw, yw;
+    const int tx = resample_axis(W_in, w_full, xs, xc, xw), ty = resample_axis(H_in, h_full, ys, yc, yw);
+    if (!resample_axis_ok(W_in, xs, xc, GS_RESAMPLE_TILE_W) || !resample_axis_ok(H_in, ys, yc, GS_RESAMPLE_TILE_H))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the windows of this geometry do not fit the kernel's tile");
+    // layout (4-byte words): x start, x count, x weights (w_full * tx), y start, y count, y weights (h_full * ty)
+    const size_t words = 2 * (size_t)w_full + (size_t)w_full * tx + 2 * (size_t)h_full + (size_t)h_full * ty;
+    ResampleTable* rt = new ResampleTable();
+    rt->H_in = H_in; rt->W_in = W_in; rt->h_full = h_full; rt->w_full = w_full;
+    rt->host.assign(words * 4, 0);
+    int32_t* hi = reinterpret_cast<int32_t*>(rt->host.data());
+    float* hf = reinterpret_cast<float*>(rt->host.data());
+    size_t o = 0;
+    const size_t o_xs = o; for (int i = 0; i < w_full; ++i) hi[o++] = xs[i];
+    const size_t o_xc = o; for (int i = 0; i < w_full; ++i) hi[o++] = xc[i];
+    const size_t o_xw = o; for (int i = 0; i < w_full; ++i) for (int k = 0; k < tx; ++k) hf[o++] = k < xc[i] ? (float)xw[i][k] : 0.0f;
+    const size_t o_ys = o; for (int i = 0; i < h_full; ++i) hi[o++] = ys[i];
+    const size_t o_yc = o; for (int i = 0; i < h_full; ++i) hi[o++] = yc[i];
+    const size_t o_yw = o; for (int i = 0; i < h_full; ++i) for (int k = 0; k < ty; ++k) hf[o++] = k < yc[i] ? (float)yw[i][k] : 0.0f;
+    if (rt->buf.ensure(words * 4, &c->device_bytes) != hipSuccess) { delete rt; return fail(GS_ERR_OUT_OF_MEMORY, "device allocation failed: resample tables"); }
+    const hipError_t e = hipMemcpyAsync(rt->buf.p, rt->host.data(), words * 4, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { rt->buf.release(&c->device_bytes); delete rt; return fail(GS_ERR_HIP, std::string("resample tables: ") + hipGetErrorString(e)); }
+    const int32_t* di = rt->buf.as<int32_t>();
+    const float* df = rt->buf.as<float>();
+    rt->ax = GsResampleAxis{ di + o_xs, di + o_xc, df + o_xw, tx };
+    rt->ay = GsResampleAxis{ di + o_ys, di + o_yc, df + o_yw, ty };
+    if (c->resample_tables.size() >= GS_RESAMPLE_MAX_GEOMETRIES) {       // the oldest goes (hipFree waits for what still reads it)
+        ResampleTable* old = c->resample_tables.front();
+        c->resample_tables.erase(c->resample_tables.begin());
+        old->buf.release(&c->device_bytes);
+        delete old;
+    }
+    c->resample_tables.push_back(rt);
+    *out = rt;
+    return GS_OK;
+}
+
+extern "C" int gs_image_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
+                                 int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
+                                 gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: ctx is NULL");
+    if (src_format != GS_IMAGE_U8_HWC && src_format != GS_IMAGE_F32_CHW) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: unknown src_format");
+    if (src_channels != 3 && src_channels != 4) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: src_channels must be 3 or 4");
+    for (int32_t v : { H_in, W_in, h_full, w_full, h_out, w_out })
+        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: every size must be in [0, 32768]");
+    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
+    if (src_format == GS_IMAGE_U8_HWC ? src_row_pitch_bytes < (int64_t)W_in * src_channels : src_row_pitch_bytes != (int64_t)W_in * 4)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: src_row_pitch_bytes must be >= W_in * src_channels (uint8), W_in * 4 (f32)");
+    if (h_out == 0 || w_out == 0) return GS_OK;
+    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: NULL src or dst");
+    if (H_in < h_full || W_in < w_full || (int64_t)H_in > (int64_t)GS_RESAMPLE_MAX_SCALE * h_full || (int64_t)W_in > (int64_t)GS_RESAMPLE_MAX_SCALE * w_full)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the scale in / out must be in [1, 8] on both axes (no upscaling)");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    int rc;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    ResampleTable* rt = nullptr;
+    if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
+    gs_launch_image_resample(src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, rt->ax, rt->ay, h_out, w_out, dst, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -519,6 +519,15 @@ size_t gs_knn_points_bytes(int64_t n);
 size_t gs_knn_tree_bytes(int64_t n);
 void gs_launch_knn(const float* xyz, const int8_t* invalid, int64_t n, int k, float* d2_out, int32_t* idx_out,
                    void* sort_ws, void* hist_ws, void* pts_ws, void* tree_ws, hipStream_t s);
+// k_targets.hip (include/gs_targets.h): the (h_out, w_out) crop of the antialiased resize of a resident image.  One axis of the
+// resize as the host made it (gs_api.hip: float64, rounded once): output i reads `count[i]` inputs from `start[i]` on with the
+// weights weight[i * taps .. + count[i]); taps <= GS_RS_MAX_TAPS.  The launcher trusts what gs_image_resample checked: the
+// window of GS_RESAMPLE_TILE_W consecutive outputs spans at most GS_RS_MAX_SPAN input pixels.
+#define GS_RS_MAX_TAPS 18
+#define GS_RS_MAX_SPAN 524
+struct GsResampleAxis { const int32_t* start; const int32_t* count; const float* weight; int taps; };
+void gs_launch_image_resample(const void* src, int src_format, int channels, int H_in, int W_in, int64_t pitch_bytes, GsResampleAxis ax,
+                              GsResampleAxis ay, int h_out, int w_out, float* dst, hipStream_t s);
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s);
 void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, const float* value_and_count, const float* upstream,
                         float* grad, hipStream_t s);

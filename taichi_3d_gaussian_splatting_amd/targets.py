@@ -1,0 +1,223 @@
+"""Training targets on the device (include/gs_targets.h, csrc/k_targets.hip).
+
+image_resample() is the library call: the top-left crop of the antialiased bilinear down-resize of a resident image --
+torchvision's resize(antialias=True) on a float tensor, i.e. ATen's _upsample_bilinear2d_aa -- from uint8 HWC (any row pitch)
+or f32 CHW to f32 CHW, in one launch.  TargetStore keeps a dataset's images on the device as the uint8 they were decoded to
+and hands out, per step, what the reference trainer makes on the host from a DataLoader item
+(GaussianPointTrainer.py:103-121, 149-159): the (3,h,w) f32 image at the current downsample factor, the pose and the
+CameraInfo with its intrinsics divided by the factor.
+
+There is no fallback path: every call goes through _native.call(), and a CPU tensor is refused.
+"""
+import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
+from typing import Optional, Tuple
+
+import torch
+
+from . import _native
+from .Camera import CameraInfo
+
+FORMAT_U8_HWC, FORMAT_F32_CHW = 0, 1
+# the output tile of one workgroup (GS_RESAMPLE_TILE_H / _W in gs_targets.h) and the bounds of a call
+TILE_H, TILE_W = 16, 64
+MAX_SCALE = 8
+MAX_SIZE = 32768
+ROW_PITCH_ALIGN = 16            # bytes: rows of a stored image start on 16-byte boundaries (aligned 16-byte loads)
+MAX_RESOLUTION_TRAIN = 1600     # ImagePoseDataset.py:13
+MAX_DECODE_THREADS = 8
+
+_VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
+ARGTYPES = {
+    # (ctx, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out, w_out, dst, stream)
+    "gs_image_resample": [_VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _VP, _VP],
+}
+_bound = False
+
+
+def _bind():
+    """argtypes of the entry point, set once on the loaded library (it is not part of _native.SYMBOLS)"""
+    global _bound
+    if not _bound:
+        L = _native.lib()
+        for name, argtypes in ARGTYPES.items():
+            if not hasattr(L, name):
+                raise _native.NativeLibraryError(f"{_native.LIB_PATH} does not export {name}")
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
+        _bound = True
+
+
+def _source_layout(src):
+    """-> (format, channels, H, W, row pitch in bytes) of a source tensor, or ValueError"""
+    if not isinstance(src, torch.Tensor) or src.dim() != 3:
+        raise ValueError("the source must be a uint8 (H,W,C) or a float32 (C,H,W) tensor")
+    if not src.is_cuda:
+        raise ValueError(f"targets are resampled on the GPU: the source is on {src.device}, move it to a cuda/hip device first "
+                         "(there is no CPU path)")
+    if src.dtype == torch.uint8:
+        H, W, ch = src.shape
+        if ch not in (3, 4) or (W > 0 and H > 0 and (src.stride(2) != 1 or src.stride(1) != ch or (H > 1 and src.stride(0) < W * ch))):
+            raise ValueError("a uint8 source must be (H,W,3) or (H,W,4) with dense pixels and a row stride >= W*C")
+        return FORMAT_U8_HWC, ch, H, W, (src.stride(0) if H > 1 else W * ch)
+    if src.dtype == torch.float32:
+        ch, H, W = src.shape
+        if ch not in (3, 4) or not src.is_contiguous():
+            raise ValueError("a float32 source must be a contiguous (3,H,W) or (4,H,W) tensor")
+        return FORMAT_F32_CHW, ch, H, W, W * 4
+    raise ValueError(f"the source must be uint8 or float32, got {src.dtype}")
+
+
+def image_resample(src: torch.Tensor, size_full: Tuple[int, int], size_out: Optional[Tuple[int, int]] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> (3, h_out, w_out) f32: the top-left size_out crop (default: all) of the antialiased resize of src to size_full.
+    src: uint8 (H,W,3|4) with any row stride, or contiguous f32 (3|4,H,W); channel 3 is ignored.  The scale H / h_full and
+    W / w_full must be in [1, 8].  Queued on the current stream of the source's device; no host synchronisation.  out: the tensor
+    to write (contiguous f32 (3,h_out,w_out) on the same device); a new one otherwise."""
+    _bind()
+    fmt, ch, H, W, pitch = _source_layout(src)
+    h_full, w_full = int(size_full[0]), int(size_full[1])
+    h_out, w_out = (h_full, w_full) if size_out is None else (int(size_out[0]), int(size_out[1]))
+    if out is None:
+        if min(h_out, w_out) < 0:
+            raise ValueError("the output size must not be negative")
+        out = torch.empty((3, h_out, w_out), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or out.device != src.device or tuple(out.shape) != (3, h_out, w_out) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 (3,{h_out},{w_out}) tensor on {src.device}")
+    _native.call("gs_image_resample", src.device, _native.shared_ctx(src.device), _native.ptr(src), fmt, ch, H, W, pitch,
+                 h_full, w_full, h_out, w_out, _native.ptr(out))
+    return out
+
+
+def autoscale_size(height: int, width: int, size: int = 1024, max_size: int = MAX_RESOLUTION_TRAIN) -> Tuple[int, int]:
+    """(h, w) of torchvision's resize(size=1024, max_size=1600): the short side to `size`, the long side capped at max_size"""
+    short, long = (width, height) if width <= height else (height, width)
+    new_short, new_long = size, int(size * long / short)
+    if new_long > max_size:
+        new_short, new_long = int(max_size * new_short / new_long), max_size
+    return (new_long, new_short) if width <= height else (new_short, new_long)
+
+
+def downsampled_geometry(height: int, width: int, downsample_factor: int) -> Tuple[int, int, int, int]:
+    """-> (h_full, w_full, h, w) of _downsample_image_and_camera_info (GaussianPointTrainer.py:104-108): the resize to
+    (H // f, W // f) and its crop to multiples of 16"""
+    h_full, w_full = height // downsample_factor, width // downsample_factor
+    return h_full, w_full, h_full - h_full % 16, w_full - w_full % 16
+
+
+def downsampled_intrinsics(camera_intrinsics: torch.Tensor, downsample_factor: int) -> torch.Tensor:
+    """fx, fy, cx, cy divided by the factor (GaussianPointTrainer.py:110-115); (3,3) or (n,3,3), a new tensor"""
+    k = camera_intrinsics.clone()
+    k[..., 0, 0] /= downsample_factor
+    k[..., 1, 1] /= downsample_factor
+    k[..., 0, 2] /= downsample_factor
+    k[..., 1, 2] /= downsample_factor
+    return k
+
+
+def scaled_intrinsics(camera_intrinsics: torch.Tensor, scale_x: float, scale_y: float) -> torch.Tensor:
+    """fx, cx times scale_x and fy, cy times scale_y (the autoscale of ImagePoseDataset.py:46-56); a new (3,3) tensor"""
+    k = camera_intrinsics.clone()
+    k[0, 0] *= scale_x
+    k[1, 1] *= scale_y
+    k[0, 2] *= scale_x
+    k[1, 2] *= scale_y
+    return k
+
+
+def autoscaled_camera_info(camera_info: CameraInfo):
+    """-> ((h_full, w_full) of the autoscale resize, the CameraInfo behind it: cropped to multiples of 16, intrinsics scaled by
+    resized / original size), or (None, camera_info) for an image within MAX_RESOLUTION_TRAIN"""
+    H, W = int(camera_info.camera_height), int(camera_info.camera_width)
+    if H <= MAX_RESOLUTION_TRAIN and W <= MAX_RESOLUTION_TRAIN:
+        return None, camera_info
+    h_full, w_full = autoscale_size(H, W)
+    return (h_full, w_full), CameraInfo(camera_intrinsics=scaled_intrinsics(camera_info.camera_intrinsics, w_full / W, h_full / H),
+                                        camera_height=h_full - h_full % 16, camera_width=w_full - w_full % 16,
+                                        camera_id=camera_info.camera_id)
+
+
+def _pitched_uint8(image_hwc: torch.Tensor, device) -> torch.Tensor:
+    """a (H,W,C) uint8 CPU tensor on the device, rows ROW_PITCH_ALIGN-byte aligned: a view into a (H, pitch) buffer"""
+    H, W, ch = image_hwc.shape
+    pitch = (W * ch + ROW_PITCH_ALIGN - 1) // ROW_PITCH_ALIGN * ROW_PITCH_ALIGN
+    host = torch.zeros((H, pitch), dtype=torch.uint8)
+    host[:, :W * ch] = image_hwc.reshape(H, W * ch)
+    return host.to(device).as_strided((H, W, ch), (pitch, ch, 1))
+
+
+class TargetStore:
+    """The images of a dataset resident on one device, and the per-step target made from them there.
+
+    from_dataset() decodes every image once, in this process (no worker processes: the GPU may be initialised), and keeps
+      - the image as uint8 (H,W,C) with 16-byte aligned rows, uncropped: the dataset's crop to multiples of 16 is the top-left
+        region the kernel reads; or, for an image over MAX_RESOLUTION_TRAIN, its autoscaled version (resize(size=1024,
+        max_size=1600) of the cropped image, ImagePoseDataset.py:41-62) as f32 (3,h,w), made once by the same kernel;
+      - q (n,4), t (n,3) and the intrinsics (n,3,3) as device tensors, and the base CameraInfo of every view.
+    target(i, f) then costs one launch.  The image it returns is the store's buffer for that geometry and is overwritten by the
+    next target() of the same geometry: use it (loss forward and backward) before asking for the next one."""
+
+    def __init__(self, images, q: torch.Tensor, t: torch.Tensor, camera_infos, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"a TargetStore lives on a GPU, got {self.device} (there is no CPU path)")
+        self.images = list(images)
+        self.q, self.t = q.to(self.device), t.to(self.device)
+        self.camera_infos = list(camera_infos)      # intrinsics on the device: views of self.intrinsics[1]
+        self.intrinsics = {1: torch.stack([c.camera_intrinsics.to(torch.float32) for c in self.camera_infos]).to(self.device)}
+        for i, c in enumerate(self.camera_infos):
+            self.camera_infos[i] = CameraInfo(camera_intrinsics=self.intrinsics[1][i], camera_height=int(c.camera_height),
+                                              camera_width=int(c.camera_width), camera_id=c.camera_id)
+        self._out = {}                              # (H, W, factor) -> the (3,h,w) buffer of that geometry
+        self._infos = {}                            # (view, factor) -> CameraInfo
+
+    def __len__(self):
+        return len(self.images)
+
+    @classmethod
+    def from_dataset(cls, dataset, device="cuda") -> "TargetStore":
+        device = torch.device(device)
+        n = len(dataset)
+        with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
+            raw = list(pool.map(dataset.load_raw, range(n)))
+        images, qs, ts, infos = [], [], [], []
+        for image_hwc, q, t, info in raw:
+            stored = _pitched_uint8(image_hwc, device)
+            H, W = int(info.camera_height), int(info.camera_width)          # the dataset's crop of the decoded image
+            size_full, info = autoscaled_camera_info(info)
+            if size_full is not None:
+                stored = image_resample(stored[:H, :W], size_full, (info.camera_height, info.camera_width))
+            images.append(stored)
+            qs.append(q.reshape(4))
+            ts.append(t.reshape(3))
+            infos.append(info)
+        return cls(images, torch.stack(qs).to(torch.float32), torch.stack(ts).to(torch.float32), infos, device)
+
+    def _source(self, i):
+        image, info = self.images[i], self.camera_infos[i]
+        if image.dtype == torch.uint8:
+            return image[:info.camera_height, :info.camera_width]
+        return image
+
+    def target(self, i: int, downsample_factor: int = 1):
+        """-> (image (3,h,w) f32, q (1,4), t (1,3), CameraInfo) of view i at the factor: sizes and intrinsics as
+        _downsample_image_and_camera_info has them; at factor 1 the dataset's own crop.  After the first use of a geometry
+        (image size, factor) the call allocates nothing on the device, copies nothing to it and does not synchronise."""
+        f = int(downsample_factor)
+        if f < 1:
+            raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
+        base = self.camera_infos[i]
+        H, W = base.camera_height, base.camera_width
+        h_full, w_full, h, w = downsampled_geometry(H, W, f)
+        key = (H, W, f)
+        out = self._out.get(key)
+        if out is None:
+            out = self._out[key] = torch.empty((3, h, w), dtype=torch.float32, device=self.device)
+        if f not in self.intrinsics:
+            self.intrinsics[f] = downsampled_intrinsics(self.intrinsics[1], f)
+        info = self._infos.get((i, f))
+        if info is None:
+            info = self._infos[(i, f)] = CameraInfo(camera_intrinsics=self.intrinsics[f][i], camera_height=h, camera_width=w,
+                                                    camera_id=base.camera_id)
+        image_resample(self._source(i), (h_full, w_full), (h, w), out=out)
+        return out, self.q[i:i + 1], self.t[i:i + 1], info

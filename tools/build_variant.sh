@@ -9,7 +9,7 @@ obj=$root/build_ab/obj_$name
 mkdir -p $obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wall -Wno-unused-function"
 pids=()
-for f in gs_api k_project k_binning k_blend_fwd k_backward k_export k_loss k_density k_pose k_channels k_sparse k_knn; do
+for f in gs_api k_project k_binning k_blend_fwd k_backward k_export k_loss k_density k_pose k_channels k_sparse k_knn k_exchange k_targets; do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c $src/$f.hip -o $obj/$f.o &
   pids+=($!)
 done
