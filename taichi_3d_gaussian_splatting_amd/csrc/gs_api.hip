@@ -8,6 +8,7 @@
 #include "../../include/gs_exchange.h"
 #include "../../include/gs_targets.h"
 #include "gs_common.h"
+#include "gs_sort_key.h"
 
 #include <algorithm>
 #include <atomic>
@@ -75,7 +76,7 @@ struct Frame {
     gs_frame_info info{};
     int depth_bits = 0;
     void* keys_sorted = nullptr;
-    int key64 = 0;
+    int key_bytes = 4;                  // element of the key arrays: 2, 4 or 8 (gs_sort_key.h)
     int32_t* vals_sorted = nullptr;
     bool live = false;
     int cut_cap = 0;                    // list-cut records the forward of this frame could claim (0: it wrote none)
@@ -482,6 +483,25 @@ static bool sort_first_pass_enabled(int64_t rows)
     return !(e && e[0] == '0');
 }
 
+// The narrow key class (gs_sort_key.h: 16-bit keys without the byte k_keygen's first pass has placed), GS_SORT_NARROW_KEYS, read on
+// every call like GS_SORT_FIRST_PASS: 0 keeps the 32-bit layout everywhere, 1 takes the narrow one where a frame can, "require"
+// does the same and makes a forward whose frame ended up in another class fail with GS_ERR_STATE (tests prove with it which path ran).
+#define GS_NARROW_KEYS_DEFAULT 1
+enum NarrowKeys { NARROW_OFF, NARROW_ON, NARROW_REQUIRED };
+static NarrowKeys sort_narrow_keys()
+{
+    const char* e = getenv("GS_SORT_NARROW_KEYS");
+    if (!e || !e[0]) return GS_NARROW_KEYS_DEFAULT ? NARROW_ON : NARROW_OFF;
+    if (e[0] == '0') return NARROW_OFF;
+    return strcmp(e, "require") == 0 ? NARROW_REQUIRED : NARROW_ON;
+}
+static int check_required_key_class(const Frame* f)
+{
+    if (sort_narrow_keys() == NARROW_REQUIRED && f->key_bytes != 2)
+        return fail(GS_ERR_STATE, "GS_SORT_NARROW_KEYS=require: the frame's sort keys are " + std::to_string(f->key_bytes) + " bytes wide");
+    return GS_OK;
+}
+
 // ---- per-point half: filter, compaction, projection (+ tile counts, scan, publication) ----------------------------
 // On success the frame's buffers hold mask / ids / cam_index / records / box / ntiles.  The counters (M, K, depth-code range,
 // bad object ids) are handed over through pinned memory; `wait` says when the host reads them:
@@ -605,12 +625,13 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     }
     f->cut_cap = cut_cap;
     const int tile_bits = bits_for((uint32_t)(T > 1 ? T - 1 : 1));
-    const int key64 = depth_bits + tile_bits > 32 ? 1 : 0;      // compact 32-bit keys whenever they fit
+    // the key class: compact 32-bit keys whenever they fit, 16-bit ones behind k_keygen's first pass when the other digits fit
+    uint32_t* const first_hist = depth_bits >= 8 ? pa.first_hist : nullptr;    // below 8 depth bits digit 0 holds tile bits: the full-pass loop
+    const int key_bytes = gs_key_bytes(depth_bits + tile_bits, depth_bits, first_hist != nullptr, sort_narrow_keys() != NARROW_OFF);
     if (depth_bits + tile_bits > 63) return fail(GS_ERR_INVALID_ARGUMENT, "sort key needs more than 63 bits");
     const size_t Kp = K_bound > 0 ? K_bound : 1;
-    const size_t key_bytes = key64 ? 8 : 4;
     const size_t hist_elems = gs_sort_hist_elems(K_bound);
-    if (const int rc = grow(c, { NEED(B.keys_a, key_bytes * Kp), NEED(B.keys_b, key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
+    if (const int rc = grow(c, { NEED(B.keys_a, (size_t)key_bytes * Kp), NEED(B.keys_b, (size_t)key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
                                  NEED(c->hist, 4 * hist_elems), NEED(c->scan_tmp, 4 * GS_SORT_DIGITS) }))
         return rc;
 
@@ -623,10 +644,10 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     ba.tile_block_sums = pa.tile_block_sums;
     ba.counters_rw = pa.counters; ba.host_mirror = publish ? pa.host_mirror : nullptr; ba.ticket = pa.ticket;   // publish: k_keygen's last block hands the counters over
     ba.block_offsets = pa.block_offsets; ba.block_counts = pa.block_counts;     // NULL for records that did not come from k_project
-    ba.keys_a = B.keys_a.p; ba.keys_b = B.keys_b.p; ba.key64 = key64;
+    ba.keys_a = B.keys_a.p; ba.keys_b = B.keys_b.p; ba.key_bytes = key_bytes;
     ba.vals_a = B.vals_a.as<int32_t>(); ba.vals_b = B.vals_b.as<int32_t>();
     ba.hist = c->hist.as<uint32_t>(); ba.scan_tmp = c->scan_tmp.as<uint32_t>();
-    ba.first_hist = depth_bits >= 8 ? pa.first_hist : nullptr;      // below 8 depth bits digit 0 holds tile bits: the full-pass loop
+    ba.first_hist = first_hist;
     ba.keys_sorted = &f->keys_sorted; ba.vals_sorted = &f->vals_sorted;
     gs_launch_binning(ba, s);
     HIP_TRY(hipGetLastError());
@@ -635,7 +656,7 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     fa.prof = &c->prof;
     fa.H = H; fa.W = W; fa.tiles_x = tiles_x; fa.rgb_only = cfg->rgb_only;
     fa.v = frame_view(*f);                  // (taken after the binning, which said where the sorted pairs are)
-    fa.key64 = key64; fa.depth_bits = depth_bits; fa.K = K_bound; fa.counters = ba.counters;
+    fa.key_bytes = key_bytes; fa.depth_bits = depth_bits; fa.K = K_bound; fa.counters = ba.counters;
     fa.image = out->rasterized_image; fa.depth = out->rasterized_depth; fa.acc_alpha = out->pixel_accumulated_alpha;
     fa.last = out->pixel_offset_of_last_effective_point; fa.count = out->pixel_valid_point_count;
     fa.cut_cap = cut_cap;
@@ -645,7 +666,7 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     gs_launch_blend_fwd(fa, s);
     HIP_TRY(hipGetLastError());
     f->depth_bits = depth_bits;
-    f->key64 = key64;
+    f->key_bytes = key_bytes;
     f->info.sort_key_bits = depth_bits + tile_bits;
     return GS_OK;
 }
@@ -670,8 +691,10 @@ static int run_forward_tail(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     int rc;
     f->info.sizing = GS_SIZING_EXACT;
     *M_out = 0; *K_out = 0u;
-    if (n_rows == 0)                                       // nothing was published: an empty frame
-        return run_raster_stage(c, f, pa, 0, 0, 0u, 1, cfg, out, s, false);
+    if (n_rows == 0) {                                     // nothing was published: an empty frame
+        rc = run_raster_stage(c, f, pa, 0, 0, 0u, 1, cfg, out, s, false);
+        return rc != GS_OK ? rc : check_required_key_class(f);
+    }
     const int tile_bits = bits_for((uint32_t)(T > 1 ? T - 1 : 1));
     bool predicted = false;
     int bits_p = 0; uint32_t K_p = 0;
@@ -707,7 +730,7 @@ static int run_forward_tail(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     if (!(c->seen.valid && c->seen.H == H && c->seen.W == W && hc.M == 0)) c->seen.max_code = hc.max_depth_code;
     c->seen.valid = true; c->seen.H = H; c->seen.W = W; c->seen.K = hc.K;
     *M_out = hc.M; *K_out = hc.K;
-    return GS_OK;
+    return check_required_key_class(f);
 }
 
 extern "C" int gs_forward(gs_ctx* c, const gs_scene* sc, const gs_camera* cam, const gs_config* cfg,
@@ -867,7 +890,7 @@ extern "C" int gs_frame_export(gs_ctx* c, const gs_frame* h, gs_export what, voi
     }
     GsExportArgs a{};
     a.what = (int)what; a.N = f->info.n_points; a.M = (int)f->info.n_points_in_camera; a.K = (uint32_t)f->info.n_keys;
-    a.T = v.T; a.depth_bits = f->depth_bits; a.key64 = f->key64;
+    a.T = v.T; a.depth_bits = f->depth_bits; a.key_bytes = f->key_bytes; a.depth_codes = v.depth_codes;
     a.ids = v.ids; a.PA = v.PA; a.PB = v.PB; a.PC = v.PC; a.PD = v.PD;
     a.ntiles = v.ntiles; a.offsets = v.offsets;
     a.keys_sorted = v.keys_sorted; a.vals_sorted = v.vals_sorted;

@@ -379,8 +379,8 @@ struct GsBinArgs {
     const uint32_t* tile_block_sums;
     GsCounters* counters_rw; GsCounters* host_mirror; int32_t ticket;   // host_mirror != NULL: the last k_keygen block publishes the frame counters
     const int32_t *block_offsets, *block_counts;   // k_project's blocks (first in-camera offset, count); NULL: 256 consecutive records per block
-    void *keys_a, *keys_b; int32_t *vals_a, *vals_b;       // ping-pong (K); keys are u32, or u64 when key64
-    int key64;                                             // depth bits + tile bits > 32
+    void *keys_a, *keys_b; int32_t *vals_a, *vals_b;       // ping-pong (K); keys of key_bytes bytes
+    int key_bytes;                                         // 2, 4 or 8: the frame's key class (gs_sort_key.h: gs_key_bytes)
     uint32_t* hist;                             // (256 * sort_blocks) + scratch
     // the per-point stage's digit table (GsProjectArgs::first_hist) when k_keygen is to do the first radix pass itself, or NULL: the
     // host's decision (gs_api.hip: run_raster_stage); taken only where depth_bits >= 8
@@ -397,7 +397,7 @@ struct GsBlendFwdArgs {
     GsProf* prof;
     int H, W, tiles_x; int rgb_only;
     GsFrameView v;                 // read: sorted pairs, records; written: tile ranges, tile_work, list cuts for the backward (v.cuts NULL: none wanted)
-    int key64, depth_bits; uint32_t K; const GsCounters* counters;   // min(counters->K, K) pairs (see GsBinArgs)
+    int key_bytes, depth_bits; uint32_t K; const GsCounters* counters;   // min(counters->K, K) pairs (see GsBinArgs)
     float* image; float* depth; float* acc_alpha; int32_t* last; int32_t* count;
     int cut_cap;
     const int32_t* order_hint;     // (T) or NULL: a permutation of the tiles, heaviest first, from an earlier frame of this ctx (scheduling only)
@@ -463,7 +463,8 @@ void gs_launch_channels_fwd(const GsChannelsArgs& a, hipStream_t s);
 hipError_t gs_launch_channels_bwd(const GsChannelsArgs& a, hipStream_t s);
 
 // the argument of k_export, passed by value
-struct GsExportArgs { int what; int64_t N; int M; uint32_t K; int T; int depth_bits; int key64;
+struct GsExportArgs { int what; int64_t N; int M; uint32_t K; int T; int depth_bits; int key_bytes;
+    const int32_t* depth_codes;     // (M) per point: the low byte a narrow key left out (gs_sort_key.h)
     const int32_t* ids; const float4 *PA, *PB, *PC, *PD; const int32_t* ntiles; const uint32_t* offsets;
     const void* keys_sorted; const int32_t* vals_sorted; const int32_t *tile_start, *tile_end; const int8_t* mask; void* dst; };
 void gs_launch_export(const GsExportArgs& a, hipStream_t s);

@@ -8,8 +8,11 @@
 // Keys are stored compactly: (tile_id << depth_bits) | depth_code, depth_bits = bits of the
 // largest depth code in THIS frame, so only the significant bits are radix-sorted.  The order
 // is identical to sorting the reference's 64-bit (tile_id << 32) + depth_code keys; exports
-// rebuild those.  HBM-bound integer work: no LDS reshaping beyond per-wave digit counters.
+// rebuild those.  Behind k_keygen's own first pass (FIRST_PASS below) the low byte of a key is never read again, and a frame whose
+// other key bits fit 16 stores uint16_t keys without it (gs_sort_key.h: the narrow class).
+// HBM-bound integer work: no LDS reshaping beyond per-wave digit counters.
 #include "gs_common.h"
+#include "gs_sort_key.h"
 #include <type_traits>
 
 #ifndef SORT_ROUNDS
@@ -69,7 +72,11 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
     __shared__ uint32_t ws[4], wpre[4];
     __shared__ uint32_t sExcl[256 + 1];
     __shared__ ushort4 sBox[256];
-    __shared__ KeyT sCode[256];
+    // a narrow key (gs_sort_key.h) is narrower than the depth code it is built from
+    constexpr bool NARROW = std::is_same<KeyT, uint16_t>::value;
+    static_assert(!NARROW || FIRST_PASS, "narrow keys exist only behind k_keygen's own first pass");
+    using CodeT = typename std::conditional<NARROW, uint32_t, KeyT>::type;
+    __shared__ CodeT sCode[256];
     __shared__ uint32_t sBase[FIRST_PASS ? 256 : 1];        // FIRST_PASS: slot of a row's pair e, minus e
     __shared__ unsigned short sOrig[FIRST_PASS ? 256 : 1];  // FIRST_PASS: the row's thread (its point is first + that)
     // same blocks as the kernel that produced ntiles / tile_block_offsets: k_project's (256 rows of the point cloud each, in-camera
@@ -83,7 +90,7 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
     const uint32_t incl = gs_wave_scan_incl(n, lane);
     gs_block_scan_put(ws, wave, lane, incl);
     const ushort4 my_box = valid ? boxes[idx] : make_ushort4(0, 1, 0, 1);
-    const KeyT my_code = valid ? (KeyT)(uint32_t)depth_codes[idx] : (KeyT)0;     // i32(depth * scale), RAST:159-160, from k_project
+    const CodeT my_code = valid ? (CodeT)(uint32_t)depth_codes[idx] : (CodeT)0;     // i32(depth * scale), RAST:159-160, from k_project
     if constexpr (!FIRST_PASS) { sBox[threadIdx.x] = my_box; sCode[threadIdx.x] = my_code; }
     // first pair of this block = the tile counts of all blocks before it (RAST:913-922 across blocks)
     gs_block_put(wpre, wave, lane, gs_sum_of_blocks_before<256>(tile_block_sums, (int)blockIdx.x));
@@ -158,12 +165,13 @@ __global__ __launch_bounds__(256) void k_keygen(const int32_t* __restrict__ dept
             if (r >= (int)dv) { tq += 1u; r -= (int)dv; }
             tr = (uint32_t)r;
         } else { tq = t / dv; tr = t - tq * dv; }
-        const KeyT tile_id = (KeyT)(((uint32_t)bx.x + tq) + ((uint32_t)bx.z + tr) * (uint32_t)tiles_x);   // RAST:163-168
+        const uint32_t tile_id = ((uint32_t)bx.x + tq) + ((uint32_t)bx.z + tr) * (uint32_t)tiles_x;      // RAST:163-168
         uint32_t slot; int point;
         if constexpr (FIRST_PASS) { slot = sBase[j] + e; point = first + (int)sOrig[j]; }
         else { slot = block_base + e; point = first + j; }
         if (slot < K_cap) {
-            keys[slot] = (tile_id << depth_bits) | sCode[j];                     // RAST:169-170, compact form
+            if constexpr (NARROW) keys[slot] = gs_narrow_key(tile_id, sCode[j], depth_bits);
+            else keys[slot] = ((KeyT)tile_id << depth_bits) | sCode[j];          // RAST:169-170, compact form
             vals[slot] = point;
         }
     }
@@ -180,8 +188,8 @@ __global__ __launch_bounds__(256) void k_sort_hist(const KeyT* __restrict__ keys
     const uint64_t begin = (uint64_t)blockIdx.x * tiles_per_block * SORT_TILE;     // multiple of 4096: 16-byte aligned
     uint64_t end = begin + (uint64_t)tiles_per_block * SORT_TILE;
     if (end > n) end = n;
-    // four keys per load (16 or 32 bytes per lane), then four LDS atomics
-    constexpr int V = 4;
+    // four keys per load (16 or 32 bytes per lane), eight of two bytes, then as many LDS atomics
+    constexpr int V = sizeof(KeyT) == 2 ? 8 : 4;
     struct alignas(sizeof(KeyT) * V) KeyVec { KeyT k[V]; };
     const uint64_t nvec = begin < end ? (end - begin) / V : 0;
     const KeyVec* kv = reinterpret_cast<const KeyVec*>(keys + begin);
@@ -348,6 +356,7 @@ size_t gs_sort_hist_elems(uint32_t K)
     return (size_t)2 * 256 * nb;      // raw counts + scanned offsets
 }
 
+// KeyT: the element of keys_a / keys_b (gs_sort_key.h)
 template <typename KeyT>
 static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
 {
@@ -366,7 +375,7 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
         GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT, true><<<kg_blocks, 256, 0, s>>>(
             a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
             a.counters_rw, a.host_mirror, a.ticket, first_offs, a.scan_tmp));
-    } else {
+    } else if constexpr (!std::is_same<KeyT, uint16_t>::value) {      // (a narrow frame has the first pass: gs_key_bytes)
         GS_TIMED(a.prof, KID_KEYGEN, s, k_keygen<KeyT, false><<<kg_blocks, 256, 0, s>>>(
             a.v.depth_codes, a.v.box, a.v.ntiles, a.tile_block_sums, a.block_offsets, a.block_counts, a.M, a.tiles_x, a.depth_bits, a.K, a.v.offsets, keys_a, a.vals_a,
             a.counters_rw, a.host_mirror, a.ticket, nullptr, nullptr));
@@ -376,7 +385,9 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
     sort_geometry(a.K, &nb, &tpb);
     KeyT *kin = keys_a, *kout = keys_b;
     int32_t *vin = a.vals_a, *vout = a.vals_b;
-    for (int shift = first_pass ? 8 : 0; shift < a.key_bits; shift += 8) {
+    // the passes over digits 1, 2 ... of the wide key (0, 1 ... without the first pass); a narrow key holds them 8 bits lower
+    const int dropped = gs_key_dropped_bits((int)sizeof(KeyT));
+    for (int shift = (first_pass ? 8 : 0) - dropped; shift < a.key_bits - dropped; shift += 8) {
         uint32_t* offs = a.hist + (size_t)256 * nb;                 // second half of the table: scanned offsets
         GS_TIMED(a.prof, KID_SORT_HIST, s, k_sort_hist<KeyT><<<nb, 256, 0, s>>>(kin, a.counters, a.K, shift, a.hist, nb, tpb));
         GS_TIMED(a.prof, KID_SORT_ROWSCAN, s, k_sort_rowscan<<<GS_SORT_DIGITS, 1024, 0, s>>>(a.hist, a.scan_tmp, offs, nb));
@@ -392,6 +403,7 @@ static void launch_binning_t(const GsBinArgs& a, hipStream_t s)
 void gs_launch_binning(const GsBinArgs& a, hipStream_t s)
 {
     // tile_start | tile_end (RAST:954-957 zero-init) | tile_work were cleared by the frame's first kernel (k_filter / k_boxes_from_records)
-    if (a.key64) launch_binning_t<uint64_t>(a, s);
+    if (a.key_bytes == 2) launch_binning_t<uint16_t>(a, s);
+    else if (a.key_bytes == 8) launch_binning_t<uint64_t>(a, s);
     else launch_binning_t<uint32_t>(a, s);
 }

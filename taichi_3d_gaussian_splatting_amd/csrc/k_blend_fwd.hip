@@ -14,22 +14,23 @@
 // Bound: FP32 VALU (exp polynomial + blend), not HBM: see DESIGN.md.
 #include "gs_common.h"
 #include "gs_cull.h"
+#include "gs_sort_key.h"
 #ifndef GS_WORK_PER_BATCH
 #define GS_WORK_PER_BATCH 8      // a walked batch in units of (splat, quadrant) evaluations, for the tile ordering / heavy-tile choice
 #endif
 
 // find_tile_start_and_end (RAST:175-193) without a launch of its own: the first index of the sorted, compact keys
-// (tile << depth_bits | depth code) whose tile is >= `tile`, by a 64-ary search -- every step the wave's 64 lanes probe
+// (tile << depth_bits | depth code; tile_shift = depth_bits, less the bits a narrow key has dropped) whose tile is >= `tile`, by a 64-ary search -- every step the wave's 64 lanes probe
 // 64 positions of the remaining span and a ballot narrows it 64-fold (four or five dependent loads for millions of keys).
 template <typename KeyT>
-__device__ __forceinline__ int gs_first_key_of_tile(const KeyT* __restrict__ keys, uint32_t K, int depth_bits, uint32_t tile, int lane)
+__device__ __forceinline__ int gs_first_key_of_tile(const KeyT* __restrict__ keys, uint32_t K, int tile_shift, uint32_t tile, int lane)
 {
     uint32_t lo = 0, hi = K;                       // answer in [lo, hi]; every index < lo is below the tile, index hi (if < K) is not
     while (lo < hi) {
         const uint32_t span = hi - lo, step = (span + 63u) / 64u;
         const uint32_t mine = (uint32_t)(lane + 1) * step;
         const uint32_t p = lo + (mine < span ? mine : span) - 1u;
-        const unsigned long long b = gs_ballot((uint32_t)(keys[p] >> depth_bits) >= tile);
+        const unsigned long long b = gs_ballot((uint32_t)(keys[p] >> tile_shift) >= tile);
         if (b == 0ull) { lo = hi; break; }
         const uint32_t f = (uint32_t)__builtin_ctzll(b);
         const uint32_t pf = lo + ((f + 1u) * step < span ? (f + 1u) * step : span) - 1u;
@@ -41,7 +42,7 @@ __device__ __forceinline__ int gs_first_key_of_tile(const KeyT* __restrict__ key
 
 template <bool RGB_ONLY>
 __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_start, int32_t* __restrict__ tile_end,
-                                                   const void* __restrict__ sorted_keys, int key64, int depth_bits,
+                                                   const void* __restrict__ sorted_keys, int key_bytes, int tile_shift,
                                                    const GsCounters* __restrict__ ctr, uint32_t K_cap,
                                                    const int32_t* __restrict__ sorted_vals,
                                                    const float4* __restrict__ PA, const float4* __restrict__ PB,
@@ -65,8 +66,10 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
     __shared__ int sRange[2];
     if (wave < 2) {
         const uint32_t want = (uint32_t)tile + (uint32_t)wave;
-        const int r = K == 0u ? 0 : (key64 ? gs_first_key_of_tile(reinterpret_cast<const uint64_t*>(sorted_keys), K, depth_bits, want, lane)
-                                           : gs_first_key_of_tile(reinterpret_cast<const uint32_t*>(sorted_keys), K, depth_bits, want, lane));
+        const int r = K == 0u ? 0
+                    : key_bytes == 2 ? gs_first_key_of_tile(reinterpret_cast<const uint16_t*>(sorted_keys), K, tile_shift, want, lane)
+                    : key_bytes == 8 ? gs_first_key_of_tile(reinterpret_cast<const uint64_t*>(sorted_keys), K, tile_shift, want, lane)
+                                     : gs_first_key_of_tile(reinterpret_cast<const uint32_t*>(sorted_keys), K, tile_shift, want, lane);
         if (lane == 0) sRange[wave] = r;
     }
     __syncthreads();
@@ -216,7 +219,7 @@ void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s)
     const GsFrameView& v = a.v;
     if (v.T <= 0) return;
     auto launch = [&](auto kernel) {
-        GS_TIMED(a.prof, KID_BLEND_FWD, s, kernel<<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key64, a.depth_bits, a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
+        GS_TIMED(a.prof, KID_BLEND_FWD, s, kernel<<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key_bytes, a.depth_bits - gs_key_dropped_bits(a.key_bytes), a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
                                                                    a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, a.cut_cap));
     };
     if (a.rgb_only) launch(k_blend_fwd<true>);

@@ -3,6 +3,7 @@
 // operator for the backward hook payload (RAST:1128-1140) and by the parity tests.
 #include "../../include/gs_rasterizer.h"
 #include "gs_common.h"
+#include "gs_sort_key.h"
 
 __global__ void k_export(GsExportArgs a)
 {
@@ -19,7 +20,12 @@ __global__ void k_export(GsExportArgs a)
     case GS_X_ACCUMULATED_NUM_OVERLAP_TILES: if (i < a.M) ((int64_t*)a.dst)[i] = (int64_t)a.offsets[i]; break;
     case GS_X_SORT_KEY:
         if (i < (int64_t)a.K) {
-            uint64_t k = a.key64 ? ((const uint64_t*)a.keys_sorted)[i] : (uint64_t)((const uint32_t*)a.keys_sorted)[i];
+            if (a.key_bytes == 2) {     // the narrow key holds the tile; the code is the point's
+                const uint32_t tile = gs_narrow_tile(((const uint16_t*)a.keys_sorted)[i], a.depth_bits);
+                ((int64_t*)a.dst)[i] = gs_reference_key(tile, (uint32_t)a.depth_codes[a.vals_sorted[i]]);
+                break;
+            }
+            uint64_t k = a.key_bytes == 8 ? ((const uint64_t*)a.keys_sorted)[i] : (uint64_t)((const uint32_t*)a.keys_sorted)[i];
             int64_t tile = (int64_t)(k >> a.depth_bits);
             int64_t code = (int64_t)(k & ((1ull << a.depth_bits) - 1ull));
             ((int64_t*)a.dst)[i] = code + (tile << 32);                    // RAST:169-170
