@@ -180,3 +180,74 @@ def add_densify_points(pc, feat, mask, obj, info, cfg, seed, call_index):
                 fillable=num_fillable_densify_points, over=num_over_reconstructed, under=num_under_reconstructed,
                 valid_before=total_valid_points_before_densify, valid_after=total_valid_points_after_densify,
                 fill_point_id=invalid_point_id_to_fill[:num_fillable_densify_points])
+
+
+ACCUMULATORS = (("accumulated_num_in_camera", torch.int32, ()), ("accumulated_num_pixels", torch.int32, ()),
+                ("accumulated_view_space_position_gradients", torch.float32, ()),
+                ("accumulated_view_space_position_gradients_avg", torch.float32, ()),
+                ("accumulated_position_gradients", torch.float32, (3,)), ("accumulated_position_gradients_norm", torch.float32, ()))
+
+
+class ReferenceController:
+    """CTRL:130-168 around find_densify_points / add_densify_points: the counter and the schedule, update()'s six
+    accumulations in f32 as the reference does them, refinement() with the apply's call index, the accumulator reset and
+    reset_alpha.  The scene and the accumulators are plain attributes (pc, feat, mask, obj; acc), edited in place as the
+    reference edits its maintained parameters, so that a caller may also replace them between two steps."""
+
+    def __init__(self, cfg, pc, feat, mask, obj, seed=0):
+        self.cfg, self.seed = cfg, seed
+        self.pc, self.feat, self.mask, self.obj = pc, feat, mask, obj
+        self.iteration_counter = -1                                                                         # CTRL:109
+        self.refinement_calls = 0
+        self.info = None
+        self.reset()
+
+    def reset(self):                                                                                        # CTRL:114-125, 154-165
+        n = self.pc.shape[0]
+        self.acc = {name: torch.zeros((n,) + shape, dtype=dtype, device=self.pc.device) for name, dtype, shape in ACCUMULATORS}
+
+    def is_densify_iteration(self):                                                                         # CTRL:142-144, 150-152
+        return (self.iteration_counter >= self.cfg.num_iterations_warm_up
+                and self.iteration_counter % self.cfg.num_iterations_densify == 0)
+
+    def update(self, payload):
+        """payload: point_id_in_camera_list, num_affected_pixels, magnitude_grad_viewspace, point_depth and
+        grad_point_in_camera of the reference's BackwardValidPointHookInput.  -> the densify info on a densify iteration"""
+        self.iteration_counter += 1                                                                         # :131
+        ids = payload.point_id_in_camera_list.long()
+        a = self.acc
+        a["accumulated_num_in_camera"][ids] += 1                                                            # :133
+        a["accumulated_num_pixels"][ids] += payload.num_affected_pixels                                     # :134
+        grad_viewspace_norm = payload.magnitude_grad_viewspace
+        a["accumulated_view_space_position_gradients"][ids] += grad_viewspace_norm                          # :136
+        avg_grad_viewspace_norm = grad_viewspace_norm / payload.num_affected_pixels                         # :137
+        avg_grad_viewspace_norm[torch.isnan(avg_grad_viewspace_norm)] = 0                                   # :138
+        a["accumulated_view_space_position_gradients_avg"][ids] += avg_grad_viewspace_norm                  # :139
+        a["accumulated_position_gradients"][ids] += payload.grad_point_in_camera                            # :140
+        a["accumulated_position_gradients_norm"][ids] += payload.grad_point_in_camera.norm(dim=1)           # :141
+        if not self.is_densify_iteration():
+            return None
+        remove_floaters = self.iteration_counter > self.cfg.iteration_start_remove_floater                  # :191
+        self.info = find_densify_points(self.pc, self.feat, self.mask, a, payload.point_id_in_camera_list,
+                                        payload.num_affected_pixels, payload.point_depth, payload.magnitude_grad_viewspace,
+                                        remove_floaters, self.cfg)
+        return self.info
+
+    def refinement(self):
+        """-> None during the warm-up, else dict(counts=the apply's counts or None, info=its densify info or None,
+        reset_alpha=whether CTRL:166 fired, rows_lowered=the rows whose alpha it lowered)"""
+        if self.iteration_counter < self.cfg.num_iterations_warm_up:                                        # :150
+            return None
+        counts = info = None
+        if self.iteration_counter % self.cfg.num_iterations_densify == 0:                                   # :152
+            assert self.info is not None                                                                    # :291
+            info, self.info = self.info, None
+            counts = add_densify_points(self.pc, self.feat, self.mask, self.obj, info, self.cfg, self.seed, self.refinement_calls)
+            self.refinement_calls += 1
+            self.reset()
+        reset_alpha = self.iteration_counter % self.cfg.num_iterations_reset_alpha == 0                     # :166
+        lowered = 0
+        if reset_alpha:
+            lowered = int((self.feat[:, 7] > self.cfg.reset_alpha_value).sum())
+            self.feat[:, 7] = torch.clamp(self.feat[:, 7], max=self.cfg.reset_alpha_value)                  # :355-358
+        return dict(counts=counts, info=info, reset_alpha=reset_alpha, rows_lowered=lowered)

@@ -112,11 +112,9 @@ def run_reference(scene, acc, hook, cfg, seed=0, call_index=0, remove_floaters=T
     return info, {k: v.numpy() for k, v in t.items()}, counts
 
 
-def assert_same_as_reference(scene, acc, hook, cfg, seed=0, remove_floaters=True, pos_rtol=1e-5):
-    plan, got, counts = run_device(scene, acc, hook, cfg, seed, remove_floaters)
-    info, want, ref_counts = run_reference(scene, acc, hook, cfg, seed, 0, remove_floaters)
+def assert_plan_matches(plan, info):
+    """a select's plan (densify_plan(), on the CPU) against find_densify_points' info: masks, ids, snapshots, factors, bit for bit"""
     flags = plan["flags"].numpy().astype(np.int64)
-    # masks and id lists, bit for bit
     assert np.array_equal((flags & 1) != 0, info["floater_mask"].numpy())
     assert np.array_equal((flags & 2) != 0, info["transparent_mask"].numpy())
     assert np.array_equal((flags & 4) != 0, info["densify_mask"].numpy())
@@ -124,6 +122,11 @@ def assert_same_as_reference(scene, acc, hook, cfg, seed=0, remove_floaters=True
     assert np.array_equal(plan["densify_point_position_before_optimization"].numpy(), info["densify_point_position_before_optimization"].numpy())
     assert np.array_equal(plan["densify_point_grad_position"].numpy(), info["densify_point_grad_position"].numpy())
     assert np.array_equal(plan["densify_size_reduction_factor"].numpy(), info["densify_size_reduction_factor"].numpy()[:, 0])
+
+
+def assert_apply_matches(got, counts, want, ref_counts, info, cfg, pos_rtol=1e-5):
+    """the scene after an apply (got: pc, feat, mask, obj, fill as numpy; counts: last_refinement_counts()) against
+    add_densify_points' scene and counts"""
     assert np.array_equal(got["fill"], ref_counts["fill_point_id"].numpy())
     for k in ["floaters", "transparent", "densify", "fillable", "over", "under", "valid_before", "valid_after"]:
         assert counts[k] == ref_counts[k], (k, counts[k], ref_counts[k])
@@ -147,6 +150,15 @@ def assert_same_as_reference(scene, acc, hook, cfg, seed=0, remove_floaters=True
         assert np.allclose(got["pc"], want["pc"], rtol=pos_rtol, atol=pos_rtol)
     err = np.abs(got["pc"][sampled] - want["pc"][sampled])
     assert np.all(err <= pos_rtol * (np.abs(want["pc"][sampled]) + 1.0)), float(err.max(initial=0))
+
+
+def assert_same_as_reference(scene, acc, hook, cfg, seed=0, remove_floaters=True, pos_rtol=1e-5, call_index=0):
+    """one select and one apply of a fresh controller against the reference's; call_index: of the reference's sample stream
+    (a fresh controller's first apply draws from call 0)"""
+    plan, got, counts = run_device(scene, acc, hook, cfg, seed, remove_floaters)
+    info, want, ref_counts = run_reference(scene, acc, hook, cfg, seed, call_index, remove_floaters)
+    assert_plan_matches(plan, info)
+    assert_apply_matches(got, counts, want, ref_counts, info, cfg, pos_rtol)
     return counts, info
 
 

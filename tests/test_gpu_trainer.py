@@ -2,7 +2,8 @@
 training and 2 validation views of 64x96 rendered by the rasteriser, quantised to uint8 PNGs).
 
   1. a run equals the hand-written iteration of tools/bench_trainer_step.py's fused_in_place leg plus refinement(), bit for bit,
-     dense and with the row-selective Adam step: call order, band schedule, lr-decay timing and the target's bits;
+     dense and with the row-selective Adam step: call order, band schedule, lr-decay timing and the target's bits; and again
+     with densification on and validation in the middle of the run;
   2. two runs with one seed are bit-identical across a change of the downsample factor;
   3. it trains: the mean validation PSNR rises from a perturbed ground truth;
   4. the run's artefacts: metrics.jsonl, scene_<it>.parquet, best_scene.parquet;
@@ -27,6 +28,7 @@ from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointC
 from taichi_3d_gaussian_splatting_amd.ImagePoseDataset import ImagePoseDataset
 from taichi_3d_gaussian_splatting_amd.LossFunction import LossFunction
 from taichi_3d_gaussian_splatting_amd.optim import FusedAdam
+from taichi_3d_gaussian_splatting_amd.targets import TargetStore
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -45,6 +47,70 @@ def make_trainer(data, out_dir, **overrides):
     return GaussianPointCloudTrainer(config, device=DEV, writer=JsonlSummaryWriter(config.summary_writer_log_dir))
 
 
+def hand_written_loop(data, config, order, n_it, band_interval, decay_interval, rate, sparse_adam, seed, downsample_factor=1,
+                      after_iteration=None, foreign_renders_after=()):
+    """The trainer's iterations by hand, without validation: the fused_in_place leg of tools/bench_trainer_step.py plus
+    refinement().  Targets at factor 1 are built here from the decoded files; at another factor they come from a TargetStore of
+    the loop's own.  after_iteration(it, scene) runs behind every iteration.  -> (scene, controller, position optimiser)
+
+    foreign_renders_after: iterations behind which the validation views are rendered, full size and band 3 under no_grad, by
+    ANOTHER rasteriser module with a context of its own, and thrown away.  A forward normalises the rotation quaternions of the
+    rows in camera in place (RAST:196-205, k_project), so a render is a write to the scene that the iterations behind it see;
+    this is that write and nothing else of a validation: the training module's context (tile-order hint, predicted sizes, frame
+    pool), the loss module and the optimisers never hear of it."""
+    scene = GaussianPointCloudScene.from_parquet(data["paths"]["cloud"], config=config.gaussian_point_cloud_scene_config, device=DEV)
+    controller = GaussianPointAdaptiveController(
+        config=config.adaptive_controller_config,
+        maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
+            pointcloud=scene.point_cloud, pointcloud_features=scene.point_cloud_features,
+            point_invalid_mask=scene.point_invalid_mask, point_object_id=scene.point_object_id), seed=seed)
+    rast = Rast(Rast.GaussianPointCloudRasterisationConfig(), backward_valid_point_hook=controller.update)
+    rast.track_touched_rows = sparse_adam
+    loss_fn = LossFunction(LossFunction.LossFunctionConfig())
+    of, op = FusedAdam([scene.point_cloud_features], lr=1e-3), FusedAdam([scene.point_cloud], lr=1e-4)
+    dataset = ImagePoseDataset(data["paths"]["train"])
+    targets = TargetStore.from_dataset(dataset, DEV) if downsample_factor != 1 else None
+    if foreign_renders_after:
+        foreign_rast = Rast(Rast.GaussianPointCloudRasterisationConfig())
+        foreign_views = TargetStore.from_dataset(ImagePoseDataset(data["paths"]["val"]), DEV)
+    for it in range(n_it):
+        of.zero_grad(); op.zero_grad()
+        if targets is None:
+            raw, q, t, info = dataset.load_raw(order[it])
+            assert np.array_equal(raw.numpy(), data["images"][TU.TRAIN_VIEWS[order[it]]])
+            gt = raw.permute(2, 0, 1).float().div(255).to(DEV)               # to_tensor: the true division, on the CPU
+            q, t = q.to(DEV), t.to(DEV)
+            camera_info = CameraInfo(info.camera_intrinsics.to(DEV), TU.H, TU.W, info.camera_id)
+        else:
+            gt, q, t, camera_info = targets.target(order[it], downsample_factor)
+        inp = Rast.GaussianPointCloudRasterisationInput(
+            point_cloud=scene.point_cloud, point_cloud_features=scene.point_cloud_features, point_object_id=scene.point_object_id,
+            point_invalid_mask=scene.point_invalid_mask, camera_info=camera_info,
+            q_pointcloud_camera=q, t_pointcloud_camera=t, color_max_sh_band=it // band_interval)
+        img, _, _ = rast(inp)
+        L = loss_fn(img.permute(2, 0, 1), gt, point_invalid_mask=scene.point_invalid_mask, pointcloud_features=scene.point_cloud_features,
+                    clamp_predicted=True)[0]
+        L.backward()
+        rows = rast.last_touched_rows if sparse_adam else None
+        assert (rows is not None) == sparse_adam
+        of.step(rows=rows); op.step(rows=rows)
+        if it % decay_interval == 0:
+            op.lr *= rate
+        controller.refinement()
+        if it in foreign_renders_after:
+            with torch.no_grad():
+                for view in range(len(foreign_views)):
+                    _, q, t, camera_info = foreign_views.target(view, 1)
+                    foreign_rast(Rast.GaussianPointCloudRasterisationInput(
+                        point_cloud=scene.point_cloud, point_cloud_features=scene.point_cloud_features,
+                        point_object_id=scene.point_object_id, point_invalid_mask=scene.point_invalid_mask, camera_info=camera_info,
+                        q_pointcloud_camera=q, t_pointcloud_camera=t, color_max_sh_band=3))
+        if after_iteration is not None:
+            after_iteration(it, scene)
+    torch.cuda.synchronize()
+    return scene, controller, op
+
+
 @pytest.mark.parametrize("sparse_adam", [False, True], ids=["dense", "sparse"])
 def test_run_equals_the_hand_written_loop(data, tmp_path, sparse_adam):
     n_it, band_interval, decay_interval, rate = 6, 2, 2, 0.9
@@ -58,43 +124,97 @@ def test_run_equals_the_hand_written_loop(data, tmp_path, sparse_adam):
 
     # the same six iterations by hand
     config = trainer.config
-    scene = GaussianPointCloudScene.from_parquet(data["paths"]["cloud"], config=GaussianPointCloudScene.PointCloudSceneConfig(), device=DEV)
-    controller = GaussianPointAdaptiveController(
-        config=config.adaptive_controller_config,
-        maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
-            pointcloud=scene.point_cloud, pointcloud_features=scene.point_cloud_features,
-            point_invalid_mask=scene.point_invalid_mask, point_object_id=scene.point_object_id), seed=3)
-    rast = Rast(Rast.GaussianPointCloudRasterisationConfig(), backward_valid_point_hook=controller.update)
-    rast.track_touched_rows = sparse_adam
-    loss_fn = LossFunction(LossFunction.LossFunctionConfig())
-    of, op = FusedAdam([scene.point_cloud_features], lr=1e-3), FusedAdam([scene.point_cloud], lr=1e-4)
-    dataset = ImagePoseDataset(data["paths"]["train"])
-    for it in range(n_it):
-        of.zero_grad(); op.zero_grad()
-        raw, q, t, info = dataset.load_raw(order[it])
-        assert np.array_equal(raw.numpy(), data["images"][TU.TRAIN_VIEWS[order[it]]])
-        gt = raw.permute(2, 0, 1).float().div(255).to(DEV)                   # to_tensor: the true division, on the CPU
-        inp = Rast.GaussianPointCloudRasterisationInput(
-            point_cloud=scene.point_cloud, point_cloud_features=scene.point_cloud_features, point_object_id=scene.point_object_id,
-            point_invalid_mask=scene.point_invalid_mask,
-            camera_info=CameraInfo(info.camera_intrinsics.to(DEV), TU.H, TU.W, info.camera_id),
-            q_pointcloud_camera=q.to(DEV), t_pointcloud_camera=t.to(DEV), color_max_sh_band=it // band_interval)
-        img, _, _ = rast(inp)
-        L = loss_fn(img.permute(2, 0, 1), gt, point_invalid_mask=scene.point_invalid_mask, pointcloud_features=scene.point_cloud_features,
-                    clamp_predicted=True)[0]
-        L.backward()
-        rows = rast.last_touched_rows if sparse_adam else None
-        assert (rows is not None) == sparse_adam
-        of.step(rows=rows); op.step(rows=rows)
-        if it % decay_interval == 0:
-            op.lr *= rate
-        controller.refinement()
-    torch.cuda.synchronize()
+    assert config.gaussian_point_cloud_scene_config == GaussianPointCloudScene.PointCloudSceneConfig()
+    scene, controller, op = hand_written_loop(data, config, order, n_it, band_interval, decay_interval, rate, sparse_adam, seed=3)
     assert op.lr == trainer.position_optimizer.lr == 1e-4 * rate * rate * rate
     assert torch.equal(trainer.scene.point_cloud, scene.point_cloud)
     assert torch.equal(trainer.scene.point_cloud_features, scene.point_cloud_features)
     start = GaussianPointCloudScene.from_parquet(data["paths"]["cloud"], device=DEV)
     assert not torch.equal(start.point_cloud, scene.point_cloud) and not torch.equal(start.point_cloud_features, scene.point_cloud_features)
+
+
+def _bits_equal(a, b):
+    """bit for bit, NaN included"""
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.detach().contiguous().view(torch.int32), b.detach().contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("sparse_adam", [False, True], ids=["dense", "sparse"])
+def test_run_with_densification_and_validation_equals_the_hand_written_loop(data, tmp_path, sparse_adam):
+    """Densification on (trainer_util.DENSIFY_*: 600 rows, cycles at iterations 2, 4 and 6) at downsample factor 2, and
+    validation() at iterations 3 and 6: full-size no_grad renders between two training iterations.  Equal scenes show the call
+    order (select inside the backward, step, apply), that a row a refinement rewrote goes through the row-selective step as
+    through the dense one, and that a validation leaves nothing behind in what the next iteration uses (order hint, predicted
+    sizes, frame pool, the loss's buffers).
+
+    One thing a validation does leave behind, in the reference as here: each of its forwards normalises the quaternions of the
+    rows in its camera in place (RAST:196-205), and the next training forward normalises the result once more, which is not
+    the bits of one normalisation of the stepped quaternion.  A hand-written loop that renders nothing at iterations 3 and 6
+    therefore differs from the trainer from iteration 4 on, by an ulp or two of 751 feature elements at first (measured, with
+    and without densification).  So the hand-written loop does no validation but makes that write: the same two renders by a
+    rasteriser module of its own (hand_written_loop's foreign_renders_after), whose context the training iterations never use.
+    The test also pins down that this is the only write of a validation: positions, mask, object ids and feature columns 4..55
+    keep their bits across it, and columns 0..3 become q / |q| of what they were."""
+    n_it, band_interval, decay_interval, rate = 8, 2, 2, 0.9
+    trainer = make_trainer(data, tmp_path, densify=True, num_iterations=n_it, val_interval=3, initial_downsample_factor=2,
+                           half_downsample_factor_interval=100, sparse_adam=sparse_adam,
+                           increase_color_max_sh_band_interval=band_interval, position_learning_rate_decay_interval=decay_interval,
+                           position_learning_rate_decay_rate=rate, position_learning_rate=1e-4, seed=3)
+    assert trainer.scene.point_cloud.shape[0] == 600 and int((trainer.scene.point_invalid_mask == 0).sum()) == TU.N_POINTS
+    held, cycles = {}, []
+    validation, refinement = trainer.validation, trainer.adaptive_controller.refinement
+
+    def recording_validation(iteration):
+        sc = trainer.scene
+        before = [t.detach().clone() for t in (sc.point_cloud, sc.point_cloud_features, sc.point_invalid_mask, sc.point_object_id)]
+        means = validation(iteration)
+        # what the validation wrote: unit quaternions over the rows in its cameras, nothing else
+        assert _bits_equal(sc.point_cloud, before[0]) and torch.equal(sc.point_invalid_mask, before[2]) and torch.equal(sc.point_object_id, before[3])
+        assert _bits_equal(sc.point_cloud_features[:, 4:], before[1][:, 4:])
+        q_old, q_new = before[1][:, 0:4].double(), sc.point_cloud_features.detach()[:, 0:4].double()
+        changed = (q_old != q_new).any(1)
+        assert changed.any() and not changed[sc.point_invalid_mask == 1].any()
+        unit = q_old[changed] / q_old[changed].norm(dim=1, keepdim=True)
+        assert float((q_new[changed] - unit).abs().max()) <= 5 * 2.0 ** -24     # f32: four squares summed (3.5 u at the root), one divide
+        valid = sc.point_invalid_mask == 0
+        held[iteration] = (sc.point_cloud.detach()[valid].clone(), sc.point_cloud_features.detach()[valid].clone())
+        return means
+
+    def recording_refinement():
+        calls = trainer.adaptive_controller.refinement_calls
+        refinement()
+        if trainer.adaptive_controller.refinement_calls != calls:
+            cycles.append(trainer.adaptive_controller.last_refinement_counts())
+    trainer.validation, trainer.adaptive_controller.refinement = recording_validation, recording_refinement
+    trainer.train()
+    order = trainer.view_order
+    assert sorted(held) == [3, 6] and trainer.last_validation[0] == 6
+    assert trainer.adaptive_controller.iteration_counter == n_it - 1            # validation did not reach the hook
+    print([{k: c[k] for k in ("densify", "fillable", "over", "under", "transparent", "floaters", "valid_before", "valid_after")} for c in cycles])
+    # the conditions trainer_util.DENSIFY_CONTROLLER was chosen for
+    assert len(cycles) == 3 and sum(c["fillable"] > 0 for c in cycles) >= 2
+    assert any(c["transparent"] + c["floaters"] > 0 for c in cycles)
+
+    at_three = {}
+
+    def after_iteration(it, scene):
+        if it == 3:
+            valid = scene.point_invalid_mask == 0
+            at_three["rows"] = (scene.point_cloud.detach()[valid].clone(), scene.point_cloud_features.detach()[valid].clone())
+    scene, controller, op = hand_written_loop(data, trainer.config, order, n_it, band_interval, decay_interval, rate, sparse_adam, seed=3,
+                                              downsample_factor=2, after_iteration=after_iteration, foreign_renders_after=(3, 6))
+    assert op.lr == trainer.position_optimizer.lr == 1e-4 * rate * rate * rate * rate
+    assert trainer.adaptive_controller.refinement_calls >= 3 and controller.refinement_calls >= 3
+    assert controller.last_refinement_counts() == trainer.adaptive_controller.last_refinement_counts()
+    assert _bits_equal(trainer.scene.point_cloud, scene.point_cloud)
+    assert _bits_equal(trainer.scene.point_cloud_features, scene.point_cloud_features)
+    assert torch.equal(trainer.scene.point_invalid_mask, scene.point_invalid_mask)
+    assert torch.equal(trainer.scene.point_object_id, scene.point_object_id)
+    assert int((scene.point_invalid_mask == 0).sum()) != TU.N_POINTS
+    # scene_3.parquet, written in the middle of the run: the valid rows the trainer held then, which are the hand loop's
+    loaded = GaussianPointCloudScene.from_parquet(os.path.join(trainer.config.output_model_dir, "scene_3.parquet"), device=DEV)
+    assert loaded.point_cloud.shape[0] == held[3][0].shape[0] != TU.N_POINTS
+    assert _bits_equal(loaded.point_cloud, held[3][0]) and _bits_equal(loaded.point_cloud_features, held[3][1])
+    assert _bits_equal(at_three["rows"][0], held[3][0]) and _bits_equal(at_three["rows"][1], held[3][1])
 
 
 def test_two_runs_with_one_seed_are_bit_identical(data, tmp_path):

@@ -60,13 +60,31 @@ def write_dataset(root, device="cuda:0", initial=None):
     return dict(paths=paths, images=images)
 
 
-def train_config(paths, out_dir, **overrides):
-    """a TrainConfig on the dataset: densification off (the controller's warm-up lies beyond any run here), nothing printed"""
+# Densification within an 8-iteration run of the 400-point scene (600 rows) at downsample factor 2 (32x48): a cycle at
+# iterations 2, 4 and 6, floater removal from iteration 4 on.  Chosen with a CPU loop of density_loop_case.py's kind on this scene
+# (the oracle's renders as targets, resized as the host target path does; loss_ref's L1+SSIM and regulariser; torch.optim.Adam at
+# the learning rates of test_gpu_trainer.py; view order of seed 3).  There the three cycles fill 84, 142 and 113 rows (over- and
+# under-reconstructed ones both, the last one cut short by a full scene), the first prunes 104 transparent rows, the second 35
+# floaters, and the valid count goes 400 -> 380 -> 487 -> 600.
+DENSIFY_SCENE = dict(max_num_points_ratio=1.5)
+DENSIFY_CONTROLLER = dict(num_iterations_warm_up=2, num_iterations_densify=2, iteration_start_remove_floater=3,
+                          densification_view_space_position_gradients_threshold=4e-4, under_reconstructed_num_pixels_threshold=25,
+                          floater_near_camrea_num_pixels_threshold=25, floater_depth_threshold=6.0)
+
+
+def train_config(paths, out_dir, densify=False, **overrides):
+    """a TrainConfig on the dataset, nothing printed.  densify=False: densification off (the controller's warm-up lies beyond
+    any run here); densify=True: DENSIFY_SCENE and DENSIFY_CONTROLLER"""
     from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
     config = GaussianPointCloudTrainer.TrainConfig(
         train_dataset_json_path=paths["train"], val_dataset_json_path=paths["val"], pointcloud_parquet_path=paths["cloud"],
         summary_writer_log_dir=os.path.join(str(out_dir), "logs"), output_model_dir=os.path.join(str(out_dir), "model"))
     config.adaptive_controller_config.num_iterations_warm_up = 10 ** 6
+    if densify:
+        for sub, values in ((config.gaussian_point_cloud_scene_config, DENSIFY_SCENE), (config.adaptive_controller_config, DENSIFY_CONTROLLER)):
+            for name, value in values.items():
+                assert hasattr(sub, name), name
+                setattr(sub, name, value)
     for name, value in overrides.items():
         assert hasattr(config, name), name
         setattr(config, name, value)
