@@ -10,3 +10,4 @@ from .LossFunction import LossFunction  # noqa: F401
 from .ImagePoseDataset import ImagePoseDataset  # noqa: F401
 from .targets import TargetStore, image_resample  # noqa: F401
 from .GaussianPointTrainer import GaussianPointCloudTrainer  # noqa: F401
+from . import mixture  # noqa: F401

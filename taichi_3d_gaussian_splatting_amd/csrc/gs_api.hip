@@ -7,6 +7,7 @@
 #include "../../include/gs_knn.h"
 #include "../../include/gs_exchange.h"
 #include "../../include/gs_targets.h"
+#include "../../include/gs_mixture.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -154,6 +155,7 @@ struct gs_ctx {
     DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
     DevBuf merge_tags, merge_ids;          // gs_merge_rows: one tag byte per point-cloud row, the id words of all lists (block totals: row_block_totals)
     DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
+    DevBuf mix_records, mix_sums, mix_partial;         // gs_mixture_*: their own work memory, read by nothing else
     std::vector<struct ResampleTable*> resample_tables;   // gs_image_resample: the tables of the geometries seen, oldest first
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
@@ -214,7 +216,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp, &c->first_hist,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
-                      &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree };
+                      &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1447,6 +1449,47 @@ extern "C" int gs_knn(gs_ctx* c, const float* xyz, const int8_t* invalid_mask, i
     gs_launch_knn(xyz, invalid_mask, n_points, k, d2_out, idx_out, c->knn_sort.p, c->knn_hist.p, c->knn_points.p, c->knn_tree.p, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
+}
+
+// ---- the scene as a Gaussian mixture (include/gs_mixture.h, k_mixture.hip) ----------------------------------------------------
+// Everything is queued on the call's stream; nothing is read back.
+static int mixture_call(const char* name, gs_ctx* c, const float* point_cloud, const float* features, const int8_t* invalid_mask,
+                        int64_t n_points, const float* queries, int64_t n_q, int fourier, const float* centre, float* out, gs_stream stream_)
+{
+    const std::string who(name);
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (n_points < 0 || n_points > (int64_t)GS_MIXTURE_MAX_POINTS)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": n_points must be in [0, 2^30]");
+    if (n_q < 0 || n_q > (int64_t)GS_MIXTURE_MAX_QUERIES)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + (fourier ? ": n_k must be in [0, 2^30]" : ": n_x must be in [0, 2^30]"));
+    if (n_points == 0 || n_q == 0) return GS_OK;
+    if (!point_cloud || !features || !queries || !out || (fourier && !centre))
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array with n_points > 0 and " + (fourier ? "n_k > 0" : "n_x > 0"));
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
+    int rc;
+    if ((rc = grow(c, { NEED(c->mix_records, gs_mix_record_bytes(n_points)), NEED(c->mix_sums, gs_mix_sum_bytes(n_points)),
+                        NEED(c->mix_partial, gs_mix_partial_bytes(n_points, n_q)) })) != GS_OK) return rc;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    gs_launch_mixture(point_cloud, features, invalid_mask, n_points, queries, n_q, fourier, centre, out, c->mix_records.p, c->mix_sums.p,
+                      c->mix_partial.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_mixture_log_density(gs_ctx* c, const float* point_cloud, const float* point_cloud_features, const int8_t* point_invalid_mask,
+                                      int64_t n_points, const float* x, int64_t n_x, float* log_density_out, gs_stream stream_)
+{
+    return mixture_call("gs_mixture_log_density", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, x, n_x, 0, nullptr,
+                        log_density_out, stream_);
+}
+
+extern "C" int gs_mixture_fourier(gs_ctx* c, const float* point_cloud, const float* point_cloud_features, const int8_t* point_invalid_mask,
+                                  int64_t n_points, const float* k, int64_t n_k, const float* centre, float* re_im_out, gs_stream stream_)
+{
+    return mixture_call("gs_mixture_fourier", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, k, n_k, 1, centre,
+                        re_im_out, stream_);
 }
 
 // ---- training targets (include/gs_targets.h, k_targets.hip) -------------------------------------------------------------------

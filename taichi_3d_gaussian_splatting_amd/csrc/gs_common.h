@@ -520,6 +520,13 @@ size_t gs_knn_points_bytes(int64_t n);
 size_t gs_knn_tree_bytes(int64_t n);
 void gs_launch_knn(const float* xyz, const int8_t* invalid, int64_t n, int k, float* d2_out, int32_t* idx_out,
                    void* sort_ws, void* hist_ws, void* pts_ws, void* tree_ws, hipStream_t s);
+// k_mixture.hip (include/gs_mixture.h): log-density (fourier == 0, out n_q floats) or Fourier transform (out n_q (re, im) pairs) of the
+// scene read as a mixture; the three work buffers hold gs_mix_*_bytes
+size_t gs_mix_record_bytes(int64_t n_points);
+size_t gs_mix_sum_bytes(int64_t n_points);
+size_t gs_mix_partial_bytes(int64_t n_points, int64_t n_q);
+void gs_launch_mixture(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points, const float* queries,
+                       int64_t n_q, int fourier, const float* centre, float* out, void* record_ws, void* sum_ws, void* partial_ws, hipStream_t s);
 // k_targets.hip (include/gs_targets.h): the (h_out, w_out) crop of the antialiased resize of a resident image.  One axis of the
 // resize as the host made it (gs_api.hip: float64, rounded once): output i reads `count[i]` inputs from `start[i]` on with the
 // weights weight[i * taps .. + count[i]); taps <= GS_RS_MAX_TAPS.  The launcher trusts what gs_image_resample checked: the
