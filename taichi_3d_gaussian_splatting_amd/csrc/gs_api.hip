@@ -8,6 +8,7 @@
 #include "../../include/gs_exchange.h"
 #include "../../include/gs_targets.h"
 #include "../../include/gs_mixture.h"
+#include "../../include/gs_mixture_grad.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -156,6 +157,7 @@ struct gs_ctx {
     DevBuf merge_tags, merge_ids;          // gs_merge_rows: one tag byte per point-cloud row, the id words of all lists (block totals: row_block_totals)
     DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
     DevBuf mix_records, mix_sums, mix_partial;         // gs_mixture_*: their own work memory, read by nothing else
+    DevBuf mixg_queries, mixg_partial, mixg_sums, mixg_x_partial;   // gs_mixture_*_backward: theirs (and mix_records, mix_sums)
     std::vector<struct ResampleTable*> resample_tables;   // gs_image_resample: the tables of the geometries seen, oldest first
     GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
     GsCounters* host_counters_dev = nullptr;   // the device's address of it
@@ -216,7 +218,8 @@ extern "C" int gs_destroy(gs_ctx* c)
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp, &c->first_hist,
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
-                      &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial };
+                      &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1490,6 +1493,53 @@ extern "C" int gs_mixture_fourier(gs_ctx* c, const float* point_cloud, const flo
 {
     return mixture_call("gs_mixture_fourier", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, k, n_k, 1, centre,
                         re_im_out, stream_);
+}
+
+// ---- its gradients (include/gs_mixture_grad.h, k_mixture_grad.hip) ------------------------------------------------------------
+static int mixture_grad_call(const char* name, gs_ctx* c, const float* point_cloud, const float* features, const int8_t* invalid_mask,
+                             int64_t n_points, const float* queries, int64_t n_q, int fourier, const float* centre, const float* log_density,
+                             const float* grad_out, float* grad_point_cloud, float* grad_features, float* grad_x, gs_stream stream_)
+{
+    const std::string who(name);
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (n_points < 0 || n_points > (int64_t)GS_MIXTURE_MAX_POINTS)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": n_points must be in [0, 2^30]");
+    if (n_q < 0 || n_q > (int64_t)GS_MIXTURE_MAX_QUERIES)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + (fourier ? ": n_k must be in [0, 2^30]" : ": n_x must be in [0, 2^30]"));
+    if (n_points == 0 || n_q == 0) return GS_OK;
+    if (!point_cloud || !features || !queries || !grad_out || !grad_point_cloud || !grad_features || (fourier ? !centre : !log_density))
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array with n_points > 0 and " + (fourier ? "n_k > 0" : "n_x > 0"));
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
+    int rc;
+    if ((rc = grow(c, { NEED(c->mix_records, gs_mix_record_bytes(n_points)), NEED(c->mix_sums, gs_mix_sum_bytes(n_points)),
+                        NEED(c->mixg_queries, gs_mixg_query_bytes(n_q)), NEED(c->mixg_partial, gs_mixg_partial_bytes(n_points, n_q)),
+                        NEED(c->mixg_sums, gs_mixg_sum_bytes(n_points, n_q)),
+                        NEED(c->mixg_x_partial, fourier ? 0 : gs_mixg_x_partial_bytes(n_points, n_q)) })) != GS_OK) return rc;
+    hipStream_t s;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    gs_launch_mixture_grad(point_cloud, features, invalid_mask, n_points, queries, n_q, fourier, centre, log_density, grad_out,
+                           grad_point_cloud, grad_features, grad_x, c->mix_records.p, c->mix_sums.p, c->mixg_queries.p, c->mixg_partial.p,
+                           c->mixg_sums.p, c->mixg_x_partial.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_mixture_log_density_backward(gs_ctx* c, const float* point_cloud, const float* point_cloud_features,
+                                               const int8_t* point_invalid_mask, int64_t n_points, const float* x, int64_t n_x,
+                                               const float* log_density, const float* grad_log_density, float* grad_point_cloud,
+                                               float* grad_features, float* grad_x, gs_stream stream_)
+{
+    return mixture_grad_call("gs_mixture_log_density_backward", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, x, n_x, 0,
+                             nullptr, log_density, grad_log_density, grad_point_cloud, grad_features, grad_x, stream_);
+}
+
+extern "C" int gs_mixture_fourier_backward(gs_ctx* c, const float* point_cloud, const float* point_cloud_features,
+                                           const int8_t* point_invalid_mask, int64_t n_points, const float* k, int64_t n_k, const float* centre,
+                                           const float* grad_re_im, float* grad_point_cloud, float* grad_features, gs_stream stream_)
+{
+    return mixture_grad_call("gs_mixture_fourier_backward", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, k, n_k, 1,
+                             centre, nullptr, grad_re_im, grad_point_cloud, grad_features, nullptr, stream_);
 }
 
 // ---- training targets (include/gs_targets.h, k_targets.hip) -------------------------------------------------------------------

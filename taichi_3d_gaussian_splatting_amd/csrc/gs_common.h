@@ -527,6 +527,22 @@ size_t gs_mix_sum_bytes(int64_t n_points);
 size_t gs_mix_partial_bytes(int64_t n_points, int64_t n_q);
 void gs_launch_mixture(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points, const float* queries,
                        int64_t n_q, int fourier, const float* centre, float* out, void* record_ws, void* sum_ws, void* partial_ws, hipStream_t s);
+// the pieces of it the backward calls share: the weights' sum and the records (-> where the sum
+// lies in sum_ws, *n_pad_out records written), and the fixed-order total block_sums[n_blocks] of block_sums[0 .. n_blocks)
+const double* gs_launch_mixture_records(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points,
+                                        int fourier, const float* centre, void* record_ws, void* sum_ws, int64_t* n_pad_out, hipStream_t s);
+void gs_launch_mix_total(double* block_sums, int64_t n_blocks, hipStream_t s);
+// k_mixture_grad.hip (include/gs_mixture_grad.h): the gradients of the two evaluations above to the scene (and to x, if grad_x is
+// given), from the upstream gradient `grad_out` (n_q floats, or n_q (re, im) pairs); log_density = the forward's output (density
+// only).  record_ws / sum_ws as above; the four others hold gs_mixg_*_bytes (x_partial_ws: the density only, with or without grad_x).
+size_t gs_mixg_query_bytes(int64_t n_q);
+size_t gs_mixg_partial_bytes(int64_t n_points, int64_t n_q);
+size_t gs_mixg_sum_bytes(int64_t n_points, int64_t n_q);
+size_t gs_mixg_x_partial_bytes(int64_t n_points, int64_t n_x);
+void gs_launch_mixture_grad(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points, const float* queries,
+                            int64_t n_q, int fourier, const float* centre, const float* log_density, const float* grad_out,
+                            float* grad_point_cloud, float* grad_features, float* grad_x, void* record_ws, void* sum_ws, void* query_ws,
+                            void* partial_ws, void* gsum_ws, void* x_partial_ws, hipStream_t s);
 // k_targets.hip (include/gs_targets.h): the (h_out, w_out) crop of the antialiased resize of a resident image.  One axis of the
 // resize as the host made it (gs_api.hip: float64, rounded once): output i reads `count[i]` inputs from `start[i]` on with the
 // weights weight[i * taps .. + count[i]); taps <= GS_RS_MAX_TAPS.  The launcher trusts what gs_image_resample checked: the

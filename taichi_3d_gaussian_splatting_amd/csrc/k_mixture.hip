@@ -26,7 +26,6 @@
 #define GS_MIX_POINTS_PER_WG 512        // queries per workgroup: 256 lanes x GS_MIX_LANE_POINTS
 #define GS_MIX_TARGET_WGS 2048          // workgroups the grid aims at when few query blocks exist (256 CUs x 8)
 #define GS_MIX_MAX_CHUNKS 1024
-#define GS_MIX_BATCH 4                  // records per step of the main loops
 static_assert(GS_MIX_POINTS_PER_WG == 256 * GS_MIX_LANE_POINTS, "a workgroup is 256 lanes");
 static_assert(GS_MIX_CHUNK % GS_MIX_BATCH == 0, "a unit is a whole number of steps");
 
@@ -56,17 +55,6 @@ size_t gs_mix_partial_bytes(int64_t n_points, int64_t n_x)
 }
 
 // ---- the weights' sum ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double gs_mix_block_sum(double v, double* lds)
-{
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
 __global__ void __launch_bounds__(256) k_mix_sigma_blocks(const float* __restrict__ mu, const float* __restrict__ feat,
                                                           const int8_t* __restrict__ mask, int64_t n, double* __restrict__ block_sums)
 {
@@ -105,20 +93,6 @@ __global__ void __launch_bounds__(256) k_mix_records(const float* __restrict__ m
 }
 
 // ---- the pair loops --------------------------------------------------------------------------------------------------------------
-// GS_MIX_BATCH records from a wave-uniform index on, as arrays the pair functions read with constant subscripts
-__device__ __forceinline__ void gs_mix_load_batch(const float4* __restrict__ rec, int64_t i, float (&r)[GS_MIX_BATCH][GS_MIX_REC_FLOATS])
-{
-#pragma unroll
-    for (int u = 0; u < GS_MIX_BATCH; ++u) {
-        const float4 a = rec[4 * (i + u)], b = rec[4 * (i + u) + 1], c = rec[4 * (i + u) + 2];
-        const float last = rec[4 * (i + u) + 3].x;
-        r[u][0] = a.x; r[u][1] = a.y; r[u][2] = a.z; r[u][3] = a.w;
-        r[u][4] = b.x; r[u][5] = b.y; r[u][6] = b.z; r[u][7] = b.w;
-        r[u][8] = c.x; r[u][9] = c.y; r[u][10] = c.z; r[u][11] = c.w;
-        r[u][12] = last; r[u][13] = 0.0f; r[u][14] = 0.0f; r[u][15] = 0.0f;
-    }
-}
-
 // the queries of this lane: row p of xyz, the last row where p is past the end (computed, never written)
 __device__ __forceinline__ void gs_mix_load_queries(const float* __restrict__ xyz, int64_t n_x, int64_t (&p)[GS_MIX_LANE_POINTS],
                                                     float (&v)[GS_MIX_LANE_POINTS][3], bool (&finite)[GS_MIX_LANE_POINTS])
@@ -234,16 +208,34 @@ __global__ void __launch_bounds__(256) k_mix_merge_fourier(const float2* __restr
 // ---- launch --------------------------------------------------------------------------------------------------------------------
 // fourier == 0: out = n_q log-densities, centre unused; else out = n_q (re, im) pairs.  n_points and n_q are > 0; the three work
 // buffers hold gs_mix_record_bytes / gs_mix_sum_bytes / gs_mix_partial_bytes.
-void gs_launch_mixture(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points, const float* queries,
-                       int64_t n_q, int fourier, const float* centre, float* out, void* record_ws, void* sum_ws, void* partial_ws, hipStream_t s)
+// block_sums[n_blocks] = the sum of block_sums[0 .. n_blocks) in the fixed order of k_mix_sigma_total
+void gs_launch_mix_total(double* block_sums, int64_t n_blocks, hipStream_t s)
+{
+    k_mix_sigma_total<<<1, 256, 0, s>>>(block_sums, n_blocks);
+}
+
+// The weights' sum and the records of a call (the first three launches of gs_launch_mixture; the backward calls read the same
+// records).  -> where the sum lies in sum_ws; *n_pad_out = records written, a multiple of GS_MIX_CHUNK.
+const double* gs_launch_mixture_records(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points,
+                                        int fourier, const float* centre, void* record_ws, void* sum_ws, int64_t* n_pad_out, hipStream_t s)
 {
     const int64_t n_pad = gs_mix_units(n_points) * GS_MIX_CHUNK, blocks = gs_mix_sigma_blocks(n_points);
     double* sums = reinterpret_cast<double*>(sum_ws);
+    k_mix_sigma_blocks<<<(unsigned)blocks, 256, 0, s>>>(point_cloud, features, invalid, n_points, sums);
+    gs_launch_mix_total(sums, blocks, s);
+    k_mix_records<<<(unsigned)(n_pad / 256), 256, 0, s>>>(point_cloud, features, invalid, n_points, n_pad, sums + blocks, fourier, centre,
+                                                          reinterpret_cast<float4*>(record_ws));
+    *n_pad_out = n_pad;
+    return sums + blocks;
+}
+
+void gs_launch_mixture(const float* point_cloud, const float* features, const int8_t* invalid, int64_t n_points, const float* queries,
+                       int64_t n_q, int fourier, const float* centre, float* out, void* record_ws, void* sum_ws, void* partial_ws, hipStream_t s)
+{
+    int64_t n_pad;
+    gs_launch_mixture_records(point_cloud, features, invalid, n_points, fourier, centre, record_ws, sum_ws, &n_pad, s);
     float4* rec = reinterpret_cast<float4*>(record_ws);
     float2* partial = reinterpret_cast<float2*>(partial_ws);
-    k_mix_sigma_blocks<<<(unsigned)blocks, 256, 0, s>>>(point_cloud, features, invalid, n_points, sums);
-    k_mix_sigma_total<<<1, 256, 0, s>>>(sums, blocks);
-    k_mix_records<<<(unsigned)(n_pad / 256), 256, 0, s>>>(point_cloud, features, invalid, n_points, n_pad, sums + blocks, fourier, centre, rec);
     int64_t upc;
     const int n_chunks = gs_mix_chunks(n_points, n_q, &upc);
     const dim3 grid((unsigned)((n_q + GS_MIX_POINTS_PER_WG - 1) / GS_MIX_POINTS_PER_WG), (unsigned)n_chunks);

@@ -11,6 +11,9 @@ together, and compare_volume_to_transform() (alias ft_grab_scene) returns the re
 difference and the cosine similarity between the DFT of the sampled volume and the analytic transform -- without printing
 or plotting.  The grid helpers are plain torch and work on any device; nothing here reads a value back to the host.
 
+log_density(), density(), fourier() and the two volumes are differentiable to the scene's parameters (and the density to x):
+mixture_grad.py, include/gs_mixture_grad.h.
+
 There is no fallback path: the two evaluations go through _native.call(), and a CPU tensor is refused.
 """
 import ctypes as C
@@ -19,7 +22,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _native
+from . import _native, mixture_grad
 
 MAX_POINTS = 2 ** 30
 MAX_QUERIES = 2 ** 30
@@ -90,34 +93,65 @@ def _check(scene_or_tensors, queries, what):
     return _f32(pc), _f32(feat), mask, _f32(queries)
 
 
-def log_density(scene_or_tensors, x):
-    """-> (P,) f32: log sum_i pi_i N(x; mu_i, Sigma_i) at the rows of x (P,3); -inf everywhere if no row takes part, NaN for a
-    non-finite row of x.  Queued on the current stream of the scene's device; no host synchronisation."""
-    _bind()
-    pc, feat, mask, x = _check(scene_or_tensors, x, "x")
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+def _log_density(pc, feat, mask, x):
+    """the library call on checked f32 tensors"""
     out = torch.full((x.shape[0],), -math.inf, dtype=torch.float32, device=pc.device)
     _native.call("gs_mixture_log_density", pc.device, _native.shared_ctx(pc.device), _native.ptr(pc), _native.ptr(feat),
                  _native.ptr(mask), pc.shape[0], _native.ptr(x), x.shape[0], _native.ptr(out))
     return out
 
 
+def log_density(scene_or_tensors, x):
+    """-> (P,) f32: log sum_i pi_i N(x; mu_i, Sigma_i) at the rows of x (P,3); -inf everywhere if no row takes part, NaN for a
+    non-finite row of x.  Queued on the current stream of the scene's device; no host synchronisation.
+    Differentiable (mixture_grad.LogDensity, the same bits) when grad mode is on and point_cloud, point_cloud_features or x
+    requires a gradient: to the positions, to q / log s / opacity logit (the SH columns get zeros) and to x."""
+    _bind()
+    pc, feat, mask, x32 = _check(scene_or_tensors, x, "x")
+    raw_pc, raw_feat, _ = _tensors(scene_or_tensors)
+    if _wants_grad(raw_pc, raw_feat, x):
+        return mixture_grad.LogDensity.apply(raw_pc, raw_feat, x, mask)
+    return _log_density(pc, feat, mask, x32)
+
+
 def density(scene_or_tensors, x):
-    """-> (P,) f32: exp(log_density)"""
+    """-> (P,) f32: exp(log_density); differentiable like it"""
     return log_density(scene_or_tensors, x).exp()
+
+
+def _centre(centre, device):
+    centre = torch.as_tensor(centre, dtype=torch.float32, device=device).detach().reshape(-1).contiguous()
+    if centre.shape[0] != 3:
+        raise ValueError("centre must hold 3 values")
+    return centre
+
+
+def _fourier(pc, feat, mask, k, centre):
+    """the library call on checked f32 tensors -> (P,2) f32, real and imaginary part"""
+    out = torch.zeros((k.shape[0], 2), dtype=torch.float32, device=pc.device)
+    _native.call("gs_mixture_fourier", pc.device, _native.shared_ctx(pc.device), _native.ptr(pc), _native.ptr(feat),
+                 _native.ptr(mask), pc.shape[0], _native.ptr(k), k.shape[0], _native.ptr(centre), _native.ptr(out))
+    return out
 
 
 def fourier(scene_or_tensors, k, centre):
     """-> (P,) complex64: sum_i pi_i exp(-1/2 k^T Sigma_i k - i k.(mu_i - centre)) at the rows of k (P,3), radians per unit;
-    centre a tensor of 3 (it stays on the device).  0 everywhere if no row takes part, NaN for a non-finite row of k."""
+    centre a tensor of 3 (it stays on the device).  0 everywhere if no row takes part, NaN for a non-finite row of k.
+    Differentiable to point_cloud and point_cloud_features (mixture_grad.Fourier, the same bits) when grad mode is on and one
+    of them requires a gradient.  k and centre get no gradient: asking for one is an error, not a silent zero."""
+    for name, t in (("k", k), ("centre", centre)):
+        if _wants_grad(t):
+            raise ValueError(f"{name} requires a gradient, and the transform has none to {name}: detach it")
     _bind()
-    pc, feat, mask, k = _check(scene_or_tensors, k, "k")
-    centre = torch.as_tensor(centre, dtype=torch.float32, device=pc.device).reshape(-1).contiguous()
-    if centre.shape[0] != 3:
-        raise ValueError("centre must hold 3 values")
-    out = torch.zeros((k.shape[0], 2), dtype=torch.float32, device=pc.device)
-    _native.call("gs_mixture_fourier", pc.device, _native.shared_ctx(pc.device), _native.ptr(pc), _native.ptr(feat),
-                 _native.ptr(mask), pc.shape[0], _native.ptr(k), k.shape[0], _native.ptr(centre), _native.ptr(out))
-    return torch.view_as_complex(out)
+    pc, feat, mask, k32 = _check(scene_or_tensors, k, "k")
+    raw_pc, raw_feat, _ = _tensors(scene_or_tensors)
+    if _wants_grad(raw_pc, raw_feat):
+        return torch.view_as_complex(mixture_grad.Fourier.apply(raw_pc, raw_feat, k, centre, mask))
+    return torch.view_as_complex(_fourier(pc, feat, mask, k32, _centre(centre, pc.device)))
 
 
 def takes_part(scene_or_tensors):
@@ -130,7 +164,9 @@ def takes_part(scene_or_tensors):
 
 def bounding_box(scene_or_tensors, n_std=3.0):
     """-> (2,3) f32 on the scene's device: per axis, mean -+ n_std population standard deviations of the means of the rows that
-    take part (the reference's estimate_gmm_bbox: a normal fit per axis, 3 deviations)."""
+    take part (the reference's estimate_gmm_bbox: a normal fit per axis, 3 deviations).  Detached: the box is where the mixture
+    is looked at, not a quantity a gradient goes through, so density_volume / fourier_volume differentiate through the two
+    evaluations at fixed sample points and frequencies."""
     pc = _tensors(scene_or_tensors)[0]
     part = takes_part(scene_or_tensors)
     w = part.to(torch.float64).unsqueeze(1)
@@ -175,16 +211,18 @@ def frequency_grid(bbox, G, sample_spacing=False, shift=True):
 
 def density_volume(scene_or_tensors, G=35, bbox=None):
     """-> (G,G,G) f32: the mixture's density on sample_grid(bbox, G) (the reference's sample_gmm); bbox defaults to
-    bounding_box(scene)"""
+    bounding_box(scene).  Differentiable like density()."""
     bbox = bounding_box(scene_or_tensors) if bbox is None else bbox
     return density(scene_or_tensors, sample_grid(bbox, G).reshape(-1, 3)).reshape(G, G, G)
 
 
 def fourier_volume(scene_or_tensors, G=35, bbox=None, sample_spacing=False, shift=True, centre=None):
     """-> (G,G,G) complex64: the analytic transform on frequency_grid(bbox, G, ...), phases relative to the middle of the box
-    (the reference's transform_gmm_to_fourier1) or to `centre`"""
+    (the reference's transform_gmm_to_fourier1) or to `centre`.  Differentiable like fourier(); a bbox or centre that requires a
+    gradient is detached here."""
     bbox = bounding_box(scene_or_tensors) if bbox is None else bbox
-    centre = (bbox[0] + bbox[1]) / 2.0 if centre is None else centre
+    bbox = bbox.detach()
+    centre = (bbox[0] + bbox[1]) / 2.0 if centre is None else torch.as_tensor(centre).detach()
     k = frequency_grid(bbox, G, sample_spacing, shift).reshape(-1, 3)
     return fourier(scene_or_tensors, k, centre).reshape(G, G, G)
 
