@@ -1,0 +1,88 @@
+"""Render a trained scene: python gaussian_point_render.py --parquet_path SCENE.parquet --poses POSES.pt|DATASET.json
+--output_prefix DIR (the reference's script and arguments).
+
+--poses is a .pt file saved with torch.save() holding (F,4,4) T_pointcloud_camera matrices, or a dataset JSON of the trainer:
+then every view is rendered under its own pose and camera, the ground truth goes to --gt_prefix (if given) and the per-view
+and mean metrics to --metrics_json (default <output_prefix>/metrics.json): 8-bit PSNR from the exact sum of squared
+differences, and the float PSNR and SSIM the trainer's validation logs.
+
+Beyond the reference: several --parquet_path values are composed into one scene (the visualiser's --parquet_path_list), with
+--placements a JSON list of {"q": [x,y,z,w], "t": [x,y,z], "scale": s} per scene; --bake_to PATH (.parquet or .ply) writes the
+composition as one ordinary scene in the world frame and exits; --format png|ppm|npy; --depth writes the colour-mapped depth
+beside every frame; --image_height / --image_width / --camera_intrinsics fx fy cx cy replace the defaults used with a .pt.
+"""
+import argparse
+import json
+import os
+from pathlib import Path
+
+import torch
+
+from taichi_3d_gaussian_splatting_amd.GaussianPointRenderer import GaussianPointRenderer
+from taichi_3d_gaussian_splatting_amd.ImagePoseDataset import ImagePoseDataset
+from taichi_3d_gaussian_splatting_amd.targets import TargetStore
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser("Render a Gaussian Point Cloud Scene")
+    parser.add_argument("--parquet_path", type=str, required=True, nargs="+")
+    parser.add_argument("--poses", type=str, help="a .pt file that was saved with torch.save(), or a dataset json file of the trainer")
+    parser.add_argument("--output_prefix", type=str)
+    parser.add_argument("--gt_prefix", type=str, default="")
+    parser.add_argument("--portrait_mode", action="store_true", default=False)
+    parser.add_argument("--format", choices=("png", "ppm", "npy"), default="png")
+    parser.add_argument("--depth", action="store_true", default=False)
+    parser.add_argument("--bake_to", type=str, default="")
+    parser.add_argument("--metrics_json", type=str, default="")
+    parser.add_argument("--placements", type=str, default="")
+    parser.add_argument("--image_height", type=int)
+    parser.add_argument("--image_width", type=int)
+    parser.add_argument("--camera_intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"))
+    parser.add_argument("--device", type=str, default="cuda")
+    args = parser.parse_args()
+    if not args.bake_to and not (args.poses and args.output_prefix):
+        parser.error("--poses and --output_prefix are required unless --bake_to is given")
+
+    parquet_path = args.parquet_path[0] if len(args.parquet_path) == 1 else list(args.parquet_path)
+    targets = None
+    if not args.poses:
+        cameras = torch.eye(4).unsqueeze(0)
+    elif args.poses.endswith(".pt"):
+        cameras = torch.load(args.poses)
+    elif args.poses.endswith(".json"):
+        targets = TargetStore.from_dataset(ImagePoseDataset(dataset_json_path=args.poses), device=args.device)
+        cameras = torch.eye(4).unsqueeze(0)             # the views carry their own poses and cameras
+    else:
+        raise ValueError(f"Unrecognized poses file format: {args.poses}, Must be .pt or .json file")
+    config = GaussianPointRenderer.GaussianPointRendererConfig(parquet_path, cameras, device=args.device)
+    if args.portrait_mode:
+        config.set_portrait_mode()
+    if args.image_height is not None:
+        config.image_height = args.image_height
+    if args.image_width is not None:
+        config.image_width = args.image_width
+    if args.camera_intrinsics is not None:
+        fx, fy, cx, cy = args.camera_intrinsics
+        config.camera_intrinsics = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+    renderer = GaussianPointRenderer(config, frame_format=args.format)
+    if args.placements:
+        with open(args.placements) as fh:
+            for k, placement in enumerate(json.load(fh)):
+                renderer.composition.place(k, placement["q"], placement["t"], placement.get("scale", 1.0))
+
+    if args.bake_to:
+        baked = renderer.composition.bake()
+        (baked.to_ply if args.bake_to.endswith(".ply") else baked.to_parquet)(args.bake_to)
+        raise SystemExit(0)
+
+    output_prefix = Path(args.output_prefix)
+    os.makedirs(output_prefix, exist_ok=True)
+    gt_prefix = None
+    if args.gt_prefix:
+        gt_prefix = Path(args.gt_prefix)
+        os.makedirs(gt_prefix, exist_ok=True)
+    metrics = renderer.run(output_prefix, depth=args.depth, targets=targets, gt_prefix=gt_prefix)
+    if metrics is not None:
+        with open(args.metrics_json or output_prefix / "metrics.json", "w") as fh:
+            json.dump(metrics, fh, indent=1)
+            fh.write("\n")
+        print(json.dumps(metrics["mean"]))

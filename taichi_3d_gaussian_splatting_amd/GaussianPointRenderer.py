@@ -1,0 +1,157 @@
+"""GaussianPointRenderer -- the reference's renderer class (gaussian_point_render.py:20-122) on this package: trained scenes
+(one parquet, or a list of them as the visualiser's --parquet_path_list) held as a compose.SceneComposition, rendered under a
+list of camera poses by the rasteriser's rgb_only path under no_grad, the frames leaving the device through frames.FrameSink.
+
+Same nested GaussianPointRendererConfig fields and defaults, set_portrait_mode, ExtraSceneInfo, crop of the image size to
+multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. and run(output_prefix).  What differs:
+  - all poses are converted once, batched (SE3_to_quaternion_and_translation_torch on (F,4,4)), and become the K pose rows of
+    every frame in one call (SceneComposition.camera_rows), instead of one conversion per frame;
+  - a frame is converted to 8 bits on the device (gs_frame_to_u8, bit for bit the reference's clamp(image * 255, 0, 255).byte())
+    and a quarter of the bytes crosses to pinned memory on a side stream while the next frame renders; files are encoded by
+    the sink's writer threads;
+  - run() can also write the colour-mapped depth, and with a targets.TargetStore it renders the store's views with their own
+    cameras and returns per-view metrics: the 8-bit PSNR from the exact sum of squared differences, and the float PSNR and
+    SSIM the trainer's validation() logs, from the same LossFunction kernels -- all read from the device once, at the end.
+"""
+import os
+from dataclasses import dataclass, field
+from typing import List, Optional, Union
+
+import numpy as np
+import torch
+
+from . import frames
+from .Camera import CameraInfo
+from .compose import SceneComposition
+from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
+from .LossFunction import LossFunction
+from .utils import SE3_to_quaternion_and_translation_torch
+
+
+class GaussianPointRenderer:
+    @dataclass
+    class GaussianPointRendererConfig:
+        parquet_path: Union[str, List[str]]
+        cameras: torch.Tensor
+        device: str = "cuda"
+        image_height: int = 544
+        image_width: int = 976
+        camera_intrinsics: torch.Tensor = field(default_factory=lambda: torch.tensor(
+            [[581.743, 0.0, 488.0], [0.0, 581.743, 272.0], [0.0, 0.0, 1.0]]))
+
+        def set_portrait_mode(self):
+            self.image_height = 976
+            self.image_width = 544
+            self.camera_intrinsics = torch.tensor(
+                [[1163.486, 0.0, 272.0], [0.0, 1163.486, 488.0], [0.0, 0.0, 1.0]])
+
+    ExtraSceneInfo = SceneComposition.ExtraSceneInfo
+
+    def __init__(self, config: "GaussianPointRenderer.GaussianPointRendererConfig", frame_format: str = "png", slots: int = 4) -> None:
+        self.config = config
+        self.config.image_height = self.config.image_height - self.config.image_height % 16
+        self.config.image_width = self.config.image_width - self.config.image_width % 16
+        paths = [config.parquet_path] if isinstance(config.parquet_path, (str, bytes, os.PathLike)) else list(config.parquet_path)
+        self.composition = SceneComposition(paths, device=config.device)
+        self.scene = self.composition.scene
+        self.extra_scene_info_dict = self.composition.extra_scene_info_dict
+        self.device = self.composition.device
+        self.cameras = self.config.cameras.to(device=self.device, dtype=torch.float32)
+        self.camera_info = CameraInfo(
+            camera_intrinsics=self.config.camera_intrinsics.to(device=self.device, dtype=torch.float32),
+            camera_width=self.config.image_width,
+            camera_height=self.config.image_height,
+            camera_id=0,
+        )
+        Rast = GaussianPointCloudRasterisation
+        self.rasteriser = Rast(config=Rast.GaussianPointCloudRasterisationConfig(
+            near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100., rgb_only=True))
+        self._rasteriser_with_depth = None
+        self.frame_format, self.slots = frame_format, slots
+        self.loss_function = LossFunction(LossFunction.LossFunctionConfig(enable_regularization=False))
+
+    def _with_depth(self):
+        if self._rasteriser_with_depth is None:
+            Rast = GaussianPointCloudRasterisation
+            self._rasteriser_with_depth = Rast(config=Rast.GaussianPointCloudRasterisationConfig(
+                near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100.))
+        return self._rasteriser_with_depth
+
+    def pose_rows(self, cameras: Optional[torch.Tensor] = None):
+        """(F,4,4) T_pointcloud_camera (default: the config's cameras) -> (F,K,4), (F,K,3): the pose rows of every frame for
+        the composition's current placements, converted once"""
+        cameras = self.cameras if cameras is None else cameras.to(device=self.device, dtype=torch.float32)
+        q, t = SE3_to_quaternion_and_translation_torch(cameras)
+        K = len(self.composition)
+        q_rows, t_rows = self.composition.camera_rows(q, t)
+        return q_rows.reshape(-1, K, 4), t_rows.reshape(-1, K, 3)
+
+    def render(self, q_rows: torch.Tensor, t_rows: torch.Tensor, camera_info: Optional[CameraInfo] = None, depth: bool = False):
+        """one frame under the (K,4), (K,3) pose rows -> (image (H,W,3) f32, depth (H,W) or None), band 3, no gradient"""
+        Rast = GaussianPointCloudRasterisation
+        with torch.no_grad():
+            image, image_depth, _ = (self._with_depth() if depth else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
+                point_cloud=self.scene.point_cloud,
+                point_cloud_features=self.scene.point_cloud_features,
+                point_invalid_mask=self.scene.point_invalid_mask,
+                point_object_id=self.scene.point_object_id,
+                camera_info=self.camera_info if camera_info is None else camera_info,
+                q_pointcloud_camera=q_rows,
+                t_pointcloud_camera=t_rows,
+                color_max_sh_band=3,
+            ))
+        return image, (image_depth if depth else None)
+
+    def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None):
+        """Render every camera of the config to <output_prefix>/frame_<i:03>.<format> (and depth_<i:03> with depth=True).
+        output_prefix None: the frames still cross to the host, nothing is written.
+
+        targets (a targets.TargetStore): its views are rendered instead, each under its own pose and camera, and compared with
+        its image; gt_prefix then receives the ground-truth frames -- the stored bytes where the store holds the decoded
+        image, RGB_ROUND of the resized f32 image otherwise.  -> None without targets, else a dict with `views` (per view:
+        psnr_8bit from the exact SSE, psnr and ssim as the trainer's validation() computes them) and their `mean`."""
+        directory = None if output_prefix is None else str(output_prefix)
+        sink = frames.FrameSink(directory, fmt=self.frame_format, slots=self.slots, device=self.device)
+        gt_sink = None
+        if targets is not None and gt_prefix is not None:
+            gt_sink = frames.FrameSink(str(gt_prefix), fmt=self.frame_format, slots=self.slots, device=self.device)
+        if targets is None:
+            q_rows, t_rows = self.pose_rows()
+            for i in range(q_rows.shape[0]):
+                image, image_depth = self.render(q_rows[i], t_rows[i], depth=depth)
+                sink.submit(image, depth=image_depth)
+            sink.close()
+            return None
+        n = len(targets)
+        K = len(self.composition)
+        q_rows, t_rows = self.composition.camera_rows(targets.q, targets.t)
+        q_rows, t_rows = q_rows.reshape(n, K, 4), t_rows.reshape(n, K, 3)
+        float_metrics = torch.zeros((n, 2), dtype=torch.float32, device=self.device)      # psnr, ssim
+        sizes = []
+        for i in range(n):
+            image_gt, _, _, info = targets.target(i, 1)
+            h, w = info.camera_height, info.camera_width
+            image, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=depth)
+            stored = targets.images[i]
+            if stored.dtype == torch.uint8:
+                gt_bytes = stored
+            else:                           # an autoscaled view: its f32 image, rounded to the bytes it is compared as
+                gt_bytes = frames.frame_to_u8(image_gt.permute(1, 2, 0).contiguous(), frames.RGB_ROUND)
+            sink.submit(image, depth=image_depth, gt=gt_bytes)
+            if gt_sink is not None:
+                gt_sink.submit(gt_bytes[:h, :w])
+            with torch.no_grad():           # GaussianPointTrainer.validation(): clamp, then the loss kernels and the mse
+                image_pred = torch.clamp(image, 0, 1).permute(2, 0, 1)
+                _, _, ssim_loss = self.loss_function(image_pred, image_gt)
+                float_metrics[i, 0] = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+                float_metrics[i, 1] = 1.0 - ssim_loss
+            sizes.append(h * w * 3)
+        sse = sink.close().numpy()
+        if gt_sink is not None:
+            gt_sink.close()
+        float_metrics = float_metrics.cpu().numpy().astype(np.float64)
+        psnr_8bit = [float(frames.psnr_from_sse(s, size)) for s, size in zip(sse, sizes)]
+        views = [dict(index=i, sse_8bit=int(sse[i]), psnr_8bit=psnr_8bit[i], psnr=float(float_metrics[i, 0]), ssim=float(float_metrics[i, 1]))
+                 for i in range(n)]
+        mean = {name: float(np.mean([v[name] for v in views])) if views else float("nan") for name in ("psnr_8bit", "psnr", "ssim")}
+        return dict(views=views, mean=mean)

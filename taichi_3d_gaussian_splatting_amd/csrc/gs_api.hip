@@ -9,6 +9,8 @@
 #include "../../include/gs_targets.h"
 #include "../../include/gs_mixture.h"
 #include "../../include/gs_mixture_grad.h"
+#include "../../include/gs_compose.h"
+#include "../../include/gs_frames.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -1652,6 +1654,83 @@ extern "C" int gs_image_resample(gs_ctx* c, const void* src, int32_t src_format,
     ResampleTable* rt = nullptr;
     if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
     gs_launch_image_resample(src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, rt->ax, rt->ay, h_out, w_out, dst, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- baking a placed scene (k_compose.hip) ----------------------------------------------------------------------------
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+extern "C" int gs_scene_bake(gs_ctx* c, const float* xyz_in, const float* features_in, int64_t n, const float* q_A, const float* t_A,
+                             float scale, const float* sh_matrices, float* xyz_out, float* features_out, int64_t row_offset,
+                             gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: ctx is NULL");
+    if (n < 0 || row_offset < 0 || n > INT32_MAX || row_offset > INT32_MAX || n + row_offset > INT32_MAX)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: n and row_offset must not be negative, and row_offset + n below 2^31");
+    if (!q_A || !t_A || !sh_matrices) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: NULL q_A, t_A or sh_matrices");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: scale must be finite and > 0");
+    const double qn = std::sqrt((double)q_A[0] * q_A[0] + (double)q_A[1] * q_A[1] + (double)q_A[2] * q_A[2] + (double)q_A[3] * q_A[3]);
+    if (!std::isfinite(qn) || !(qn > 0.0)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: q_A must have a finite norm > 0");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(t_A[k])) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: t_A must be finite");
+    for (int k = 0; k < GS_BAKE_SH_FLOATS; ++k)
+        if (!std::isfinite(sh_matrices[k])) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: sh_matrices must be finite");
+    if (n == 0) return GS_OK;
+    if (!xyz_in || !features_in || !xyz_out || !features_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: NULL array");
+    const size_t xyz_bytes = (size_t)n * 3 * sizeof(float), feat_bytes = (size_t)n * GS_BAKE_FEATURES * sizeof(float);
+    const float* xyz_w = xyz_out + row_offset * 3;
+    const float* feat_w = features_out + row_offset * GS_BAKE_FEATURES;
+    if (ranges_overlap(xyz_in, xyz_bytes, xyz_w, xyz_bytes) || ranges_overlap(xyz_in, xyz_bytes, feat_w, feat_bytes) ||
+        ranges_overlap(features_in, feat_bytes, xyz_w, xyz_bytes) || ranges_overlap(features_in, feat_bytes, feat_w, feat_bytes) ||
+        ranges_overlap(xyz_w, xyz_bytes, feat_w, feat_bytes))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: the rows read and the rows written overlap (the call runs out of place)");
+    // the transform in float64, rounded once
+    GsBakeTransform A;
+    const double x = q_A[0] / qn, y = q_A[1] / qn, z = q_A[2] / qn, w = q_A[3] / qn, s = (double)scale;
+    const double R[9] = { 1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                          2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                          2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y) };
+    for (int k = 0; k < 9; ++k) A.m[k] = (float)(s * R[k]);
+    for (int k = 0; k < 3; ++k) A.t[k] = t_A[k];
+    A.q[0] = (float)x; A.q[1] = (float)y; A.q[2] = (float)z; A.q[3] = (float)w;
+    A.log_scale = (float)std::log(s);
+    std::memcpy(A.sh, sh_matrices, sizeof(A.sh));
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t st;
+    if (const int rc = enter_call(c, stream_, &st)) return rc;
+    gs_launch_scene_bake(xyz_in, features_in, n, A, xyz_out, features_out, row_offset, st);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- frames out (k_frames.hip) ------------------------------------------------------------------------------------------
+extern "C" int gs_frame_to_u8(gs_ctx* c, const float* src, int32_t mode, int32_t h, int32_t w, uint8_t* dst, int64_t dst_row_pitch_bytes,
+                              const uint8_t* gt, int32_t gt_channels, int64_t gt_row_pitch_bytes, int64_t* sse, gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: ctx is NULL");
+    if (mode != GS_FRAME_RGB_TRUNC && mode != GS_FRAME_RGB_ROUND && mode != GS_FRAME_DEPTH_CMAP)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: unknown mode");
+    if (h < 0 || w < 0 || h > GS_FRAME_MAX_SIZE || w > GS_FRAME_MAX_SIZE)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: every size must be in [0, 32768]");
+    if (dst_row_pitch_bytes < (int64_t)3 * w) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: dst_row_pitch_bytes must be >= 3 * w");
+    if (gt) {
+        if (gt_channels != 3 && gt_channels != 4) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: gt_channels must be 3 or 4");
+        if (gt_row_pitch_bytes < (int64_t)w * gt_channels) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: gt_row_pitch_bytes must be >= w * gt_channels");
+        if (!sse) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: a ground truth needs the sse word");
+    } else if (sse) {
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: the sse word needs a ground truth");
+    }
+    if (h == 0 || w == 0) return GS_OK;
+    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: NULL src or dst");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_frame_to_u8(src, mode, h, w, dst, dst_row_pitch_bytes, gt, gt_channels, gt_row_pitch_bytes, sse, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

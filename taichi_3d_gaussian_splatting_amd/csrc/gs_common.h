@@ -552,6 +552,16 @@ void gs_launch_mixture_grad(const float* point_cloud, const float* features, con
 struct GsResampleAxis { const int32_t* start; const int32_t* count; const float* weight; int taps; };
 void gs_launch_image_resample(const void* src, int src_format, int channels, int H_in, int W_in, int64_t pitch_bytes, GsResampleAxis ax,
                               GsResampleAxis ay, int h_out, int w_out, float* dst, hipStream_t s);
+// k_compose.hip (include/gs_compose.h): rows [0, n) of the inputs under the transform A into rows [row_offset, row_offset + n)
+// of the outputs.  A as gs_scene_bake made it on the host (float64, rounded once): m = s R_A row-major, t = t_A, q = q_A / |q_A|
+// (xyzw), log_scale = log(s), sh = M_0 | M_1 | M_2 | M_3 row-major (1 + 9 + 25 + 49 floats).  Passed by value: wave-uniform.
+struct GsBakeTransform { float m[9]; float t[3]; float q[4]; float log_scale; float sh[84]; };
+void gs_launch_scene_bake(const float* xyz_in, const float* feat_in, int64_t n, const GsBakeTransform& A, float* xyz_out, float* feat_out,
+                          int64_t row_offset, hipStream_t s);
+// k_frames.hip (include/gs_frames.h): the uint8 (h,w,3) form of an f32 frame, and with gt the sum of squared byte differences
+// added to *sse.  The launcher trusts what gs_frame_to_u8 checked.
+void gs_launch_frame_to_u8(const float* src, int mode, int h, int w, uint8_t* dst, int64_t pitch, const uint8_t* gt, int gt_channels,
+                           int64_t gt_pitch, int64_t* sse, hipStream_t s);
 void gs_launch_reg_value(const float* feat, const int8_t* invalid, int64_t N, float* workspace, float* out, hipStream_t s);
 void gs_launch_reg_grad(const float* feat, const int8_t* invalid, int64_t N, const float* value_and_count, const float* upstream,
                         float* grad, hipStream_t s);

@@ -1,0 +1,118 @@
+"""GPU: gaussian_point_render.py end to end in child processes -- frames from a .pt of poses, metrics and ground truth from a
+dataset JSON, and --bake_to -- against the rasteriser's own output in this process."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import PIL.Image
+import pytest
+import torch
+
+import compose_ref as R
+import trainer_util
+from taichi_3d_gaussian_splatting_amd import CameraInfo, GaussianPointCloudRasterisation as Rast, GaussianPointCloudScene, compose, scene_io
+from taichi_3d_gaussian_splatting_amd.synthetic import synth, view_pose
+from taichi_3d_gaussian_splatting_amd.utils import SE3_to_quaternion_and_translation_torch, quaternion_to_rotation_matrix_torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCRIPT = os.path.join(ROOT, "gaussian_point_render.py")
+
+
+def _cli(*args):
+    p = subprocess.run([sys.executable, SCRIPT, "--device", DEV] + [str(a) for a in args], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return p
+
+
+def _rasterise(scene, q, t, info):
+    module = Rast(Rast.GaussianPointCloudRasterisationConfig(near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100.))
+    with torch.no_grad():
+        image, _, count = module(Rast.GaussianPointCloudRasterisationInput(
+            point_cloud=scene.point_cloud.detach(), point_cloud_features=scene.point_cloud_features.detach(),
+            point_object_id=scene.point_object_id, point_invalid_mask=scene.point_invalid_mask, camera_info=info,
+            q_pointcloud_camera=q, t_pointcloud_camera=t, color_max_sh_band=3))
+    return image, count
+
+
+def _poses(n):
+    cameras = torch.zeros(n, 4, 4)
+    for i in range(n):
+        q, t = view_pose(i, n)
+        cameras[i, :3, :3] = quaternion_to_rotation_matrix_torch(torch.tensor(q))[0]
+        cameras[i, :3, 3] = torch.tensor(t[0])
+        cameras[i, 3, 3] = 1.0
+    return cameras
+
+
+def test_frames_from_a_pt_of_poses_equal_the_reference_expression(tmp_path):
+    s = synth(64, 64, 48, 0.5, sh_deg=3, seed=1)
+    parquet, poses, out = tmp_path / "scene.parquet", tmp_path / "poses.pt", tmp_path / "out"
+    scene_io.save_parquet(str(parquet), s.point_cloud, s.point_cloud_features)
+    cameras = _poses(5)
+    torch.save(cameras, str(poses))
+    k = s.camera_intrinsics
+    _cli("--parquet_path", parquet, "--poses", poses, "--output_prefix", out, "--image_height", 48, "--image_width", 64,
+         "--camera_intrinsics", k[0, 0], k[1, 1], k[0, 2], k[1, 2], "--depth")
+    assert sorted(os.listdir(out)) == [f"depth_{i:03}.png" for i in range(5)] + [f"frame_{i:03}.png" for i in range(5)]
+    scene = GaussianPointCloudScene.from_parquet(str(parquet), device=DEV)
+    info = CameraInfo(torch.tensor(k, device=DEV), 48, 64, 0)
+    for i in range(5):
+        q, t = SE3_to_quaternion_and_translation_torch(cameras[i:i + 1].to(DEV))
+        image, _ = _rasterise(scene, q.contiguous(), t.contiguous(), info)
+        want = torch.clamp(image * 255, 0, 255).byte().cpu().numpy()           # gaussian_point_render.py:121 of the reference
+        with PIL.Image.open(out / f"frame_{i:03}.png") as im:
+            assert im.mode == "RGB" and np.array_equal(np.array(im), want), i
+        assert want.max() > 0
+
+
+def test_metrics_and_ground_truth_from_a_dataset_json(tmp_path):
+    data = trainer_util.write_dataset(tmp_path / "data", DEV, initial=trainer_util.perturbed(trainer_util.ground_truth_scene()))
+    views = trainer_util.TRAIN_VIEWS[:3]
+    records = json.load(open(data["paths"]["train"]))[:3]
+    three = tmp_path / "three.json"
+    three.write_text(json.dumps(records))
+    out, gt = tmp_path / "out", tmp_path / "gt"
+    _cli("--parquet_path", data["paths"]["cloud"], "--poses", three, "--output_prefix", out, "--gt_prefix", gt)
+    doc = json.loads((out / "metrics.json").read_text())
+    assert set(doc) == {"views", "mean"} and len(doc["views"]) == 3 and set(doc["mean"]) == {"psnr_8bit", "psnr", "ssim"}
+    H, W = trainer_util.H, trainer_util.W
+    for i, (view, entry) in enumerate(zip(views, doc["views"])):
+        assert set(entry) == {"index", "sse_8bit", "psnr_8bit", "psnr", "ssim"} and entry["index"] == i
+        frame = np.array(PIL.Image.open(out / f"frame_{i:03}.png")).astype(np.int64)
+        truth = np.array(PIL.Image.open(gt / f"frame_{i:03}.png"))
+        assert np.array_equal(truth, data["images"][view])                        # the stored bytes, written as they are
+        sse = int(((frame - truth.astype(np.int64)) ** 2).sum())
+        assert entry["sse_8bit"] == sse and sse > 0
+        assert abs(entry["psnr_8bit"] - 10.0 * np.log10(255.0 ** 2 / (sse / (H * W * 3)))) < 1e-9
+        # the float metrics look at the same pair of images before quantisation
+        assert abs(entry["psnr"] - entry["psnr_8bit"]) < 0.5 and 0.0 < entry["ssim"] <= 1.0
+    for name in ("psnr_8bit", "psnr", "ssim"):
+        assert abs(doc["mean"][name] - np.mean([v[name] for v in doc["views"]])) < 1e-9
+
+
+def test_bake_to_writes_a_scene_that_renders_as_the_composition(tmp_path):
+    scene, q, t, placements = R.equivalence_case(2, 256, 0.5, 48)
+    paths = []
+    for k in range(3):
+        rows = scene.point_object_id == k
+        paths.append(str(tmp_path / f"object_{k}.parquet"))
+        scene_io.save_parquet(paths[-1], scene.point_cloud[rows], scene.point_cloud_features[rows])
+    (tmp_path / "placements.json").write_text(json.dumps([dict(q=list(map(float, p[0])), t=list(map(float, p[1])), scale=p[2]) for p in placements]))
+    baked_path = tmp_path / "baked.parquet"
+    _cli("--parquet_path", *paths, "--placements", tmp_path / "placements.json", "--bake_to", baked_path)
+    assert sorted(f for f in os.listdir(tmp_path) if f.startswith("baked")) == ["baked.parquet"]
+    baked = GaussianPointCloudScene.from_parquet(str(baked_path), device=DEV)
+    assert baked.point_cloud.shape == (256, 3) and int(baked.point_object_id.abs().max()) == 0
+    comp = compose.SceneComposition(paths, device=DEV)
+    for k, p in enumerate(placements):
+        comp.place(k, *p)
+    info = CameraInfo(torch.tensor(scene.camera_intrinsics, device=DEV), scene.height, scene.width, 0)
+    q_cam, t_cam = torch.from_numpy(q[:1]).to(DEV), torch.from_numpy(t[:1]).to(DEV)
+    image_rows, count_rows = _rasterise(comp.scene, *comp.camera_rows(q_cam, t_cam), info)
+    image_baked, count_baked = _rasterise(baked, q_cam, t_cam, info)
+    assert int(count_rows.max()) > 0
+    R.assert_same_picture(image_baked.cpu().numpy(), count_baked.cpu().numpy(), image_rows.cpu().numpy(), count_rows.cpu().numpy())
