@@ -9,7 +9,12 @@ differences, and the float PSNR and SSIM the trainer's validation logs.
 Beyond the reference: several --parquet_path values are composed into one scene (the visualiser's --parquet_path_list), with
 --placements a JSON list of {"q": [x,y,z,w], "t": [x,y,z], "scale": s} per scene; --bake_to PATH (.parquet or .ply) writes the
 composition as one ordinary scene in the world frame and exits; --format png|ppm|npy; --depth writes the colour-mapped depth
-beside every frame; --image_height / --image_width / --camera_intrinsics fx fy cx cy replace the defaults used with a .pt.
+beside every frame; --image_height / --image_width / --camera_intrinsics fx fy cx cy replace the defaults used with a .pt;
+--mesh_to PATH.ply fuses the depth of every pose of a .pt into a truncated signed distance volume on the device and writes its
+zero surface as a coloured triangle mesh: --mesh_bbox X0 Y0 Z0 X1 Y1 Z1 is the volume's box (default: mixture.bounding_box of
+the scene, mean -+ 3 standard deviations of the Gaussians' positions per axis), --mesh_voxel its voxel size (default: the
+box's longest side / 255) and --mesh_trunc the truncation distance (default: 4 voxels).  With --mesh_to, --output_prefix is
+optional: without it only the mesh is written.
 """
 import argparse
 import json
@@ -18,6 +23,7 @@ from pathlib import Path
 
 import torch
 
+from taichi_3d_gaussian_splatting_amd import fusion, mixture
 from taichi_3d_gaussian_splatting_amd.GaussianPointRenderer import GaussianPointRenderer
 from taichi_3d_gaussian_splatting_amd.ImagePoseDataset import ImagePoseDataset
 from taichi_3d_gaussian_splatting_amd.targets import TargetStore
@@ -37,10 +43,17 @@ if __name__ == "__main__":
     parser.add_argument("--image_height", type=int)
     parser.add_argument("--image_width", type=int)
     parser.add_argument("--camera_intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"))
+    parser.add_argument("--mesh_to", type=str, default="", help="write the fused surface of the poses of a .pt as a binary PLY mesh")
+    parser.add_argument("--mesh_voxel", type=float, help="voxel size (default: the box's longest side / 255)")
+    parser.add_argument("--mesh_trunc", type=float, help="truncation distance (default: fusion.TRUNC_VOXELS = 4 voxels)")
+    parser.add_argument("--mesh_bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                        help="the volume's box (default: mixture.bounding_box of the scene)")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
-    if not args.bake_to and not (args.poses and args.output_prefix):
-        parser.error("--poses and --output_prefix are required unless --bake_to is given")
+    if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to)):
+        parser.error("--poses and --output_prefix (or --mesh_to) are required unless --bake_to is given")
+    if args.mesh_to and not (args.poses or "").endswith(".pt"):
+        parser.error("--mesh_to fuses the poses of a .pt file")
 
     parquet_path = args.parquet_path[0] if len(args.parquet_path) == 1 else list(args.parquet_path)
     targets = None
@@ -73,6 +86,17 @@ if __name__ == "__main__":
         baked = renderer.composition.bake()
         (baked.to_ply if args.bake_to.endswith(".ply") else baked.to_parquet)(args.bake_to)
         raise SystemExit(0)
+
+    if args.mesh_to:
+        bbox = torch.tensor(args.mesh_bbox).reshape(2, 3) if args.mesh_bbox is not None else mixture.bounding_box(renderer.scene).cpu()
+        voxel = args.mesh_voxel if args.mesh_voxel is not None else float((bbox[1] - bbox[0]).max()) / 255.0
+        volume = fusion.TSDFVolume(bbox=bbox, voxel=voxel, trunc=args.mesh_trunc, device=renderer.device)
+        mesh = renderer.fuse(volume).extract_mesh()
+        mesh.to_ply(args.mesh_to)
+        print(json.dumps({"mesh": args.mesh_to, "vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
+                          "dims": list(volume.dims), "voxel": volume.voxel, "trunc": volume.trunc}))
+        if not args.output_prefix:
+            raise SystemExit(0)
 
     output_prefix = Path(args.output_prefix)
     os.makedirs(output_prefix, exist_ok=True)

@@ -11,7 +11,9 @@ multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. a
     the sink's writer threads;
   - run() can also write the colour-mapped depth, and with a targets.TargetStore it renders the store's views with their own
     cameras and returns per-view metrics: the 8-bit PSNR from the exact sum of squared differences, and the float PSNR and
-    SSIM the trainer's validation() logs, from the same LossFunction kernels -- all read from the device once, at the end.
+    SSIM the trainer's validation() logs, from the same LossFunction kernels -- all read from the device once, at the end;
+  - fuse() renders the poses with depth and accumulated alpha and integrates them into a fusion.TSDFVolume on the device, from
+    which a triangle mesh is extracted (fusion.py).
 """
 import os
 from dataclasses import dataclass, field
@@ -20,7 +22,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
-from . import frames
+from . import frames, fusion
 from .Camera import CameraInfo
 from .compose import SceneComposition
 from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
@@ -86,11 +88,13 @@ class GaussianPointRenderer:
         q_rows, t_rows = self.composition.camera_rows(q, t)
         return q_rows.reshape(-1, K, 4), t_rows.reshape(-1, K, 3)
 
-    def render(self, q_rows: torch.Tensor, t_rows: torch.Tensor, camera_info: Optional[CameraInfo] = None, depth: bool = False):
-        """one frame under the (K,4), (K,3) pose rows -> (image (H,W,3) f32, depth (H,W) or None), band 3, no gradient"""
+    def render(self, q_rows: torch.Tensor, t_rows: torch.Tensor, camera_info: Optional[CameraInfo] = None, depth: bool = False,
+               alpha: bool = False):
+        """one frame under the (K,4), (K,3) pose rows -> (image (H,W,3) f32, depth (H,W) or None), band 3, no gradient; with
+        alpha=True (which takes the depth rasteriser) a third value, the accumulated alpha (H,W)"""
         Rast = GaussianPointCloudRasterisation
         with torch.no_grad():
-            image, image_depth, _ = (self._with_depth() if depth else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
+            outputs = (self._with_depth() if depth or alpha else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
                 point_cloud=self.scene.point_cloud,
                 point_cloud_features=self.scene.point_cloud_features,
                 point_invalid_mask=self.scene.point_invalid_mask,
@@ -99,8 +103,29 @@ class GaussianPointRenderer:
                 q_pointcloud_camera=q_rows,
                 t_pointcloud_camera=t_rows,
                 color_max_sh_band=3,
-            ))
+            ), **({"return_accumulated_alpha": True} if alpha else {}))
+        image, image_depth = outputs[0], outputs[1]
+        if alpha:
+            return image, (image_depth if depth else None), outputs[3]
         return image, (image_depth if depth else None)
+
+    def fuse(self, volume: fusion.TSDFVolume, cameras: Optional[torch.Tensor] = None) -> fusion.TSDFVolume:
+        """Render every pose ((F,4,4) T_pointcloud_camera, default: the config's cameras) with depth and accumulated alpha
+        through the depth rasteriser under no_grad and integrate the frames into `volume`, fusion.VIEWS_PER_LAUNCH views per
+        library call.  The poses and the intrinsics are taken from their host copies; no frame is copied to the host and
+        nothing here waits for the device.  -> volume"""
+        cameras = self.config.cameras if cameras is None else cameras
+        q_rows, t_rows = self.pose_rows(cameras)
+        q_world, t_world = SE3_to_quaternion_and_translation_torch(cameras.detach().to(device="cpu", dtype=torch.float32))
+        q_world, t_world = q_world.numpy(), t_world.numpy()
+        host_info = CameraInfo(camera_intrinsics=self.config.camera_intrinsics.detach().to(device="cpu", dtype=torch.float32),
+                               camera_width=self.config.image_width, camera_height=self.config.image_height, camera_id=0)
+        for first in range(0, q_rows.shape[0], fusion.VIEWS_PER_LAUNCH):
+            batch = range(first, min(first + fusion.VIEWS_PER_LAUNCH, q_rows.shape[0]))
+            rendered = [self.render(q_rows[i], t_rows[i], depth=True, alpha=True) for i in batch]
+            volume.integrate([r[1] for r in rendered], [q_world[i] for i in batch], [t_world[i] for i in batch], host_info,
+                             alpha=[r[2] for r in rendered], image=[r[0] for r in rendered])
+        return volume
 
     def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None):
         """Render every camera of the config to <output_prefix>/frame_<i:03>.<format> (and depth_<i:03> with depth=True).

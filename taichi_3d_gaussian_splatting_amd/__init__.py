@@ -11,5 +11,5 @@ from .ImagePoseDataset import ImagePoseDataset  # noqa: F401
 from .targets import TargetStore, image_resample  # noqa: F401
 from .GaussianPointTrainer import GaussianPointCloudTrainer  # noqa: F401
 from . import mixture  # noqa: F401
-from . import compose, frames  # noqa: F401
+from . import compose, frames, fusion  # noqa: F401
 from .GaussianPointRenderer import GaussianPointRenderer  # noqa: F401

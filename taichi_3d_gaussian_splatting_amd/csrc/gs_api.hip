@@ -11,6 +11,7 @@
 #include "../../include/gs_mixture_grad.h"
 #include "../../include/gs_compose.h"
 #include "../../include/gs_frames.h"
+#include "../../include/gs_fusion.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -1731,6 +1732,99 @@ extern "C" int gs_frame_to_u8(gs_ctx* c, const float* src, int32_t mode, int32_t
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_frame_to_u8(src, mode, h, w, dst, dst_row_pitch_bytes, gt, gt_channels, gt_row_pitch_bytes, sse, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- meshes from a scene (k_fusion.hip) --------------------------------------------------------------------------------------
+static bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
+
+// the checks the three calls share on (nx, ny, nz, origin, step); *n_out = nx ny nz
+static int fusion_grid(const char* who, int32_t nx, int32_t ny, int32_t nz, const float* origin, const float* step, const char* step_name,
+                       int64_t* n_out)
+{
+    if (nx < 0 || ny < 0 || nz < 0) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": a dimension is negative");
+    // each factor is below 2^31: the product of two fits 63 bits, and is compared before the third enters
+    const int64_t nxy = (int64_t)nx * ny;
+    if (nxy > GS_FUSION_MAX_VOXELS || (nz > 0 && nxy > GS_FUSION_MAX_VOXELS / nz))
+        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": nx * ny * nz exceeds GS_FUSION_MAX_VOXELS (2^30)");
+    for (int a = 0; a < 3; ++a) {
+        if (!positive_finite(step[a])) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": " + step_name + " must be finite and > 0");
+        if (!std::isfinite(origin[a])) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": origin must be finite");
+    }
+    *n_out = nxy * nz;
+    return GS_OK;
+}
+
+extern "C" int gs_tsdf_integrate(gs_ctx* c, const gs_tsdf_volume* vol, const gs_tsdf_view* views, int32_t n_views, gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: ctx is NULL");
+    if (!vol) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: volume is NULL");
+    if (n_views < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: n_views is negative");
+    int64_t n = 0;
+    if (const int rc = fusion_grid("gs_tsdf_integrate", vol->nx, vol->ny, vol->nz, vol->origin, vol->voxel, "voxel", &n)) return rc;
+    if (!positive_finite(vol->trunc)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: trunc must be finite and > 0");
+    if (!positive_finite(vol->max_weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: max_weight must be finite and > 0");
+    if (!std::isfinite(vol->min_alpha) || !std::isfinite(vol->near)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: min_alpha and near must be finite");
+    if (n > 0 && (!vol->tsdf || !vol->weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: NULL tsdf or weight");
+    if (n_views > 0 && !views) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: views is NULL");
+    for (int32_t v = 0; v < n_views; ++v) {
+        const gs_tsdf_view& V = views[v];
+        if (!V.depth) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + " has a NULL depth");
+        if (V.h < 0 || V.w < 0 || V.h > GS_FUSION_MAX_IMAGE_SIZE || V.w > GS_FUSION_MAX_IMAGE_SIZE)
+            return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + ": h and w must be in [0, 32768]");
+        bool finite = std::isfinite(V.fx) && std::isfinite(V.fy) && std::isfinite(V.cx) && std::isfinite(V.cy);
+        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(V.m[k / 4][k % 4]);
+        if (!finite) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + ": fx, fy, cx, cy and m must be finite");
+    }
+    if (n == 0 || n_views == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_tsdf_integrate(*vol, views, n_views, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+static int iso_volume_checks(const char* who, gs_ctx* c, const gs_iso_volume* vol, const void* cell_ws, const void* block_ws, int64_t* n_out)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
+    if (!vol) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": volume is NULL");
+    if (const int rc = fusion_grid(who, vol->nx, vol->ny, vol->nz, vol->origin, vol->spacing, "spacing", n_out)) return rc;
+    if (!std::isfinite(vol->level)) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": level must be finite");
+    if (*n_out > 0 && !vol->values) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values");
+    if (*n_out > 0 && (!cell_ws || !block_ws)) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL work buffer");
+    return GS_OK;
+}
+
+extern "C" int gs_isosurface_plan(gs_ctx* c, const gs_iso_volume* vol, void* cell_ws, void* block_ws, int64_t* totals, gs_stream stream_)
+{
+    int64_t n = 0;
+    if (const int rc = iso_volume_checks("gs_isosurface_plan", c, vol, cell_ws, block_ws, &n)) return rc;
+    if (n == 0) return GS_OK;
+    if (!totals) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_plan: NULL totals");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_iso_plan(*vol, cell_ws, block_ws, totals, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_isosurface_emit(gs_ctx* c, const gs_iso_volume* vol, const void* cell_ws, const void* block_ws, void* voxel_ws,
+                                  int64_t n_vertices, int64_t n_faces, float* vertices, float* colours, int32_t* faces, gs_stream stream_)
+{
+    int64_t n = 0;
+    if (const int rc = iso_volume_checks("gs_isosurface_emit", c, vol, cell_ws, block_ws, &n)) return rc;
+    if (n_vertices < 0 || n_faces < 0 || n_vertices > INT32_MAX || n_faces > INT32_MAX)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: n_vertices and n_faces must be in [0, 2^31 - 1]");
+    if (n == 0 || (n_vertices == 0 && n_faces == 0)) return GS_OK;
+    if (!voxel_ws) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: NULL work buffer");
+    if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: NULL vertices or faces");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_iso_emit(*vol, cell_ws, block_ws, voxel_ws, n_vertices, n_faces, vertices, colours, faces, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

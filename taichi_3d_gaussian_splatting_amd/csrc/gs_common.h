@@ -596,3 +596,14 @@ void gs_launch_density_apply(const gs_density_scene& scene, const gs_density_con
 void gs_launch_controller_accumulate(const int32_t* ids, const int32_t* npix, const float* mag, const float* gpc, int64_t M, int64_t N,
                                      const gs_controller_accumulators& acc, hipStream_t s);
 size_t gs_density_scratch_size(int64_t N);
+
+// k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
+// order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry
+// points checked: a non-empty volume, non-NULL arrays and work buffers, counts below 2^31.
+struct gs_tsdf_volume;
+struct gs_tsdf_view;
+struct gs_iso_volume;
+void gs_launch_tsdf_integrate(const gs_tsdf_volume& vol, const gs_tsdf_view* views, int n_views, hipStream_t s);
+void gs_launch_iso_plan(const gs_iso_volume& vol, void* cell_ws, void* block_ws, int64_t* totals, hipStream_t s);
+void gs_launch_iso_emit(const gs_iso_volume& vol, const void* cell_ws, const void* block_ws, void* voxel_ws, int64_t n_vertices,
+                        int64_t n_faces, float* vertices, float* colours, int32_t* faces, hipStream_t s);
