@@ -1,4 +1,5 @@
-"""Train a scene from images: python gaussian_point_train.py --train_config PATH (the reference's script and YAML format)."""
+"""Train a scene from images: python gaussian_point_train.py --train_config PATH (the reference's script and YAML format).
+--pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -7,6 +8,9 @@ if __name__ == "__main__":
     parser = argparse.ArgumentParser("Train a Gaussian Point Cloud Scene")
     parser.add_argument("--train_config", type=str, required=True)
     parser.add_argument("--gen_template_only", action="store_true", default=False)
+    parser.add_argument("--pixel_weights", choices=("none", "alpha", "file"), default="none",
+                        help="the loss's per-pixel weights: the RGBA images' alpha, or the dataset's mask_path images")
+    parser.add_argument("--mask_erode", type=int, default=0, help="shrink the mask by this many pixels at load")
     args = parser.parse_args()
     if args.gen_template_only:
         import dataclasses
@@ -18,5 +22,5 @@ if __name__ == "__main__":
     config = GaussianPointCloudTrainer.TrainConfig.from_yaml_file(args.train_config)
     if config.unknown_keys:
         print("ignored keys of the config:", ", ".join(config.unknown_keys))
-    trainer = GaussianPointCloudTrainer(config)
+    trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode)
     trainer.train()

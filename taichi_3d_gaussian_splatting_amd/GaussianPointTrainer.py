@@ -10,6 +10,10 @@ What differs from the reference
   - The view order is a seeded torch.randperm per epoch (trainer.view_order), not a shuffling DataLoader.
   - The clamp of the predicted image runs inside the loss kernels (clamp_predicted=True), and SSIM for the logged metrics is
     1 - the loss's third term instead of pytorch_msssim.
+  - GaussianPointCloudTrainer(config, pixel_weights="alpha" | "file") trains with a weight per pixel (masked training): the
+    store hands the weight out with the target, in the same launch, and the fused loss takes it (LossFunction's pixel_weight).
+    "none", the default, is the loop as it was.  These two settings are constructor arguments like device and writer:
+    TrainConfig keeps the reference's fields and the three extensions it has.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -192,10 +196,13 @@ class GaussianPointCloudTrainer:
             config.unknown_keys = unknown
             return config
 
-    def __init__(self, config: TrainConfig, device="cuda", writer=None):
-        """device and writer are extensions: the GPU to train on, and a summary writer to use instead of the one
-        make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter otherwise)"""
+    def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0):
+        """device, writer, pixel_weights and mask_erode are extensions: the GPU to train on; a summary writer to use instead of
+        the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter otherwise); where the per-pixel
+        weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the dataset's mask_path column);
+        and by how many pixels the mask is shrunk at load (5: no weighted SSIM window sees a masked pixel)"""
         self.config = config
+        self.pixel_weights, self.mask_erode = pixel_weights, int(mask_erode)
         self.device = torch.device(device)
         os.makedirs(self.config.summary_writer_log_dir, exist_ok=True)
         if self.config.output_model_dir is None:
@@ -225,7 +232,20 @@ class GaussianPointCloudTrainer:
         self.best_psnr_score = 0.
 
         self.train_targets = self.val_targets = None
-        if self.config.targets_on_device:
+        if self.pixel_weights not in ("none", "alpha", "file"):
+            raise ValueError(f'pixel_weights must be "none", "alpha" or "file", got {self.pixel_weights!r}')
+        self.weighted = self.pixel_weights != "none"
+        if self.weighted and not self.config.targets_on_device:
+            raise ValueError(f'pixel_weights="{self.pixel_weights}" needs targets_on_device=True: masks are not supported on the '
+                             "host target path")
+        if self.mask_erode < 0 or (not self.weighted and self.mask_erode):
+            raise ValueError('mask_erode must be >= 0, and needs pixel_weights="alpha" or "file"')
+        if self.weighted:
+            self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device, mask_source=self.pixel_weights,
+                                                          mask_erode=self.mask_erode)
+            self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device, mask_source=self.pixel_weights,
+                                                        mask_erode=self.mask_erode)
+        elif self.config.targets_on_device:
             self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device)
             self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device)
         else:
@@ -275,12 +295,16 @@ class GaussianPointCloudTrainer:
             iteration += 1
 
     def _validation_targets(self):
-        if self.val_targets is not None:
+        """-> (image, q, t, CameraInfo, weight or None) of every validation view"""
+        if self.weighted:
             for i in range(len(self.val_targets)):
-                yield self.val_targets.target(i, 1)
+                yield self.val_targets.target(i, 1, with_weight=True)
+        elif self.val_targets is not None:
+            for i in range(len(self.val_targets)):
+                yield self.val_targets.target(i, 1) + (None,)
         else:
             for item in self._val_loader:
-                yield self._host_target(item, 1)
+                yield self._host_target(item, 1) + (None,)
 
     def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band):
         return GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput(
@@ -314,7 +338,11 @@ class GaussianPointCloudTrainer:
             optimizer.zero_grad()
             position_optimizer.zero_grad()
 
-            if self.train_targets is not None:
+            pixel_weight = None
+            if self.weighted:
+                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self.train_targets.target(
+                    self._view_at(iteration), downsample_factor, with_weight=True)
+            elif self.train_targets is not None:
                 image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self.train_targets.target(
                     self._view_at(iteration), downsample_factor)
             else:
@@ -330,7 +358,8 @@ class GaussianPointCloudTrainer:
                 image_gt,
                 point_invalid_mask=self.scene.point_invalid_mask,
                 pointcloud_features=self.scene.point_cloud_features,
-                clamp_predicted=True)
+                clamp_predicted=True,
+                pixel_weight=pixel_weight)          # None: the unweighted loss
             loss.backward()
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
             optimizer.step(rows=rows)
@@ -353,38 +382,56 @@ class GaussianPointCloudTrainer:
                     print(f"train_l1_loss={l1_loss.item()};")
                     print(f"train_ssim_loss={ssim_loss.item()};")
             if iteration % config.log_metrics_interval == 0:
-                with torch.no_grad():
-                    psnr_score, ssim_score = self._compute_pnsr_and_ssim(torch.clamp(image_pred.detach(), 0, 1), image_gt)
-                    self.writer.add_scalar("value/num_valid_points", int((self.scene.point_invalid_mask == 0).sum().item()), iteration)
-                self.writer.add_scalar("train/psnr", psnr_score.item(), iteration)
-                self.writer.add_scalar("train/ssim", ssim_score.item(), iteration)
-                if config.print_metrics_to_console:
-                    print(f"train_psnr={psnr_score.item()};")
-                    print(f"train_psnr_{iteration}={psnr_score.item()};")
-                    print(f"train_ssim={ssim_score.item()};")
-                    print(f"train_ssim_{iteration}={ssim_score.item()};")
+                self.writer.add_scalar("value/num_valid_points", int((self.scene.point_invalid_mask == 0).sum().item()), iteration)
+                # (a view whose mask is empty has no PSNR or SSIM: nothing is logged for it)
+                if pixel_weight is None or bool((pixel_weight > 0).any()):
+                    psnr_score, ssim_score = self._compute_pnsr_and_ssim(torch.clamp(image_pred.detach(), 0, 1), image_gt, pixel_weight)
+                    self.writer.add_scalar("train/psnr", psnr_score.item(), iteration)
+                    self.writer.add_scalar("train/ssim", ssim_score.item(), iteration)
+                    if config.print_metrics_to_console:
+                        print(f"train_psnr={psnr_score.item()};")
+                        print(f"train_psnr_{iteration}={psnr_score.item()};")
+                        print(f"train_ssim={ssim_score.item()};")
+                        print(f"train_ssim_{iteration}={ssim_score.item()};")
             del image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, rasterisation_input, image_pred, loss, l1_loss, ssim_loss
+            del pixel_weight
             # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
             if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
                 self.validation(iteration)
         if hasattr(self.writer, "flush"):
             self.writer.flush()
 
-    def _compute_pnsr_and_ssim(self, image_pred, image_gt):
-        """PSNR = 10 log10(1 / mse); SSIM = 1 - the third term of the loss (pytorch_msssim.ssim's definition, in its kernels)"""
+    @staticmethod
+    def _weighted_mse(image_pred, image_gt, pixel_weight):
+        """sum w (x - y)^2 / (3 sum w), w as the loss has it (anything not > 0 is 0, by selection); plain torch.  The callers
+        leave out a view whose weights are all zero: it has no mean."""
+        w = torch.where(pixel_weight > 0, pixel_weight, torch.zeros_like(pixel_weight))
+        squared = torch.where(w > 0, w * (image_pred - image_gt) ** 2, torch.zeros_like(image_pred))
+        return squared.sum() / (3 * w.sum())
+
+    def _compute_pnsr_and_ssim(self, image_pred, image_gt, pixel_weight=None):
+        """PSNR = 10 log10(1 / mse); SSIM = 1 - the third term of the loss (pytorch_msssim.ssim's definition, in its kernels).
+        With a weight: the mse over the weighted pixels and the weighted SSIM term."""
         with torch.no_grad():
-            psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
-            _, _, ssim_loss = self.loss_function(image_pred, image_gt)
+            if pixel_weight is None:
+                psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+                _, _, ssim_loss = self.loss_function(image_pred, image_gt)
+            else:
+                psnr_score = 10 * torch.log10(1.0 / self._weighted_mse(image_pred, image_gt, pixel_weight))
+                _, _, ssim_loss = self.loss_function(image_pred, image_gt, pixel_weight=pixel_weight)
             return psnr_score, 1.0 - ssim_loss
 
     def validation(self, iteration):
         """TRAIN:342-423: every validation view at band 3 and full resolution; the means of loss, PSNR, SSIM and of the
         rasteriser's time by device events are logged, the scene written as scene_<iteration>.parquet and, when the mean PSNR is
-        the best so far, as best_scene.parquet.  -> the means, as a dict"""
+        the best so far, as best_scene.parquet.  -> the means, as a dict.  With pixel weights a view whose mask is empty is left
+        out of every mean: it has no weighted pixel to measure."""
         with torch.no_grad():
             total_loss = total_psnr_score = total_ssim_score = total_inference_time = 0.0
             count = 0
-            for image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info in self._validation_targets():
+            for image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight in self._validation_targets():
+                if pixel_weight is not None and not bool((pixel_weight > 0).any()):
+                    continue
                 start_event = torch.cuda.Event(enable_timing=True)
                 end_event = torch.cuda.Event(enable_timing=True)
                 rasterisation_input = self._rasterisation_input(camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band=3)
@@ -394,8 +441,12 @@ class GaussianPointCloudTrainer:
                 torch.cuda.synchronize()
                 total_inference_time += start_event.elapsed_time(end_event)
                 image_pred = torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
-                loss, _, ssim_loss = self.loss_function(image_pred, image_gt)
-                psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+                if pixel_weight is None:
+                    loss, _, ssim_loss = self.loss_function(image_pred, image_gt)
+                    psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
+                else:
+                    loss, _, ssim_loss = self.loss_function(image_pred, image_gt, pixel_weight=pixel_weight)
+                    psnr_score = 10 * torch.log10(1.0 / self._weighted_mse(image_pred, image_gt, pixel_weight))
                 total_loss += loss.item()
                 total_psnr_score += psnr_score.item()
                 total_ssim_score += 1.0 - ssim_loss.item()

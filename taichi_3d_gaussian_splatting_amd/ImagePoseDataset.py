@@ -71,6 +71,19 @@ class ImagePoseDataset(torch.utils.data.Dataset):
                           camera_id=row["camera_id"])
         return image, q, t, info
 
+    def load_mask(self, idx):
+        """-> the mask of record idx as a uint8 (H,W) array, 255 = use and 0 = ignore, or None when the dataset has no
+        mask_path column or the record's entry is empty.  The file is an 8-bit single-channel image of the picture's size
+        (anything else is converted to 8-bit grey)."""
+        if "mask_path" not in self.df.columns:
+            return None
+        path = self.df.iloc[idx]["mask_path"]
+        if not isinstance(path, str) or not path:
+            return None
+        import PIL.Image
+        with PIL.Image.open(path) as pil:
+            return np.array(pil if pil.mode == "L" else pil.convert("L"), dtype=np.uint8)
+
     def __getitem__(self, idx):
         image, q, t, info = self.load_raw(idx)
         image = image.permute(2, 0, 1).to(torch.float32).div(255)               # torchvision's to_tensor

@@ -7,6 +7,8 @@
 #include "../../include/gs_knn.h"
 #include "../../include/gs_exchange.h"
 #include "../../include/gs_targets.h"
+#include "../../include/gs_targets_rgba.h"
+#include "../../include/gs_loss_weighted.h"
 #include "../../include/gs_mixture.h"
 #include "../../include/gs_mixture_grad.h"
 #include "../../include/gs_compose.h"
@@ -1269,6 +1271,42 @@ extern "C" int gs_loss_l1_ssim_backward(gs_ctx* c, const gs_loss_image* pred, co
     return GS_OK;
 }
 
+// ---- per-pixel weights (include/gs_loss_weighted.h) ----
+extern "C" int gs_loss_l1_ssim_weighted_forward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, const float* pixel_weight,
+                                                int32_t H, int32_t W, int32_t clamp_pred, float lambda_value, float* maps, float* loss_terms,
+                                                gs_stream stream_)
+{
+    if (!c || !pixel_weight || !maps || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_weighted_forward: NULL argument");
+    if (int rc = loss_check("gs_loss_l1_ssim_weighted_forward", pred, gt, H, W)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    hipError_t e = c->loss_ws.ensure(gs_loss_weighted_partials_floats(H, W) * sizeof(float), &c->device_bytes);
+    if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim_weighted_forward: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_loss_weighted_forward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), pixel_weight, H, W, lambda_value, maps,
+                                    c->loss_ws.as<float>(), loss_terms, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_loss_l1_ssim_weighted_backward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, const float* pixel_weight,
+                                                 int32_t H, int32_t W, int32_t clamp_pred, float lambda_value, const float* maps,
+                                                 const float* loss_terms, const float* upstream, const gs_loss_image* grad_pred,
+                                                 gs_stream stream_)
+{
+    if (!c || !pixel_weight || !maps || !loss_terms || !grad_pred || !grad_pred->data)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_weighted_backward: NULL argument");
+    if (int rc = loss_check("gs_loss_l1_ssim_weighted_backward", pred, gt, H, W)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_loss_weighted_backward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), pixel_weight, H, W, lambda_value, maps, loss_terms,
+                                     upstream, loss_image(grad_pred, 0), s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
 // the one-call form: contiguous (3,H,W) images, the maps in the context's own workspace, upstream = 1
 extern "C" int gs_loss_l1_ssim(gs_ctx* c, const float* pred, const float* gt, int32_t H, int32_t W, float lambda_value,
                                float* loss_terms, float* grad_pred, gs_stream stream_)
@@ -1632,31 +1670,49 @@ static int resample_tables(gs_ctx* c, int H_in, int W_in, int h_full, int w_full
     return GS_OK;
 }
 
-extern "C" int gs_image_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
-                                 int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
-                                 gs_stream stream_)
+// gs_image_resample (dst_channels 3) and gs_image_resample_rgba (4, include/gs_targets_rgba.h): the same checks, tables and launch
+static int image_resample(const char* who_, int dst_channels, gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in,
+                          int32_t W_in, int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
+                          gs_stream stream_)
 {
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: ctx is NULL");
-    if (src_format != GS_IMAGE_U8_HWC && src_format != GS_IMAGE_F32_CHW) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: unknown src_format");
-    if (src_channels != 3 && src_channels != 4) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: src_channels must be 3 or 4");
+    const std::string who(who_);
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (src_format != GS_IMAGE_U8_HWC && src_format != GS_IMAGE_F32_CHW) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown src_format");
+    if (src_channels != 4 && (dst_channels == 4 || src_channels != 3)) return fail(GS_ERR_INVALID_ARGUMENT, who + (dst_channels == 4 ? ": src_channels must be 4" : ": src_channels must be 3 or 4"));
     for (int32_t v : { H_in, W_in, h_full, w_full, h_out, w_out })
-        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: every size must be in [0, 32768]");
-    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
+        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, who + ": every size must be in [0, 32768]");
+    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, who + ": the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
     if (src_format == GS_IMAGE_U8_HWC ? src_row_pitch_bytes < (int64_t)W_in * src_channels : src_row_pitch_bytes != (int64_t)W_in * 4)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: src_row_pitch_bytes must be >= W_in * src_channels (uint8), W_in * 4 (f32)");
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": src_row_pitch_bytes must be >= W_in * src_channels (uint8), W_in * 4 (f32)");
     if (h_out == 0 || w_out == 0) return GS_OK;
-    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: NULL src or dst");
+    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL src or dst");
     if (H_in < h_full || W_in < w_full || (int64_t)H_in > (int64_t)GS_RESAMPLE_MAX_SCALE * h_full || (int64_t)W_in > (int64_t)GS_RESAMPLE_MAX_SCALE * w_full)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the scale in / out must be in [1, 8] on both axes (no upscaling)");
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": the scale in / out must be in [1, 8] on both axes (no upscaling)");
     std::lock_guard<std::mutex> lock(c->mu);
     hipStream_t s;
     int rc;
     if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     ResampleTable* rt = nullptr;
     if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
-    gs_launch_image_resample(src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, rt->ax, rt->ay, h_out, w_out, dst, s);
+    gs_launch_image_resample(src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, rt->ax, rt->ay, h_out, w_out, dst, dst_channels, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
+}
+
+extern "C" int gs_image_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
+                                 int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
+                                 gs_stream stream_)
+{
+    return image_resample("gs_image_resample", 3, c, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out, w_out,
+                          dst, stream_);
+}
+
+extern "C" int gs_image_resample_rgba(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
+                                      int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
+                                      gs_stream stream_)
+{
+    return image_resample("gs_image_resample_rgba", 4, c, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out,
+                          w_out, dst, stream_);
 }
 
 // ---- baking a placed scene (k_compose.hip) ----------------------------------------------------------------------------

@@ -478,6 +478,12 @@ void gs_launch_loss_forward(const GsLossImage& X, const GsLossImage& Y, int H, i
                             hipStream_t s);
 void gs_launch_loss_backward(const GsLossImage& X, const GsLossImage& Y, int H, int W, float lambda, const float* maps, const float* upstream,
                              const GsLossImage& G, hipStream_t s);
+// the same with per-pixel weights (include/gs_loss_weighted.h): weight is a contiguous (H,W) plane; terms has five floats
+size_t gs_loss_weighted_partials_floats(int H, int W);
+void gs_launch_loss_weighted_forward(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, float lambda, float* maps,
+                                     float* partials, float* terms, hipStream_t s);
+void gs_launch_loss_weighted_backward(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, float lambda,
+                                      const float* maps, const float* terms, const float* upstream, const GsLossImage& G, hipStream_t s);
 void gs_launch_adam(float* param, const float* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     int64_t step, hipStream_t s);
 // torch.optim.Adam's update of ONE element (no weight decay, no amsgrad): the arithmetic of k_adam (k_loss.hip) and of
@@ -550,8 +556,9 @@ void gs_launch_mixture_grad(const float* point_cloud, const float* features, con
 #define GS_RS_MAX_TAPS 18
 #define GS_RS_MAX_SPAN 524
 struct GsResampleAxis { const int32_t* start; const int32_t* count; const float* weight; int taps; };
+// dst_channels 3, or 4 (include/gs_targets_rgba.h; channels must be 4 then): channel 3 through the same filter into plane 3
 void gs_launch_image_resample(const void* src, int src_format, int channels, int H_in, int W_in, int64_t pitch_bytes, GsResampleAxis ax,
-                              GsResampleAxis ay, int h_out, int w_out, float* dst, hipStream_t s);
+                              GsResampleAxis ay, int h_out, int w_out, float* dst, int dst_channels, hipStream_t s);
 // k_compose.hip (include/gs_compose.h): rows [0, n) of the inputs under the transform A into rows [row_offset, row_offset + n)
 // of the outputs.  A as gs_scene_bake made it on the host (float64, rounded once): m = s R_A row-major, t = t_A, q = q_A / |q_A|
 // (xyzw), log_scale = log(s), sh = M_0 | M_1 | M_2 | M_3 row-major (1 + 9 + 25 + 49 floats).  Passed by value: wave-uniform.

@@ -16,6 +16,11 @@
 // keeps the sixteen-float row loads of both kernels 16-byte aligned.
 // The predicted image may be any strided (3,H,W) view -- in particular the permuted (H,W,3) output of the rasteriser, read in
 // place -- and torch.clamp(., 0, 1) (GaussianPointTrainer.py:173) can be applied on the fly (value and gradient as torch's).
+// Per-pixel weights (include/gs_loss_weighted.h): the WT = true instantiations of the same two kernels and k_loss_finish_weighted.
+// w(p) = weight[p] if that is > 0, else 0 (one comparison: negative and NaN weights select nothing).  The L1 term of a pixel
+// counts with w(p), a window with the weight v(q) of its centre pixel; the forward stores v A, v B, v D, so the backward's
+// transposed filter is the unweighted one and reads the weight for the L1 sign term only.  Weight zero SELECTS: such a pixel
+// or window is not multiplied in (0 * NaN), it is left out.
 // Also here: gs_adam_step's kernel (torch.optim.Adam semantics, GaussianPointTrainer.py:131-134,183-184).
 // No float atomics, results reproducible.
 #include "gs_common.h"
@@ -105,18 +110,34 @@ __device__ __forceinline__ float gs_loss_pixel(const GsLossImage& im, int ch, in
     return v;
 }
 
-template <int XMODE, int YMODE>
+// What the WT instantiations take besides the images; the WT = false ones take GsLossNone, which holds nothing.
+//   forward:  the weight plane, contiguous (H,W) f32 (vec: W % 4 == 0 and a 16-byte aligned base, so rows are aligned too), and
+//             the per-block sums of v and w it leaves for the finish
+//   backward: the weight plane and the forward's five terms (S_w and V are read from them on the device)
+struct GsLossNone {};
+struct GsLossWeightFwd { const float* w; float* partial_v; float* partial_w; int vec; };
+struct GsLossWeightBwd { const float* w; const float* terms; };
+template <bool WT, class T> struct GsLossArg { typedef GsLossNone type; };
+template <class T> struct GsLossArg<true, T> { typedef T type; };
+__device__ __forceinline__ float gs_loss_weight(const float* __restrict__ weight, int iy, int ix, int H, int W)
+{
+    if (iy < 0 || iy >= H || ix < 0 || ix >= W) return 0.0f;
+    const float w = weight[(size_t)iy * W + ix];
+    return w > 0.0f ? w : 0.0f;
+}
+
+template <int XMODE, int YMODE, bool WT>
 __global__ __launch_bounds__(256) void k_loss_ssim_maps(const GsLossImage X, const GsLossImage Y, int H, int W, int Hp, int Wp,
                                                         const GsGaussWin win, float* __restrict__ mapA, float* __restrict__ mapB,
                                                         float* __restrict__ mapC, float* __restrict__ partial_ssim,
-                                                        float* __restrict__ partial_l1)
+                                                        float* __restrict__ partial_l1, const typename GsLossArg<WT, GsLossWeightFwd>::type wt)
 {
     __shared__ __attribute__((aligned(16))) float hz[5][MHR][LHS];
-    __shared__ float wsum[2][4];
+    __shared__ float wsum[WT ? 4 : 2][4];
     const int ch = blockIdx.z;
     const int X0 = blockIdx.x * LT, Y0 = blockIdx.y * MTY;       // this block's corner of P
     const int t = threadIdx.x;
-    float local_l1 = 0.0f;
+    float local_l1 = 0.0f, local_w = 0.0f, local_v = 0.0f;
     // horizontal pass: patch row r is image row Y0 - 10 + r; output column X0 + 4 g + j is map column X0 + 4 g + j - 12 and
     // takes image columns (X0 + 4 g - 12) + j .. + j + 10
 #pragma unroll 1
@@ -129,8 +150,28 @@ __global__ __launch_bounds__(256) void k_loss_ssim_maps(const GsLossImage X, con
         // the L1 term of the four pixels the last 16-byte load brought (row Y0 - 10 + r, columns X0 + 4 g .. + 3): every pixel of the
         // block's own rows and columns once, from registers (pixels outside the image were loaded as 0 for both images)
         if (r >= LH) {
+            if constexpr (WT) {
+                // the weights of the same four pixels: one 16-byte load of the weight row (all in or all out, as the image's)
+                const int wy_ = Y0 - LH + r, wx_ = X0 + 4 * g;
+                float w4[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+                if (wy_ < H) {
+                    if (wt.vec) {
+                        if (wx_ + 3 < W) {
+                            const float4 q = *reinterpret_cast<const float4*>(wt.w + (size_t)wy_ * W + wx_);
+                            w4[0] = q.x; w4[1] = q.y; w4[2] = q.z; w4[3] = q.w;
+                        }
+                    } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) local_l1 += fabsf(xin[12 + j] - yin[12 + j]);
+                        for (int j = 0; j < 4; ++j) if (wx_ + j < W) w4[j] = wt.w[(size_t)wy_ * W + wx_ + j];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (w4[j] > 0.0f) { local_l1 += w4[j] * fabsf(xin[12 + j] - yin[12 + j]); local_w += w4[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) local_l1 += fabsf(xin[12 + j] - yin[12 + j]);
+            }
         }
         float acc[5][4];
 #pragma unroll
@@ -155,9 +196,16 @@ __global__ __launch_bounds__(256) void k_loss_ssim_maps(const GsLossImage X, con
         for (int m = 0; m < 5; ++m)
             *reinterpret_cast<float4*>(&hz[m][r][4 * g]) = make_float4(acc[m][0], acc[m][1], acc[m][2], acc[m][3]);
     }
-    __syncthreads();
     // vertical pass: thread (c, rg) takes the outputs of rows MVR rg .. MVR rg + MVR - 1 of column c
     const int c = t & 31, r0 = (t >> 5) * MVR;
+    // the weights of this thread's windows, v = w at the window's centre: map pixel (y - 10, x - 12) is centred on image pixel
+    // (y - 5, x - 7).  Asked for before the barrier, used after the filter.
+    float vq[MVR];
+    if constexpr (WT) {
+#pragma unroll
+        for (int j = 0; j < MVR; ++j) vq[j] = gs_loss_weight(wt.w, Y0 + r0 + j - LH + LW / 2, X0 + c - LXS + LW / 2, H, W);
+    }
+    __syncthreads();
     float out[5][MVR];
 #pragma unroll
     for (int m = 0; m < 5; ++m) {
@@ -191,22 +239,43 @@ __global__ __launch_bounds__(256) void k_loss_ssim_maps(const GsLossImage X, con
             const float pq = A1 * iB1, qq = A2 * iB2;
             const float S = pq * qq;
             const float S_A1 = iB1 * qq, S_A2 = pq * iB2;
-            local += S;
-            A = 2.0f * m2 * (S_A1 - S_A2) + 2.0f * m1 * S * (iB2 - iB1);
-            B = -S * iB2;
-            D = 2.0f * S_A2;
+            if constexpr (WT) {
+                const float v = vq[j];
+                if (v > 0.0f) {                     // a window of weight zero is left out, whatever it holds
+                    local += v * S; local_v += v;
+                    A = v * (2.0f * m2 * (S_A1 - S_A2) + 2.0f * m1 * S * (iB2 - iB1));
+                    B = v * (-S * iB2);
+                    D = v * (2.0f * S_A2);
+                }
+            } else {
+                local += S;
+                A = 2.0f * m2 * (S_A1 - S_A2) + 2.0f * m1 * S * (iB2 - iB1);
+                B = -S * iB2;
+                D = 2.0f * S_A2;
+            }
         }
         const size_t o = ((size_t)ch * Hp + y) * Wp + x;
         mapA[o] = A; mapB[o] = B; mapC[o] = D;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { local += __shfl_xor(local, o, 64); local_l1 += __shfl_xor(local_l1, o, 64); }
-    if ((t & 63) == 0) { wsum[0][t >> 6] = local; wsum[1][t >> 6] = local_l1; }
+    if constexpr (WT) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { local_v += __shfl_xor(local_v, o, 64); local_w += __shfl_xor(local_w, o, 64); }
+    }
+    if ((t & 63) == 0) {
+        wsum[0][t >> 6] = local; wsum[1][t >> 6] = local_l1;
+        if constexpr (WT) { wsum[2][t >> 6] = local_v; wsum[3][t >> 6] = local_w; }
+    }
     __syncthreads();
     if (t == 0) {
         const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         partial_ssim[b] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
         partial_l1[b] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
+        if constexpr (WT) {
+            wt.partial_v[b] = (wsum[2][0] + wsum[2][1]) + (wsum[2][2] + wsum[2][3]);
+            wt.partial_w[b] = (wsum[3][0] + wsum[3][1]) + (wsum[3][2] + wsum[3][3]);
+        }
     }
 }
 
@@ -214,28 +283,39 @@ __global__ __launch_bounds__(256) void k_loss_ssim_maps(const GsLossImage X, con
 // ix + 2 .. ix + 12, weights g[k] g[l] (the window is symmetric)
 // (one block per channel also for a gradient in (H,W,3) memory order: a block that takes the three channels of its tile in turn, so
 // that the three 4-byte stores per pixel meet in one L2, measured slower -- 63.8 against 60.5 us; the planar layout runs in 44)
+// WT: the maps already carry v; k_l1 and k_ssim come from S_w = terms[3] and V = terms[4] on the device (zero where the sum is
+// zero), and the L1 sign term takes w(p)
+template <bool WT>
 __global__ __launch_bounds__(256) void k_loss_grad(const GsLossImage X, const GsLossImage Y, int H, int W, int Hp, int Wp,
                                                    const GsGaussWin win, const float* __restrict__ mapA, const float* __restrict__ mapB,
                                                    const float* __restrict__ mapC, float lambda, const float* __restrict__ upstream,
-                                                   const GsLossImage G)
+                                                   const GsLossImage G, const typename GsLossArg<WT, GsLossWeightBwd>::type wt)
 {
     __shared__ __attribute__((aligned(16))) float hz[3][LHR][LHS];
     const int X0 = blockIdx.x * LT, I0 = blockIdx.y * LTY;
     const int t = threadIdx.x;
     const float* maps[3] = { mapA, mapB, mapC };
     const float up = upstream ? upstream[0] : 1.0f;
-    const float k_ssim = lambda / (3.0f * (float)(H - LH) * (float)(W - LH));
-    const float k_l1 = (1.0f - lambda) / (3.0f * (float)H * (float)W);
+    float k_ssim, k_l1;
+    if constexpr (WT) {
+        const float Sw = wt.terms[3], V = wt.terms[4];
+        k_ssim = V > 0.0f ? lambda / (3.0f * V) : 0.0f;
+        k_l1 = Sw > 0.0f ? (1.0f - lambda) / (3.0f * Sw) : 0.0f;
+    } else {
+        k_ssim = lambda / (3.0f * (float)(H - LH) * (float)(W - LH));
+        k_l1 = (1.0f - lambda) / (3.0f * (float)H * (float)W);
+    }
     const int ch = blockIdx.z;
     // this thread's seven pixels of both images, asked for now and used after the two filter passes
     const int ix = X0 + (t & 31), iy_first = I0 + (t >> 5) * LVR;
-    float px[LVR], py[LVR];
+    float px[LVR], py[LVR], pw[WT ? LVR : 1];
 #pragma unroll
     for (int j = 0; j < LVR; ++j) {
         const int iy = iy_first + j;
         const bool in = (t >> 5) * LVR + j < LTY && iy < H && ix < W;
         px[j] = in ? gs_loss_pixel(X, ch, iy, ix, false) : 0.0f;
         py[j] = in ? gs_loss_pixel(Y, ch, iy, ix, Y.clamp != 0) : 0.0f;
+        if constexpr (WT) pw[j] = in ? gs_loss_weight(wt.w, iy, ix, H, W) : 0.0f;
     }
 #pragma unroll 1
     for (int it = 0; it < 2; ++it) {
@@ -282,10 +362,17 @@ __global__ __launch_bounds__(256) void k_loss_grad(const GsLossImage X, const Gs
         const float raw = px[j];
         const float x = X.clamp ? (raw < 0.0f ? 0.0f : (raw > 1.0f ? 1.0f : raw)) : raw;
         const float y = py[j];
-        const float dS = out[0][j] + 2.0f * x * out[1][j] + y * out[2][j];          // d(sum of the SSIM map)/dx
+        float dS, kl = k_l1;
+        if constexpr (WT) {
+            // a filtered map that is exactly zero (every window over this pixel has weight zero) selects nothing of x and y
+            dS = out[0][j] + (out[1][j] != 0.0f ? 2.0f * x * out[1][j] : 0.0f) + (out[2][j] != 0.0f ? y * out[2][j] : 0.0f);
+            kl = k_l1 * pw[j];
+        } else {
+            dS = out[0][j] + 2.0f * x * out[1][j] + y * out[2][j];          // d(sum of the SSIM map)/dx
+        }
         const float diff = x - y;
         const float sgn = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f);
-        float gval = up * (k_l1 * sgn - k_ssim * dS);
+        float gval = up * (kl * sgn - k_ssim * dS);
         if (X.clamp && !(raw >= 0.0f && raw <= 1.0f)) gval = 0.0f;                  // torch.clamp's backward: the gradient passes where min <= x <= max
         const_cast<float*>(G.p)[(long long)ch * G.sc + (long long)iy * G.sy + (long long)ix * G.sx] = gval;
     }
@@ -314,10 +401,42 @@ __global__ __launch_bounds__(1024) void k_loss_finish(const float* __restrict__ 
     }
 }
 
+// the four partials; v and w are the same in the three channels' blocks, so the first n / 3 blocks (channel 0) give V and S_w
+__global__ __launch_bounds__(1024) void k_loss_finish_weighted(const float* __restrict__ partial_ssim, const float* __restrict__ partial_l1,
+                                                               const float* __restrict__ partial_v, const float* __restrict__ partial_w,
+                                                               int n, float lambda, float* __restrict__ terms)
+{
+    __shared__ double ws[4][16];
+    const int t = threadIdx.x;
+    double a = 0.0, b = 0.0, v = 0.0, w = 0.0;
+    for (int i = t; i < n; i += 1024) {
+        a += (double)partial_ssim[i]; b += (double)partial_l1[i];
+        if (i < n / 3) { v += (double)partial_v[i]; w += (double)partial_w[i]; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); v += __shfl_xor(v, o, 64); w += __shfl_xor(w, o, 64);
+    }
+    if ((t & 63) == 0) { ws[0][t >> 6] = a; ws[1][t >> 6] = b; ws[2][t >> 6] = v; ws[3][t >> 6] = w; }
+    __syncthreads();
+    if (t == 0) {
+        double sa = 0.0, sb = 0.0, sv = 0.0, sw = 0.0;
+        for (int k = 0; k < 16; ++k) { sa += ws[0][k]; sb += ws[1][k]; sv += ws[2][k]; sw += ws[3][k]; }
+        const double l1 = sw > 0.0 ? sb / (3.0 * sw) : 0.0;           // an empty mask: the term is 0, not 0 / 0
+        const double ld = sv > 0.0 ? 1.0 - sa / (3.0 * sv) : 0.0;
+        terms[0] = (float)((1.0 - (double)lambda) * l1 + (double)lambda * ld);
+        terms[1] = (float)l1;
+        terms[2] = (float)ld;
+        terms[3] = (float)sw;
+        terms[4] = (float)sv;
+    }
+}
+
 static dim3 gs_loss_grid_maps(int H, int W) { return dim3((unsigned)((gs_loss_wp(W) + LT - 1) / LT), (unsigned)((gs_loss_hp(H) + MTY - 1) / MTY), 3); }
 
 size_t gs_loss_maps_size(int H, int W) { return (size_t)3 * 3 * (size_t)gs_loss_hp(H) * (size_t)gs_loss_wp(W); }
 size_t gs_loss_partials_floats(int H, int W) { const dim3 g = gs_loss_grid_maps(H, W); return 2 * (size_t)g.x * g.y * g.z + 64; }
+size_t gs_loss_weighted_partials_floats(int H, int W) { const dim3 g = gs_loss_grid_maps(H, W); return 4 * (size_t)g.x * g.y * g.z + 64; }
 
 static GsGaussWin gs_loss_window()
 {
@@ -345,7 +464,7 @@ void gs_launch_loss_forward(const GsLossImage& X, const GsLossImage& Y, int H, i
     const int nb = (int)(grid.x * grid.y * grid.z);
     float* p_ssim = partials; float* p_l1 = partials + nb;
     const int xm = gs_loss_mode(X, W), ym = gs_loss_mode(Y, W);
-#define GS_LOSS_MAPS(XM_, YM_) k_loss_ssim_maps<XM_, YM_><<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, p_ssim, p_l1)
+#define GS_LOSS_MAPS(XM_, YM_) k_loss_ssim_maps<XM_, YM_, false><<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, p_ssim, p_l1, GsLossNone{})
     if (xm == GS_LOSS_VEC && ym == GS_LOSS_VEC) GS_LOSS_MAPS(GS_LOSS_VEC, GS_LOSS_VEC);
     else if (xm == GS_LOSS_VEC3 && ym == GS_LOSS_VEC) GS_LOSS_MAPS(GS_LOSS_VEC3, GS_LOSS_VEC);          // the trainer's case: rasteriser output against a (3,H,W) photograph
     else GS_LOSS_MAPS(GS_LOSS_SCALAR, GS_LOSS_SCALAR);
@@ -359,7 +478,38 @@ void gs_launch_loss_backward(const GsLossImage& X, const GsLossImage& Y, int H, 
     const int Hp = gs_loss_hp(H), Wp = gs_loss_wp(W);
     const size_t map = (size_t)3 * Hp * Wp;
     const dim3 grid((unsigned)((W + LT - 1) / LT), (unsigned)((H + LTY - 1) / LTY), 3);
-    k_loss_grad<<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, lambda, upstream, G);
+    k_loss_grad<false><<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, lambda, upstream, G,
+                                            GsLossNone{});
+}
+
+static int gs_loss_weight_vec(const float* weight, int W) { return ((W & 3) == 0 && ((uintptr_t)weight & 15u) == 0) ? 1 : 0; }
+
+void gs_launch_loss_weighted_forward(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, float lambda, float* maps,
+                                     float* partials, float* terms, hipStream_t s)
+{
+    const int Hp = gs_loss_hp(H), Wp = gs_loss_wp(W);
+    const size_t map = (size_t)3 * Hp * Wp;
+    const dim3 grid = gs_loss_grid_maps(H, W);
+    const int nb = (int)(grid.x * grid.y * grid.z);
+    float* p_ssim = partials; float* p_l1 = partials + nb;
+    const GsLossWeightFwd wt{ weight, partials + 2 * (size_t)nb, partials + 3 * (size_t)nb, gs_loss_weight_vec(weight, W) };
+    const int xm = gs_loss_mode(X, W), ym = gs_loss_mode(Y, W);
+#define GS_LOSS_MAPS(XM_, YM_) k_loss_ssim_maps<XM_, YM_, true><<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, p_ssim, p_l1, wt)
+    if (xm == GS_LOSS_VEC && ym == GS_LOSS_VEC) GS_LOSS_MAPS(GS_LOSS_VEC, GS_LOSS_VEC);
+    else if (xm == GS_LOSS_VEC3 && ym == GS_LOSS_VEC) GS_LOSS_MAPS(GS_LOSS_VEC3, GS_LOSS_VEC);
+    else GS_LOSS_MAPS(GS_LOSS_SCALAR, GS_LOSS_SCALAR);
+#undef GS_LOSS_MAPS
+    k_loss_finish_weighted<<<1, 1024, 0, s>>>(p_ssim, p_l1, wt.partial_v, wt.partial_w, nb, lambda, terms);
+}
+
+void gs_launch_loss_weighted_backward(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, float lambda,
+                                      const float* maps, const float* terms, const float* upstream, const GsLossImage& G, hipStream_t s)
+{
+    const int Hp = gs_loss_hp(H), Wp = gs_loss_wp(W);
+    const size_t map = (size_t)3 * Hp * Wp;
+    const dim3 grid((unsigned)((W + LT - 1) / LT), (unsigned)((H + LTY - 1) / LTY), 3);
+    k_loss_grad<true><<<grid, 256, 0, s>>>(X, Y, H, W, Hp, Wp, gs_loss_window(), maps, maps + map, maps + 2 * map, lambda, upstream, G,
+                                           GsLossWeightBwd{ weight, terms });
 }
 
 // ---------------------------------------------------------------------------------

@@ -14,6 +14,8 @@
 // and ends in one 16-byte store per channel plane and thread (scalar stores where w_out or dst do not allow it).
 // Static LDS: 33792 (staged bytes) + 12288 (f32 rows) + 5760 (the tile's weights) + 640 (its windows) = 52480 bytes at any
 // scale; the f32 source stages nothing and uses 18704.
+// NC = 4 (gs_image_resample_rgba, include/gs_targets_rgba.h): channel 3 of a four-channel source runs through the same two
+// passes into plane 3 -- one more fmaf chain per pass and one more plane of stores; the f32 rows take 16384 bytes then.
 #include "gs_common.h"
 #include "../../include/gs_targets.h"
 
@@ -26,12 +28,12 @@
 static_assert(RS_TILE_W % 4 == 0 && RS_TILE_H * (RS_TILE_W / 4) == RS_THREADS, "one thread per tile row and four columns");
 static_assert(RS_THREADS % RS_TILE_W == 0 && RS_CHUNK_ROWS % (RS_THREADS / RS_TILE_W) == 0, "the horizontal pass covers a chunk in whole rounds");
 
-template <bool U8>
+template <bool U8, int NC>
 __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __restrict__ src, int C, int H_in, int W_in, int64_t pitch,
                                                               GsResampleAxis ax, GsResampleAxis ay, int h_out, int w_out,
                                                               float* __restrict__ dst, int vec_store)
 {
-    __shared__ __align__(16) float hbuf[RS_CHUNK_ROWS][3][RS_TILE_W];
+    __shared__ __align__(16) float hbuf[RS_CHUNK_ROWS][NC][RS_TILE_W];
     __shared__ __align__(16) uint8_t raw[U8 ? RS_CHUNK_ROWS * RS_RAW_PITCH : 16];
     __shared__ float wx[RS_TILE_W * GS_RS_MAX_TAPS], wy[RS_TILE_H * GS_RS_MAX_TAPS];
     __shared__ int sx[RS_TILE_W], cx[RS_TILE_W], sy[RS_TILE_H], cy[RS_TILE_H];
@@ -60,8 +62,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
 
     const int vy = t / (RS_TILE_W / 4), vg = t % (RS_TILE_W / 4);       // vertical pass: tile row, group of four columns
     const int hx = t % RS_TILE_W, hr0 = t / RS_TILE_W;                     // horizontal pass: tile column, first chunk row
-    float4 acc[3];
-    for (int c = 0; c < 3; ++c) acc[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 acc[NC];
+    for (int c = 0; c < NC; ++c) acc[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
     for (int r0 = R0; r0 < R1; r0 += RS_CHUNK_ROWS) {
         const int n_rows = min(RS_CHUNK_ROWS, R1 - r0);
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
         }
         // horizontal pass of the chunk's rows
         for (int rr = hr0; rr < RS_CHUNK_ROWS; rr += RS_THREADS / RS_TILE_W) {
-            float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+            float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, h3 = 0.0f;
             if (rr < n_rows) {
                 const int n = cx[hx];
                 const float* w = &wx[hx * GS_RS_MAX_TAPS];
@@ -94,6 +96,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
                         h0 = fmaf(w[k], (float)p[0] / 255.0f, h0);
                         h1 = fmaf(w[k], (float)p[1] / 255.0f, h1);
                         h2 = fmaf(w[k], (float)p[2] / 255.0f, h2);
+                        if constexpr (NC == 4) h3 = fmaf(w[k], (float)p[3] / 255.0f, h3);
                     }
                 } else {
                     const size_t plane = (size_t)H_in * W_in;
@@ -102,10 +105,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
                         h0 = fmaf(w[k], p[k], h0);
                         h1 = fmaf(w[k], p[plane + k], h1);
                         h2 = fmaf(w[k], p[2 * plane + k], h2);
+                        if constexpr (NC == 4) h3 = fmaf(w[k], p[3 * plane + k], h3);
                     }
                 }
             }
             hbuf[rr][0][hx] = h0; hbuf[rr][1][hx] = h1; hbuf[rr][2][hx] = h2;
+            if constexpr (NC == 4) hbuf[rr][3][hx] = h3;
         }
         __syncthreads();
         // vertical pass: the taps of this thread's output row that lie in the chunk
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
             for (int k = k0; k < k1; ++k) {
                 const float w = wy[vy * GS_RS_MAX_TAPS + k];
                 const int rr = first + k - r0;
-                for (int c = 0; c < 3; ++c) {
+                for (int c = 0; c < NC; ++c) {
                     const float4 h = *reinterpret_cast<const float4*>(&hbuf[rr][c][4 * vg]);
                     acc[c].x = fmaf(w, h.x, acc[c].x); acc[c].y = fmaf(w, h.y, acc[c].y);
                     acc[c].z = fmaf(w, h.z, acc[c].z); acc[c].w = fmaf(w, h.w, acc[c].w);
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
 
     const int oy = ty0 + vy, ox = tx0 + 4 * vg;
     if (oy >= h_out || ox >= w_out) return;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NC; ++c) {
         float* d = dst + ((size_t)c * h_out + oy) * w_out + ox;
         if (vec_store && ox + 3 < w_out) {
             *reinterpret_cast<float4*>(d) = acc[c];
@@ -139,13 +144,16 @@ __global__ __launch_bounds__(RS_THREADS) void k_image_resample(const uint8_t* __
 }
 
 void gs_launch_image_resample(const void* src, int src_format, int channels, int H_in, int W_in, int64_t pitch_bytes, GsResampleAxis ax,
-                              GsResampleAxis ay, int h_out, int w_out, float* dst, hipStream_t s)
+                              GsResampleAxis ay, int h_out, int w_out, float* dst, int dst_channels, hipStream_t s)
 {
     const dim3 grid((w_out + RS_TILE_W - 1) / RS_TILE_W, (h_out + RS_TILE_H - 1) / RS_TILE_H);
     const int vec_store = (w_out % 4 == 0 && ((uintptr_t)dst & 15) == 0) ? 1 : 0;
     const uint8_t* p = reinterpret_cast<const uint8_t*>(src);
-    if (src_format == GS_IMAGE_U8_HWC)
-        hipLaunchKernelGGL(k_image_resample<true>, grid, dim3(RS_THREADS), 0, s, p, channels, H_in, W_in, pitch_bytes, ax, ay, h_out, w_out, dst, vec_store);
-    else
-        hipLaunchKernelGGL(k_image_resample<false>, grid, dim3(RS_THREADS), 0, s, p, channels, H_in, W_in, pitch_bytes, ax, ay, h_out, w_out, dst, vec_store);
+#define RS_LAUNCH(U8_, NC_) hipLaunchKernelGGL((k_image_resample<U8_, NC_>), grid, dim3(RS_THREADS), 0, s, p, channels, H_in, W_in, pitch_bytes, ax, ay, h_out, w_out, dst, vec_store)
+    if (dst_channels == 4) {
+        if (src_format == GS_IMAGE_U8_HWC) RS_LAUNCH(true, 4); else RS_LAUNCH(false, 4);
+    } else {
+        if (src_format == GS_IMAGE_U8_HWC) RS_LAUNCH(true, 3); else RS_LAUNCH(false, 3);
+    }
+#undef RS_LAUNCH
 }

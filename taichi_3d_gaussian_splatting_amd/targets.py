@@ -31,6 +31,8 @@ _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 ARGTYPES = {
     # (ctx, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out, w_out, dst, stream)
     "gs_image_resample": [_VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _VP, _VP],
+    # the same arguments; src_channels must be 4 and dst is (4, h_out, w_out) (include/gs_targets_rgba.h)
+    "gs_image_resample_rgba": [_VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _VP, _VP],
 }
 _bound = False
 
@@ -69,22 +71,27 @@ def _source_layout(src):
 
 
 def image_resample(src: torch.Tensor, size_full: Tuple[int, int], size_out: Optional[Tuple[int, int]] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, alpha: bool = False) -> torch.Tensor:
     """-> (3, h_out, w_out) f32: the top-left size_out crop (default: all) of the antialiased resize of src to size_full.
     src: uint8 (H,W,3|4) with any row stride, or contiguous f32 (3|4,H,W); channel 3 is ignored.  The scale H / h_full and
     W / w_full must be in [1, 8].  Queued on the current stream of the source's device; no host synchronisation.  out: the tensor
-    to write (contiguous f32 (3,h_out,w_out) on the same device); a new one otherwise."""
+    to write (contiguous f32 (3,h_out,w_out) on the same device); a new one otherwise.
+    alpha=True (gs_image_resample_rgba): the source must have four channels, and the result is (4, h_out, w_out): planes 0..2
+    as without it, bit for bit, plane 3 channel 3 through the same filter -- the per-pixel weight of the target, same launch."""
     _bind()
     fmt, ch, H, W, pitch = _source_layout(src)
+    planes, entry = (4, "gs_image_resample_rgba") if alpha else (3, "gs_image_resample")
+    if alpha and ch != 4:
+        raise ValueError(f"alpha=True needs a four-channel source, got {ch} channels")
     h_full, w_full = int(size_full[0]), int(size_full[1])
     h_out, w_out = (h_full, w_full) if size_out is None else (int(size_out[0]), int(size_out[1]))
     if out is None:
         if min(h_out, w_out) < 0:
             raise ValueError("the output size must not be negative")
-        out = torch.empty((3, h_out, w_out), dtype=torch.float32, device=src.device)
-    elif out.dtype != torch.float32 or out.device != src.device or tuple(out.shape) != (3, h_out, w_out) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 (3,{h_out},{w_out}) tensor on {src.device}")
-    _native.call("gs_image_resample", src.device, _native.shared_ctx(src.device), _native.ptr(src), fmt, ch, H, W, pitch,
+        out = torch.empty((planes, h_out, w_out), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or out.device != src.device or tuple(out.shape) != (planes, h_out, w_out) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 ({planes},{h_out},{w_out}) tensor on {src.device}")
+    _native.call(entry, src.device, _native.shared_ctx(src.device), _native.ptr(src), fmt, ch, H, W, pitch,
                  h_full, w_full, h_out, w_out, _native.ptr(out))
     return out
 
@@ -137,6 +144,25 @@ def autoscaled_camera_info(camera_info: CameraInfo):
                                         camera_id=camera_info.camera_id)
 
 
+def erode_mask(mask_hw: torch.Tensor, k: int) -> torch.Tensor:
+    """a uint8 (H,W) mask shrunk by k pixels: a pixel keeps the minimum of its (2k+1) x (2k+1) neighbourhood (what lies outside
+    the image does not shrink it).  Plain torch, once at load."""
+    k = int(k)
+    if k <= 0:
+        return mask_hw
+    inv = 255.0 - mask_hw.to(torch.float32)[None, None]
+    grown = torch.nn.functional.max_pool2d(inv, kernel_size=2 * k + 1, stride=1, padding=k)      # pads with -inf
+    return (255.0 - grown[0, 0]).to(torch.uint8)
+
+
+def _with_mask(image_hwc: torch.Tensor, mask_hw: torch.Tensor) -> torch.Tensor:
+    """(H,W,4) uint8: channels 0..2 of the image, the mask as channel 3"""
+    H, W = image_hwc.shape[0], image_hwc.shape[1]
+    if mask_hw.dtype != torch.uint8 or tuple(mask_hw.shape) != (H, W):
+        raise ValueError(f"a mask must be uint8 ({H},{W}), the picture's size; got {mask_hw.dtype} {tuple(mask_hw.shape)}")
+    return torch.cat([image_hwc[:, :, :3], mask_hw[:, :, None]], dim=2).contiguous()
+
+
 def _pitched_uint8(image_hwc: torch.Tensor, device) -> torch.Tensor:
     """a (H,W,C) uint8 CPU tensor on the device, rows ROW_PITCH_ALIGN-byte aligned: a view into a (H, pitch) buffer"""
     H, W, ch = image_hwc.shape
@@ -154,6 +180,8 @@ class TargetStore:
         region the kernel reads; or, for an image over MAX_RESOLUTION_TRAIN, its autoscaled version (resize(size=1024,
         max_size=1600) of the cropped image, ImagePoseDataset.py:41-62) as f32 (3,h,w), made once by the same kernel;
       - q (n,4), t (n,3) and the intrinsics (n,3,3) as device tensors, and the base CameraInfo of every view.
+    With mask_source ("alpha": the RGBA image's own alpha; "file": the dataset's mask_path image, packed into channel 3 at load)
+    every stored image has four channels, and target(i, f, with_weight=True) also returns the mask through the same filter.
     target(i, f) then costs one launch.  The image it returns is the store's buffer for that geometry and is overwritten by the
     next target() of the same geometry: use it (loss forward and backward) before asking for the next one."""
 
@@ -169,24 +197,43 @@ class TargetStore:
             self.camera_infos[i] = CameraInfo(camera_intrinsics=self.intrinsics[1][i], camera_height=int(c.camera_height),
                                               camera_width=int(c.camera_width), camera_id=c.camera_id)
         self._out = {}                              # (H, W, factor) -> the (3,h,w) buffer of that geometry
+        self._out_rgba = {}                         # the same for with_weight=True: (4,h,w), image and weight in one buffer
         self._infos = {}                            # (view, factor) -> CameraInfo
 
     def __len__(self):
         return len(self.images)
 
     @classmethod
-    def from_dataset(cls, dataset, device="cuda") -> "TargetStore":
+    def from_dataset(cls, dataset, device="cuda", mask_source: Optional[str] = None, mask_erode: int = 0) -> "TargetStore":
+        """mask_source None: as ever.  "alpha": every image must decode to RGBA; its alpha is the weight.  "file": every record
+        must have a mask_path (dataset.load_mask); the mask replaces channel 3.  mask_erode=k shrinks the mask by k pixels
+        first (k = 5: no 11-tap SSIM window with a weight sees a masked pixel)."""
+        if mask_source not in (None, "alpha", "file"):
+            raise ValueError(f'mask_source must be None, "alpha" or "file", got {mask_source!r}')
+        if int(mask_erode) < 0 or (mask_source is None and int(mask_erode) != 0):
+            raise ValueError("mask_erode must be >= 0, and needs a mask_source")
         device = torch.device(device)
         n = len(dataset)
         with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
             raw = list(pool.map(dataset.load_raw, range(n)))
+            masks = list(pool.map(dataset.load_mask, range(n))) if mask_source == "file" else [None] * n
         images, qs, ts, infos = [], [], [], []
-        for image_hwc, q, t, info in raw:
+        for i, (image_hwc, q, t, info) in enumerate(raw):
+            if mask_source == "file":
+                if masks[i] is None:
+                    raise ValueError(f'mask_source="file": record {i} of the dataset has no mask_path')
+                mask = masks[i] if isinstance(masks[i], torch.Tensor) else torch.from_numpy(masks[i])
+                image_hwc = _with_mask(image_hwc, erode_mask(mask, mask_erode))
+            elif mask_source == "alpha":
+                if image_hwc.shape[2] != 4:
+                    raise ValueError(f'mask_source="alpha": image {i} of the dataset has no alpha channel')
+                if mask_erode:
+                    image_hwc = _with_mask(image_hwc, erode_mask(image_hwc[:, :, 3], mask_erode))
             stored = _pitched_uint8(image_hwc, device)
             H, W = int(info.camera_height), int(info.camera_width)          # the dataset's crop of the decoded image
             size_full, info = autoscaled_camera_info(info)
             if size_full is not None:
-                stored = image_resample(stored[:H, :W], size_full, (info.camera_height, info.camera_width))
+                stored = image_resample(stored[:H, :W], size_full, (info.camera_height, info.camera_width), alpha=mask_source is not None)
             images.append(stored)
             qs.append(q.reshape(4))
             ts.append(t.reshape(3))
@@ -199,10 +246,13 @@ class TargetStore:
             return image[:info.camera_height, :info.camera_width]
         return image
 
-    def target(self, i: int, downsample_factor: int = 1):
+    def target(self, i: int, downsample_factor: int = 1, with_weight: bool = False):
         """-> (image (3,h,w) f32, q (1,4), t (1,3), CameraInfo) of view i at the factor: sizes and intrinsics as
         _downsample_image_and_camera_info has them; at factor 1 the dataset's own crop.  After the first use of a geometry
-        (image size, factor) the call allocates nothing on the device, copies nothing to it and does not synchronise."""
+        (image size, factor) the call allocates nothing on the device, copies nothing to it and does not synchronise.
+        with_weight=True (the stored image must have four channels): -> (image, q, t, CameraInfo, weight (h,w) f32); image and
+        weight are out[:3] and out[3] of one (4,h,w) buffer, both contiguous, written by one launch; the image is bit for bit
+        the one target(i, f) returns."""
         f = int(downsample_factor)
         if f < 1:
             raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
@@ -210,14 +260,17 @@ class TargetStore:
         H, W = base.camera_height, base.camera_width
         h_full, w_full, h, w = downsampled_geometry(H, W, f)
         key = (H, W, f)
-        out = self._out.get(key)
+        outs, planes = (self._out_rgba, 4) if with_weight else (self._out, 3)
+        out = outs.get(key)
         if out is None:
-            out = self._out[key] = torch.empty((3, h, w), dtype=torch.float32, device=self.device)
+            out = outs[key] = torch.empty((planes, h, w), dtype=torch.float32, device=self.device)
         if f not in self.intrinsics:
             self.intrinsics[f] = downsampled_intrinsics(self.intrinsics[1], f)
         info = self._infos.get((i, f))
         if info is None:
             info = self._infos[(i, f)] = CameraInfo(camera_intrinsics=self.intrinsics[f][i], camera_height=h, camera_width=w,
                                                     camera_id=base.camera_id)
-        image_resample(self._source(i), (h_full, w_full), (h, w), out=out)
+        image_resample(self._source(i), (h_full, w_full), (h, w), out=out, alpha=with_weight)
+        if with_weight:
+            return out[:3], self.q[i:i + 1], self.t[i:i + 1], info, out[3]
         return out, self.q[i:i + 1], self.t[i:i + 1], info
