@@ -150,9 +150,12 @@ def world_to_camera(q, t):
 
 
 def _intrinsics(camera_info):
-    """(fx, fy, cx, cy) as Python floats of the f32 intrinsics"""
+    """(fx, fy, cx, cy) as Python floats of the f32 intrinsics.  The integration rule has no place for K[0,1] and K[1,0], which
+    the rasteriser that produced the depth honours: a camera that has either is refused."""
     K = camera_info.camera_intrinsics
     K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float32)
+    if K[0, 1] != 0 or K[1, 0] != 0:
+        raise ValueError(f"fusion takes fx, fy, cx, cy only: camera_intrinsics has K[0,1] = {float(K[0, 1])}, K[1,0] = {float(K[1, 0])}")
     return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
 
 

@@ -280,22 +280,24 @@ def look_at_pose(eye, target, up=(0.0, -1.0, 0.0)):
 
 
 def synthetic_view(eye, target, h, w, focal, centre, radius, rng, plane_z=None, alpha=True, image=True, specials=True,
-                   min_alpha=0.5):
+                   min_alpha=0.5, principal=None):
     """A view of a sphere (centre, radius) in front of a plane at camera depth plane_z (None: depth 0 where the sphere is
-    missed): depth by ray casting through the pixel centres, in float64 rounded to f32.  specials: a few pixels hold 0, a
+    missed): depth by ray casting through the pixel centres, in float64 rounded to f32.  focal: one number, or (fx, fy);
+    principal: (cx, cy), the middle of the image if None; the rays are cast with them.  specials: a few pixels hold 0, a
     negative depth, NaN and +inf; alpha holds values below and exactly at min_alpha besides 1."""
     q, t = look_at_pose(eye, target)
     m = world_to_camera(q, t)
     c = m[:, :3].astype(np.float64) @ np.asarray(centre, np.float64) + m[:, 3]
     pv, pu = np.meshgrid(np.arange(h) + 0.5, np.arange(w) + 0.5, indexing="ij")
-    cx, cy = w / 2.0, h / 2.0
-    d = np.stack([(pu - cx) / focal, (pv - cy) / focal, np.ones_like(pu)], -1)
+    fx, fy = (focal, focal) if np.ndim(focal) == 0 else focal
+    cx, cy = (w / 2.0, h / 2.0) if principal is None else principal
+    d = np.stack([(pu - cx) / fx, (pv - cy) / fy, np.ones_like(pu)], -1)
     a, b, k = (d * d).sum(-1), -2 * (d @ c), c @ c - radius * radius
     disc = b * b - 4 * a * k
     with np.errstate(invalid="ignore"):
         s = (-b - np.sqrt(disc)) / (2 * a)
     depth = np.where((disc >= 0) & (s > 0), s, 0.0 if plane_z is None else plane_z).astype(np.float32)
-    view = dict(q=q, t=t, m=m, fx=np.float32(focal), fy=np.float32(focal), cx=np.float32(cx), cy=np.float32(cy), alpha=None, image=None)
+    view = dict(q=q, t=t, m=m, fx=np.float32(fx), fy=np.float32(fy), cx=np.float32(cx), cy=np.float32(cy), alpha=None, image=None)
     if specials:
         flat = depth.reshape(-1)
         where = rng.choice(flat.size, size=max(8, flat.size // 40), replace=False)

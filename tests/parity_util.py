@@ -174,12 +174,19 @@ def assert_backward_parity(module, inp, g_image, f, band, extras=None, cfg=None,
     return b
 
 
-def assert_pose_gradient_parity(scene, q, t, partial, gq, gt, g_image=None, g_depth=None, g_alpha=None, per_element=True):
+def assert_pose_gradient_parity(scene, q, t, partial, gq, gt, g_image=None, g_depth=None, g_alpha=None, per_element=True, use=None):
     """grad_q (K,4) and grad_t (K,3) against torch_ref.pose_gradients for the given upstreams: GRAD_TOL of the tensor maximum;
     per element within ELEM_RTOL of its value plus ELEM_FLOOR of the summed per-point magnitudes; rows no visible point depends
-    on exactly zero.  -> the reference's (grad_q, grad_t)"""
+    on exactly zero.  -> the reference's (grad_q, grad_t).  use: a dict that receives, before anything is asserted, what q and t
+    use of the tensor bar and of the per-element bar (1.0 = at the bar)"""
     f, feat_after = oracle_frame(scene, q, t, partial)
     rq, rt, sq, st = torch_ref.pose_gradients(scene, q, t, f, feat_after, g_image, g_depth, g_alpha)
+    if use is not None:
+        for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
+            err = np.abs(a.astype(np.float64) - ref)
+            bar = ELEM_RTOL * np.abs(ref) + ELEM_FLOOR * summed
+            use[name] = float(err.max() / max(np.abs(ref).max(), 1e-300) / GRAD_TOL)
+            use[name + " element"] = float((err / np.maximum(bar, 1e-300))[bar > 0].max()) if (bar > 0).any() else 0.0
     for name, a, ref, summed in (("q", gq, rq, sq), ("t", gt, rt, st)):
         assert a.shape == ref.shape, name
         scale = np.abs(ref).max()
@@ -193,14 +200,109 @@ def assert_pose_gradient_parity(scene, q, t, partial, gq, gt, g_image=None, g_de
     return rq, rt
 
 
+def random_target(scene, seed):
+    """A target image of the scene's size, uniform in 0..1 -> (H,W,3) f32"""
+    return np.random.default_rng(seed).uniform(0, 1, (scene.height, scene.width, 3)).astype(np.float32)
+
+
+def assert_oracle_matches_autograd(s, q, t, target, partial):
+    """The two references against each other on the CPU: the oracle's image against torch_ref.render's in float64 (atol 2e-5),
+    and its analytic backward of the upstream 2 (image - target), all grad factors 1, against float64 autograd (2e-4 of the
+    tensor maximum per column group, and of the view-space gradient) -> {what: error} as measured"""
+    cfg = oracle.default_config(allow_partial_tiles=int(partial), **UNIT_FACTORS)
+    f, feat_after = run_oracle(s, q, t, cfg)
+    assert f.K > 0 and f.pixel_valid_point_count.max() >= 3
+    pc = torch.tensor(s.point_cloud, dtype=torch.float64, requires_grad=True)
+    ft = torch.tensor(feat_after, dtype=torch.float64, requires_grad=True)
+    img, _, _, aux = torch_ref.render(pc, ft, q, t, s.camera_intrinsics, s.height, s.width, f)
+    # forward agreement first (f32 oracle vs f64 restatement)
+    errors = {"image": float(np.abs(img.detach().numpy() - f.rasterized_image).max())}
+    assert np.allclose(img.detach().numpy(), f.rasterized_image, atol=2e-5), errors
+    g_img = 2.0 * (f.rasterized_image.astype(np.float64) - target)
+    img.backward(torch.tensor(g_img))
+    b = oracle.backward(f, g_img.astype(np.float32), color_max_sh_band=3, cfg=cfg)
+
+    def close(a, ref, name):
+        scale = np.abs(ref).max() + 1e-12
+        errors[name] = err = float(np.abs(a - ref).max() / scale)
+        assert err < 2e-4, f"{name}: max err / max|ref| = {err:.3e}"
+
+    close(b["grad_pointcloud"], pc.grad.numpy(), "xyz")
+    gf = ft.grad.numpy()
+    close(b["grad_pointcloud_features"][:, 0:4], gf[:, 0:4], "q")
+    close(b["grad_pointcloud_features"][:, 4:7], gf[:, 4:7], "s")
+    close(b["grad_pointcloud_features"][:, 7], gf[:, 7], "opacity")
+    close(b["grad_pointcloud_features"][:, 8:], gf[:, 8:], "sh")
+    ids = f.point_id_in_camera_list
+    close(b["grad_viewspace"][ids], aux["uv"].grad.numpy(), "viewspace")
+    return errors
+
+
+# ---- gradients of the depth and accumulated-alpha outputs against float64 (test_gpu_depth_alpha_grad.py, test_gpu_cameras.py) ----
+def upstream(shape, seed, positive=False):
+    rng = np.random.default_rng(seed)
+    g = rng.uniform(0, 1, shape) if positive else rng.normal(0, 1, shape)
+    return torch.tensor(g.astype(np.float32), device=DEV)
+
+
+UPSTREAM_SEEDS = {"image": 0, "depth": 17, "alpha": 34}
+
+
+def run_outputs(module, inp, which, seed=0, retain=False, positive=False):
+    """forward, then backward of sum(g_k * output_k) over the outputs named in `which` ("image", "depth", "alpha"); the
+    upstream of each output depends on its name only; -> ({name: upstream (H,W[,3]) f32 numpy}, the outputs)"""
+    outs = module(inp, return_accumulated_alpha=True)
+    named = {"image": outs[0], "depth": outs[1], "alpha": outs[3]}
+    tensors, grads, ups = [], [], {}
+    for name in which:
+        g = upstream(named[name].shape, seed + UPSTREAM_SEEDS[name], positive)
+        tensors.append(named[name])
+        grads.append(g)
+        ups[name] = g.cpu().numpy()
+    torch.autograd.backward(tensors, grads, retain_graph=retain)
+    return ups, outs
+
+
+def check_point_gradients(gp, gf, ref_p, ref_f, ids):
+    """Point gradients against a float64 reference: GRAD_TOL of the maximum of each column group (exact zeros where the group's
+    reference is all zero), and exact zeros on the rows outside the frustum -> {group: max |a - ref| / max |ref|}"""
+    errors = {}
+    for name, a, ref in [("xyz", gp, ref_p)] + [(n, gf[:, lo:hi], ref_f[:, lo:hi]) for lo, hi, n in GROUPS]:
+        scale = np.abs(ref).max()
+        err = np.abs(a.astype(np.float64) - ref)
+        if scale == 0:
+            assert not a.any(), name
+            continue
+        errors[name] = float(err.max() / scale)
+        assert err.max() / scale < GRAD_TOL, (name, err.max() / scale)
+    out = np.setdiff1d(np.arange(gp.shape[0]), ids)                # rows outside the frustum: exact zeros
+    assert not gp[out].any() and not gf[out].any()
+    return errors
+
+
+def float64_point_gradients(scene, q, t, partial, ups):
+    """-> (grad_pointcloud, grad_features) of the float64 reference for the upstreams `ups`, and the in-camera ids"""
+    f, feat_after = oracle_frame(scene, q, t, partial)
+    g = [ups.get(k) for k in ("image", "depth", "alpha")]
+    g = [None if x is None else x.astype(np.float64) for x in g]
+    tp, tf = torch_ref.point_gradients(scene, q, t, f, feat_after, *g)
+    return tp, tf, f.point_id_in_camera_list
+
+
 # ---- scenes ---------------------------------------------------------------------------------------------------------
-def tiny_case(seed, n, sigma0, width=32, height=None):
-    """A scene small enough for torch_ref, under a pose whose quaternion is deliberately not unit -> (scene, q, t, partial)"""
-    height = width if height is None else height
-    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
+def tiny_pose():
+    """The pose of tiny_case: its quaternion is deliberately not unit -> (q (1,4), t (1,3))"""
     ang = 0.05
     q = np.array([[0.02, np.sin(ang / 2), -0.01, np.cos(ang / 2)]], np.float32)
     t = np.array([[0.03, -0.02, 0.1]], np.float32)
+    return q, t
+
+
+def tiny_case(seed, n, sigma0, width=32, height=None):
+    """A scene small enough for torch_ref, under tiny_pose() -> (scene, q, t, partial)"""
+    height = width if height is None else height
+    s = synth(n, width, height, sigma0, sh_deg=3, seed=seed)
+    q, t = tiny_pose()
     return s, q, t, int(width % 16 != 0 or height % 16 != 0)
 
 

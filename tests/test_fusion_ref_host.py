@@ -112,6 +112,20 @@ def test_integration_rule_by_hand_on_one_voxel():
     assert tsdf[0, 0, 0] == np.float32((np.float32((2 * 0.5 - 1) / 3) * 2 + 0) / 3)
 
 
+def test_a_camera_with_skew_is_refused():
+    """fusion._intrinsics hands fx, fy, cx, cy to the library; the rasteriser that rendered the depth multiplies by the whole
+    matrix, so a K[0,1] or K[1,0] that is not zero must not be dropped silently"""
+    from taichi_3d_gaussian_splatting_amd import CameraInfo, fusion
+    K = np.array([[57.6, 0, 19.84], [0, 28.8, 34.56], [0, 0, 1]], np.float32)
+    for make in (torch.tensor, np.array):
+        assert fusion._intrinsics(CameraInfo(make(K), 48, 64, 0)) == tuple(float(x) for x in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+        for entry in ((0, 1), (1, 0)):
+            bad = K.copy()
+            bad[entry] = 0.5
+            with pytest.raises(ValueError, match="fx, fy, cx, cy only"):
+                fusion._intrinsics(CameraInfo(make(bad), 48, 64, 0))
+
+
 @pytest.mark.parametrize("with_colours", [True, False])
 def test_ply_round_trip(tmp_path, with_colours):
     from taichi_3d_gaussian_splatting_amd import fusion

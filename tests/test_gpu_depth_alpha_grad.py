@@ -16,7 +16,6 @@ import pytest
 import torch
 
 import parity_util as P
-import torch_ref
 from taichi_3d_gaussian_splatting_amd import _host, _native
 from taichi_3d_gaussian_splatting_amd.synthetic import synth, synth_clustered, view_pose
 
@@ -25,28 +24,8 @@ pytestmark = pytest.mark.gpu
 _depth_module = functools.partial(P.module, depth=True)          # config.differentiable_depth on, unless a test says otherwise
 
 
-def _upstream(shape, seed, positive=False):
-    rng = np.random.default_rng(seed)
-    g = rng.uniform(0, 1, shape) if positive else rng.normal(0, 1, shape)
-    return torch.tensor(g.astype(np.float32), device=P.DEV)
-
-
-SEEDS = {"image": 0, "depth": 17, "alpha": 34}
-
-
-def _run(module, inp, which, seed=0, retain=False, positive=False):
-    """forward, then backward of sum(g_k * output_k) over the outputs named in `which` ("image", "depth", "alpha"); the
-    upstream of each output depends on its name only; -> {name: upstream (H,W[,3]) f32 numpy}"""
-    outs = module(inp, return_accumulated_alpha=True)
-    named = {"image": outs[0], "depth": outs[1], "alpha": outs[3]}
-    tensors, grads, ups = [], [], {}
-    for name in which:
-        g = _upstream(named[name].shape, seed + SEEDS[name], positive)
-        tensors.append(named[name])
-        grads.append(g)
-        ups[name] = g.cpu().numpy()
-    torch.autograd.backward(tensors, grads, retain_graph=retain)
-    return ups, outs
+# the upstreams, the run, the float64 reference and the comparison are parity_util's, shared with test_gpu_cameras.py
+_upstream, _run, _check_points, _reference = P.upstream, P.run_outputs, P.check_point_gradients, P.float64_point_gradients
 
 
 def _scaled(gf, band, factors):
@@ -62,27 +41,6 @@ def _scaled(gf, band, factors):
         out[:, base + 1:base + keep] *= factors.get("grad_high_order_color_factor", 1.0)
         out[:, base + keep:base + 16] = 0.0
     return out
-
-
-def _check_points(gp, gf, ref_p, ref_f, ids):
-    for name, a, ref in [("xyz", gp, ref_p)] + [(n, gf[:, lo:hi], ref_f[:, lo:hi]) for lo, hi, n in P.GROUPS]:
-        scale = np.abs(ref).max()
-        err = np.abs(a.astype(np.float64) - ref)
-        if scale == 0:
-            assert not a.any(), name
-            continue
-        assert err.max() / scale < P.GRAD_TOL, (name, err.max() / scale)
-    out = np.setdiff1d(np.arange(gp.shape[0]), ids)                # rows outside the frustum: exact zeros
-    assert not gp[out].any() and not gf[out].any()
-
-
-def _reference(scene, q, t, partial, ups):
-    """-> (grad_pointcloud, grad_features) of the float64 reference for the upstreams `ups`, and the in-camera ids"""
-    f, feat_after = P.oracle_frame(scene, q, t, partial)
-    g = [ups.get(k) for k in ("image", "depth", "alpha")]
-    g = [None if x is None else x.astype(np.float64) for x in g]
-    tp, tf = torch_ref.point_gradients(scene, q, t, f, feat_after, *g)
-    return tp, tf, f.point_id_in_camera_list
 
 
 # Waves per tile of the backward blend (GS_BWD_WAVES_PER_TILE, read by every backward).  These small frames get 4 by default, i.e.

@@ -84,6 +84,25 @@ def test_integrate_equals_the_restatement_on_every_voxel(dims, size, n_views):
         assert min(total[k] for k in ("left", "right", "above", "below")) > 0, total
 
 
+@pytest.mark.parametrize("size", [(32, 48), (35, 50)])
+def test_integrate_under_a_camera_whose_four_numbers_differ(size):
+    """fy = 0.6 fx, cx = 0.4 w, cy = 0.65 h (the ring's other views have fx = fy and the principal point in the middle, so an
+    integration that took one of the four for another would pass them): the smallest volume, three views, every voxel bit for
+    bit.  The restatement itself gives another volume with fx and fy exchanged, and with cx and cy exchanged."""
+    dims, (h, w) = (9, 7, 5), size
+    origin, voxel = VOLUMES[dims]
+    views = R.ring_of_views(3, dims, origin, voxel, h, w, (90.0, 54.0), np.random.default_rng(0), plane_z=2.6, principal=(0.4 * w, 0.65 * h))
+    assert len({float(views[0][k]) for k in ("fx", "fy", "cx", "cy")}) == 4
+    stats = []
+    want = _reference(dims, views, stats=stats)
+    for a, b in (("fx", "fy"), ("cx", "cy")):
+        exchanged = _reference(dims, [dict(v, **{a: v[b], b: v[a]}) for v in views])
+        assert not np.array_equal(exchanged[0], want[0]) and not np.array_equal(exchanged[1], want[1]), (a, b)
+    _assert_same_volume(_gpu_integrate(_volume(dims), views), want)
+    total = {k: sum(s[k] for s in stats) for k in stats[0]}
+    assert total["updated"] > 0 and total["no_depth"] > 0 and total["low_alpha"] > 0 and total["at_min_alpha"] > 0 and total["far_behind"] > 0, total
+
+
 def test_a_camera_with_the_volume_behind_it_changes_nothing():
     dims = (9, 7, 5)
     rng = np.random.default_rng(2)

@@ -50,6 +50,9 @@ def _poses(n):
 
 def test_frames_from_a_pt_of_poses_equal_the_reference_expression(tmp_path):
     s = synth(64, 64, 48, 0.5, sh_deg=3, seed=1)
+    # fx, fy, cx, cy that cannot be mistaken for one another (the `anisotropic` and `offcentre` values of camera_cases.py):
+    # --camera_intrinsics FX FY CX CY is checked in its order
+    s.camera_intrinsics = np.array([[0.9 * 64, 0, 0.31 * 64], [0, 0.45 * 64, 0.72 * 48], [0, 0, 1]], np.float32)
     parquet, poses, out = tmp_path / "scene.parquet", tmp_path / "poses.pt", tmp_path / "out"
     scene_io.save_parquet(str(parquet), s.point_cloud, s.point_cloud_features)
     cameras = _poses(5)

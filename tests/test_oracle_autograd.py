@@ -3,18 +3,15 @@
 SH colour gradient, opacity gradient, loop-2 chain, band masks and grad factors."""
 import numpy as np
 import pytest
-import torch
 
 import parity_util as P
-import torch_ref
 from oracle import oracle
 
 
 def _case(seed, n, sigma0, width=32, height=None):
-    """P.tiny_case and a random target image -> (scene, q, t, target)"""
+    """P.tiny_case and P.random_target -> (scene, q, t, target)"""
     s, q, t, _ = P.tiny_case(seed, n, sigma0, width, height)
-    target = np.random.default_rng(seed + 100).uniform(0, 1, (s.height, s.width, 3)).astype(np.float32)
-    return s, q, t, target
+    return s, q, t, P.random_target(s, seed + 100)
 
 
 @pytest.mark.parametrize("seed,n,sigma0,width,height", [(0, 48, 0.25, 32, 32), (1, 64, 0.6, 32, 32), (2, 24, 1.2, 32, 32),
@@ -22,33 +19,7 @@ def _case(seed, n, sigma0, width=32, height=None):
 def test_backward_matches_autograd(seed, n, sigma0, width, height):
     """The last case is the partial-tile extension (41x27: neither side a multiple of 16)."""
     s, q, t, target = _case(seed, n, sigma0, width, height)
-    partial = int(width % 16 != 0 or height % 16 != 0)
-    cfg = oracle.default_config(allow_partial_tiles=partial, **P.UNIT_FACTORS)
-    f, feat_after = oracle.forward(s.point_cloud, s.point_cloud_features, s.point_invalid_mask,
-                                   s.point_object_id, q, t, s.camera_intrinsics, s.height, s.width, cfg)
-    assert f.K > 0 and f.pixel_valid_point_count.max() >= 3
-    pc = torch.tensor(s.point_cloud, dtype=torch.float64, requires_grad=True)
-    ft = torch.tensor(feat_after, dtype=torch.float64, requires_grad=True)
-    img, _, _, aux = torch_ref.render(pc, ft, q, t, s.camera_intrinsics, s.height, s.width, f)
-    # forward agreement first (f32 oracle vs f64 restatement)
-    assert np.allclose(img.detach().numpy(), f.rasterized_image, atol=2e-5)
-    g_img = 2.0 * (f.rasterized_image.astype(np.float64) - target)
-    img.backward(torch.tensor(g_img))
-    b = oracle.backward(f, g_img.astype(np.float32), color_max_sh_band=3, cfg=cfg)
-
-    def close(a, ref, name):
-        scale = np.abs(ref).max() + 1e-12
-        err = np.abs(a - ref).max() / scale
-        assert err < 2e-4, f"{name}: max err / max|ref| = {err:.3e}"
-
-    close(b["grad_pointcloud"], pc.grad.numpy(), "xyz")
-    gf = ft.grad.numpy()
-    close(b["grad_pointcloud_features"][:, 0:4], gf[:, 0:4], "q")
-    close(b["grad_pointcloud_features"][:, 4:7], gf[:, 4:7], "s")
-    close(b["grad_pointcloud_features"][:, 7], gf[:, 7], "opacity")
-    close(b["grad_pointcloud_features"][:, 8:], gf[:, 8:], "sh")
-    ids = f.point_id_in_camera_list
-    close(b["grad_viewspace"][ids], aux["uv"].grad.numpy(), "viewspace")
+    P.assert_oracle_matches_autograd(s, q, t, target, int(width % 16 != 0 or height % 16 != 0))
 
 
 def test_band_mask_and_factors():
