@@ -1,5 +1,6 @@
 """Train a scene from images: python gaussian_point_train.py --train_config PATH (the reference's script and YAML format).
---pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training")."""
+--pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training");
+--density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -11,7 +12,13 @@ if __name__ == "__main__":
     parser.add_argument("--pixel_weights", choices=("none", "alpha", "file"), default="none",
                         help="the loss's per-pixel weights: the RGBA images' alpha, or the dataset's mask_path images")
     parser.add_argument("--mask_erode", type=int, default=0, help="shrink the mask by this many pixels at load")
+    parser.add_argument("--density", choices=("adaptive", "mcmc"), default="adaptive",
+                        help="how the scene grows: the adaptive controller's clone / split, or relocation under a fixed budget")
+    parser.add_argument("--mcmc_cap", type=int, default=None, help="with --density mcmc: the number of Gaussians to reach and keep "
+                        "(default: every row the scene allocates, max_num_points_ratio)")
     args = parser.parse_args()
+    if args.mcmc_cap is not None and args.density != "mcmc":
+        parser.error("--mcmc_cap needs --density mcmc")
     if args.gen_template_only:
         import dataclasses
 
@@ -22,5 +29,10 @@ if __name__ == "__main__":
     config = GaussianPointCloudTrainer.TrainConfig.from_yaml_file(args.train_config)
     if config.unknown_keys:
         print("ignored keys of the config:", ", ".join(config.unknown_keys))
-    trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode)
+    mcmc_config = None
+    if args.density == "mcmc":
+        from taichi_3d_gaussian_splatting_amd.mcmc import MCMCConfig
+        mcmc_config = MCMCConfig(cap_max=args.mcmc_cap, seed=int(config.seed))
+    trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
+                                        mcmc_config=mcmc_config)
     trainer.train()

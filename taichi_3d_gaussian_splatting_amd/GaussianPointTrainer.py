@@ -14,6 +14,9 @@ What differs from the reference
     store hands the weight out with the target, in the same launch, and the fused loss takes it (LossFunction's pixel_weight).
     "none", the default, is the loop as it was.  These two settings are constructor arguments like device and writer:
     TrainConfig keeps the reference's fields and the three extensions it has.
+  - GaussianPointCloudTrainer(config, density="mcmc", mcmc_config=MCMCConfig(cap_max=...)) trains with a fixed budget of
+    Gaussians (mcmc.py): no adaptive controller and no backward hook; the strategy's two calls bracket the optimiser steps.
+    "adaptive", the default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -36,6 +39,7 @@ from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .GaussianPointCloudScene import GaussianPointCloudScene
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
+from .mcmc import MCMCConfig, MCMCStrategy
 from .optim import FusedAdam
 from .targets import TargetStore, downsampled_geometry, downsampled_intrinsics
 
@@ -196,12 +200,24 @@ class GaussianPointCloudTrainer:
             config.unknown_keys = unknown
             return config
 
-    def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0):
-        """device, writer, pixel_weights and mask_erode are extensions: the GPU to train on; a summary writer to use instead of
-        the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter otherwise); where the per-pixel
-        weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the dataset's mask_path column);
-        and by how many pixels the mask is shrunk at load (5: no weighted SSIM window sees a masked pixel)"""
+    def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
+                 density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None):
+        """device, writer, pixel_weights, mask_erode, density and mcmc_config are extensions: the GPU to train on; a summary
+        writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
+        otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
+        dataset's mask_path column); by how many pixels the mask is shrunk at load (5: no weighted SSIM window sees a masked
+        pixel); how the scene grows and shrinks -- "adaptive" (the reference's controller) or "mcmc" (mcmc.MCMCStrategy: a fixed
+        budget of Gaussians, mcmc_config.cap_max) -- and the MCMCConfig of the latter (None: the defaults, seeded by config.seed)"""
         self.config = config
+        if density not in ("adaptive", "mcmc"):
+            raise ValueError(f'density must be "adaptive" or "mcmc", got {density!r}')
+        if density == "mcmc" and self.config.sparse_adam:
+            raise ValueError('density="mcmc" cannot be combined with sparse_adam=True: its regulariser touches every valid row')
+        if density != "mcmc" and mcmc_config is not None:
+            raise ValueError('mcmc_config needs density="mcmc"')
+        self.density = density
+        self.mcmc_config = (mcmc_config or MCMCConfig(seed=int(self.config.seed))) if density == "mcmc" else None
+        self.mcmc = None                        # the MCMCStrategy of the running train()
         self.pixel_weights, self.mask_erode = pixel_weights, int(mask_erode)
         self.device = torch.device(device)
         os.makedirs(self.config.summary_writer_log_dir, exist_ok=True)
@@ -215,18 +231,22 @@ class GaussianPointCloudTrainer:
         self.val_dataset = ImagePoseDataset(dataset_json_path=self.config.val_dataset_json_path)
         self.scene = GaussianPointCloudScene.from_parquet(
             self.config.pointcloud_parquet_path, config=self.config.gaussian_point_cloud_scene_config, device=self.device)
-        self.adaptive_controller = GaussianPointAdaptiveController(
-            config=self.config.adaptive_controller_config,
-            maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
-                pointcloud=self.scene.point_cloud,
-                pointcloud_features=self.scene.point_cloud_features,
-                point_invalid_mask=self.scene.point_invalid_mask,
-                point_object_id=self.scene.point_object_id,
-            ), seed=self.config.seed)
-        self.rasterisation = GaussianPointCloudRasterisation(
-            config=self.config.rasterisation_config,
-            backward_valid_point_hook=self.adaptive_controller.update,
-        )
+        if self.density == "mcmc":
+            self.adaptive_controller = None
+            self.rasterisation = GaussianPointCloudRasterisation(config=self.config.rasterisation_config)
+        else:
+            self.adaptive_controller = GaussianPointAdaptiveController(
+                config=self.config.adaptive_controller_config,
+                maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
+                    pointcloud=self.scene.point_cloud,
+                    pointcloud_features=self.scene.point_cloud_features,
+                    point_invalid_mask=self.scene.point_invalid_mask,
+                    point_object_id=self.scene.point_object_id,
+                ), seed=self.config.seed)
+            self.rasterisation = GaussianPointCloudRasterisation(
+                config=self.config.rasterisation_config,
+                backward_valid_point_hook=self.adaptive_controller.update,
+            )
         self.rasterisation.track_touched_rows = bool(self.config.sparse_adam)
         self.loss_function = LossFunction(config=self.config.loss_function_config)
         self.best_psnr_score = 0.
@@ -326,6 +346,8 @@ class GaussianPointCloudTrainer:
         optimizer = FusedAdam([self.scene.point_cloud_features], lr=config.feature_learning_rate, betas=(0.9, 0.999))
         position_optimizer = FusedAdam([self.scene.point_cloud], lr=config.position_learning_rate, betas=(0.9, 0.999))
         self.optimizer, self.position_optimizer = optimizer, position_optimizer
+        if self.density == "mcmc":
+            self.mcmc = MCMCStrategy(self.mcmc_config, self.scene, optimizer, position_optimizer)
         downsample_factor = config.initial_downsample_factor
         try:
             from tqdm import tqdm
@@ -361,13 +383,18 @@ class GaussianPointCloudTrainer:
                 clamp_predicted=True,
                 pixel_weight=pixel_weight)          # None: the unweighted loss
             loss.backward()
+            if self.mcmc is not None:
+                self.mcmc.before_step(iteration)
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
             optimizer.step(rows=rows)
             position_optimizer.step(rows=rows)
 
+            if self.mcmc is not None:
+                self.mcmc.after_step(iteration, position_optimizer.lr)       # the rate this iteration stepped with
             if iteration % config.position_learning_rate_decay_interval == 0:
                 position_optimizer.lr *= config.position_learning_rate_decay_rate
-            self.adaptive_controller.refinement()
+            if self.adaptive_controller is not None:
+                self.adaptive_controller.refinement()
 
             # (the reference reads loss.item() every iteration to pick "problematic" images for its image log; there is no
             # image log here, so the loss is read -- and the host waits for the device -- only where it is logged)

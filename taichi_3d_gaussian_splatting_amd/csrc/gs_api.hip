@@ -14,6 +14,7 @@
 #include "../../include/gs_compose.h"
 #include "../../include/gs_frames.h"
 #include "../../include/gs_fusion.h"
+#include "../../include/gs_mcmc.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -152,6 +153,7 @@ struct gs_ctx {
     // nothing else touches it, and the K-sized hist of the later passes is a buffer of its own
     DevBuf first_hist;
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
+    DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
@@ -224,7 +226,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
-                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial };
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1909,6 +1911,81 @@ extern "C" int gs_frame_release(gs_ctx* c, gs_frame* h)
     Frame* f = resolve(c, h);
     if (!f) return fail(GS_ERR_STATE, "gs_frame_release: not a live frame of this context (already released?)");
     drop_frame(c, f);
+    return GS_OK;
+}
+
+// ---- fixed-budget densification (k_mcmc.hip) ------------------------------------------------------------------------------
+extern "C" int64_t gs_mcmc_scratch_bytes(int64_t n_points) { return n_points < 0 ? 0 : (int64_t)gs_mcmc_scratch_size(n_points); }
+
+static int mcmc_rows_check(const char* who, gs_ctx* c, int64_t N)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
+    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_points must be in [0, 2^31)");
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_noise(gs_ctx* c, float* point_cloud, const float* features, const int8_t* mask, int64_t N, float noise_scale,
+                             float gate_k, float gate_x0, uint64_t seed, uint32_t step_index, gs_stream stream_)
+{
+    if (const int rc = mcmc_rows_check("gs_mcmc_noise", c, N)) return rc;
+    if (N > 0 && (!point_cloud || !features || !mask)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: NULL array");
+    if (((uintptr_t)features & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: features must be 16-byte aligned");
+    if (!std::isfinite(noise_scale) || !std::isfinite(gate_k) || !std::isfinite(gate_x0))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: noise_scale, gate_k and gate_x0 must be finite");
+    if (N == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_mcmc_noise(point_cloud, features, mask, N, noise_scale, gate_k, gate_x0, seed, step_index, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_regulariser(gs_ctx* c, const float* features, const int8_t* mask, int64_t N, float lambda_opacity, float lambda_scale,
+                                   const float* upstream, float* grad_features, float* value_and_count, gs_stream stream_)
+{
+    if (const int rc = mcmc_rows_check("gs_mcmc_regulariser", c, N)) return rc;
+    if (N > 0 && (!features || !mask)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: NULL array");
+    if ((((uintptr_t)features | (uintptr_t)grad_features) & 15u) != 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: features and grad_features must be 16-byte aligned");
+    if (!std::isfinite(lambda_opacity) || !std::isfinite(lambda_scale))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: lambda_opacity and lambda_scale must be finite");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    if (c->mcmc_ws.ensure(gs_mcmc_reg_ws_size(N), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_mcmc_regulariser: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_mcmc_regulariser(features, mask, N, lambda_opacity, lambda_scale, upstream, grad_features, value_and_count, c->mcmc_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_relocate(gs_ctx* c, const gs_density_scene* scene, float* features_exp_avg, float* features_exp_avg_sq,
+                                float* point_cloud_exp_avg, float* point_cloud_exp_avg_sq, const gs_mcmc_config* cfg,
+                                const gs_mcmc_plan* plan, uint64_t seed, uint32_t call_index, gs_stream stream_)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: ctx is NULL");
+    if (!scene || !cfg || !plan || !plan->counts) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL scene, config, plan or plan->counts");
+    const int64_t N = scene->n_points;
+    if (const int rc = mcmc_rows_check("gs_mcmc_relocate", c, N)) return rc;
+    if (plan->n_points < N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: plan is smaller than the scene");
+    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask || !scene->point_object_id))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL scene array");
+    if (N > 0 && (!plan->source_of || !plan->dest_row || !plan->multiplicity || !plan->scratch))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL plan array");
+    if ((((uintptr_t)scene->point_cloud_features | (uintptr_t)features_exp_avg | (uintptr_t)features_exp_avg_sq) & 15u) != 0 ||
+        ((uintptr_t)plan->scratch & 7u) != 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: features and their moments must be 16-byte aligned, scratch 8-byte aligned");
+    if (cfg->n_max < 1 || cfg->n_max > GS_MCMC_N_MAX) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: n_max must be in [1, 51]");
+    if (cfg->grow_permille < 0 || cfg->cap_max < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: grow_permille and cap_max must be >= 0");
+    if (std::isnan(cfg->min_opacity_logit)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: min_opacity_logit is NaN");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    float* const moments[4] = { features_exp_avg, features_exp_avg_sq, point_cloud_exp_avg, point_cloud_exp_avg_sq };
+    gs_launch_mcmc_relocate(*scene, moments, *cfg, *plan, seed, call_index, s);
+    HIP_TRY(hipGetLastError());
     return GS_OK;
 }
 

@@ -304,6 +304,22 @@ __device__ __forceinline__ uint32_t gs_block_scan_excl(const uint32_t* ws, int w
     for (int w = 0; w < wave; ++w) woff += ws[w];
     return woff + incl - v;
 }
+// in-block exclusive rank of `pred` in thread order and the block's total, for a block of NW waves (every thread of the block must call
+// it; s_wave: NW words of LDS, free for the next call when this one returns)
+template <int NW>
+__device__ __forceinline__ int gs_block_rank(bool pred, int* s_wave, int* total)
+{
+    const unsigned long long b = gs_ballot(pred);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) s_wave[w] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { const int c = s_wave[i]; before += i < w ? c : 0; all += c; }
+    __syncthreads();
+    *total = all;
+    return before + __popcll(b & ((1ull << lane) - 1ull));
+}
 // counts[0 .. block) summed by a block of NT threads (a few thousand L2-resident words read by every block, instead of a scan launch in
 // between): every lane gets its WAVE's share, the caller folds the shares with a block sum
 template <int NT, typename T> __device__ __forceinline__ T gs_sum_of_blocks_before(const T* __restrict__ counts, int block)
@@ -603,6 +619,19 @@ void gs_launch_density_apply(const gs_density_scene& scene, const gs_density_con
 void gs_launch_controller_accumulate(const int32_t* ids, const int32_t* npix, const float* mag, const float* gpc, int64_t M, int64_t N,
                                      const gs_controller_accumulators& acc, hipStream_t s);
 size_t gs_density_scratch_size(int64_t N);
+
+// k_mcmc.hip (include/gs_mcmc.h): fixed-budget densification.  The launchers trust what the entry points checked.  ws of the
+// regulariser: gs_mcmc_reg_ws_size(N) bytes of the context's; moments: exp_avg, exp_avg_sq of the features, then of the positions.
+struct gs_mcmc_config;
+struct gs_mcmc_plan;
+void gs_launch_mcmc_noise(float* pc, const float* feat, const int8_t* mask, int64_t N, float noise_scale, float gate_k, float gate_x0,
+                          uint64_t seed, uint32_t step_index, hipStream_t s);
+void gs_launch_mcmc_regulariser(const float* feat, const int8_t* mask, int64_t N, float lambda_opacity, float lambda_scale,
+                                const float* upstream, float* grad, float* value_and_count, void* ws, hipStream_t s);
+void gs_launch_mcmc_relocate(const gs_density_scene& scene, float* const moments[4], const gs_mcmc_config& cfg, const gs_mcmc_plan& plan,
+                             uint64_t seed, uint32_t call_index, hipStream_t s);
+size_t gs_mcmc_scratch_size(int64_t N);
+size_t gs_mcmc_reg_ws_size(int64_t N);
 
 // k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
 // order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry

@@ -17,6 +17,7 @@
 // No float atomics, no host waits: the counts the host would learn with .item() (CTRL:220,223,244,301,318) are read
 // on the device by the next kernel.  Integer atomics only for the over / under tallies of the fill pass.
 #include "gs_point_math.h"
+#include "gs_random.h"
 
 #include <algorithm>
 
@@ -32,30 +33,11 @@ size_t gs_density_scratch_size(int64_t N)
     return (size_t)(DEN_ARRAYS * DEN_NBLK(N) + 16) * sizeof(int32_t);
 }
 
-// ---- Philox4x32-10 (Salmon et al., SC'11; constants of Random123) -----------------------------------------------
-__device__ __forceinline__ uint4 gs_philox4x32_10(uint4 c, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    }
-    return c;
-}
-
-// 24 random bits -> (0, 1]: log never sees 0
-__device__ __forceinline__ float gs_unit(uint32_t x) { return (float)((x >> 8) + 1u) * 5.9604644775390625e-8f; }
-
-// GP3D:391-406 GaussianPoint3D.sample(): centre + R S (z1, z2, z3), z from Box-Muller (GP3D:91-94) on four uniforms
+// GP3D:391-406 GaussianPoint3D.sample(): centre + R S (z1, z2, z3), z from Box-Muller on the four uniforms of one draw (gs_random.h)
 __device__ __forceinline__ void gs_sample_point(const float* centre, const float* feat, uint4 ctr, uint32_t k0, uint32_t k1, float out[3])
 {
-    const uint4 u = gs_philox4x32_10(ctr, k0, k1);
-    const float u1 = gs_unit(u.x), u2 = gs_unit(u.y), u3 = gs_unit(u.z), u4 = gs_unit(u.w);
-    const float two_pi = (float)(2.0 * 3.141592653589);                 // the reference's constant
-    const float r1 = sqrtf(-2.0f * logf(u1)), r3 = sqrtf(-2.0f * logf(u3));
-    const float z[3] = { r1 * cosf(two_pi * u2), r1 * sinf(two_pi * u2), r3 * cosf(two_pi * u4) };
+    float z[3];
+    gs_normal3(gs_philox4x32_10(ctr, k0, k1), z);
     float R[3][3];
     rotation_from_quaternion(feat, &R[0][0]);
     const float s[3] = { gs_expf(feat[4]), gs_expf(feat[5]), gs_expf(feat[6]) };
@@ -80,21 +62,6 @@ __device__ __forceinline__ void gs_foci_vector(const float* feat, float out[3])
     const float len = sqrtf(rc * rc - ra * ra);
 #pragma unroll
     for (int i = 0; i < 3; ++i) out[i] = len * R[i][axis];
-}
-
-// in-block exclusive rank of `pred` in row order and the block's total (every thread of the block must call it)
-__device__ __forceinline__ int gs_block_rank(bool pred, int* s_wave, int* total)
-{
-    const unsigned long long b = gs_ballot(pred);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_wave[w] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < DEN_BLOCK / 64; ++i) { const int c = s_wave[i]; before += i < w ? c : 0; all += c; }
-    __syncthreads();
-    *total = all;
-    return before + __popcll(b & ((1ull << lane) - 1ull));
 }
 
 // ---- select ---------------------------------------------------------------------------------------------------------
@@ -165,7 +132,7 @@ __global__ __launch_bounds__(DEN_BLOCK) void k_density_rows(
 #pragma unroll
     for (int a = 0; a < DEN_ARRAYS; ++a) {
         int total;
-        (void)gs_block_rank(preds[a], s_wave, &total);
+        (void)gs_block_rank<DEN_BLOCK / 64>(preds[a], s_wave, &total);
         if (threadIdx.x == 0) bc[a * nb + blockIdx.x] = total;
     }
 }
@@ -221,7 +188,7 @@ __global__ __launch_bounds__(DEN_BLOCK) void k_density_scatter(
     const int64_t n = (int64_t)blockIdx.x * DEN_BLOCK + threadIdx.x;
     const int f = n < N ? flags[n] : 0;
     int total;
-    const int r = gs_block_rank(f & GS_DENSITY_DENSIFY, s_wave, &total);
+    const int r = gs_block_rank<DEN_BLOCK / 64>(f & GS_DENSITY_DENSIFY, s_wave, &total);
     if (!(f & GS_DENSITY_DENSIFY)) return;
     const size_t d = (size_t)offsets[blockIdx.x] + r;
     ids_out[d] = (int32_t)n;
@@ -250,9 +217,9 @@ __global__ __launch_bounds__(DEN_BLOCK) void k_density_prune(const int8_t* __res
         free_row = prune || m == 1;
     }
     int total;
-    (void)gs_block_rank(free_row, s_wave, &total);
+    (void)gs_block_rank<DEN_BLOCK / 64>(free_row, s_wave, &total);
     if (threadIdx.x == 0) bc[blockIdx.x] = total;
-    (void)gs_block_rank(valid, s_wave, &total);
+    (void)gs_block_rank<DEN_BLOCK / 64>(valid, s_wave, &total);
     if (threadIdx.x == 0) bc[gridDim.x + blockIdx.x] = total;
 }
 
@@ -266,7 +233,7 @@ __global__ __launch_bounds__(DEN_BLOCK) void k_density_free_rows(const int8_t* _
     const int64_t n = (int64_t)blockIdx.x * DEN_BLOCK + threadIdx.x;
     const bool free_row = n < N && mask[n] == 1;
     int total;
-    const int r = gs_block_rank(free_row, s_wave, &total);
+    const int r = gs_block_rank<DEN_BLOCK / 64>(free_row, s_wave, &total);
     if (free_row && base + r < want) fill_out[base + r] = (int32_t)n;
 }
 
