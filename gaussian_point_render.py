@@ -14,7 +14,10 @@ beside every frame; --image_height / --image_width / --camera_intrinsics fx fy c
 zero surface as a coloured triangle mesh: --mesh_bbox X0 Y0 Z0 X1 Y1 Z1 is the volume's box (default: mixture.bounding_box of
 the scene, mean -+ 3 standard deviations of the Gaussians' positions per axis), --mesh_voxel its voxel size (default: the
 box's longest side / 255) and --mesh_trunc the truncation distance (default: 4 voxels).  With --mesh_to, --output_prefix is
-optional: without it only the mesh is written.
+optional: without it only the mesh is written.  --appearance FILE (an appearance_<iteration>.pt of a trainer run with --appearance
+affine) with a dataset JSON as --poses: a frame whose image_path is in the file is corrected by its trained colour transform
+before it is written and measured, every other frame is rendered as without the flag, and metrics.json gains psnr_cc per view
+(the PSNR after the best affine fit of the rendering to its ground truth).
 """
 import argparse
 import json
@@ -48,6 +51,7 @@ if __name__ == "__main__":
     parser.add_argument("--mesh_trunc", type=float, help="truncation distance (default: fusion.TRUNC_VOXELS = 4 voxels)")
     parser.add_argument("--mesh_bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                         help="the volume's box (default: mixture.bounding_box of the scene)")
+    parser.add_argument("--appearance", type=str, default="", help="an appearance_<iteration>.pt of the trainer: per-view colour transforms")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
     if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to)):
@@ -55,14 +59,19 @@ if __name__ == "__main__":
     if args.mesh_to and not (args.poses or "").endswith(".pt"):
         parser.error("--mesh_to fuses the poses of a .pt file")
 
+    if args.appearance and not (args.poses or "").endswith(".json"):
+        parser.error("--appearance corrects the views of a dataset json given as --poses")
+
     parquet_path = args.parquet_path[0] if len(args.parquet_path) == 1 else list(args.parquet_path)
-    targets = None
+    targets = image_paths = None
     if not args.poses:
         cameras = torch.eye(4).unsqueeze(0)
     elif args.poses.endswith(".pt"):
         cameras = torch.load(args.poses)
     elif args.poses.endswith(".json"):
-        targets = TargetStore.from_dataset(ImagePoseDataset(dataset_json_path=args.poses), device=args.device)
+        dataset = ImagePoseDataset(dataset_json_path=args.poses)
+        targets = TargetStore.from_dataset(dataset, device=args.device)
+        image_paths = [str(p) for p in dataset.df["image_path"].tolist()]
         cameras = torch.eye(4).unsqueeze(0)             # the views carry their own poses and cameras
     else:
         raise ValueError(f"Unrecognized poses file format: {args.poses}, Must be .pt or .json file")
@@ -104,7 +113,13 @@ if __name__ == "__main__":
     if args.gt_prefix:
         gt_prefix = Path(args.gt_prefix)
         os.makedirs(gt_prefix, exist_ok=True)
-    metrics = renderer.run(output_prefix, depth=args.depth, targets=targets, gt_prefix=gt_prefix)
+    transforms = None
+    if args.appearance:
+        from taichi_3d_gaussian_splatting_amd.appearance import AppearanceTable
+        table, table_paths = AppearanceTable.load(args.appearance, device=renderer.device)
+        transforms = table.by_image_path(table_paths)
+    metrics = renderer.run(output_prefix, depth=args.depth, targets=targets, gt_prefix=gt_prefix, appearance=transforms,
+                           image_paths=image_paths if transforms is not None else None)
     if metrics is not None:
         with open(args.metrics_json or output_prefix / "metrics.json", "w") as fh:
             json.dump(metrics, fh, indent=1)

@@ -1,6 +1,7 @@
 """Train a scene from images: python gaussian_point_train.py --train_config PATH (the reference's script and YAML format).
 --pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training");
---density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification")."""
+--density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification");
+--appearance affine trains a colour transform per training image with the scene (INTEGRATION.md "Exposure compensation")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -16,6 +17,8 @@ if __name__ == "__main__":
                         help="how the scene grows: the adaptive controller's clone / split, or relocation under a fixed budget")
     parser.add_argument("--mcmc_cap", type=int, default=None, help="with --density mcmc: the number of Gaussians to reach and keep "
                         "(default: every row the scene allocates, max_num_points_ratio)")
+    parser.add_argument("--appearance", choices=("none", "affine"), default="none",
+                        help="exposure compensation: a learnable 3x4 affine colour transform per training image")
     args = parser.parse_args()
     if args.mcmc_cap is not None and args.density != "mcmc":
         parser.error("--mcmc_cap needs --density mcmc")
@@ -34,5 +37,5 @@ if __name__ == "__main__":
         from taichi_3d_gaussian_splatting_amd.mcmc import MCMCConfig
         mcmc_config = MCMCConfig(cap_max=args.mcmc_cap, seed=int(config.seed))
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
-                                        mcmc_config=mcmc_config)
+                                        mcmc_config=mcmc_config, appearance=args.appearance)
     trainer.train()

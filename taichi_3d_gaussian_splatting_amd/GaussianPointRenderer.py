@@ -12,6 +12,9 @@ multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. a
   - run() can also write the colour-mapped depth, and with a targets.TargetStore it renders the store's views with their own
     cameras and returns per-view metrics: the 8-bit PSNR from the exact sum of squared differences, and the float PSNR and
     SSIM the trainer's validation() logs, from the same LossFunction kernels -- all read from the device once, at the end;
+  - run(appearance=...) corrects the frames of the views a trained appearance table knows (appearance.py: the per-view affine
+    colour transform of exposure compensation) before they are converted to 8 bits, and adds psnr_cc per view: the PSNR after
+    the best affine fit of the rendering to its ground truth;
   - fuse() renders the poses with depth and accumulated alpha and integrates them into a fusion.TSDFVolume on the device, from
     which a triangle mesh is extracted (fusion.py).
 """
@@ -22,6 +25,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
+from . import appearance as _appearance
 from . import frames, fusion
 from .Camera import CameraInfo
 from .compose import SceneComposition
@@ -127,14 +131,22 @@ class GaussianPointRenderer:
                              alpha=[r[2] for r in rendered], image=[r[0] for r in rendered])
         return volume
 
-    def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None):
+    def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None, appearance=None, image_paths=None):
         """Render every camera of the config to <output_prefix>/frame_<i:03>.<format> (and depth_<i:03> with depth=True).
         output_prefix None: the frames still cross to the host, nothing is written.
 
         targets (a targets.TargetStore): its views are rendered instead, each under its own pose and camera, and compared with
         its image; gt_prefix then receives the ground-truth frames -- the stored bytes where the store holds the decoded
         image, RGB_ROUND of the resized f32 image otherwise.  -> None without targets, else a dict with `views` (per view:
-        psnr_8bit from the exact SSE, psnr and ssim as the trainer's validation() computes them) and their `mean`."""
+        psnr_8bit from the exact SSE, psnr and ssim as the trainer's validation() computes them) and their `mean`.
+
+        appearance ({image path: (12,) transform on the device}, AppearanceTable.by_image_path) with image_paths (the path of
+        every view of `targets`, in order): a view whose path is in the dict is corrected by its transform before it is
+        converted to 8 bits and measured; every other frame is rendered as without it.  Every view then also gets psnr_cc:
+        the float PSNR after appearance.fit_affine(rendering, ground truth), which reads 23 numbers to the host per view."""
+        if appearance is not None:
+            if targets is None or image_paths is None or len(image_paths) != len(targets):
+                raise ValueError("appearance needs targets and the image path of every one of its views")
         directory = None if output_prefix is None else str(output_prefix)
         sink = frames.FrameSink(directory, fmt=self.frame_format, slots=self.slots, device=self.device)
         gt_sink = None
@@ -151,12 +163,15 @@ class GaussianPointRenderer:
         K = len(self.composition)
         q_rows, t_rows = self.composition.camera_rows(targets.q, targets.t)
         q_rows, t_rows = q_rows.reshape(n, K, 4), t_rows.reshape(n, K, 3)
-        float_metrics = torch.zeros((n, 2), dtype=torch.float32, device=self.device)      # psnr, ssim
+        float_metrics = torch.zeros((n, 3), dtype=torch.float32, device=self.device)      # psnr, ssim, psnr_cc
         sizes = []
         for i in range(n):
             image_gt, _, _, info = targets.target(i, 1)
             h, w = info.camera_height, info.camera_width
             image, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=depth)
+            if appearance is not None and str(image_paths[i]) in appearance:
+                # in the rasteriser's layout, so the corrected frame is again a contiguous (H,W,3)
+                image = _appearance.apply_forward(image.permute(2, 0, 1), appearance[str(image_paths[i])]).permute(1, 2, 0)
             stored = targets.images[i]
             if stored.dtype == torch.uint8:
                 gt_bytes = stored
@@ -170,6 +185,9 @@ class GaussianPointRenderer:
                 _, _, ssim_loss = self.loss_function(image_pred, image_gt)
                 float_metrics[i, 0] = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
                 float_metrics[i, 1] = 1.0 - ssim_loss
+                if appearance is not None:
+                    image_cc = torch.clamp(_appearance.apply_forward(image_pred, _appearance.fit_affine(image_pred, image_gt)), 0, 1)
+                    float_metrics[i, 2] = 10 * torch.log10(1.0 / torch.mean((image_cc - image_gt) ** 2))
             sizes.append(h * w * 3)
         sse = sink.close().numpy()
         if gt_sink is not None:
@@ -178,5 +196,10 @@ class GaussianPointRenderer:
         psnr_8bit = [float(frames.psnr_from_sse(s, size)) for s, size in zip(sse, sizes)]
         views = [dict(index=i, sse_8bit=int(sse[i]), psnr_8bit=psnr_8bit[i], psnr=float(float_metrics[i, 0]), ssim=float(float_metrics[i, 1]))
                  for i in range(n)]
-        mean = {name: float(np.mean([v[name] for v in views])) if views else float("nan") for name in ("psnr_8bit", "psnr", "ssim")}
+        names = ("psnr_8bit", "psnr", "ssim")
+        if appearance is not None:
+            names += ("psnr_cc",)
+            for i, v in enumerate(views):
+                v["psnr_cc"] = float(float_metrics[i, 2])
+        mean = {name: float(np.mean([v[name] for v in views])) if views else float("nan") for name in names}
         return dict(views=views, mean=mean)

@@ -17,6 +17,11 @@ What differs from the reference
   - GaussianPointCloudTrainer(config, density="mcmc", mcmc_config=MCMCConfig(cap_max=...)) trains with a fixed budget of
     Gaussians (mcmc.py): no adaptive controller and no backward hook; the strategy's two calls bracket the optimiser steps.
     "adaptive", the default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, appearance="affine", appearance_config=AppearanceConfig(...)) trains a 3x4 affine colour
+    transform per training image with the scene (appearance.py): exposure compensation for captures whose exposure and white
+    balance differ between views.  The transform is applied to the rendered image in front of the loss; validation views have
+    none and are rendered uncorrected, and additionally measured after the best affine fit to their ground truth (val/psnr_cc,
+    val/ssim_cc, val/loss_cc).  "none", the default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -37,6 +42,8 @@ from .Camera import CameraInfo
 from .GaussianPointAdaptiveController import GaussianPointAdaptiveController
 from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .GaussianPointCloudScene import GaussianPointCloudScene
+from . import appearance as _appearance
+from .appearance import AppearanceConfig, AppearanceTable
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
 from .mcmc import MCMCConfig, MCMCStrategy
@@ -201,14 +208,23 @@ class GaussianPointCloudTrainer:
             return config
 
     def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
-                 density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None):
-        """device, writer, pixel_weights, mask_erode, density and mcmc_config are extensions: the GPU to train on; a summary
+                 density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
+                 appearance_config: Optional[AppearanceConfig] = None):
+        """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
         dataset's mask_path column); by how many pixels the mask is shrunk at load (5: no weighted SSIM window sees a masked
         pixel); how the scene grows and shrinks -- "adaptive" (the reference's controller) or "mcmc" (mcmc.MCMCStrategy: a fixed
-        budget of Gaussians, mcmc_config.cap_max) -- and the MCMCConfig of the latter (None: the defaults, seeded by config.seed)"""
+        budget of Gaussians, mcmc_config.cap_max) -- and the MCMCConfig of the latter (None: the defaults, seeded by config.seed);
+        whether every training image gets a learnable colour transform -- "none" or "affine" (appearance.AppearanceTable, in
+        self.appearance_table) -- and its AppearanceConfig (None: the defaults, over config.num_iterations)"""
         self.config = config
+        if appearance not in ("none", "affine"):
+            raise ValueError(f'appearance must be "none" or "affine", got {appearance!r}')
+        if appearance == "none" and appearance_config is not None:
+            raise ValueError('appearance_config needs appearance="affine"')
+        self.appearance = appearance
+        self.appearance_table = None
         if density not in ("adaptive", "mcmc"):
             raise ValueError(f'density must be "adaptive" or "mcmc", got {density!r}')
         if density == "mcmc" and self.config.sparse_adam:
@@ -271,6 +287,11 @@ class GaussianPointCloudTrainer:
         else:
             # batch_size=None: the dataset's items as they are; num_workers=0: no process is started behind an initialised GPU
             self._val_loader = torch.utils.data.DataLoader(self.val_dataset, batch_size=None, shuffle=False, num_workers=0)
+        if self.appearance == "affine":
+            appearance_config = appearance_config or AppearanceConfig()
+            if appearance_config.num_iterations is None:
+                appearance_config = dataclasses.replace(appearance_config, num_iterations=max(int(self.config.num_iterations), 1))
+            self.appearance_table = AppearanceTable(len(self.train_dataset), self.device, appearance_config)
         # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
         self._order_generator = torch.Generator().manual_seed(int(self.config.seed))
         self.view_order: List[int] = []
@@ -326,6 +347,10 @@ class GaussianPointCloudTrainer:
             for item in self._val_loader:
                 yield self._host_target(item, 1) + (None,)
 
+    def train_image_paths(self) -> List[str]:
+        """the image_path of every training view, in the dataset's order: what the rows of the appearance table belong to"""
+        return [str(p) for p in self.train_dataset.df["image_path"].tolist()]
+
     def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band):
         return GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput(
             point_cloud=self.scene.point_cloud,
@@ -361,12 +386,13 @@ class GaussianPointCloudTrainer:
             position_optimizer.zero_grad()
 
             pixel_weight = None
+            view = self._view_at(iteration)         # (the host path's sampler walks the same list)
             if self.weighted:
                 image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self.train_targets.target(
-                    self._view_at(iteration), downsample_factor, with_weight=True)
+                    view, downsample_factor, with_weight=True)
             elif self.train_targets is not None:
                 image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self.train_targets.target(
-                    self._view_at(iteration), downsample_factor)
+                    view, downsample_factor)
             else:
                 image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self._host_target(next(train_items), downsample_factor)
             rasterisation_input = self._rasterisation_input(
@@ -375,6 +401,9 @@ class GaussianPointCloudTrainer:
             image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
             # hxwx3->3xhxw, read where it lies; the clamp to [0, 1] runs inside the loss kernels
             image_pred = image_pred.permute(2, 0, 1)
+            if self.appearance_table is not None:
+                # the view's colour transform, in the rasteriser's layout: the loss reads the corrected image where it lies
+                image_pred = _appearance.apply(image_pred, self.appearance_table.row(view))
             loss, l1_loss, ssim_loss = self.loss_function(
                 image_pred,
                 image_gt,
@@ -388,6 +417,8 @@ class GaussianPointCloudTrainer:
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
             optimizer.step(rows=rows)
             position_optimizer.step(rows=rows)
+            if self.appearance_table is not None:
+                self.appearance_table.step(view, iteration)
 
             if self.mcmc is not None:
                 self.mcmc.after_step(iteration, position_optimizer.lr)       # the rate this iteration stepped with
@@ -455,6 +486,7 @@ class GaussianPointCloudTrainer:
         out of every mean: it has no weighted pixel to measure."""
         with torch.no_grad():
             total_loss = total_psnr_score = total_ssim_score = total_inference_time = 0.0
+            total_cc = dict(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
             count = 0
             for image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight in self._validation_targets():
                 if pixel_weight is not None and not bool((pixel_weight > 0).any()):
@@ -477,10 +509,25 @@ class GaussianPointCloudTrainer:
                 total_loss += loss.item()
                 total_psnr_score += psnr_score.item()
                 total_ssim_score += 1.0 - ssim_loss.item()
+                if self.appearance_table is not None:
+                    # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
+                    fitted = _appearance.fit_affine(image_pred, image_gt, pixel_weight)
+                    image_cc = torch.clamp(_appearance.apply_forward(image_pred, fitted), 0, 1)
+                    if pixel_weight is None:
+                        loss_cc, _, ssim_loss_cc = self.loss_function(image_cc, image_gt)
+                        psnr_cc = 10 * torch.log10(1.0 / torch.mean((image_cc - image_gt) ** 2))
+                    else:
+                        loss_cc, _, ssim_loss_cc = self.loss_function(image_cc, image_gt, pixel_weight=pixel_weight)
+                        psnr_cc = 10 * torch.log10(1.0 / self._weighted_mse(image_cc, image_gt, pixel_weight))
+                    total_cc["loss_cc"] += loss_cc.item()
+                    total_cc["psnr_cc"] += psnr_cc.item()
+                    total_cc["ssim_cc"] += 1.0 - ssim_loss_cc.item()
                 count += 1
             count = max(count, 1)
             means = dict(loss=total_loss / count, psnr=total_psnr_score / count, ssim=total_ssim_score / count,
                          inference_time=total_inference_time / count)
+            if self.appearance_table is not None:
+                means.update({name: value / count for name, value in total_cc.items()})
             for name, value in means.items():
                 self.writer.add_scalar(f"val/{name}", value, iteration)
             if self.config.print_metrics_to_console:
@@ -491,9 +538,13 @@ class GaussianPointCloudTrainer:
                 print(f"val_ssim_{iteration}={means['ssim']};")
                 print(f"val_inference_time={means['inference_time']};")
             self.scene.to_parquet(os.path.join(self.config.output_model_dir, f"scene_{iteration}.parquet"))
+            if self.appearance_table is not None:
+                self.appearance_table.save(os.path.join(self.config.output_model_dir, f"appearance_{iteration}.pt"), self.train_image_paths())
             if means["psnr"] > self.best_psnr_score:
                 self.best_psnr_score = means["psnr"]
                 self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
+                if self.appearance_table is not None:
+                    self.appearance_table.save(os.path.join(self.config.output_model_dir, "best_appearance.pt"), self.train_image_paths())
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
             self.last_validation = (iteration, means)

@@ -15,6 +15,7 @@
 #include "../../include/gs_frames.h"
 #include "../../include/gs_fusion.h"
 #include "../../include/gs_mcmc.h"
+#include "../../include/gs_appearance.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -154,6 +155,7 @@ struct gs_ctx {
     DevBuf first_hist;
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
+    DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
@@ -226,7 +228,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
-                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws };
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1985,6 +1987,70 @@ extern "C" int gs_mcmc_relocate(gs_ctx* c, const gs_density_scene* scene, float*
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     float* const moments[4] = { features_exp_avg, features_exp_avg_sq, point_cloud_exp_avg, point_cloud_exp_avg_sq };
     gs_launch_mcmc_relocate(*scene, moments, *cfg, *plan, seed, call_index, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- per-view exposure compensation (include/gs_appearance.h, k_appearance.hip) ---------------------------------------------
+static int appearance_check(const char* who, gs_ctx* c, const gs_loss_image* image, int32_t H, int32_t W)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
+    if (!image || !image->data) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL image");
+    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": H and W must be >= 1");
+    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many pixels");
+    return GS_OK;
+}
+
+extern "C" int gs_appearance_apply(gs_ctx* c, const gs_loss_image* image, const float* transform, int32_t H, int32_t W,
+                                   const gs_loss_image* corrected, gs_stream stream_)
+{
+    if (const int rc = appearance_check("gs_appearance_apply", c, image, H, W)) return rc;
+    if (!transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_apply: transform is NULL");
+    if (!corrected || !corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_apply: NULL corrected image");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_appearance_apply(loss_image(image, 0), transform, H, W, loss_image(corrected, 0), s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_appearance_backward(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* grad_corrected, const float* transform,
+                                      int32_t H, int32_t W, const gs_loss_image* grad_image, float* grad_transform, gs_stream stream_)
+{
+    if (const int rc = appearance_check("gs_appearance_backward", c, image, H, W)) return rc;
+    if (!grad_corrected || !grad_corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: NULL grad_corrected");
+    if (!transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: transform is NULL");
+    const bool want_image = grad_image && grad_image->data;
+    if (!want_image && !grad_transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: grad_image and grad_transform are both NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (grad_transform) {
+        HIP_TRY(hipSetDevice(c->device));       // the workspace grows before the stream enters: a call that fails here leaves it alone
+        if (c->appearance_ws.ensure(gs_appearance_ws_size(H, W), &c->device_bytes) != hipSuccess)
+            return fail(GS_ERR_OUT_OF_MEMORY, "gs_appearance_backward: workspace");
+    }
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    const GsLossImage none{ nullptr, 0, 0, 0, 0 };
+    gs_launch_appearance_backward(loss_image(image, 0), loss_image(grad_corrected, 0), transform, H, W,
+                                  want_image ? loss_image(grad_image, 0) : none, grad_transform, c->appearance_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* target, const float* pixel_weight,
+                                     int32_t H, int32_t W, double* moments, gs_stream stream_)
+{
+    if (const int rc = appearance_check("gs_appearance_moments", c, image, H, W)) return rc;
+    if (!target || !target->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_moments: NULL target");
+    if (!moments || ((uintptr_t)moments & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_moments: moments must be 8-byte aligned and not NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    if (c->appearance_ws.ensure(gs_appearance_ws_size(H, W), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_appearance_moments: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -633,6 +633,16 @@ void gs_launch_mcmc_relocate(const gs_density_scene& scene, float* const moments
 size_t gs_mcmc_scratch_size(int64_t N);
 size_t gs_mcmc_reg_ws_size(int64_t N);
 
+// k_appearance.hip (include/gs_appearance.h): the affine colour transform of an image.  The launchers trust what the entry
+// points checked.  ws: gs_appearance_ws_size(H, W) bytes of the context's, 8-byte aligned (the per-block sums).  GI.p NULL:
+// no image gradient; grad_transform NULL: no sums.
+size_t gs_appearance_ws_size(int H, int W);
+void gs_launch_appearance_apply(const GsLossImage& X, const float* M, int H, int W, const GsLossImage& C, hipStream_t s);
+void gs_launch_appearance_backward(const GsLossImage& X, const GsLossImage& G, const float* M, int H, int W, const GsLossImage& GI,
+                                   float* grad_transform, void* ws, hipStream_t s);
+void gs_launch_appearance_moments(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, double* moments, void* ws,
+                                  hipStream_t s);
+
 // k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
 // order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry
 // points checked: a non-empty volume, non-NULL arrays and work buffers, counts below 2^31.
