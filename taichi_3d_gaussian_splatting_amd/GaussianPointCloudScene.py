@@ -118,6 +118,22 @@ class GaussianPointCloudScene(torch.nn.Module):
     def to_ply(self, path: str):
         scene_io.save_inria_ply(path, *self._host_arrays())
 
+    def to_compressed(self, path: str, **kw):
+        """The valid rows behind an SH codebook, as one .npz (compression.compress(self, **kw).save(path)): about a seventh of
+        the parquet.  The k-means runs on the GPU; a module on the CPU is refused.  -> the compression.CompressedScene written"""
+        from . import compression
+        compressed = compression.compress(self, **kw)
+        compressed.save(path)
+        return compressed
+
+    @staticmethod
+    def from_compressed(path: str, config=None, device="cuda"):
+        """The scene a compressed file decodes to (compression.load(path).decode()), on `device`"""
+        from . import compression
+        config = config if config is not None else GaussianPointCloudScene.PointCloudSceneConfig()
+        point_cloud, features = compression.load(path).decode()
+        return GaussianPointCloudScene(point_cloud, config, point_cloud_features=features).to(device)
+
     @staticmethod
     def from_parquet(path: str, config=None, device="cuda"):
         """A file with feature columns loads as it is; a bare x,y,z[,r,g,b] cloud (with the sphere of config.add_sphere around

@@ -12,6 +12,7 @@ evaluates no basis function.  There is no fallback path: every bake goes through
 """
 import ctypes as C
 import functools
+import os
 from dataclasses import dataclass
 from typing import Dict, Sequence, Tuple
 
@@ -153,7 +154,7 @@ class SceneComposition:
     placement A_k = (q, t, scale) per object (object frame -> world frame; the identity at first) and one visibility flag.
 
     sources: GaussianPointCloudScene objects, (point_cloud, features[, point_invalid_mask]) tuples of arrays or tensors, or
-    paths of parquet files with trained features.
+    paths of parquet files with trained features or of compressed scenes (.npz, compression.py).
 
       scene                  the merged GaussianPointCloudScene (object frames, as loaded); its point_invalid_mask carries the
                              sources' masks and the hidden objects
@@ -201,7 +202,11 @@ class SceneComposition:
     def _load(self, source):
         if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
             from . import scene_io
-            source = scene_io.load_parquet(str(source))
+            if os.fsdecode(source).endswith(".npz"):        # a compressed scene (compression.py)
+                from . import compression
+                source = compression.load(os.fsdecode(source)).decode()
+            else:
+                source = scene_io.load_parquet(str(source))
         if isinstance(source, GaussianPointCloudScene):
             source = (source.point_cloud.detach(), source.point_cloud_features.detach(), source.point_invalid_mask)
         as_f32 = lambda a: torch.as_tensor(a).detach().to(device=self.device, dtype=torch.float32).contiguous()

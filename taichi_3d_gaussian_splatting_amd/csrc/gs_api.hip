@@ -16,6 +16,7 @@
 #include "../../include/gs_fusion.h"
 #include "../../include/gs_mcmc.h"
 #include "../../include/gs_appearance.h"
+#include "../../include/gs_vq.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -2051,6 +2052,57 @@ extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, cons
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- vector quantisation (include/gs_vq.h, k_vq.hip) --------------------------------------------------------------------------
+static int vq_check(const char* who, gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* codebook, int64_t ldc,
+                    int32_t K)
+{
+    const std::string w(who);
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
+    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, w + ": n_rows must be in [0, 2^31)");
+    if (dim < 1 || dim > GS_VQ_MAX_DIM) return fail(GS_ERR_INVALID_ARGUMENT, w + ": dim must be in [1, 64]");
+    if (K < 1 || K > GS_VQ_MAX_CODES) return fail(GS_ERR_INVALID_ARGUMENT, w + ": n_codes must be in [1, 65536]");
+    if (ldx < dim || (ldx & 3) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ldx must be a multiple of 4 and >= dim");
+    if (ldc < dim || (ldc & 3) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ldc must be a multiple of 4 and >= dim");
+    if ((((uintptr_t)x | (uintptr_t)codebook) & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": x and codebook must be 16-byte aligned");
+    return GS_OK;
+}
+
+extern "C" int64_t gs_vq_scratch_bytes(int64_t n_rows, int32_t n_codes, int32_t dim)
+{
+    if (n_rows < 0 || n_rows > INT32_MAX || n_codes < 1 || n_codes > GS_VQ_MAX_CODES || dim < 1 || dim > GS_VQ_MAX_DIM) return 0;
+    return (int64_t)gs_vq_scratch_size(n_rows, n_codes, dim);
+}
+
+extern "C" int gs_vq_assign(gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* codebook, int64_t ldc, int32_t K,
+                            int32_t* labels, float* dist, void* scratch, gs_stream stream_)
+{
+    if (const int rc = vq_check("gs_vq_assign", c, x, ldx, N, dim, codebook, ldc, K)) return rc;
+    if (N > 0 && (!x || !codebook || !labels || !scratch)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_assign: NULL array");
+    if (((uintptr_t)scratch & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_assign: scratch must be 8-byte aligned");
+    if (N == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_vq_assign(x, ldx, N, dim, codebook, ldc, K, labels, dist, scratch, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_vq_update(gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* weights, const int32_t* labels,
+                            float* codebook, int64_t ldc, int32_t K, int32_t* counts, double* weight_sums, void* scratch, gs_stream stream_)
+{
+    (void)scratch;
+    if (const int rc = vq_check("gs_vq_update", c, x, ldx, N, dim, codebook, ldc, K)) return rc;
+    if (!codebook || !counts || (N > 0 && (!x || !labels))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_update: NULL array");
+    if (((uintptr_t)weight_sums & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_update: weight_sums must be 8-byte aligned");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_vq_update(x, ldx, N, dim, weights, labels, codebook, ldc, K, counts, weight_sums, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

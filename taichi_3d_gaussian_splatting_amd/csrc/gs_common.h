@@ -633,6 +633,14 @@ void gs_launch_mcmc_relocate(const gs_density_scene& scene, float* const moments
 size_t gs_mcmc_scratch_size(int64_t N);
 size_t gs_mcmc_reg_ws_size(int64_t N);
 
+// k_vq.hip (include/gs_vq.h): nearest centroid per row and weighted mean per centroid.  The launchers trust what the entry
+// points checked.  scratch of the assignment: gs_vq_scratch_size() bytes of the caller's.
+void gs_launch_vq_assign(const float* x, int64_t ldx, int64_t N, int dim, const float* cb, int64_t ldc, int K, int32_t* labels, float* dist,
+                         void* scratch, hipStream_t s);
+void gs_launch_vq_update(const float* x, int64_t ldx, int64_t N, int dim, const float* weights, const int32_t* labels, float* cb, int64_t ldc,
+                         int K, int32_t* counts, double* weight_sums, hipStream_t s);
+size_t gs_vq_scratch_size(int64_t n_rows, int n_codes, int dim);
+
 // k_appearance.hip (include/gs_appearance.h): the affine colour transform of an image.  The launchers trust what the entry
 // points checked.  ws: gs_appearance_ws_size(H, W) bytes of the context's, 8-byte aligned (the per-block sums).  GI.p NULL:
 // no image gradient; grad_transform NULL: no sums.
