@@ -1,7 +1,9 @@
 """Train a scene from images: python gaussian_point_train.py --train_config PATH (the reference's script and YAML format).
 --pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training");
 --density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification");
---appearance affine trains a colour transform per training image with the scene (INTEGRATION.md "Exposure compensation")."""
+--appearance affine trains a colour transform per training image with the scene (INTEGRATION.md "Exposure compensation");
+--depth metric|relative [--depth_weight W --depth_space depth|inverse --depth_norm l1|l2] adds a depth term from the dataset's
+depth_path maps (INTEGRATION.md "Depth supervision in the trainer")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -19,7 +21,16 @@ if __name__ == "__main__":
                         "(default: every row the scene allocates, max_num_points_ratio)")
     parser.add_argument("--appearance", choices=("none", "affine"), default="none",
                         help="exposure compensation: a learnable 3x4 affine colour transform per training image")
+    parser.add_argument("--depth", choices=("none", "metric", "relative"), default="none",
+                        help="depth supervision from the dataset's depth_path maps: metres, or a monocular network's relative "
+                        "inverse depth aligned per view by scale and shift")
+    parser.add_argument("--depth_weight", type=float, default=None, help="with --depth: the term's weight at iteration 0 (it falls to "
+                        "a hundredth of it over the run)")
+    parser.add_argument("--depth_space", choices=("depth", "inverse"), default=None, help="with --depth: the space of the residual")
+    parser.add_argument("--depth_norm", choices=("l1", "l2"), default=None, help="with --depth: the norm of the residual")
     args = parser.parse_args()
+    if args.depth == "none" and (args.depth_weight is not None or args.depth_space is not None or args.depth_norm is not None):
+        parser.error("--depth_weight, --depth_space and --depth_norm need --depth metric or relative")
     if args.mcmc_cap is not None and args.density != "mcmc":
         parser.error("--mcmc_cap needs --density mcmc")
     if args.gen_template_only:
@@ -36,6 +47,16 @@ if __name__ == "__main__":
     if args.density == "mcmc":
         from taichi_3d_gaussian_splatting_amd.mcmc import MCMCConfig
         mcmc_config = MCMCConfig(cap_max=args.mcmc_cap, seed=int(config.seed))
+    depth_config = None
+    if args.depth != "none":
+        from taichi_3d_gaussian_splatting_amd.depth import DepthConfig
+        depth_config = DepthConfig()
+        if args.depth_weight is not None:
+            depth_config.weight_init, depth_config.weight_final = args.depth_weight, args.depth_weight / 100.0
+        if args.depth_space is not None:
+            depth_config.space = args.depth_space
+        if args.depth_norm is not None:
+            depth_config.norm = args.depth_norm
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
-                                        mcmc_config=mcmc_config, appearance=args.appearance)
+                                        mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config)
     trainer.train()

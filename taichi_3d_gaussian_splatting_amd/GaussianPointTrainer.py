@@ -22,12 +22,18 @@ What differs from the reference
     balance differ between views.  The transform is applied to the rendered image in front of the loss; validation views have
     none and are rendered uncorrected, and additionally measured after the best affine fit to their ground truth (val/psnr_cc,
     val/ssim_cc, val/loss_cc).  "none", the default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, depth="metric" | "relative", depth_config=DepthConfig(...)) adds a depth term to the loss
+    (depth.py): the dataset's depth_path maps -- metres for "metric", a monocular network's relative inverse depth for
+    "relative", aligned per view by a closed-form scale and shift -- resident on the device, one launch per step for the
+    target and its validity weight, and the fused masked depth loss on the rasteriser's depth output.  "none", the default, is
+    the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
     for the device only at the logging intervals.  The FTGMM scene grab (TRAIN:188-189) and the Taichi kernel profiler are
     left out.
 """
+import copy
 import dataclasses
 import json
 import os
@@ -44,6 +50,8 @@ from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .GaussianPointCloudScene import GaussianPointCloudScene
 from . import appearance as _appearance
 from .appearance import AppearanceConfig, AppearanceTable
+from . import depth as _depth
+from .depth import DepthConfig, DepthStore
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
 from .mcmc import MCMCConfig, MCMCStrategy
@@ -209,7 +217,7 @@ class GaussianPointCloudTrainer:
 
     def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
                  density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
-                 appearance_config: Optional[AppearanceConfig] = None):
+                 appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -217,8 +225,32 @@ class GaussianPointCloudTrainer:
         pixel); how the scene grows and shrinks -- "adaptive" (the reference's controller) or "mcmc" (mcmc.MCMCStrategy: a fixed
         budget of Gaussians, mcmc_config.cap_max) -- and the MCMCConfig of the latter (None: the defaults, seeded by config.seed);
         whether every training image gets a learnable colour transform -- "none" or "affine" (appearance.AppearanceTable, in
-        self.appearance_table) -- and its AppearanceConfig (None: the defaults, over config.num_iterations)"""
+        self.appearance_table) -- and its AppearanceConfig (None: the defaults, over config.num_iterations); whether the
+        dataset's depth maps supervise the rendered depth -- "none", "metric" (metres) or "relative" (relative inverse depth,
+        aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations)"""
         self.config = config
+        if depth not in ("none", "metric", "relative"):
+            raise ValueError(f'depth must be "none", "metric" or "relative", got {depth!r}')
+        if depth == "none" and depth_config is not None:
+            raise ValueError('depth_config needs depth="metric" or "relative"')
+        self.depth = depth
+        self.depth_config = None
+        self.train_depth = self.val_depth = None
+        self.depth_flags = 0
+        if depth != "none":
+            depth_config = depth_config or DepthConfig()
+            depth_config.check()
+            if depth == "relative" and depth_config.space != "inverse":
+                raise ValueError('depth="relative" needs depth_config.space="inverse": the files hold relative inverse depth')
+            if not self.config.targets_on_device:
+                raise ValueError(f'depth="{depth}" needs targets_on_device=True: depth targets are made on the device')
+            if self.config.rasterisation_config.rgb_only:
+                raise ValueError(f'depth="{depth}" cannot be combined with rasterisation_config.rgb_only=True: no depth is rendered')
+            if depth_config.num_iterations is None:
+                depth_config = dataclasses.replace(depth_config, num_iterations=max(int(self.config.num_iterations), 1))
+            self.depth_config = depth_config
+            self.depth_flags = _depth.loss_flags(depth_config.space, depth_config.norm, align=depth == "relative",
+                                                 target_is_inverse=depth == "relative")
         if appearance not in ("none", "affine"):
             raise ValueError(f'appearance must be "none" or "affine", got {appearance!r}')
         if appearance == "none" and appearance_config is not None:
@@ -292,6 +324,16 @@ class GaussianPointCloudTrainer:
             if appearance_config.num_iterations is None:
                 appearance_config = dataclasses.replace(appearance_config, num_iterations=max(int(self.config.num_iterations), 1))
             self.appearance_table = AppearanceTable(len(self.train_dataset), self.device, appearance_config)
+        if self.depth != "none":
+            # the depth term's gradient reaches the scene: set on the trainer's own rasteriser, not on the caller's config object
+            self.rasterisation.config = copy.copy(self.rasterisation.config)
+            self.rasterisation.config.differentiable_depth = True
+            try:
+                self.train_depth = DepthStore.from_dataset(self.train_dataset, self.device, depth_scale=self.depth_config.depth_scale)
+            except ValueError as e:
+                raise ValueError(f'depth="{self.depth}": every training record needs a depth_path ({e})') from e
+            self.val_depth = DepthStore.from_dataset(self.val_dataset, self.device, depth_scale=self.depth_config.depth_scale,
+                                                     require_all=False)
         # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
         self._order_generator = torch.Generator().manual_seed(int(self.config.seed))
         self.view_order: List[int] = []
@@ -411,7 +453,11 @@ class GaussianPointCloudTrainer:
                 pointcloud_features=self.scene.point_cloud_features,
                 clamp_predicted=True,
                 pixel_weight=pixel_weight)          # None: the unweighted loss
-            loss.backward()
+            if self.train_depth is not None:
+                depth_loss = self._depth_loss(self.train_depth, view, downsample_factor, image_depth, pixel_weight)
+                (loss + self.depth_config.weight_at(iteration) * depth_loss).backward()
+            else:
+                loss.backward()
             if self.mcmc is not None:
                 self.mcmc.before_step(iteration)
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
@@ -434,6 +480,12 @@ class GaussianPointCloudTrainer:
                 self.writer.add_scalar("train/loss", loss_value, iteration)
                 self.writer.add_scalar("train/l1 loss", l1_loss.item(), iteration)
                 self.writer.add_scalar("train/ssim loss", ssim_loss.item(), iteration)
+                if self.train_depth is not None:
+                    terms = depth_loss.terms.tolist()       # {L, S_w, s, t, ...}: one read
+                    self.writer.add_scalar("train/depth loss", terms[0], iteration)
+                    if self.depth == "relative":
+                        self.writer.add_scalar("train/depth scale", terms[2], iteration)
+                        self.writer.add_scalar("train/depth shift", terms[3], iteration)
                 if config.print_metrics_to_console:
                     print(f"train_iteration={iteration};")
                     print(f"train_loss={loss_value};")
@@ -453,11 +505,19 @@ class GaussianPointCloudTrainer:
                         print(f"train_ssim_{iteration}={ssim_score.item()};")
             del image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, rasterisation_input, image_pred, loss, l1_loss, ssim_loss
             del pixel_weight
+            if self.train_depth is not None:
+                del depth_loss, image_depth
             # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
             if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
                 self.validation(iteration)
         if hasattr(self.writer, "flush"):
             self.writer.flush()
+
+    def _depth_loss(self, store, view: int, downsample_factor: int, image_depth, pixel_weight):
+        """the depth term of one view: the store's target and weight at the factor (one launch) and the fused loss on the
+        rendered depth; its .terms holds the fitted scale and shift"""
+        target, target_weight = store.target(view, downsample_factor, self.depth_config.min_coverage)
+        return _depth.depth_loss_flags(image_depth, target, target_weight, pixel_weight, self.depth_flags)
 
     @staticmethod
     def _weighted_mse(image_pred, image_gt, pixel_weight):
@@ -488,7 +548,8 @@ class GaussianPointCloudTrainer:
             total_loss = total_psnr_score = total_ssim_score = total_inference_time = 0.0
             total_cc = dict(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
             count = 0
-            for image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight in self._validation_targets():
+            total_depth_loss, depth_count = 0.0, 0
+            for val_view, (image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight) in enumerate(self._validation_targets()):
                 if pixel_weight is not None and not bool((pixel_weight > 0).any()):
                     continue
                 start_event = torch.cuda.Event(enable_timing=True)
@@ -509,6 +570,10 @@ class GaussianPointCloudTrainer:
                 total_loss += loss.item()
                 total_psnr_score += psnr_score.item()
                 total_ssim_score += 1.0 - ssim_loss.item()
+                if self.val_depth is not None and self.val_depth.has(val_view):
+                    # (for "relative" the aligned loss: the fit is part of the forward)
+                    total_depth_loss += self._depth_loss(self.val_depth, val_view, 1, image_depth, pixel_weight).item()
+                    depth_count += 1
                 if self.appearance_table is not None:
                     # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
                     fitted = _appearance.fit_affine(image_pred, image_gt, pixel_weight)
@@ -528,6 +593,8 @@ class GaussianPointCloudTrainer:
                          inference_time=total_inference_time / count)
             if self.appearance_table is not None:
                 means.update({name: value / count for name, value in total_cc.items()})
+            if depth_count:
+                means["depth_loss"] = total_depth_loss / depth_count
             for name, value in means.items():
                 self.writer.add_scalar(f"val/{name}", value, iteration)
             if self.config.print_metrics_to_console:

@@ -84,6 +84,46 @@ class ImagePoseDataset(torch.utils.data.Dataset):
         with PIL.Image.open(path) as pil:
             return np.array(pil if pil.mode == "L" else pil.convert("L"), dtype=np.uint8)
 
+    def load_depth(self, idx):
+        """-> (depth map, depth_scale) of record idx, or None when the dataset has no depth_path column or the record's entry is
+        empty.  depth_path names a 16-bit single-channel PNG (-> a uint16 (H,W) array, 0 = no measurement) or a .npy of float32
+        metres (-> a float32 (H,W) array; anything not finite and > 0 = no measurement).  depth_scale: the record's depth_scale
+        column, metres per unit of the 16-bit file, or None (the caller's default applies).  The map must have the decoded
+        picture's size, and the picture must be within MAX_RESOLUTION_TRAIN: there is no autoscale path for depth."""
+        if "depth_path" not in self.df.columns:
+            return None
+        row = self.df.iloc[idx]
+        path = row["depth_path"]
+        if not isinstance(path, str) or not path:
+            return None
+        import PIL.Image
+        with PIL.Image.open(row["image_path"]) as pil:
+            width, height = pil.size                            # the header only: nothing is decoded
+        if height > MAX_RESOLUTION_TRAIN or width > MAX_RESOLUTION_TRAIN:
+            raise ValueError(f"{path}: depth for a picture over {MAX_RESOLUTION_TRAIN} pixels ({width}x{height}) is not supported "
+                             "(there is no autoscale path for depth)")
+        if path.lower().endswith(".npy"):
+            depth = np.load(path)
+            if depth.ndim != 2 or depth.dtype.kind != "f":
+                raise ValueError(f"{path}: a .npy depth map must be a 2-D float array, got {depth.dtype} {depth.shape}")
+            depth = depth.astype(np.float32, copy=False)
+        else:
+            with PIL.Image.open(path) as pil:
+                if pil.mode not in ("I;16", "I;16L", "I;16B", "I"):
+                    raise ValueError(f"{path}: a depth image must be a 16-bit single-channel PNG, got mode {pil.mode}")
+                depth = np.array(pil)
+            if depth.ndim != 2 or depth.min() < 0 or depth.max() > 65535:
+                raise ValueError(f"{path}: a depth image must hold 16-bit values")
+            depth = depth.astype(np.uint16)
+        if depth.shape != (height, width):
+            raise ValueError(f"{path}: the depth map is {depth.shape[1]}x{depth.shape[0]}, the picture {width}x{height}")
+        scale = None
+        if "depth_scale" in self.df.columns:
+            value = row["depth_scale"]
+            if value is not None and not (isinstance(value, float) and np.isnan(value)):
+                scale = float(value)
+        return depth, scale
+
     def __getitem__(self, idx):
         image, q, t, info = self.load_raw(idx)
         image = image.permute(2, 0, 1).to(torch.float32).div(255)               # torchvision's to_tensor

@@ -17,6 +17,7 @@
 #include "../../include/gs_mcmc.h"
 #include "../../include/gs_appearance.h"
 #include "../../include/gs_vq.h"
+#include "../../include/gs_depth.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -157,6 +158,7 @@ struct gs_ctx {
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
     DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
+    DevBuf depth_ws;                    // gs_depth_loss_forward: its finished moments and per-block sums, read by nothing else
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
@@ -229,7 +231,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
-                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws };
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->depth_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2052,6 +2054,77 @@ extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, cons
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- depth supervision (include/gs_depth.h, k_depth.hip) ------------------------------------------------------------------------
+extern "C" int gs_depth_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t H_in, int32_t W_in, int64_t src_row_pitch_bytes,
+                                 float depth_scale, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float min_coverage,
+                                 float* dst, gs_stream stream_)
+{
+    const std::string who("gs_depth_resample");
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (src_format != GS_DEPTH_U16 && src_format != GS_DEPTH_F32) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown src_format");
+    if (!(min_coverage >= 0.0f && min_coverage <= 1.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": min_coverage must be in [0, 1]");
+    if (!(depth_scale > 0.0f && std::isfinite(depth_scale))) return fail(GS_ERR_INVALID_ARGUMENT, who + ": depth_scale must be finite and > 0");
+    for (int32_t v : { H_in, W_in, h_full, w_full, h_out, w_out })
+        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, who + ": every size must be in [0, 32768]");
+    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, who + ": the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
+    if (src_format == GS_DEPTH_U16 ? src_row_pitch_bytes < (int64_t)W_in * 2 : src_row_pitch_bytes != (int64_t)W_in * 4)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": src_row_pitch_bytes must be >= W_in * 2 (uint16), W_in * 4 (f32)");
+    if (h_out == 0 || w_out == 0) return GS_OK;
+    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL src or dst");
+    if (H_in < h_full || W_in < w_full || (int64_t)H_in > (int64_t)GS_RESAMPLE_MAX_SCALE * h_full || (int64_t)W_in > (int64_t)GS_RESAMPLE_MAX_SCALE * w_full)
+        return fail(GS_ERR_INVALID_ARGUMENT, who + ": the scale in / out must be in [1, 8] on both axes (no upscaling)");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    int rc;
+    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
+    ResampleTable* rt = nullptr;
+    if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
+    gs_launch_depth_resample(src, src_format, H_in, W_in, src_row_pitch_bytes, depth_scale, rt->ax, rt->ay, h_out, w_out, min_coverage, dst, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+static int depth_loss_check(const char* who_, gs_ctx* c, const float* D, const float* Z, const float* w_t, int32_t H, int32_t W, int32_t flags,
+                            const float* terms)
+{
+    const std::string who(who_);
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (!D || !Z || !w_t) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL plane (D, Z or w_t)");
+    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": loss_terms is NULL");
+    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": H and W must be >= 1");
+    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
+    if ((flags & ~GS_DEPTH_FLAGS_ALL) != 0) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown flag bits");
+    return GS_OK;
+}
+
+extern "C" int gs_depth_loss_forward(gs_ctx* c, const float* D, const float* Z, const float* w_t, const float* w_p, int32_t H, int32_t W,
+                                     int32_t flags, float* loss_terms, gs_stream stream_)
+{
+    if (const int rc = depth_loss_check("gs_depth_loss_forward", c, D, Z, w_t, H, W, flags, loss_terms)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    if (c->depth_ws.ensure(gs_depth_ws_size(H, W), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_depth_loss_forward: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_depth_loss_forward(D, Z, w_t, w_p, H, W, flags, loss_terms, c->depth_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_depth_loss_backward(gs_ctx* c, const float* D, const float* Z, const float* w_t, const float* w_p, int32_t H, int32_t W,
+                                      int32_t flags, const float* loss_terms, const float* upstream, float* grad_D, gs_stream stream_)
+{
+    if (const int rc = depth_loss_check("gs_depth_loss_backward", c, D, Z, w_t, H, W, flags, loss_terms)) return rc;
+    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_depth_loss_backward: grad_D is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_depth_loss_backward(D, Z, w_t, w_p, H, W, flags, loss_terms, upstream, grad_D, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -650,6 +650,15 @@ void gs_launch_appearance_backward(const GsLossImage& X, const GsLossImage& G, c
                                    float* grad_transform, void* ws, hipStream_t s);
 void gs_launch_appearance_moments(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, double* moments, void* ws,
                                   hipStream_t s);
+// k_depth.hip (include/gs_depth.h): the depth target with its weight plane, and the depth loss.  The launchers trust what the
+// entry points checked.  ws: gs_depth_ws_size(H, W) bytes of the context's, 8-byte aligned (finished moments, per-block sums).
+void gs_launch_depth_resample(const void* src, int src_format, int H_in, int W_in, int64_t pitch_bytes, float depth_scale, GsResampleAxis ax,
+                              GsResampleAxis ay, int h_out, int w_out, float min_coverage, float* dst, hipStream_t s);
+size_t gs_depth_ws_size(int H, int W);
+void gs_launch_depth_loss_forward(const float* D, const float* Z, const float* wt, const float* wp, int H, int W, int flags, float* terms, void* ws,
+                                  hipStream_t s);
+void gs_launch_depth_loss_backward(const float* D, const float* Z, const float* wt, const float* wp, int H, int W, int flags, const float* terms,
+                                   const float* upstream, float* G, hipStream_t s);
 
 // k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
 // order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry
