@@ -17,7 +17,10 @@ box's longest side / 255) and --mesh_trunc the truncation distance (default: 4 v
 optional: without it only the mesh is written.  --appearance FILE (an appearance_<iteration>.pt of a trainer run with --appearance
 affine) with a dataset JSON as --poses: a frame whose image_path is in the file is corrected by its trained colour transform
 before it is written and measured, every other frame is rendered as without the flag, and metrics.json gains psnr_cc per view
-(the PSNR after the best affine fit of the rendering to its ground truth).
+(the PSNR after the best affine fit of the rendering to its ground truth).  --normals_to DIR writes, per pose, the normal map
+derived from the rendered depth (geometry.depth_normals) as an 8-bit PNG (n + 1) / 2, (0,0,0) where there is none:
+DIR/normal_<i:03>.png, in the camera frame of the rasteriser (x right, y down, z forward); --normals_max_rel_jump J (default 0.1)
+leaves out the normals across a depth change of more than J times the depth.  With --normals_to, --output_prefix is optional.
 """
 import argparse
 import json
@@ -52,10 +55,12 @@ if __name__ == "__main__":
     parser.add_argument("--mesh_bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                         help="the volume's box (default: mixture.bounding_box of the scene)")
     parser.add_argument("--appearance", type=str, default="", help="an appearance_<iteration>.pt of the trainer: per-view colour transforms")
+    parser.add_argument("--normals_to", type=str, default="", help="write the depth-derived normal map of every pose into this directory")
+    parser.add_argument("--normals_max_rel_jump", type=float, default=0.1, help="no normal across a depth change above this share of the depth")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
-    if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to)):
-        parser.error("--poses and --output_prefix (or --mesh_to) are required unless --bake_to is given")
+    if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to or args.normals_to)):
+        parser.error("--poses and --output_prefix (or --mesh_to, or --normals_to) are required unless --bake_to is given")
     if args.mesh_to and not (args.poses or "").endswith(".pt"):
         parser.error("--mesh_to fuses the poses of a .pt file")
 
@@ -104,6 +109,12 @@ if __name__ == "__main__":
         mesh.to_ply(args.mesh_to)
         print(json.dumps({"mesh": args.mesh_to, "vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
                           "dims": list(volume.dims), "voxel": volume.voxel, "trunc": volume.trunc}))
+        if not args.output_prefix and not args.normals_to:
+            raise SystemExit(0)
+
+    if args.normals_to:
+        count = renderer.write_normals(args.normals_to, targets=targets, max_rel_jump=args.normals_max_rel_jump)
+        print(json.dumps({"normals": args.normals_to, "frames": count}))
         if not args.output_prefix:
             raise SystemExit(0)
 

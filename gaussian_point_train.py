@@ -3,7 +3,10 @@
 --density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification");
 --appearance affine trains a colour transform per training image with the scene (INTEGRATION.md "Exposure compensation");
 --depth metric|relative [--depth_weight W --depth_space depth|inverse --depth_norm l1|l2] adds a depth term from the dataset's
-depth_path maps (INTEGRATION.md "Depth supervision in the trainer")."""
+depth_path maps (INTEGRATION.md "Depth supervision in the trainer");
+--depth_smooth W [--smooth_order 1|2 --smooth_space depth|inverse --smooth_edge_lambda L] adds an edge-aware smoothness of the
+rendered depth, and --normal_prior W [--normal_convention opencv|opengl] a normal loss against the dataset's normal_path priors
+(INTEGRATION.md "Geometry regularisers")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -28,7 +31,18 @@ if __name__ == "__main__":
                         "a hundredth of it over the run)")
     parser.add_argument("--depth_space", choices=("depth", "inverse"), default=None, help="with --depth: the space of the residual")
     parser.add_argument("--depth_norm", choices=("l1", "l2"), default=None, help="with --depth: the norm of the residual")
+    parser.add_argument("--depth_smooth", type=float, default=None, metavar="W", help="weight of the edge-aware smoothness of the rendered depth")
+    parser.add_argument("--smooth_order", type=int, choices=(1, 2), default=None, help="with --depth_smooth: first or second differences")
+    parser.add_argument("--smooth_space", choices=("depth", "inverse"), default=None, help="with --depth_smooth: the space of the differences")
+    parser.add_argument("--smooth_edge_lambda", type=float, default=None, help="with --depth_smooth: how fast an edge of the picture relaxes it")
+    parser.add_argument("--normal_prior", type=float, default=None, metavar="W", help="weight of the normal loss against the dataset's "
+                        "normal_path priors")
+    parser.add_argument("--normal_convention", choices=("opencv", "opengl"), default=None, help="with --normal_prior: the priors' camera frame")
     args = parser.parse_args()
+    if args.depth_smooth is None and (args.smooth_order is not None or args.smooth_space is not None or args.smooth_edge_lambda is not None):
+        parser.error("--smooth_order, --smooth_space and --smooth_edge_lambda need --depth_smooth")
+    if args.normal_prior is None and args.normal_convention is not None:
+        parser.error("--normal_convention needs --normal_prior")
     if args.depth == "none" and (args.depth_weight is not None or args.depth_space is not None or args.depth_norm is not None):
         parser.error("--depth_weight, --depth_space and --depth_norm need --depth metric or relative")
     if args.mcmc_cap is not None and args.density != "mcmc":
@@ -57,6 +71,13 @@ if __name__ == "__main__":
             depth_config.space = args.depth_space
         if args.depth_norm is not None:
             depth_config.norm = args.depth_norm
+    geometry_config = None
+    if args.depth_smooth is not None or args.normal_prior is not None:
+        from taichi_3d_gaussian_splatting_amd.geometry import GeometryConfig
+        chosen = dict(smooth_weight=args.depth_smooth, smooth_order=args.smooth_order, smooth_space=args.smooth_space,
+                      smooth_edge_lambda=args.smooth_edge_lambda, normal_weight=args.normal_prior, normal_convention=args.normal_convention)
+        geometry_config = GeometryConfig(**{name: value for name, value in chosen.items() if value is not None})
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
-                                        mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config)
+                                        mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,
+                                        geometry=geometry_config)
     trainer.train()

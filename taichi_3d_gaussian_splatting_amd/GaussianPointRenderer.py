@@ -131,6 +131,31 @@ class GaussianPointRenderer:
                              alpha=[r[2] for r in rendered], image=[r[0] for r in rendered])
         return volume
 
+    def write_normals(self, directory, targets=None, max_rel_jump: float = 0.1):
+        """Render every camera of the config (or every view of `targets`, a targets.TargetStore, under its own pose and camera)
+        with depth and write the depth-derived camera-space normal map (geometry.depth_normals: x right, y down, z forward)
+        to <directory>/normal_<i:03>.png as the 8-bit RGB image (n + 1) / 2, (0,0,0) where there is no normal -- the encoding
+        ImagePoseDataset.load_normal reads.  The intrinsics are read by the host once per camera.  -> the number of files"""
+        import PIL.Image
+        from . import geometry
+        os.makedirs(str(directory), exist_ok=True)
+        if targets is None:
+            q_rows, t_rows = self.pose_rows()
+            infos = [self.camera_info] * q_rows.shape[0]
+        else:
+            K = len(self.composition)
+            q_rows, t_rows = self.composition.camera_rows(targets.q, targets.t)
+            q_rows, t_rows = q_rows.reshape(len(targets), K, 4), t_rows.reshape(len(targets), K, 3)
+            infos = [targets.target(i, 1)[3] for i in range(len(targets))]
+        intrinsics = {}
+        for i, info in enumerate(infos):
+            if id(info.camera_intrinsics) not in intrinsics:
+                intrinsics[id(info.camera_intrinsics)] = geometry.intrinsics_tuple(info.camera_intrinsics)
+            _, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=True)
+            normals = geometry.depth_normals(image_depth.contiguous(), intrinsics[id(info.camera_intrinsics)], max_rel_jump)
+            PIL.Image.fromarray(geometry.normals_to_uint8(normals).cpu().numpy()).save(os.path.join(str(directory), f"normal_{i:03d}.png"))
+        return len(infos)
+
     def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None, appearance=None, image_paths=None):
         """Render every camera of the config to <output_prefix>/frame_<i:03>.<format> (and depth_<i:03> with depth=True).
         output_prefix None: the frames still cross to the host, nothing is written.

@@ -27,6 +27,10 @@ What differs from the reference
     "relative", aligned per view by a closed-form scale and shift -- resident on the device, one launch per step for the
     target and its validity weight, and the fused masked depth loss on the rasteriser's depth output.  "none", the default, is
     the loop as it was.
+  - GaussianPointCloudTrainer(config, geometry=GeometryConfig(smooth_weight=..., normal_weight=...)) adds geometry regularisers
+    on the rendered depth (geometry.py): an edge-aware smoothness with the colour target as its guide -- it needs no extra data
+    -- and a cosine loss of the depth-derived normal against the dataset's normal_path priors, resident on the device.  None,
+    the default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -52,6 +56,8 @@ from . import appearance as _appearance
 from .appearance import AppearanceConfig, AppearanceTable
 from . import depth as _depth
 from .depth import DepthConfig, DepthStore
+from . import geometry as _geometry
+from .geometry import GeometryConfig, NormalStore
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
 from .mcmc import MCMCConfig, MCMCStrategy
@@ -217,7 +223,8 @@ class GaussianPointCloudTrainer:
 
     def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
                  density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
-                 appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None):
+                 appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None,
+                 geometry: Optional[GeometryConfig] = None):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -227,8 +234,22 @@ class GaussianPointCloudTrainer:
         whether every training image gets a learnable colour transform -- "none" or "affine" (appearance.AppearanceTable, in
         self.appearance_table) -- and its AppearanceConfig (None: the defaults, over config.num_iterations); whether the
         dataset's depth maps supervise the rendered depth -- "none", "metric" (metres) or "relative" (relative inverse depth,
-        aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations)"""
+        aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations); geometry:
+        the GeometryConfig of the regularisers on the rendered depth (None: none)"""
         self.config = config
+        self.geometry = None
+        self.train_normals = self.val_normals = None
+        if geometry is not None:
+            if not isinstance(geometry, GeometryConfig):
+                raise ValueError(f"geometry must be a GeometryConfig or None, got {type(geometry).__name__}")
+            geometry.check()
+            if not self.config.targets_on_device:
+                raise ValueError("geometry needs targets_on_device=True: its guide and priors are made on the device")
+            if self.config.rasterisation_config.rgb_only:
+                raise ValueError("geometry cannot be combined with rasterisation_config.rgb_only=True: no depth is rendered")
+            self.geometry = dataclasses.replace(geometry)
+            self._smooth_flags = _geometry.smooth_flags(geometry.smooth_space, geometry.smooth_order)
+            self._intrinsics = {}                   # (split, view, factor) -> (fx, fy, cx, cy), read by the host once
         if depth not in ("none", "metric", "relative"):
             raise ValueError(f'depth must be "none", "metric" or "relative", got {depth!r}')
         if depth == "none" and depth_config is not None:
@@ -334,6 +355,15 @@ class GaussianPointCloudTrainer:
                 raise ValueError(f'depth="{self.depth}": every training record needs a depth_path ({e})') from e
             self.val_depth = DepthStore.from_dataset(self.val_dataset, self.device, depth_scale=self.depth_config.depth_scale,
                                                      require_all=False)
+        if self.geometry is not None:
+            self.rasterisation.config = copy.copy(self.rasterisation.config)       # (a copy of a copy when depth= set it too)
+            self.rasterisation.config.differentiable_depth = True
+            if self.geometry.normal_weight > 0.0:
+                try:
+                    self.train_normals = NormalStore.from_dataset(self.train_dataset, self.device)
+                except ValueError as e:
+                    raise ValueError(f"geometry.normal_weight > 0: every training record needs a normal_path ({e})") from e
+                self.val_normals = NormalStore.from_dataset(self.val_dataset, self.device, require_all=False)
         # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
         self._order_generator = torch.Generator().manual_seed(int(self.config.seed))
         self.view_order: List[int] = []
@@ -453,9 +483,18 @@ class GaussianPointCloudTrainer:
                 pointcloud_features=self.scene.point_cloud_features,
                 clamp_predicted=True,
                 pixel_weight=pixel_weight)          # None: the unweighted loss
+            geometry_terms = None
+            if self.geometry is not None and iteration >= self.geometry.start_iteration:
+                geometry_terms = self._geometry_losses("train", self.train_targets, self.train_normals, view, downsample_factor,
+                                                       image_depth, image_gt, pixel_weight)
             if self.train_depth is not None:
                 depth_loss = self._depth_loss(self.train_depth, view, downsample_factor, image_depth, pixel_weight)
-                (loss + self.depth_config.weight_at(iteration) * depth_loss).backward()
+                total = loss + self.depth_config.weight_at(iteration) * depth_loss
+                if geometry_terms is not None:
+                    total = self._add_geometry(total, geometry_terms)
+                total.backward()
+            elif geometry_terms is not None:
+                self._add_geometry(loss, geometry_terms).backward()
             else:
                 loss.backward()
             if self.mcmc is not None:
@@ -486,6 +525,10 @@ class GaussianPointCloudTrainer:
                     if self.depth == "relative":
                         self.writer.add_scalar("train/depth scale", terms[2], iteration)
                         self.writer.add_scalar("train/depth shift", terms[3], iteration)
+                if geometry_terms is not None:
+                    for name, term in zip(("smooth", "normal"), geometry_terms):
+                        if term is not None:
+                            self.writer.add_scalar(f"train/{name} loss", term.terms.tolist()[0], iteration)       # one read per term
                 if config.print_metrics_to_console:
                     print(f"train_iteration={iteration};")
                     print(f"train_loss={loss_value};")
@@ -507,6 +550,8 @@ class GaussianPointCloudTrainer:
             del pixel_weight
             if self.train_depth is not None:
                 del depth_loss, image_depth
+            if self.geometry is not None:
+                del geometry_terms
             # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
             if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
                 self.validation(iteration)
@@ -518,6 +563,32 @@ class GaussianPointCloudTrainer:
         rendered depth; its .terms holds the fitted scale and shift"""
         target, target_weight = store.target(view, downsample_factor, self.depth_config.min_coverage)
         return _depth.depth_loss_flags(image_depth, target, target_weight, pixel_weight, self.depth_flags)
+
+    def _geometry_losses(self, split, targets, normals, view: int, downsample_factor: int, image_depth, image_gt, pixel_weight):
+        """-> (smoothness or None, normal loss or None) of one view: the smoothness of the rendered depth with the colour target
+        as its guide, and the cosine loss against the view's normal prior at the factor (one launch for the prior)"""
+        g = self.geometry
+        smooth = normal = None
+        if g.smooth_weight > 0.0:
+            smooth = _geometry.depth_smoothness_flags(image_depth, image_gt, pixel_weight, g.smooth_edge_lambda, self._smooth_flags)
+        if g.normal_weight > 0.0 and normals is not None and normals.has(view):
+            key = (split, view, downsample_factor)
+            intrinsics = self._intrinsics.get(key)
+            if intrinsics is None:
+                info = targets.target(view, downsample_factor)[3]
+                intrinsics = self._intrinsics[key] = _geometry.intrinsics_tuple(info.camera_intrinsics)
+            prior, prior_weight = normals.target(view, downsample_factor)
+            normal = _geometry.normal_loss_flags(image_depth, intrinsics, prior, prior_weight, pixel_weight, g.normal_max_rel_jump,
+                                                 _geometry.normal_flags(normals.unit_range(view), g.normal_convention))
+        return smooth, normal
+
+    def _add_geometry(self, loss, geometry_terms):
+        smooth, normal = geometry_terms
+        if smooth is not None:
+            loss = loss + self.geometry.smooth_weight * smooth
+        if normal is not None:
+            loss = loss + self.geometry.normal_weight * normal
+        return loss
 
     @staticmethod
     def _weighted_mse(image_pred, image_gt, pixel_weight):
@@ -549,6 +620,7 @@ class GaussianPointCloudTrainer:
             total_cc = dict(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
             count = 0
             total_depth_loss, depth_count = 0.0, 0
+            total_geometry, geometry_count = dict(smooth_loss=0.0, normal_loss=0.0), dict(smooth_loss=0, normal_loss=0)
             for val_view, (image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight) in enumerate(self._validation_targets()):
                 if pixel_weight is not None and not bool((pixel_weight > 0).any()):
                     continue
@@ -574,6 +646,12 @@ class GaussianPointCloudTrainer:
                     # (for "relative" the aligned loss: the fit is part of the forward)
                     total_depth_loss += self._depth_loss(self.val_depth, val_view, 1, image_depth, pixel_weight).item()
                     depth_count += 1
+                if self.geometry is not None:
+                    terms = self._geometry_losses("val", self.val_targets, self.val_normals, val_view, 1, image_depth, image_gt, pixel_weight)
+                    for name, term in zip(("smooth_loss", "normal_loss"), terms):
+                        if term is not None:
+                            total_geometry[name] += term.item()
+                            geometry_count[name] += 1
                 if self.appearance_table is not None:
                     # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
                     fitted = _appearance.fit_affine(image_pred, image_gt, pixel_weight)
@@ -595,6 +673,9 @@ class GaussianPointCloudTrainer:
                 means.update({name: value / count for name, value in total_cc.items()})
             if depth_count:
                 means["depth_loss"] = total_depth_loss / depth_count
+            for name, n_views in geometry_count.items():
+                if n_views:
+                    means[name] = total_geometry[name] / n_views
             for name, value in means.items():
                 self.writer.add_scalar(f"val/{name}", value, iteration)
             if self.config.print_metrics_to_console:

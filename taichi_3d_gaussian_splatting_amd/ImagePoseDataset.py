@@ -124,6 +124,38 @@ class ImagePoseDataset(torch.utils.data.Dataset):
                 scale = float(value)
         return depth, scale
 
+    def load_normal(self, idx):
+        """-> the normal prior of record idx, or None when the dataset has no normal_path column or the record's entry is
+        empty.  normal_path names an 8-bit RGB image that holds (n + 1) / 2 (-> a uint8 (H,W,3) array; (0,0,0) = no prior) or
+        a .npy of float32 (H,W,3) normals (-> a float32 (H,W,3) array; all zero or not finite = no prior).  Which camera frame the
+        normals are in is the caller's to say (geometry.normal_flags).  The map must have the decoded picture's size, and the
+        picture must be within MAX_RESOLUTION_TRAIN: there is no autoscale path for normals."""
+        if "normal_path" not in self.df.columns:
+            return None
+        row = self.df.iloc[idx]
+        path = row["normal_path"]
+        if not isinstance(path, str) or not path:
+            return None
+        import PIL.Image
+        with PIL.Image.open(row["image_path"]) as pil:
+            width, height = pil.size                            # the header only: nothing is decoded
+        if height > MAX_RESOLUTION_TRAIN or width > MAX_RESOLUTION_TRAIN:
+            raise ValueError(f"{path}: normals for a picture over {MAX_RESOLUTION_TRAIN} pixels ({width}x{height}) are not supported "
+                             "(there is no autoscale path for normals)")
+        if path.lower().endswith(".npy"):
+            normal = np.load(path)
+            if normal.ndim != 3 or normal.shape[2] != 3 or normal.dtype.kind != "f":
+                raise ValueError(f"{path}: a .npy normal map must be a float (H,W,3) array, got {normal.dtype} {normal.shape}")
+            normal = normal.astype(np.float32, copy=False)
+        else:
+            with PIL.Image.open(path) as pil:
+                if pil.mode not in ("RGB", "RGBA"):
+                    raise ValueError(f"{path}: a normal image must be an 8-bit RGB image, got mode {pil.mode}")
+                normal = np.array(pil, dtype=np.uint8)[:, :, :3]
+        if normal.shape[:2] != (height, width):
+            raise ValueError(f"{path}: the normal map is {normal.shape[1]}x{normal.shape[0]}, the picture {width}x{height}")
+        return normal
+
     def __getitem__(self, idx):
         image, q, t, info = self.load_raw(idx)
         image = image.permute(2, 0, 1).to(torch.float32).div(255)               # torchvision's to_tensor

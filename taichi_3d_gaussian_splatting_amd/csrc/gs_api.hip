@@ -18,6 +18,7 @@
 #include "../../include/gs_appearance.h"
 #include "../../include/gs_vq.h"
 #include "../../include/gs_depth.h"
+#include "../../include/gs_geometry.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -159,6 +160,7 @@ struct gs_ctx {
     DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
     DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
     DevBuf depth_ws;                    // gs_depth_loss_forward: its finished moments and per-block sums, read by nothing else
+    DevBuf geometry_ws;                 // gs_normal_loss_forward / gs_depth_smooth_forward: their per-tile sums, read by nothing else
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
     uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
     // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
@@ -231,7 +233,8 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
-                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->depth_ws };
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->depth_ws,
+                      &c->geometry_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2125,6 +2128,115 @@ extern "C" int gs_depth_loss_backward(gs_ctx* c, const float* D, const float* Z,
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_depth_loss_backward(D, Z, w_t, w_p, H, W, flags, loss_terms, upstream, grad_D, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- geometry regularisers (include/gs_geometry.h, k_geometry.hip) ---------------------------------------------------------------
+static int geometry_check(const std::string& who, gs_ctx* c, const float* D, int32_t H, int32_t W, int32_t flags, int32_t flags_all)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (!D) return fail(GS_ERR_INVALID_ARGUMENT, who + ": D is NULL");
+    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": H and W must be >= 1");
+    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
+    if ((flags & ~flags_all) != 0) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown flag bits");
+    return GS_OK;
+}
+
+static int geometry_check_camera(const std::string& who, float fx, float fy, float cx, float cy, float max_rel_jump)
+{
+    if (!(std::isfinite(fx) && std::isfinite(fy) && fx > 0.0f && fy > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": fx and fy must be finite and > 0");
+    if (!(std::isfinite(cx) && std::isfinite(cy))) return fail(GS_ERR_INVALID_ARGUMENT, who + ": cx and cy must be finite");
+    if (!(std::isfinite(max_rel_jump) && max_rel_jump >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": max_rel_jump must be finite and >= 0");
+    return GS_OK;
+}
+
+extern "C" int gs_depth_normals(gs_ctx* c, const float* D, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float max_rel_jump,
+                                float* normals, gs_stream stream_)
+{
+    const std::string who("gs_depth_normals");
+    if (const int rc = geometry_check(who, c, D, H, W, 0, 0)) return rc;
+    if (!normals) return fail(GS_ERR_INVALID_ARGUMENT, who + ": normals is NULL");
+    if (const int rc = geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_depth_normals(D, H, W, fx, fy, cx, cy, max_rel_jump, normals, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+static int normal_loss_check(const std::string& who, gs_ctx* c, const float* D, const float* N, const float* w_n, int32_t H, int32_t W, float fx,
+                             float fy, float cx, float cy, float max_rel_jump, int32_t flags, const float* terms)
+{
+    if (const int rc = geometry_check(who, c, D, H, W, flags, GS_GEOM_NORMAL_FLAGS_ALL)) return rc;
+    if (!N || !w_n) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL plane (N or w_n)");
+    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
+    return geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump);
+}
+
+extern "C" int gs_normal_loss_forward(gs_ctx* c, const float* D, const float* N, const float* w_n, const float* w_p, int32_t H, int32_t W,
+                                      float fx, float fy, float cx, float cy, float max_rel_jump, int32_t flags, float* terms, gs_stream stream_)
+{
+    if (const int rc = normal_loss_check("gs_normal_loss_forward", c, D, N, w_n, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_normal_loss_forward: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_normal_loss_forward(D, N, w_n, w_p, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms, c->geometry_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_normal_loss_backward(gs_ctx* c, const float* D, const float* N, const float* w_n, const float* w_p, int32_t H, int32_t W,
+                                       float fx, float fy, float cx, float cy, float max_rel_jump, int32_t flags, const float* terms,
+                                       const float* upstream, float* grad_D, gs_stream stream_)
+{
+    if (const int rc = normal_loss_check("gs_normal_loss_backward", c, D, N, w_n, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms)) return rc;
+    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_normal_loss_backward: grad_D is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_normal_loss_backward(D, N, w_n, w_p, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms, upstream, grad_D, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+static int depth_smooth_check(const std::string& who, gs_ctx* c, const float* D, int32_t H, int32_t W, float edge_lambda, int32_t flags,
+                              const float* terms)
+{
+    if (const int rc = geometry_check(who, c, D, H, W, flags, GS_GEOM_SMOOTH_FLAGS_ALL)) return rc;
+    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
+    if (!(std::isfinite(edge_lambda) && edge_lambda >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": edge_lambda must be finite and >= 0");
+    return GS_OK;
+}
+
+extern "C" int gs_depth_smooth_forward(gs_ctx* c, const float* D, const float* I, const float* w_p, int32_t H, int32_t W, float edge_lambda,
+                                       int32_t flags, float* terms, gs_stream stream_)
+{
+    if (const int rc = depth_smooth_check("gs_depth_smooth_forward", c, D, H, W, edge_lambda, flags, terms)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_depth_smooth_forward: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_depth_smooth_forward(D, I, w_p, H, W, edge_lambda, flags, terms, c->geometry_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_depth_smooth_backward(gs_ctx* c, const float* D, const float* I, const float* w_p, int32_t H, int32_t W, float edge_lambda,
+                                        int32_t flags, const float* terms, const float* upstream, float* grad_D, gs_stream stream_)
+{
+    if (const int rc = depth_smooth_check("gs_depth_smooth_backward", c, D, H, W, edge_lambda, flags, terms)) return rc;
+    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_depth_smooth_backward: grad_D is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_depth_smooth_backward(D, I, w_p, H, W, edge_lambda, flags, terms, upstream, grad_D, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

@@ -660,6 +660,19 @@ void gs_launch_depth_loss_forward(const float* D, const float* Z, const float* w
 void gs_launch_depth_loss_backward(const float* D, const float* Z, const float* wt, const float* wp, int H, int W, int flags, const float* terms,
                                    const float* upstream, float* G, hipStream_t s);
 
+// k_geometry.hip (include/gs_geometry.h): the depth-derived normal, the normal loss and the depth smoothness.  The launchers trust
+// what the entry points checked.  ws: gs_geometry_ws_size(H, W) bytes of the context's, 8-byte aligned (per-tile sums).
+size_t gs_geometry_ws_size(int H, int W);
+void gs_launch_depth_normals(const float* D, int H, int W, float fx, float fy, float cx, float cy, float jump, float* normals, hipStream_t s);
+void gs_launch_normal_loss_forward(const float* D, const float* N, const float* wn, const float* wp, int H, int W, float fx, float fy, float cx,
+                                   float cy, float jump, int flags, float* terms, void* ws, hipStream_t s);
+void gs_launch_normal_loss_backward(const float* D, const float* N, const float* wn, const float* wp, int H, int W, float fx, float fy, float cx,
+                                    float cy, float jump, int flags, const float* terms, const float* upstream, float* G, hipStream_t s);
+void gs_launch_depth_smooth_forward(const float* D, const float* I, const float* wp, int H, int W, float lambda, int flags, float* terms, void* ws,
+                                    hipStream_t s);
+void gs_launch_depth_smooth_backward(const float* D, const float* I, const float* wp, int H, int W, float lambda, int flags, const float* terms,
+                                     const float* upstream, float* G, hipStream_t s);
+
 // k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
 // order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry
 // points checked: a non-empty volume, non-NULL arrays and work buffers, counts below 2^31.

@@ -1,0 +1,179 @@
+"""GPU (-m gpu): the geometry regularisers through GaussianPointCloudTrainer(config, geometry=GeometryConfig(...)) on the 64x96
+views of tests/trainer_util.py's dataset with the normal priors of tests/geometry_trainer_util.py: None is the loop as it was, a
+run with the terms ends with normals closer to the ground truth's than the same run without, the combination with masks and
+depth supervision runs, and what cannot work is refused."""
+import json
+import os
+
+import numpy as np
+import PIL.Image
+import pytest
+import torch
+
+import depth_trainer_util as DU
+import geometry_trainer_util as GU
+import trainer_util as TU
+from taichi_3d_gaussian_splatting_amd import geometry
+from taichi_3d_gaussian_splatting_amd.geometry import GeometryConfig
+from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer, JsonlSummaryWriter
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MASK_BOX = (8, 56, 10, 80)
+
+
+@pytest.fixture(scope="module")
+def data(tmp_path_factory):
+    """`plain`: trainer_util's dataset from the perturbed scene; `normal`: with the ground truth's normals in 8-bit PNGs"""
+    root = tmp_path_factory.mktemp("geometry_data")
+    base = TU.write_dataset(root, DEV, initial=TU.perturbed(TU.ground_truth_scene()))
+    return dict(plain=base, normal=GU.add_normals(base, root, DEV))
+
+
+def make_trainer(data, out_dir, regularise=True, **kwargs):
+    """kwargs that TrainConfig has are config overrides, the others constructor arguments"""
+    fields = {f for f in GaussianPointCloudTrainer.TrainConfig.__dataclass_fields__}
+    config = TU.train_config(data["paths"], out_dir, **{k: v for k, v in kwargs.items() if k in fields})
+    config.loss_function_config.enable_regularization = regularise
+    return GaussianPointCloudTrainer(config, device=DEV, writer=JsonlSummaryWriter(config.summary_writer_log_dir),
+                                     **{k: v for k, v in kwargs.items() if k not in fields})
+
+
+def logged(trainer, tag):
+    trainer.writer.flush()
+    return [(r["step"], r["value"]) for r in JsonlSummaryWriter.read(trainer.writer.path) if r["tag"] == tag]
+
+
+def test_the_normal_files_hold_the_ground_truth_and_the_store_hands_them_out(data):
+    normal = data["normal"]
+    fx, fy, cx, cy = GU.intrinsics()
+    yy, xx = np.mgrid[0:TU.H, 0:TU.W].astype(np.float64)
+    rays = np.stack([(xx + 0.5 - cx) / fx, (yy + 0.5 - cy) / fy, np.ones_like(xx)])
+    for view, n in normal["normals"].items():
+        stored = np.array(PIL.Image.open(os.path.join(os.path.dirname(normal["paths"]["train"]), "normal", f"view_{view}.png")))
+        assert stored.dtype == np.uint8 and np.array_equal(stored, normal["stored"][view])
+        has = (n != 0).any(axis=0)
+        assert np.array_equal(stored.any(axis=2), has) and 0.01 < has.mean() < 0.95                  # surface and none both
+        assert np.abs(np.linalg.norm(n, axis=0)[has] - 1.0).max() < 1e-12 and ((n * rays).sum(axis=0)[has] < 0).all()    # unit, facing the camera
+        assert np.abs(stored / 127.5 - 1.0 - n.transpose(1, 2, 0))[has].max() <= 1.0 / 255 * 1.001
+    from taichi_3d_gaussian_splatting_amd.ImagePoseDataset import ImagePoseDataset
+    store = geometry.NormalStore.from_dataset(ImagePoseDataset(normal["paths"]["train"]), DEV)
+    assert len(store) == len(TU.TRAIN_VIEWS) and store.has(0) and store.unit_range(0)
+    prior, weight = store.target(1, 1)
+    view = TU.TRAIN_VIEWS[1]
+    has = torch.from_numpy((normal["normals"][view] != 0).any(axis=0)).to(DEV)
+    assert prior.shape == (3, TU.H, TU.W) and weight.shape == (TU.H, TU.W) and prior.is_contiguous() and weight.is_contiguous()
+    assert torch.equal(weight > 0, has) and torch.equal(weight[has], torch.ones_like(weight[has]))
+    want = torch.from_numpy(normal["stored"][view]).to(DEV).permute(2, 0, 1).float() / 255
+    assert torch.allclose(prior[:, has], want[:, has], atol=1e-6)
+    assert torch.allclose(prior[:, ~has], torch.full_like(prior[:, ~has], geometry.NO_PRIOR_U8 / 255), atol=1e-6)
+    again, _ = store.target(1, 1)
+    assert again.data_ptr() == prior.data_ptr()                                # the buffer of the geometry is reused
+    half, half_weight = store.target(1, 2)
+    assert half.shape == (3, TU.H // 2, TU.W // 2) and half_weight.shape == (TU.H // 2, TU.W // 2)
+    assert bool(((half_weight > 0) & (half_weight < 1)).any())                 # soft at the border of the surface
+
+
+def test_none_leaves_the_run_bit_identical(data, tmp_path):
+    """geometry=None on a dataset that has normal files against a trainer built without the argument"""
+    runs = []
+    for name, kwargs in (("without", {}), ("none", dict(geometry=None))):
+        trainer = make_trainer(data["normal"], tmp_path / name, num_iterations=5, initial_downsample_factor=2, log_loss_interval=1,
+                               log_metrics_interval=10 ** 6, position_learning_rate=1e-4, seed=3, **kwargs)
+        assert trainer.geometry is None and trainer.train_normals is None and trainer.val_normals is None
+        assert not getattr(trainer.rasterisation.config, "differentiable_depth", False)
+        trainer.train()
+        runs.append(trainer)
+    a, b = runs
+    assert torch.equal(a.scene.point_cloud, b.scene.point_cloud) and torch.equal(a.scene.point_cloud_features, b.scene.point_cloud_features)
+    for tag in ("train/loss", "train/l1 loss", "train/ssim loss"):
+        assert logged(a, tag) == logged(b, tag) and len(logged(a, tag)) == 5
+    assert logged(b, "train/smooth loss") == [] and logged(b, "train/normal loss") == []
+    assert set(b.validation(5)) == {"loss", "psnr", "ssim", "inference_time"}
+
+
+def test_the_terms_bring_the_normals_closer_to_the_ground_truth(data, tmp_path):
+    """The same seeded run of trainer_util.SMOKE with geometry_trainer_util.SHORT_RUN (both terms, at the weights chosen there before
+    this comparison was first run) and without: the mean angle between the normals of the validation renders and the ground
+    truth's is smaller with the terms.  Both angles and both PSNRs go to profiles/geometry_margins.json (tools/bench_geometry.py
+    --margins-out).  Measured on an MI355X: 22.43 degrees without, 6.78 with; val/psnr 39.03 without, 37.04 with.  (On this
+    scene the normal term does it: the smoothness alone, at 0.5, leaves 23.5 degrees.)"""
+    runs = GU.regularised_and_plain_runs(data["normal"], tmp_path, DEV)
+    none, geo = runs["none"], runs["geometry"]
+    print(f"validation normal angle: without {none['angle']:.4f} degrees, with the terms {geo['angle']:.4f}; "
+          f"val/psnr without {none['psnr']:.3f}, with {geo['psnr']:.3f}")
+    assert none["trainer"].view_order == geo["trainer"].view_order
+    assert geo["trainer"].rasterisation.config.differentiable_depth is True
+    assert not getattr(geo["trainer"].config.rasterisation_config, "differentiable_depth", False)      # the caller's config is left alone
+    for t in (geo["trainer"].scene.point_cloud, geo["trainer"].scene.point_cloud_features):
+        assert bool(torch.isfinite(t.detach()).all())
+    for name in ("smooth", "normal"):
+        assert f"{name}_loss" in geo["means"] and f"{name}_loss" not in none["means"] and np.isfinite(geo["means"][f"{name}_loss"])
+        steps = [s for s, _ in logged(geo["trainer"], f"train/{name} loss")]
+        assert steps == list(range(0, TU.SMOKE["num_iterations"], 10)) and logged(none["trainer"], f"train/{name} loss") == []
+        assert all(np.isfinite(v) and v >= 0 for _, v in logged(geo["trainer"], f"train/{name} loss"))
+    assert not torch.equal(none["trainer"].scene.point_cloud, geo["trainer"].scene.point_cloud)
+    assert geo["angle"] < none["angle"]
+
+
+def test_start_iteration_and_single_terms(data, tmp_path):
+    trainer = make_trainer(data["plain"], tmp_path / "smooth", num_iterations=4, initial_downsample_factor=2, log_loss_interval=1,
+                           log_metrics_interval=10 ** 6, seed=3, geometry=GeometryConfig(smooth_weight=0.5, smooth_order=2, smooth_space="depth",
+                                                                                          start_iteration=2))
+    assert trainer.train_normals is None                               # the smoothness needs no normal_path
+    trainer.train()
+    assert [s for s, _ in logged(trainer, "train/smooth loss")] == [2, 3] and logged(trainer, "train/normal loss") == []
+    assert set(trainer.validation(4)) == {"loss", "psnr", "ssim", "inference_time", "smooth_loss"}
+
+
+def test_masks_depth_and_geometry_run_together(data, tmp_path):
+    root = tmp_path / "all"
+    os.makedirs(root)
+    with_depth = DU.add_depth(data["normal"], root, DEV)                 # the records keep their normal_path
+    mask = np.zeros((TU.H, TU.W), np.uint8)
+    mask[MASK_BOX[0]:MASK_BOX[1], MASK_BOX[2]:MASK_BOX[3]] = 255
+    PIL.Image.fromarray(mask, mode="L").save(root / "mask.png")
+    paths = dict(with_depth["paths"])
+    for split in ("train", "val"):
+        records = [dict(r, mask_path=str(root / "mask.png")) for r in json.load(open(paths[split]))]
+        assert all("normal_path" in r and "depth_path" in r for r in records)
+        paths[split] = str(root / f"{split}.json")
+        json.dump(records, open(paths[split], "w"))
+    trainer = make_trainer(dict(paths=paths), tmp_path / "run", num_iterations=2, initial_downsample_factor=1, pixel_weights="file",
+                           depth="metric", geometry=GeometryConfig(smooth_weight=0.5, normal_weight=0.1), log_loss_interval=1,
+                           log_metrics_interval=1, seed=3)
+    trainer.train()
+    means = trainer.validation(2)
+    assert all(np.isfinite(v) for v in means.values()) and {"depth_loss", "smooth_loss", "normal_loss"} <= set(means)
+    for t in (trainer.scene.point_cloud, trainer.scene.point_cloud_features):
+        assert bool(torch.isfinite(t.detach()).all())
+    assert len(logged(trainer, "train/smooth loss")) == len(logged(trainer, "train/normal loss")) == len(logged(trainer, "train/depth loss")) == 2
+    # the mask reaches both terms: outside the box nothing is selected
+    view = trainer.view_order[0]
+    image_gt, _, _, info, weight = trainer.train_targets.target(view, 1, with_weight=True)
+    prior, prior_weight = trainer.train_normals.target(view, 1)
+    rendered = torch.from_numpy(with_depth["depth"][TU.TRAIN_VIEWS[view]]).to(DEV).contiguous()
+    K = geometry.intrinsics_tuple(info.camera_intrinsics)
+    both = geometry.normal_loss(rendered, K, prior, prior_weight, weight).terms[2].item()
+    one = geometry.normal_loss(rendered, K, prior, prior_weight).terms[2].item()
+    assert 0 < both < one
+    inside = geometry.depth_smoothness(rendered, image_gt, weight).terms[2].item()
+    assert 0 < inside < geometry.depth_smoothness(rendered, image_gt).terms[2].item()
+
+
+def test_what_cannot_work_is_refused(data, tmp_path):
+    with pytest.raises(ValueError, match="GeometryConfig"):
+        make_trainer(data["normal"], tmp_path / "a", geometry=dict(smooth_weight=1.0))
+    with pytest.raises(ValueError, match="smooth_weight"):
+        make_trainer(data["normal"], tmp_path / "b", geometry=GeometryConfig())
+    with pytest.raises(ValueError, match="targets_on_device"):
+        make_trainer(data["normal"], tmp_path / "c", geometry=GeometryConfig(smooth_weight=1.0), targets_on_device=False)
+    with pytest.raises(ValueError, match="normal_path"):
+        make_trainer(data["plain"], tmp_path / "d", geometry=GeometryConfig(normal_weight=0.1))
+    config = TU.train_config(data["normal"]["paths"], tmp_path / "f")
+    config.rasterisation_config.rgb_only = True
+    with pytest.raises(ValueError, match="rgb_only"):
+        GaussianPointCloudTrainer(config, device=DEV, geometry=GeometryConfig(smooth_weight=1.0))
+    with pytest.raises(ValueError, match="convention"):
+        make_trainer(data["normal"], tmp_path / "g", geometry=GeometryConfig(normal_weight=0.1, normal_convention="directx"))
