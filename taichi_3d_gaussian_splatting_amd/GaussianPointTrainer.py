@@ -55,9 +55,9 @@ from .GaussianPointCloudScene import GaussianPointCloudScene
 from . import appearance as _appearance
 from .appearance import AppearanceConfig, AppearanceTable
 from . import depth as _depth
-from .depth import DepthConfig, DepthStore
+from .depth import DepthConfig
 from . import geometry as _geometry
-from .geometry import GeometryConfig, NormalStore
+from .geometry import GeometryConfig
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
 from .mcmc import MCMCConfig, MCMCStrategy
@@ -237,41 +237,16 @@ class GaussianPointCloudTrainer:
         aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations); geometry:
         the GeometryConfig of the regularisers on the rendered depth (None: none)"""
         self.config = config
-        self.geometry = None
-        self.train_normals = self.val_normals = None
-        if geometry is not None:
-            if not isinstance(geometry, GeometryConfig):
-                raise ValueError(f"geometry must be a GeometryConfig or None, got {type(geometry).__name__}")
-            geometry.check()
-            if not self.config.targets_on_device:
-                raise ValueError("geometry needs targets_on_device=True: its guide and priors are made on the device")
-            if self.config.rasterisation_config.rgb_only:
-                raise ValueError("geometry cannot be combined with rasterisation_config.rgb_only=True: no depth is rendered")
-            self.geometry = dataclasses.replace(geometry)
-            self._smooth_flags = _geometry.smooth_flags(geometry.smooth_space, geometry.smooth_order)
-            self._intrinsics = {}                   # (split, view, factor) -> (fx, fy, cx, cy), read by the host once
-        if depth not in ("none", "metric", "relative"):
-            raise ValueError(f'depth must be "none", "metric" or "relative", got {depth!r}')
-        if depth == "none" and depth_config is not None:
-            raise ValueError('depth_config needs depth="metric" or "relative"')
+        # the extra loss terms, in the order they are summed and logged in; each checks its arguments where it is made
+        geometry_terms = _geometry.trainer_terms(geometry, config)
+        depth_terms = _depth.trainer_terms(depth, depth_config, config)
+        self.terms = depth_terms + geometry_terms
+        # The order their autograd nodes on the rendered depth are made in.  Autograd runs the node made last first and adds
+        # the gradients up in that order: another order is another float32 sum.
+        self._node_order = geometry_terms + depth_terms
+        self.geometry = geometry_terms[0].config if geometry_terms else None
         self.depth = depth
-        self.depth_config = None
-        self.train_depth = self.val_depth = None
-        self.depth_flags = 0
-        if depth != "none":
-            depth_config = depth_config or DepthConfig()
-            depth_config.check()
-            if depth == "relative" and depth_config.space != "inverse":
-                raise ValueError('depth="relative" needs depth_config.space="inverse": the files hold relative inverse depth')
-            if not self.config.targets_on_device:
-                raise ValueError(f'depth="{depth}" needs targets_on_device=True: depth targets are made on the device')
-            if self.config.rasterisation_config.rgb_only:
-                raise ValueError(f'depth="{depth}" cannot be combined with rasterisation_config.rgb_only=True: no depth is rendered')
-            if depth_config.num_iterations is None:
-                depth_config = dataclasses.replace(depth_config, num_iterations=max(int(self.config.num_iterations), 1))
-            self.depth_config = depth_config
-            self.depth_flags = _depth.loss_flags(depth_config.space, depth_config.norm, align=depth == "relative",
-                                                 target_is_inverse=depth == "relative")
+        self.depth_config, self.depth_flags = (depth_terms[0].config, depth_terms[0].flags) if depth_terms else (None, 0)
         if appearance not in ("none", "affine"):
             raise ValueError(f'appearance must be "none" or "affine", got {appearance!r}')
         if appearance == "none" and appearance_config is not None:
@@ -329,14 +304,10 @@ class GaussianPointCloudTrainer:
                              "host target path")
         if self.mask_erode < 0 or (not self.weighted and self.mask_erode):
             raise ValueError('mask_erode must be >= 0, and needs pixel_weights="alpha" or "file"')
-        if self.weighted:
-            self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device, mask_source=self.pixel_weights,
-                                                          mask_erode=self.mask_erode)
-            self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device, mask_source=self.pixel_weights,
-                                                        mask_erode=self.mask_erode)
-        elif self.config.targets_on_device:
-            self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device)
-            self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device)
+        if self.config.targets_on_device:
+            mask = dict(mask_source=self.pixel_weights, mask_erode=self.mask_erode) if self.weighted else {}
+            self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device, **mask)
+            self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device, **mask)
         else:
             # batch_size=None: the dataset's items as they are; num_workers=0: no process is started behind an initialised GPU
             self._val_loader = torch.utils.data.DataLoader(self.val_dataset, batch_size=None, shuffle=False, num_workers=0)
@@ -345,25 +316,15 @@ class GaussianPointCloudTrainer:
             if appearance_config.num_iterations is None:
                 appearance_config = dataclasses.replace(appearance_config, num_iterations=max(int(self.config.num_iterations), 1))
             self.appearance_table = AppearanceTable(len(self.train_dataset), self.device, appearance_config)
-        if self.depth != "none":
-            # the depth term's gradient reaches the scene: set on the trainer's own rasteriser, not on the caller's config object
+        if self.terms:
+            # their gradients reach the scene: set on the trainer's own rasteriser, not on the caller's config object
             self.rasterisation.config = copy.copy(self.rasterisation.config)
             self.rasterisation.config.differentiable_depth = True
-            try:
-                self.train_depth = DepthStore.from_dataset(self.train_dataset, self.device, depth_scale=self.depth_config.depth_scale)
-            except ValueError as e:
-                raise ValueError(f'depth="{self.depth}": every training record needs a depth_path ({e})') from e
-            self.val_depth = DepthStore.from_dataset(self.val_dataset, self.device, depth_scale=self.depth_config.depth_scale,
-                                                     require_all=False)
-        if self.geometry is not None:
-            self.rasterisation.config = copy.copy(self.rasterisation.config)       # (a copy of a copy when depth= set it too)
-            self.rasterisation.config.differentiable_depth = True
-            if self.geometry.normal_weight > 0.0:
-                try:
-                    self.train_normals = NormalStore.from_dataset(self.train_dataset, self.device)
-                except ValueError as e:
-                    raise ValueError(f"geometry.normal_weight > 0: every training record needs a normal_path ({e})") from e
-                self.val_normals = NormalStore.from_dataset(self.val_dataset, self.device, require_all=False)
+        for term in self.terms:
+            term.load(self.train_dataset, self.val_dataset, self.device)
+        stores = {term.name: (term.stores["train"], term.stores["val"]) for term in self.terms}
+        self.train_depth, self.val_depth = stores.get("depth", (None, None))
+        self.train_normals, self.val_normals = stores.get("normal", (None, None))
         # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
         self._order_generator = torch.Generator().manual_seed(int(self.config.seed))
         self.view_order: List[int] = []
@@ -407,17 +368,20 @@ class GaussianPointCloudTrainer:
             yield self._view_at(iteration)
             iteration += 1
 
+    def _target(self, store, host_items, view: int, downsample_factor: int):
+        """-> (image, q, t, CameraInfo, pixel weight or None) of a view by the configured path: the split's store, with the
+        weight when the loss has one, or (store None) the next item of the host path's loader, which walks the same views"""
+        if store is None:
+            return self._host_target(next(host_items), downsample_factor) + (None,)
+        if self.weighted:
+            return store.target(view, downsample_factor, with_weight=True)
+        return store.target(view, downsample_factor) + (None,)
+
     def _validation_targets(self):
         """-> (image, q, t, CameraInfo, weight or None) of every validation view"""
-        if self.weighted:
-            for i in range(len(self.val_targets)):
-                yield self.val_targets.target(i, 1, with_weight=True)
-        elif self.val_targets is not None:
-            for i in range(len(self.val_targets)):
-                yield self.val_targets.target(i, 1) + (None,)
-        else:
-            for item in self._val_loader:
-                yield self._host_target(item, 1) + (None,)
+        host_items = iter(self._val_loader) if self.val_targets is None else None
+        for view in range(len(self.val_dataset)):
+            yield self._target(self.val_targets, host_items, view, 1)
 
     def train_image_paths(self) -> List[str]:
         """the image_path of every training view, in the dataset's order: what the rows of the appearance table belong to"""
@@ -438,6 +402,7 @@ class GaussianPointCloudTrainer:
     # ---- the loop ---------------------------------------------------------------------------------------------------------
     def train(self):
         config = self.config
+        train_items = None
         if self.train_targets is None:
             train_items = iter(torch.utils.data.DataLoader(self.train_dataset, batch_size=None, sampler=self._views_from(0), num_workers=0))
         optimizer = FusedAdam([self.scene.point_cloud_features], lr=config.feature_learning_rate, betas=(0.9, 0.999))
@@ -457,16 +422,9 @@ class GaussianPointCloudTrainer:
             optimizer.zero_grad()
             position_optimizer.zero_grad()
 
-            pixel_weight = None
-            view = self._view_at(iteration)         # (the host path's sampler walks the same list)
-            if self.weighted:
-                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self.train_targets.target(
-                    view, downsample_factor, with_weight=True)
-            elif self.train_targets is not None:
-                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self.train_targets.target(
-                    view, downsample_factor)
-            else:
-                image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info = self._host_target(next(train_items), downsample_factor)
+            view = self._view_at(iteration)
+            image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self._target(
+                self.train_targets, train_items, view, downsample_factor)
             rasterisation_input = self._rasterisation_input(
                 camera_info, q_pointcloud_camera, t_pointcloud_camera,
                 color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval))
@@ -483,20 +441,13 @@ class GaussianPointCloudTrainer:
                 pointcloud_features=self.scene.point_cloud_features,
                 clamp_predicted=True,
                 pixel_weight=pixel_weight)          # None: the unweighted loss
-            geometry_terms = None
-            if self.geometry is not None and iteration >= self.geometry.start_iteration:
-                geometry_terms = self._geometry_losses("train", self.train_targets, self.train_normals, view, downsample_factor,
-                                                       image_depth, image_gt, pixel_weight)
-            if self.train_depth is not None:
-                depth_loss = self._depth_loss(self.train_depth, view, downsample_factor, image_depth, pixel_weight)
-                total = loss + self.depth_config.weight_at(iteration) * depth_loss
-                if geometry_terms is not None:
-                    total = self._add_geometry(total, geometry_terms)
-                total.backward()
-            elif geometry_terms is not None:
-                self._add_geometry(loss, geometry_terms).backward()
-            else:
-                loss.backward()
+            values = {term: term.value("train", view, downsample_factor, image_depth, image_gt, camera_info, pixel_weight)
+                      for term in self._node_order if iteration >= term.start_iteration}
+            total = loss
+            for term in self.terms:
+                if values.get(term) is not None:
+                    total = total + term.weight_at(iteration) * values[term]
+            total.backward()
             if self.mcmc is not None:
                 self.mcmc.before_step(iteration)
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
@@ -519,16 +470,10 @@ class GaussianPointCloudTrainer:
                 self.writer.add_scalar("train/loss", loss_value, iteration)
                 self.writer.add_scalar("train/l1 loss", l1_loss.item(), iteration)
                 self.writer.add_scalar("train/ssim loss", ssim_loss.item(), iteration)
-                if self.train_depth is not None:
-                    terms = depth_loss.terms.tolist()       # {L, S_w, s, t, ...}: one read
-                    self.writer.add_scalar("train/depth loss", terms[0], iteration)
-                    if self.depth == "relative":
-                        self.writer.add_scalar("train/depth scale", terms[2], iteration)
-                        self.writer.add_scalar("train/depth shift", terms[3], iteration)
-                if geometry_terms is not None:
-                    for name, term in zip(("smooth", "normal"), geometry_terms):
-                        if term is not None:
-                            self.writer.add_scalar(f"train/{name} loss", term.terms.tolist()[0], iteration)       # one read per term
+                for term in self.terms:
+                    if values.get(term) is not None:
+                        for tag, value in term.train_scalars(values[term].terms.tolist()):       # one read per term
+                            self.writer.add_scalar(tag, value, iteration)
                 if config.print_metrics_to_console:
                     print(f"train_iteration={iteration};")
                     print(f"train_loss={loss_value};")
@@ -538,7 +483,8 @@ class GaussianPointCloudTrainer:
                 self.writer.add_scalar("value/num_valid_points", int((self.scene.point_invalid_mask == 0).sum().item()), iteration)
                 # (a view whose mask is empty has no PSNR or SSIM: nothing is logged for it)
                 if pixel_weight is None or bool((pixel_weight > 0).any()):
-                    psnr_score, ssim_score = self._compute_pnsr_and_ssim(torch.clamp(image_pred.detach(), 0, 1), image_gt, pixel_weight)
+                    _, psnr_score, ssim_loss_clamped = self._metrics(torch.clamp(image_pred.detach(), 0, 1), image_gt, pixel_weight)
+                    ssim_score = 1.0 - ssim_loss_clamped
                     self.writer.add_scalar("train/psnr", psnr_score.item(), iteration)
                     self.writer.add_scalar("train/ssim", ssim_score.item(), iteration)
                     if config.print_metrics_to_console:
@@ -547,48 +493,12 @@ class GaussianPointCloudTrainer:
                         print(f"train_ssim={ssim_score.item()};")
                         print(f"train_ssim_{iteration}={ssim_score.item()};")
             del image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, rasterisation_input, image_pred, loss, l1_loss, ssim_loss
-            del pixel_weight
-            if self.train_depth is not None:
-                del depth_loss, image_depth
-            if self.geometry is not None:
-                del geometry_terms
+            del pixel_weight, image_depth, values, total
             # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
             if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
                 self.validation(iteration)
         if hasattr(self.writer, "flush"):
             self.writer.flush()
-
-    def _depth_loss(self, store, view: int, downsample_factor: int, image_depth, pixel_weight):
-        """the depth term of one view: the store's target and weight at the factor (one launch) and the fused loss on the
-        rendered depth; its .terms holds the fitted scale and shift"""
-        target, target_weight = store.target(view, downsample_factor, self.depth_config.min_coverage)
-        return _depth.depth_loss_flags(image_depth, target, target_weight, pixel_weight, self.depth_flags)
-
-    def _geometry_losses(self, split, targets, normals, view: int, downsample_factor: int, image_depth, image_gt, pixel_weight):
-        """-> (smoothness or None, normal loss or None) of one view: the smoothness of the rendered depth with the colour target
-        as its guide, and the cosine loss against the view's normal prior at the factor (one launch for the prior)"""
-        g = self.geometry
-        smooth = normal = None
-        if g.smooth_weight > 0.0:
-            smooth = _geometry.depth_smoothness_flags(image_depth, image_gt, pixel_weight, g.smooth_edge_lambda, self._smooth_flags)
-        if g.normal_weight > 0.0 and normals is not None and normals.has(view):
-            key = (split, view, downsample_factor)
-            intrinsics = self._intrinsics.get(key)
-            if intrinsics is None:
-                info = targets.target(view, downsample_factor)[3]
-                intrinsics = self._intrinsics[key] = _geometry.intrinsics_tuple(info.camera_intrinsics)
-            prior, prior_weight = normals.target(view, downsample_factor)
-            normal = _geometry.normal_loss_flags(image_depth, intrinsics, prior, prior_weight, pixel_weight, g.normal_max_rel_jump,
-                                                 _geometry.normal_flags(normals.unit_range(view), g.normal_convention))
-        return smooth, normal
-
-    def _add_geometry(self, loss, geometry_terms):
-        smooth, normal = geometry_terms
-        if smooth is not None:
-            loss = loss + self.geometry.smooth_weight * smooth
-        if normal is not None:
-            loss = loss + self.geometry.normal_weight * normal
-        return loss
 
     @staticmethod
     def _weighted_mse(image_pred, image_gt, pixel_weight):
@@ -598,17 +508,15 @@ class GaussianPointCloudTrainer:
         squared = torch.where(w > 0, w * (image_pred - image_gt) ** 2, torch.zeros_like(image_pred))
         return squared.sum() / (3 * w.sum())
 
-    def _compute_pnsr_and_ssim(self, image_pred, image_gt, pixel_weight=None):
-        """PSNR = 10 log10(1 / mse); SSIM = 1 - the third term of the loss (pytorch_msssim.ssim's definition, in its kernels).
-        With a weight: the mse over the weighted pixels and the weighted SSIM term."""
+    def _metrics(self, image_pred, image_gt, pixel_weight=None):
+        """-> (loss, PSNR, SSIM loss) of a predicted image in [0, 1], device scalars: PSNR = 10 log10(1 / mse); SSIM is 1 - the
+        SSIM loss, the third term of the loss (pytorch_msssim.ssim's definition, in its kernels).  With a weight: the weighted
+        loss and the mse over the weighted pixels.  (The SSIM loss and not the SSIM: the train log subtracts in float32, the
+        validation the host's number from 1, and both keep their last bit.)"""
         with torch.no_grad():
-            if pixel_weight is None:
-                psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
-                _, _, ssim_loss = self.loss_function(image_pred, image_gt)
-            else:
-                psnr_score = 10 * torch.log10(1.0 / self._weighted_mse(image_pred, image_gt, pixel_weight))
-                _, _, ssim_loss = self.loss_function(image_pred, image_gt, pixel_weight=pixel_weight)
-            return psnr_score, 1.0 - ssim_loss
+            loss, _, ssim_loss = self.loss_function(image_pred, image_gt, pixel_weight=pixel_weight)     # None: the unweighted loss
+            mse = torch.mean((image_pred - image_gt) ** 2) if pixel_weight is None else self._weighted_mse(image_pred, image_gt, pixel_weight)
+            return loss, 10 * torch.log10(1.0 / mse), ssim_loss
 
     def validation(self, iteration):
         """TRAIN:342-423: every validation view at band 3 and full resolution; the means of loss, PSNR, SSIM and of the
@@ -616,11 +524,11 @@ class GaussianPointCloudTrainer:
         the best so far, as best_scene.parquet.  -> the means, as a dict.  With pixel weights a view whose mask is empty is left
         out of every mean: it has no weighted pixel to measure."""
         with torch.no_grad():
-            total_loss = total_psnr_score = total_ssim_score = total_inference_time = 0.0
-            total_cc = dict(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
+            sums = dict(loss=0.0, psnr=0.0, ssim=0.0, inference_time=0.0)
+            if self.appearance_table is not None:
+                sums.update(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
             count = 0
-            total_depth_loss, depth_count = 0.0, 0
-            total_geometry, geometry_count = dict(smooth_loss=0.0, normal_loss=0.0), dict(smooth_loss=0, normal_loss=0)
+            total_terms, term_count = {term: 0.0 for term in self.terms}, {term: 0 for term in self.terms}
             for val_view, (image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight) in enumerate(self._validation_targets()):
                 if pixel_weight is not None and not bool((pixel_weight > 0).any()):
                     continue
@@ -631,51 +539,28 @@ class GaussianPointCloudTrainer:
                 image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
                 end_event.record()
                 torch.cuda.synchronize()
-                total_inference_time += start_event.elapsed_time(end_event)
+                sums["inference_time"] += start_event.elapsed_time(end_event)
                 image_pred = torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
-                if pixel_weight is None:
-                    loss, _, ssim_loss = self.loss_function(image_pred, image_gt)
-                    psnr_score = 10 * torch.log10(1.0 / torch.mean((image_pred - image_gt) ** 2))
-                else:
-                    loss, _, ssim_loss = self.loss_function(image_pred, image_gt, pixel_weight=pixel_weight)
-                    psnr_score = 10 * torch.log10(1.0 / self._weighted_mse(image_pred, image_gt, pixel_weight))
-                total_loss += loss.item()
-                total_psnr_score += psnr_score.item()
-                total_ssim_score += 1.0 - ssim_loss.item()
-                if self.val_depth is not None and self.val_depth.has(val_view):
-                    # (for "relative" the aligned loss: the fit is part of the forward)
-                    total_depth_loss += self._depth_loss(self.val_depth, val_view, 1, image_depth, pixel_weight).item()
-                    depth_count += 1
-                if self.geometry is not None:
-                    terms = self._geometry_losses("val", self.val_targets, self.val_normals, val_view, 1, image_depth, image_gt, pixel_weight)
-                    for name, term in zip(("smooth_loss", "normal_loss"), terms):
-                        if term is not None:
-                            total_geometry[name] += term.item()
-                            geometry_count[name] += 1
+                images = {"": image_pred}
                 if self.appearance_table is not None:
                     # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
                     fitted = _appearance.fit_affine(image_pred, image_gt, pixel_weight)
-                    image_cc = torch.clamp(_appearance.apply_forward(image_pred, fitted), 0, 1)
-                    if pixel_weight is None:
-                        loss_cc, _, ssim_loss_cc = self.loss_function(image_cc, image_gt)
-                        psnr_cc = 10 * torch.log10(1.0 / torch.mean((image_cc - image_gt) ** 2))
-                    else:
-                        loss_cc, _, ssim_loss_cc = self.loss_function(image_cc, image_gt, pixel_weight=pixel_weight)
-                        psnr_cc = 10 * torch.log10(1.0 / self._weighted_mse(image_cc, image_gt, pixel_weight))
-                    total_cc["loss_cc"] += loss_cc.item()
-                    total_cc["psnr_cc"] += psnr_cc.item()
-                    total_cc["ssim_cc"] += 1.0 - ssim_loss_cc.item()
+                    images["_cc"] = torch.clamp(_appearance.apply_forward(image_pred, fitted), 0, 1)
+                for suffix, image in images.items():
+                    loss, psnr_score, ssim_loss = self._metrics(image, image_gt, pixel_weight)
+                    sums["loss" + suffix] += loss.item()
+                    sums["psnr" + suffix] += psnr_score.item()
+                    sums["ssim" + suffix] += 1.0 - ssim_loss.item()
+                for term in self.terms:
+                    # (for depth="relative" the aligned loss: the fit is part of the forward)
+                    value = term.value("val", val_view, 1, image_depth, image_gt, camera_info, pixel_weight)
+                    if value is not None:
+                        total_terms[term] += value.item()
+                        term_count[term] += 1
                 count += 1
             count = max(count, 1)
-            means = dict(loss=total_loss / count, psnr=total_psnr_score / count, ssim=total_ssim_score / count,
-                         inference_time=total_inference_time / count)
-            if self.appearance_table is not None:
-                means.update({name: value / count for name, value in total_cc.items()})
-            if depth_count:
-                means["depth_loss"] = total_depth_loss / depth_count
-            for name, n_views in geometry_count.items():
-                if n_views:
-                    means[name] = total_geometry[name] / n_views
+            means = {name: total / count for name, total in sums.items()}
+            means.update({f"{term.name}_loss": total_terms[term] / n_views for term, n_views in term_count.items() if n_views})
             for name, value in means.items():
                 self.writer.add_scalar(f"val/{name}", value, iteration)
             if self.config.print_metrics_to_console:

@@ -16,17 +16,17 @@ depth are all usable; every other pixel adds nothing and gets a gradient of exac
 There is no fallback path: every call goes through _native.call(), and a CPU tensor is refused.
 """
 import ctypes as C
+import dataclasses
 import math
-from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _native
-from .appearance import MAX_PIXELS
-from .targets import MAX_DECODE_THREADS, ROW_PITCH_ALIGN, downsampled_geometry
+from . import _native, _terms
+from ._terms import MAX_PIXELS, check_plane                # (MAX_PIXELS and ROW_PITCH_ALIGN: the bounds of gs_depth.h, kept as names here)
+from .targets import ROW_PITCH_ALIGN, ResidentStore, _pitched
 
 FORMAT_U16, FORMAT_F32 = 0, 1                   # GS_DEPTH_U16, GS_DEPTH_F32
 INVERT_PREDICTED, INVERT_TARGET, L2, ALIGN = 1, 2, 4, 8     # GS_DEPTH_INVERT_PREDICTED, _INVERT_TARGET, _L2, _ALIGN
@@ -83,29 +83,6 @@ def loss_flags(space: str = "inverse", norm: str = "l1", align: bool = False, ta
     if align:
         flags |= ALIGN
     return flags
-
-
-def check_plane(plane, what="depth", like=None, device=True):
-    """Raise unless `plane` is a contiguous float32 (H,W) tensor on a GPU (of like's shape and device, when given).
-    device=False: dtype, shape and strides only"""
-    if not isinstance(plane, torch.Tensor):
-        raise TypeError(f"{what} must be a tensor")
-    if plane.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32, got {plane.dtype}")
-    if plane.dim() != 2 or plane.shape[0] < 1 or plane.shape[1] < 1:
-        raise ValueError(f"{what} must be (H,W) with H, W >= 1, got {tuple(plane.shape)}")
-    if plane.shape[0] * plane.shape[1] > MAX_PIXELS:
-        raise ValueError(f"{what} has more than {MAX_PIXELS} pixels")
-    if like is not None and plane.shape != like.shape:
-        raise ValueError(f"{what} must have the depth's shape {tuple(like.shape)}, got {tuple(plane.shape)}")
-    if not plane.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
-    if not device:
-        return
-    if not plane.is_cuda:
-        raise ValueError(f"depth supervision runs on the GPU: {what} must be on a cuda/hip device (there is no CPU path)")
-    if like is not None and plane.device != like.device:
-        raise ValueError(f"{what} is on {plane.device}, the depth on {like.device}")
 
 
 def _check_flags(flags):
@@ -203,8 +180,7 @@ def depth_loss_backward(depth, target, target_weight, pixel_weight, flags: int, 
         out = torch.empty_like(depth)
     else:
         check_plane(out, "out", depth)
-    if upstream is not None and (upstream.dtype != torch.float32 or upstream.numel() != 1 or upstream.device != depth.device):
-        raise ValueError("upstream must be one float32 on the depth's device")
+    _terms.check_upstream(upstream, depth)
     _bind()
     H, W = int(depth.shape[0]), int(depth.shape[1])
     _native.call("gs_depth_loss_backward", depth.device, _native.shared_ctx(depth.device), depth.data_ptr(), target.data_ptr(),
@@ -213,31 +189,12 @@ def depth_loss_backward(depth, target, target_weight, pixel_weight, flags: int, 
     return out
 
 
-class _DepthLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, depth, target, target_weight, pixel_weight, flags):
-        terms = depth_loss_forward(depth.detach(), target, target_weight, pixel_weight, flags)
-        ctx.save_for_backward(depth, target, target_weight, pixel_weight, terms)
-        ctx.flags = flags
-        ctx.mark_non_differentiable(terms)
-        return terms[0], terms
-
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_terms):
-        depth, target, target_weight, pixel_weight, terms = ctx.saved_tensors
-        if not ctx.needs_input_grad[0] or grad_loss is None:
-            return None, None, None, None, None
-        upstream = grad_loss.detach().to(torch.float32).reshape(1).contiguous()
-        return depth_loss_backward(depth.detach(), target, target_weight, pixel_weight, ctx.flags, terms, upstream), None, None, None, None
-
-
 def depth_loss_flags(depth, target, target_weight, pixel_weight=None, flags: int = 0):
     """depth_loss() by its flag bits (loss_flags): what a caller that fixed them once calls per step"""
     flags = _check_flags(flags)
     _check_loss_inputs(depth, target, target_weight, pixel_weight)
-    loss, terms = _DepthLoss.apply(depth, target, target_weight, pixel_weight, flags)
-    loss.terms = terms
-    return loss
+    return _terms.depth_term(depth, depth_loss_forward, depth_loss_backward,
+                             dict(target=target, target_weight=target_weight, pixel_weight=pixel_weight), dict(flags=flags))
 
 
 def depth_loss(depth, target, target_weight, pixel_weight=None, space: str = "inverse", norm: str = "l1", align: bool = False,
@@ -283,56 +240,32 @@ class DepthConfig:
 
 
 # ---- the depth maps of a dataset --------------------------------------------------------------------------------------------
-def _pitched_uint16(depth_hw: np.ndarray, device) -> torch.Tensor:
-    """a (H,W) uint16 array on the device, rows ROW_PITCH_ALIGN-byte aligned: a view into a (H, pitch) buffer"""
-    H, W = depth_hw.shape
-    pitch = (2 * W + ROW_PITCH_ALIGN - 1) // ROW_PITCH_ALIGN * ROW_PITCH_ALIGN // 2
-    host = np.zeros((H, pitch), dtype=np.uint16)
-    host[:, :W] = depth_hw
-    return torch.from_numpy(host).to(device)[:, :W]
-
-
-class DepthStore:
+class DepthStore(ResidentStore):
     """The depth maps of a dataset resident on one device -- uint16 with 16-byte aligned rows as the 16-bit PNG held them, f32
     for .npy files -- and the per-step depth target made from them there.  A view without a depth file holds None.  target()
     returns the store's buffer of that geometry, overwritten by the next target() of the same geometry."""
+    column, holds = "depth_path", "depth map"
 
     def __init__(self, maps, scales, sizes, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"a DepthStore lives on a GPU, got {self.device} (there is no CPU path)")
-        self.maps, self.scales, self.sizes = list(maps), list(scales), list(sizes)
-        self._out = {}                              # (H, W, factor) -> the (2,h,w) buffer of that geometry
-
-    def __len__(self):
-        return len(self.maps)
-
-    def has(self, i: int) -> bool:
-        return self.maps[i] is not None
+        super().__init__(maps, sizes, device)
+        self.maps, self.scales = self.records, list(scales)
 
     @classmethod
     def from_dataset(cls, dataset, device="cuda", depth_scale: Optional[float] = None, require_all: bool = True) -> "DepthStore":
         """Every record's depth map (dataset.load_depth), decoded once.  A 16-bit map's metres per unit: the record's
         depth_scale, else the argument, else DEFAULT_DEPTH_SCALE.  require_all: a record without a depth_path is an error
         (False: its view holds None, as the validation set may)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError(f"a DepthStore lives on a GPU, got {device} (there is no CPU path)")
-        n = len(dataset)
-        with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
-            loaded = list(pool.map(dataset.load_depth, range(n)))
+        device = cls.on_gpu(device)
         maps, scales, sizes = [], [], []
-        for i, item in enumerate(loaded):
+        for item in cls._decode(dataset.load_depth, len(dataset), require_all):
             if item is None:
-                if require_all:
-                    raise ValueError(f"record {i} of the dataset has no depth_path")
                 maps.append(None); scales.append(None); sizes.append(None)
                 continue
             depth_hw, scale = item
             H, W = depth_hw.shape
             if depth_hw.dtype == np.uint16:
                 scale = scale if scale is not None else (depth_scale if depth_scale is not None else DEFAULT_DEPTH_SCALE)
-                maps.append(_pitched_uint16(depth_hw, device))
+                maps.append(_pitched(depth_hw, device))
             else:
                 scale = 1.0                 # metres as stored; kept as the dataset's crop, which a contiguous plane must be
                 maps.append(torch.from_numpy(np.ascontiguousarray(depth_hw[:H - H % 16, :W - W % 16], dtype=np.float32)).to(device))
@@ -344,18 +277,53 @@ class DepthStore:
         """-> (depth (h,w) f32, weight (h,w) f32) of view i at the factor: the two planes of one (2,h,w) buffer, written by one
         launch, with the geometry of the colour target (targets.downsampled_geometry of the picture's size).  After the first
         use of a geometry the call allocates nothing on the device and does not synchronise."""
-        f = int(downsample_factor)
-        if f < 1:
-            raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
-        if self.maps[i] is None:
-            raise ValueError(f"view {i} has no depth map")
-        H, W = self.sizes[i]
-        h_full, w_full, h, w = downsampled_geometry(H, W, f)
-        out = self._out.get((H, W, f))
-        if out is None:
-            out = self._out[(H, W, f)] = torch.empty((2, h, w), dtype=torch.float32, device=self.device)
-        src = self.maps[i]
-        if src.dtype == torch.uint16:
-            src = src[:H, :W]
-        depth_resample(src, (h_full, w_full), (h, w), depth_scale=self.scales[i], min_coverage=min_coverage, out=out)
+        size_full, size, out = self._buffer(i, downsample_factor, 2)
+        depth_resample(self._source(i), size_full, size, depth_scale=self.scales[i], min_coverage=min_coverage, out=out)
         return out[0], out[1]
+
+
+# ---- the trainer's term -----------------------------------------------------------------------------------------------------
+class DepthTerm(_terms.TrainerTerm):
+    """GaussianPointCloudTrainer's depth term: depth_loss of the rendered depth against the dataset's depth_path maps, by the
+    weight schedule of its DepthConfig; with mode "relative" the fitted scale and shift are logged with it"""
+    name = "depth"
+
+    def __init__(self, mode: str, config: Optional[DepthConfig], train_config):
+        """mode, config: the trainer's depth ("metric" | "relative") and depth_config arguments, checked here against its
+        TrainConfig; nothing is read from disk and no device is touched before load()"""
+        super().__init__()
+        config = config or DepthConfig()
+        config.check()
+        if mode == "relative" and config.space != "inverse":
+            raise ValueError('depth="relative" needs depth_config.space="inverse": the files hold relative inverse depth')
+        _terms.check_depth_is_rendered(train_config, f'depth="{mode}"', "depth targets are made on the device")
+        if config.num_iterations is None:
+            config = dataclasses.replace(config, num_iterations=max(int(train_config.num_iterations), 1))
+        self.mode, self.config, self.weight_at = mode, config, config.weight_at
+        self.flags = loss_flags(config.space, config.norm, align=mode == "relative", target_is_inverse=mode == "relative")
+
+    def load(self, train_dataset, val_dataset, device):
+        self.load_stores(DepthStore, train_dataset, val_dataset, device, f'depth="{self.mode}"', depth_scale=self.config.depth_scale)
+
+    def value(self, split, view, downsample_factor, image_depth, image_gt, camera_info, pixel_weight):
+        """the store's target and weight at the factor (one launch) and the fused loss on the rendered depth"""
+        store = self.stores[split]
+        if not store.has(view):
+            return None
+        target, target_weight = store.target(view, downsample_factor, self.config.min_coverage)
+        return depth_loss_flags(image_depth, target, target_weight, pixel_weight, self.flags)
+
+    def train_scalars(self, terms):
+        scalars = super().train_scalars(terms)              # terms: {L, S_w, s, t, ...}
+        if self.mode == "relative":
+            scalars += [("train/depth scale", terms[2]), ("train/depth shift", terms[3])]
+        return scalars
+
+
+def trainer_terms(mode: str, config: Optional[DepthConfig], train_config) -> list:
+    """the terms of a trainer's depth and depth_config arguments: a DepthTerm, or none for depth="none" """
+    if mode not in ("none", "metric", "relative"):
+        raise ValueError(f'depth must be "none", "metric" or "relative", got {mode!r}')
+    if mode == "none" and config is not None:
+        raise ValueError('depth_config needs depth="metric" or "relative"')
+    return [] if mode == "none" else [DepthTerm(mode, config, train_config)]

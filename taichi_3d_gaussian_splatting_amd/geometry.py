@@ -17,17 +17,17 @@ pixel without a prior, a normal across a depth edge add nothing and get a gradie
 There is no fallback path: every call goes through _native.call(), and a CPU tensor is refused.
 """
 import ctypes as C
+import dataclasses
 import math
-from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _native
-from .depth import check_plane
-from .targets import MAX_DECODE_THREADS, _pitched_uint8, downsampled_geometry, image_resample
+from . import _native, _terms
+from ._terms import check_plane
+from .targets import ResidentStore, _pitched, image_resample
 
 PRIOR_UNIT_RANGE, PRIOR_FLIP_YZ, NORMAL_FLAGS_ALL = 1, 2, 3        # GS_GEOM_PRIOR_UNIT_RANGE, _PRIOR_FLIP_YZ, _NORMAL_FLAGS_ALL
 INVERSE, SECOND_ORDER, SMOOTH_FLAGS_ALL = 4, 8, 12                  # GS_GEOM_INVERSE, _SECOND_ORDER, _SMOOTH_FLAGS_ALL
@@ -133,11 +133,6 @@ def _check_flags(flags, allowed):
     return flags
 
 
-def _check_upstream(upstream, depth):
-    if upstream is not None and (upstream.dtype != torch.float32 or upstream.numel() != 1 or upstream.device != depth.device):
-        raise ValueError("upstream must be one float32 on the depth's device")
-
-
 def _check_normal_inputs(depth, prior, prior_weight, pixel_weight):
     # what is wrong with a tensor is found before any device is looked at
     for device in (False, True):
@@ -209,7 +204,7 @@ def normal_loss_backward(depth, intrinsics, prior, prior_weight, pixel_weight, m
         out = torch.empty_like(depth)
     else:
         check_plane(out, "out", depth)
-    _check_upstream(upstream, depth)
+    _terms.check_upstream(upstream, depth)
     _bind()
     H, W = int(depth.shape[0]), int(depth.shape[1])
     _native.call("gs_normal_loss_backward", depth.device, _native.shared_ctx(depth.device), depth.data_ptr(), prior.data_ptr(),
@@ -241,54 +236,12 @@ def depth_smooth_backward(depth, guide, pixel_weight, edge_lambda: float, flags:
         out = torch.empty_like(depth)
     else:
         check_plane(out, "out", depth)
-    _check_upstream(upstream, depth)
+    _terms.check_upstream(upstream, depth)
     _bind()
     H, W = int(depth.shape[0]), int(depth.shape[1])
     _native.call("gs_depth_smooth_backward", depth.device, _native.shared_ctx(depth.device), depth.data_ptr(), _ptr(guide), _ptr(pixel_weight),
                  H, W, edge_lambda, flags, terms.data_ptr(), _ptr(upstream), out.data_ptr())
     return out
-
-
-def _upstream_of(grad_loss):
-    return grad_loss.detach().to(torch.float32).reshape(1).contiguous()
-
-
-class _NormalLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, depth, prior, prior_weight, pixel_weight, intrinsics, max_rel_jump, flags):
-        terms = normal_loss_forward(depth.detach(), intrinsics, prior, prior_weight, pixel_weight, max_rel_jump, flags)
-        ctx.save_for_backward(depth, prior, prior_weight, pixel_weight, terms)
-        ctx.scalars = (intrinsics, max_rel_jump, flags)
-        ctx.mark_non_differentiable(terms)
-        return terms[0], terms
-
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_terms):
-        depth, prior, prior_weight, pixel_weight, terms = ctx.saved_tensors
-        if not ctx.needs_input_grad[0] or grad_loss is None:
-            return (None,) * 7
-        intrinsics, max_rel_jump, flags = ctx.scalars
-        grad = normal_loss_backward(depth.detach(), intrinsics, prior, prior_weight, pixel_weight, max_rel_jump, flags, terms,
-                                    _upstream_of(grad_loss))
-        return (grad,) + (None,) * 6
-
-
-class _DepthSmoothness(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, depth, guide, pixel_weight, edge_lambda, flags):
-        terms = depth_smooth_forward(depth.detach(), guide, pixel_weight, edge_lambda, flags)
-        ctx.save_for_backward(depth, guide, pixel_weight, terms)
-        ctx.scalars = (edge_lambda, flags)
-        ctx.mark_non_differentiable(terms)
-        return terms[0], terms
-
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_terms):
-        depth, guide, pixel_weight, terms = ctx.saved_tensors
-        if not ctx.needs_input_grad[0] or grad_loss is None:
-            return (None,) * 5
-        edge_lambda, flags = ctx.scalars
-        return (depth_smooth_backward(depth.detach(), guide, pixel_weight, edge_lambda, flags, terms, _upstream_of(grad_loss)),) + (None,) * 4
 
 
 def normal_loss_flags(depth, intrinsics, prior, prior_weight, pixel_weight=None, max_rel_jump: float = 0.1, flags: int = 0):
@@ -298,9 +251,8 @@ def normal_loss_flags(depth, intrinsics, prior, prior_weight, pixel_weight=None,
     intrinsics = intrinsics_tuple(intrinsics)
     max_rel_jump = _non_negative(max_rel_jump, "max_rel_jump")
     _check_normal_inputs(depth, prior, prior_weight, pixel_weight)
-    loss, terms = _NormalLoss.apply(depth, prior, prior_weight, pixel_weight, intrinsics, max_rel_jump, flags)
-    loss.terms = terms
-    return loss
+    return _terms.depth_term(depth, normal_loss_forward, normal_loss_backward, dict(prior=prior, prior_weight=prior_weight, pixel_weight=pixel_weight),
+                             dict(intrinsics=intrinsics, max_rel_jump=max_rel_jump, flags=flags))
 
 
 def normal_loss(depth, intrinsics, prior, prior_weight, pixel_weight=None, unit_range: bool = True, convention: str = "opencv",
@@ -319,9 +271,8 @@ def depth_smoothness_flags(depth, guide=None, pixel_weight=None, edge_lambda: fl
     flags = _check_flags(flags, SMOOTH_FLAGS_ALL)
     edge_lambda = _non_negative(edge_lambda, "edge_lambda")
     _check_smooth_inputs(depth, guide, pixel_weight)
-    loss, terms = _DepthSmoothness.apply(depth, guide, pixel_weight, edge_lambda, flags)
-    loss.terms = terms
-    return loss
+    return _terms.depth_term(depth, depth_smooth_forward, depth_smooth_backward, dict(guide=guide, pixel_weight=pixel_weight),
+                             dict(edge_lambda=edge_lambda, flags=flags))
 
 
 def depth_smoothness(depth, guide=None, pixel_weight=None, space: str = "inverse", order: int = 1, edge_lambda: float = 10.0):
@@ -383,24 +334,16 @@ def _prior_f32(normal_hw3: np.ndarray, H: int, W: int) -> torch.Tensor:
     return torch.from_numpy(out)
 
 
-class NormalStore:
+class NormalStore(ResidentStore):
     """The normal priors of a dataset resident on one device -- uint8 (H,W,4) with 16-byte aligned rows for 8-bit images, f32
     (4,H,W) for .npy files, the fourth channel the prior's validity -- and the per-step prior made from them there by
     targets.image_resample, with the geometry of the colour target.  A view without a prior holds None.  target() returns the
     store's buffer of that geometry, overwritten by the next target() of the same geometry."""
+    column, holds = "normal_path", "normal prior"
 
     def __init__(self, priors, sizes, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"a NormalStore lives on a GPU, got {self.device} (there is no CPU path)")
-        self.priors, self.sizes = list(priors), list(sizes)
-        self._out = {}                              # (H, W, factor) -> the (4,h,w) buffer of that geometry
-
-    def __len__(self):
-        return len(self.priors)
-
-    def has(self, i: int) -> bool:
-        return self.priors[i] is not None
+        super().__init__(priors, sizes, device)
+        self.priors = self.records
 
     def unit_range(self, i: int) -> bool:
         """whether view i's prior holds (n + 1) / 2 (an 8-bit image) and not n itself (a .npy file)"""
@@ -410,22 +353,15 @@ class NormalStore:
     def from_dataset(cls, dataset, device="cuda", require_all: bool = True) -> "NormalStore":
         """Every record's normal prior (dataset.load_normal), decoded once.  require_all: a record without a normal_path is an
         error (False: its view holds None, as the validation set may)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError(f"a NormalStore lives on a GPU, got {device} (there is no CPU path)")
-        n = len(dataset)
-        with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
-            loaded = list(pool.map(dataset.load_normal, range(n)))
+        device = cls.on_gpu(device)
         priors, sizes = [], []
-        for i, normal in enumerate(loaded):
+        for normal in cls._decode(dataset.load_normal, len(dataset), require_all):
             if normal is None:
-                if require_all:
-                    raise ValueError(f"record {i} of the dataset has no normal_path")
                 priors.append(None); sizes.append(None)
                 continue
             H, W = normal.shape[0] - normal.shape[0] % 16, normal.shape[1] - normal.shape[1] % 16     # the dataset's crop of the picture
             if normal.dtype == np.uint8:
-                priors.append(_pitched_uint8(_prior_u8(normal), device))
+                priors.append(_pitched(_prior_u8(normal), device))
             else:
                 priors.append(_prior_f32(normal, H, W).to(device))
             sizes.append((H, W))
@@ -435,21 +371,71 @@ class NormalStore:
         """-> (prior (3,h,w) f32, weight (h,w) f32) of view i at the factor: out[:3] and out[3] of one (4,h,w) buffer, written
         by one launch.  The weight is the share of the filter that pixels with a prior cover.  After the first use of a geometry
         the call allocates nothing on the device and does not synchronise."""
-        f = int(downsample_factor)
-        if f < 1:
-            raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
-        if self.priors[i] is None:
-            raise ValueError(f"view {i} has no normal prior")
-        H, W = self.sizes[i]
-        h_full, w_full, h, w = downsampled_geometry(H, W, f)
-        out = self._out.get((H, W, f))
-        if out is None:
-            out = self._out[(H, W, f)] = torch.empty((4, h, w), dtype=torch.float32, device=self.device)
-        src = self.priors[i]
-        if src.dtype == torch.uint8:
-            src = src[:H, :W]
-        image_resample(src, (h_full, w_full), (h, w), out=out, alpha=True)
+        size_full, size, out = self._buffer(i, downsample_factor, 4)
+        image_resample(self._source(i), size_full, size, out=out, alpha=True)
         return out[:3], out[3]
+
+
+# ---- the trainer's terms ----------------------------------------------------------------------------------------------------
+class _GeometryTerm(_terms.TrainerTerm):
+    """a term of a checked GeometryConfig: constant weight <name>_weight from start_iteration on"""
+
+    def __init__(self, config: GeometryConfig):
+        super().__init__()
+        self.config, self.start_iteration, self.weight = config, config.start_iteration, getattr(config, f"{self.name}_weight")
+
+    def weight_at(self, iteration):
+        return self.weight
+
+
+class SmoothTerm(_GeometryTerm):
+    """depth_smoothness of the rendered depth with the colour target as its guide: it needs no data of its own"""
+    name = "smooth"
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.flags = smooth_flags(config.smooth_space, config.smooth_order)
+
+    def value(self, split, view, downsample_factor, image_depth, image_gt, camera_info, pixel_weight):
+        return depth_smoothness_flags(image_depth, image_gt, pixel_weight, self.config.smooth_edge_lambda, self.flags)
+
+
+class NormalTerm(_GeometryTerm):
+    """normal_loss of the rendered depth against the dataset's normal_path priors, resident on the device"""
+    name = "normal"
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._intrinsics = {}                       # (split, view, factor) -> (fx, fy, cx, cy), read by the host once
+
+    def load(self, train_dataset, val_dataset, device):
+        self.load_stores(NormalStore, train_dataset, val_dataset, device, "geometry.normal_weight > 0")
+
+    def value(self, split, view, downsample_factor, image_depth, image_gt, camera_info, pixel_weight):
+        """the cosine loss against the view's prior at the factor (one launch for the prior)"""
+        store = self.stores[split]
+        if not store.has(view):
+            return None
+        key = (split, view, downsample_factor)
+        intrinsics = self._intrinsics.get(key)
+        if intrinsics is None:
+            intrinsics = self._intrinsics[key] = intrinsics_tuple(camera_info.camera_intrinsics)
+        prior, prior_weight = store.target(view, downsample_factor)
+        return normal_loss_flags(image_depth, intrinsics, prior, prior_weight, pixel_weight, self.config.normal_max_rel_jump,
+                                 normal_flags(store.unit_range(view), self.config.normal_convention))
+
+
+def trainer_terms(geometry: Optional[GeometryConfig], train_config) -> list:
+    """the terms of a trainer's geometry argument, checked against its TrainConfig, over a copy of it: smoothness, then normal
+    prior, each if its weight is > 0; nothing is read from disk and no device is touched before their load()"""
+    if geometry is None:
+        return []
+    if not isinstance(geometry, GeometryConfig):
+        raise ValueError(f"geometry must be a GeometryConfig or None, got {type(geometry).__name__}")
+    geometry.check()
+    _terms.check_depth_is_rendered(train_config, "geometry", "its guide and priors are made on the device")
+    config = dataclasses.replace(geometry)
+    return [term(config) for term in (SmoothTerm, NormalTerm) if getattr(config, f"{term.name}_weight") > 0.0]
 
 
 def normals_to_uint8(normals: torch.Tensor) -> torch.Tensor:

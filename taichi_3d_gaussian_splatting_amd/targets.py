@@ -163,16 +163,78 @@ def _with_mask(image_hwc: torch.Tensor, mask_hw: torch.Tensor) -> torch.Tensor:
     return torch.cat([image_hwc[:, :, :3], mask_hw[:, :, None]], dim=2).contiguous()
 
 
-def _pitched_uint8(image_hwc: torch.Tensor, device) -> torch.Tensor:
-    """a (H,W,C) uint8 CPU tensor on the device, rows ROW_PITCH_ALIGN-byte aligned: a view into a (H, pitch) buffer"""
-    H, W, ch = image_hwc.shape
-    pitch = (W * ch + ROW_PITCH_ALIGN - 1) // ROW_PITCH_ALIGN * ROW_PITCH_ALIGN
-    host = torch.zeros((H, pitch), dtype=torch.uint8)
-    host[:, :W * ch] = image_hwc.reshape(H, W * ch)
-    return host.to(device).as_strided((H, W, ch), (pitch, ch, 1))
+def _pitched(image, device) -> torch.Tensor:
+    """a (H,W) or (H,W,C) uint8 or uint16 CPU tensor or array on the device, rows ROW_PITCH_ALIGN-byte aligned: a view into a
+    (H, pitch) buffer"""
+    image = torch.as_tensor(image).contiguous()
+    H, row = image.shape[0], image[0].numel()
+    align = ROW_PITCH_ALIGN // image.element_size()
+    pitch = (row + align - 1) // align * align
+    host = torch.zeros((H, pitch), dtype=image.dtype)
+    host[:, :row] = image.reshape(H, row)
+    return host.to(device).as_strided(image.shape, (pitch,) + image.stride()[1:])
 
 
-class TargetStore:
+class ResidentStore:
+    """What the stores of a dataset's per-view data resident on one device share (TargetStore here, depth.DepthStore,
+    geometry.NormalStore): `records`, one device tensor per view or None, and `sizes`, the (H, W) of the dataset's crop of each
+    picture.  A store adds what a decoded record becomes on the device (from_dataset) and a target() that fills the buffer of
+    _buffer() from _source() with its resample call."""
+    column = holds = ""                             # the dataset column and what a record holds, for the messages
+
+    def __init__(self, records, sizes, device):
+        self.device = self.on_gpu(device)
+        self.records, self.sizes = list(records), list(sizes)
+        self._outs = {}                             # planes -> {(H, W, factor) -> the (planes,h,w) buffer of that geometry}
+
+    @classmethod
+    def on_gpu(cls, device) -> torch.device:
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"a {cls.__name__} lives on a GPU, got {device} (there is no CPU path)")
+        return device
+
+    def __len__(self):
+        return len(self.records)
+
+    def has(self, i: int) -> bool:
+        return self.records[i] is not None
+
+    @classmethod
+    def _decode(cls, loader, n: int, require_all: bool = True) -> list:
+        """-> [loader(i) for i < n], decoded once in this process (no worker processes: the GPU may be initialised).
+        require_all: a record the loader has nothing for is an error (False: it stays None)"""
+        with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
+            loaded = list(pool.map(loader, range(n)))
+        missing = [i for i, item in enumerate(loaded) if item is None]
+        if require_all and missing:
+            raise ValueError(f"record {missing[0]} of the dataset has no {cls.column}")
+        return loaded
+
+    def _source(self, i: int) -> torch.Tensor:
+        """what the resample call reads of view i: an integer-typed record is stored uncropped, the dataset's crop is its
+        top-left region"""
+        src, (H, W) = self.records[i], self.sizes[i]
+        return src if src.dtype.is_floating_point else src[:H, :W]
+
+    def _buffer(self, i: int, downsample_factor: int, planes: int):
+        """-> ((h_full, w_full), (h, w), out): downsampled_geometry of view i at the factor and the store's (planes,h,w) f32
+        buffer of that geometry, allocated at its first use"""
+        f = int(downsample_factor)
+        if f < 1:
+            raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
+        if self.records[i] is None:
+            raise ValueError(f"view {i} has no {self.holds}")
+        H, W = self.sizes[i]
+        h_full, w_full, h, w = downsampled_geometry(H, W, f)
+        outs = self._outs.setdefault(planes, {})
+        out = outs.get((H, W, f))
+        if out is None:
+            out = outs[(H, W, f)] = torch.empty((planes, h, w), dtype=torch.float32, device=self.device)
+        return (h_full, w_full), (h, w), out
+
+
+class TargetStore(ResidentStore):
     """The images of a dataset resident on one device, and the per-step target made from them there.
 
     from_dataset() decodes every image once, in this process (no worker processes: the GPU may be initialised), and keeps
@@ -184,24 +246,23 @@ class TargetStore:
     every stored image has four channels, and target(i, f, with_weight=True) also returns the mask through the same filter.
     target(i, f) then costs one launch.  The image it returns is the store's buffer for that geometry and is overwritten by the
     next target() of the same geometry: use it (loss forward and backward) before asking for the next one."""
+    column = "image_path"
 
     def __init__(self, images, q: torch.Tensor, t: torch.Tensor, camera_infos, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"a TargetStore lives on a GPU, got {self.device} (there is no CPU path)")
-        self.images = list(images)
+        camera_infos = list(camera_infos)
+        super().__init__(images, [(int(c.camera_height), int(c.camera_width)) for c in camera_infos], device)
+        self.images = self.records
         self.q, self.t = q.to(self.device), t.to(self.device)
-        self.camera_infos = list(camera_infos)      # intrinsics on the device: views of self.intrinsics[1]
-        self.intrinsics = {1: torch.stack([c.camera_intrinsics.to(torch.float32) for c in self.camera_infos]).to(self.device)}
-        for i, c in enumerate(self.camera_infos):
-            self.camera_infos[i] = CameraInfo(camera_intrinsics=self.intrinsics[1][i], camera_height=int(c.camera_height),
-                                              camera_width=int(c.camera_width), camera_id=c.camera_id)
-        self._out = {}                              # (H, W, factor) -> the (3,h,w) buffer of that geometry
-        self._out_rgba = {}                         # the same for with_weight=True: (4,h,w), image and weight in one buffer
+        self.intrinsics = {1: torch.stack([c.camera_intrinsics.to(torch.float32) for c in camera_infos]).to(self.device)}
+        # intrinsics on the device: views of self.intrinsics[1]
+        self.camera_infos = [CameraInfo(camera_intrinsics=self.intrinsics[1][i], camera_height=int(c.camera_height),
+                                        camera_width=int(c.camera_width), camera_id=c.camera_id) for i, c in enumerate(camera_infos)]
         self._infos = {}                            # (view, factor) -> CameraInfo
 
-    def __len__(self):
-        return len(self.images)
+    @property
+    def _out(self):
+        """the (3,h,w) buffers handed out so far, by geometry"""
+        return self._outs.get(3, {})
 
     @classmethod
     def from_dataset(cls, dataset, device="cuda", mask_source: Optional[str] = None, mask_erode: int = 0) -> "TargetStore":
@@ -214,9 +275,8 @@ class TargetStore:
             raise ValueError("mask_erode must be >= 0, and needs a mask_source")
         device = torch.device(device)
         n = len(dataset)
-        with ThreadPoolExecutor(max_workers=max(1, min(MAX_DECODE_THREADS, n))) as pool:
-            raw = list(pool.map(dataset.load_raw, range(n)))
-            masks = list(pool.map(dataset.load_mask, range(n))) if mask_source == "file" else [None] * n
+        raw = cls._decode(dataset.load_raw, n)
+        masks = cls._decode(dataset.load_mask, n, require_all=False) if mask_source == "file" else [None] * n
         images, qs, ts, infos = [], [], [], []
         for i, (image_hwc, q, t, info) in enumerate(raw):
             if mask_source == "file":
@@ -229,7 +289,7 @@ class TargetStore:
                     raise ValueError(f'mask_source="alpha": image {i} of the dataset has no alpha channel')
                 if mask_erode:
                     image_hwc = _with_mask(image_hwc, erode_mask(image_hwc[:, :, 3], mask_erode))
-            stored = _pitched_uint8(image_hwc, device)
+            stored = _pitched(image_hwc, device)
             H, W = int(info.camera_height), int(info.camera_width)          # the dataset's crop of the decoded image
             size_full, info = autoscaled_camera_info(info)
             if size_full is not None:
@@ -240,12 +300,6 @@ class TargetStore:
             infos.append(info)
         return cls(images, torch.stack(qs).to(torch.float32), torch.stack(ts).to(torch.float32), infos, device)
 
-    def _source(self, i):
-        image, info = self.images[i], self.camera_infos[i]
-        if image.dtype == torch.uint8:
-            return image[:info.camera_height, :info.camera_width]
-        return image
-
     def target(self, i: int, downsample_factor: int = 1, with_weight: bool = False):
         """-> (image (3,h,w) f32, q (1,4), t (1,3), CameraInfo) of view i at the factor: sizes and intrinsics as
         _downsample_image_and_camera_info has them; at factor 1 the dataset's own crop.  After the first use of a geometry
@@ -253,24 +307,15 @@ class TargetStore:
         with_weight=True (the stored image must have four channels): -> (image, q, t, CameraInfo, weight (h,w) f32); image and
         weight are out[:3] and out[3] of one (4,h,w) buffer, both contiguous, written by one launch; the image is bit for bit
         the one target(i, f) returns."""
+        size_full, (h, w), out = self._buffer(i, downsample_factor, 4 if with_weight else 3)
         f = int(downsample_factor)
-        if f < 1:
-            raise ValueError(f"downsample_factor must be >= 1, got {downsample_factor}")
-        base = self.camera_infos[i]
-        H, W = base.camera_height, base.camera_width
-        h_full, w_full, h, w = downsampled_geometry(H, W, f)
-        key = (H, W, f)
-        outs, planes = (self._out_rgba, 4) if with_weight else (self._out, 3)
-        out = outs.get(key)
-        if out is None:
-            out = outs[key] = torch.empty((planes, h, w), dtype=torch.float32, device=self.device)
         if f not in self.intrinsics:
             self.intrinsics[f] = downsampled_intrinsics(self.intrinsics[1], f)
         info = self._infos.get((i, f))
         if info is None:
             info = self._infos[(i, f)] = CameraInfo(camera_intrinsics=self.intrinsics[f][i], camera_height=h, camera_width=w,
-                                                    camera_id=base.camera_id)
-        image_resample(self._source(i), (h_full, w_full), (h, w), out=out, alpha=with_weight)
+                                                    camera_id=self.camera_infos[i].camera_id)
+        image_resample(self._source(i), size_full, (h, w), out=out, alpha=with_weight)
         if with_weight:
             return out[:3], self.q[i:i + 1], self.t[i:i + 1], info, out[3]
         return out, self.q[i:i + 1], self.t[i:i + 1], info

@@ -218,7 +218,7 @@ def store_of(images):
     n = len(images)
     infos = [CameraInfo(torch.tensor([[100.0 + i, 0.0, 56.0], [0.0, 90.0, 40.0], [0.0, 0.0, 1.0]]), im.shape[0] // 16 * 16,
                         im.shape[1] // 16 * 16, i) for i, im in enumerate(images)]
-    stored = [targets._pitched_uint8(torch.from_numpy(np.array(im)), DEV) for im in images]
+    stored = [targets._pitched(torch.from_numpy(np.array(im)), DEV) for im in images]
     q = torch.nn.functional.normalize(torch.arange(4.0 * n).reshape(n, 4) + 1.0, dim=1)
     return targets.TargetStore(stored, q, torch.arange(3.0 * n).reshape(n, 3), infos, DEV), q
 

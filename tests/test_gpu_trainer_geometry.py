@@ -127,8 +127,8 @@ def test_start_iteration_and_single_terms(data, tmp_path):
     assert set(trainer.validation(4)) == {"loss", "psnr", "ssim", "inference_time", "smooth_loss"}
 
 
-def test_masks_depth_and_geometry_run_together(data, tmp_path):
-    root = tmp_path / "all"
+def masked_depth_and_normal_data(data, root):
+    """-> (the dataset JSON paths, depth_trainer_util's data): data["normal"] with a depth_path and a mask_path on every record too"""
     os.makedirs(root)
     with_depth = DU.add_depth(data["normal"], root, DEV)                 # the records keep their normal_path
     mask = np.zeros((TU.H, TU.W), np.uint8)
@@ -140,6 +140,11 @@ def test_masks_depth_and_geometry_run_together(data, tmp_path):
         assert all("normal_path" in r and "depth_path" in r for r in records)
         paths[split] = str(root / f"{split}.json")
         json.dump(records, open(paths[split], "w"))
+    return paths, with_depth
+
+
+def test_masks_depth_and_geometry_run_together(data, tmp_path):
+    paths, with_depth = masked_depth_and_normal_data(data, tmp_path / "all")
     trainer = make_trainer(dict(paths=paths), tmp_path / "run", num_iterations=2, initial_downsample_factor=1, pixel_weights="file",
                            depth="metric", geometry=GeometryConfig(smooth_weight=0.5, normal_weight=0.1), log_loss_interval=1,
                            log_metrics_interval=1, seed=3)
@@ -160,6 +165,72 @@ def test_masks_depth_and_geometry_run_together(data, tmp_path):
     assert 0 < both < one
     inside = geometry.depth_smoothness(rendered, image_gt, weight).terms[2].item()
     assert 0 < inside < geometry.depth_smoothness(rendered, image_gt).terms[2].item()
+
+
+def test_first_step_with_every_term_is_the_manual_step(data, tmp_path):
+    """One trainer iteration with a mask, metric depth and both geometry terms at 32x48 against the same step written out by
+    hand: the nodes on the rendered depth made in the order smoothness, normal, depth, the scalars summed as
+    ((loss + w_d depth) + w_s smooth) + w_n normal.  Gradients and logged values are equal bit for bit."""
+    import copy
+    import dataclasses
+    from taichi_3d_gaussian_splatting_amd import depth as depth_module
+    from taichi_3d_gaussian_splatting_amd import GaussianPointCloudRasterisation as Rast
+    from taichi_3d_gaussian_splatting_amd.GaussianPointAdaptiveController import GaussianPointAdaptiveController
+    from taichi_3d_gaussian_splatting_amd.GaussianPointCloudScene import GaussianPointCloudScene
+    from taichi_3d_gaussian_splatting_amd.ImagePoseDataset import ImagePoseDataset
+    from taichi_3d_gaussian_splatting_amd.LossFunction import LossFunction
+    from taichi_3d_gaussian_splatting_amd.targets import TargetStore
+    factor = 2
+    g = GeometryConfig(smooth_weight=0.5, normal_weight=0.1)
+    paths, _ = masked_depth_and_normal_data(data, tmp_path / "all")
+    trainer = make_trainer(dict(paths=paths), tmp_path / "run", num_iterations=1, initial_downsample_factor=factor, pixel_weights="file",
+                           depth="metric", geometry=g, log_loss_interval=1, log_metrics_interval=10 ** 6, seed=3)
+    trainer.train()
+    torch.cuda.synchronize()
+    view = trainer.view_order[0]
+
+    config = trainer.config
+    scene = GaussianPointCloudScene.from_parquet(paths["cloud"], config=config.gaussian_point_cloud_scene_config, device=DEV)
+    controller = GaussianPointAdaptiveController(
+        config=config.adaptive_controller_config,
+        maintained_parameters=GaussianPointAdaptiveController.GaussianPointAdaptiveControllerMaintainedParameters(
+            pointcloud=scene.point_cloud, pointcloud_features=scene.point_cloud_features,
+            point_invalid_mask=scene.point_invalid_mask, point_object_id=scene.point_object_id), seed=3)
+    rast_config = copy.copy(config.rasterisation_config)
+    rast_config.differentiable_depth = True
+    rast = Rast(rast_config, backward_valid_point_hook=controller.update)
+    loss_fn = LossFunction(config.loss_function_config)
+    dataset = ImagePoseDataset(paths["train"])
+    depth_config = dataclasses.replace(depth_module.DepthConfig(), num_iterations=1)
+    targets = TargetStore.from_dataset(dataset, DEV, mask_source="file")
+    depths = depth_module.DepthStore.from_dataset(dataset, DEV, depth_scale=depth_config.depth_scale)
+    normals = geometry.NormalStore.from_dataset(dataset, DEV)
+    gt, q, t, info, weight = targets.target(view, factor, with_weight=True)
+    assert tuple(weight.shape) == (32, 48) and 0 < weight.sum().item() < 32 * 48
+    img, rendered, _ = rast(Rast.GaussianPointCloudRasterisationInput(
+        point_cloud=scene.point_cloud, point_cloud_features=scene.point_cloud_features, point_object_id=scene.point_object_id,
+        point_invalid_mask=scene.point_invalid_mask, camera_info=info, q_pointcloud_camera=q, t_pointcloud_camera=t,
+        color_max_sh_band=0))
+    L, l1, ld = loss_fn(img.permute(2, 0, 1), gt, point_invalid_mask=scene.point_invalid_mask,
+                        pointcloud_features=scene.point_cloud_features, clamp_predicted=True, pixel_weight=weight)
+    smooth = geometry.depth_smoothness_flags(rendered, gt, weight, g.smooth_edge_lambda, geometry.smooth_flags(g.smooth_space, g.smooth_order))
+    prior, prior_weight = normals.target(view, factor)
+    normal = geometry.normal_loss_flags(rendered, geometry.intrinsics_tuple(info.camera_intrinsics), prior, prior_weight, weight,
+                                        g.normal_max_rel_jump, geometry.normal_flags(normals.unit_range(view), g.normal_convention))
+    target, target_weight = depths.target(view, factor, depth_config.min_coverage)
+    depth_term = depth_module.depth_loss_flags(rendered, target, target_weight, weight,
+                                               depth_module.loss_flags(depth_config.space, depth_config.norm))
+    total = ((L + depth_config.weight_at(0) * depth_term) + g.smooth_weight * smooth) + g.normal_weight * normal
+    total.backward()
+    torch.cuda.synchronize()
+    for term in (depth_term, smooth, normal):
+        assert term.terms[0].item() > 0                                  # every term is live in this step
+    for tag, value in (("train/loss", L.item()), ("train/l1 loss", l1.item()), ("train/ssim loss", ld.item()),
+                       ("train/depth loss", depth_term.terms[0].item()), ("train/smooth loss", smooth.terms[0].item()),
+                       ("train/normal loss", normal.terms[0].item())):
+        assert logged(trainer, tag) == [(0, float(value))], tag
+    assert torch.equal(trainer.scene.point_cloud.grad, scene.point_cloud.grad) and bool(scene.point_cloud.grad.any())
+    assert torch.equal(trainer.scene.point_cloud_features.grad, scene.point_cloud_features.grad)
 
 
 def test_what_cannot_work_is_refused(data, tmp_path):

@@ -42,7 +42,7 @@ def main():
     host_f32 = u8.permute(2, 0, 1).float().div(255).contiguous()
     dev_f32 = host_f32.to(DEV)
     info = CameraInfo(torch.tensor([[1152.0, 0.0, 960.0], [0.0, 1152.0, 544.0], [0.0, 0.0, 1.0]]), HEIGHT, WIDTH, 0)
-    store = targets.TargetStore([targets._pitched_uint8(u8, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
+    store = targets.TargetStore([targets._pitched(u8, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
 
     def resized(image, f):
         h_full, w_full, h, w = targets.downsampled_geometry(HEIGHT, WIDTH, f)

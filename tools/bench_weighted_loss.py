@@ -116,7 +116,7 @@ def main():
         # the target: the same picture resident as uint8 RGBA, at the size itself (factor 1) and at half of it
         u8 = torch.cat([(gt.permute(1, 2, 0) * 255).round().to(torch.uint8), (weight * 255).round().to(torch.uint8)[..., None]], dim=2).cpu()
         info = CameraInfo(torch.tensor([[1152.0, 0.0, w / 2], [0.0, 1152.0, h / 2], [0.0, 0.0, 1.0]]), h - h % 16, w - w % 16, 0)
-        store = targets.TargetStore([targets._pitched_uint8(u8, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
+        store = targets.TargetStore([targets._pitched(u8, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
         for f in (1, 2):
             plain = store.target(0, f)[0].clone()
             both = store.target(0, f, with_weight=True)
@@ -144,7 +144,7 @@ def main():
                           (soft_mask(s.height, s.width, "cpu") * 255).round().to(torch.uint8)[..., None]], dim=2)
         info = CameraInfo(torch.tensor(s.camera_intrinsics), s.height - s.height % 16, s.width - s.width % 16, 0)
         assert (info.camera_height, info.camera_width) == (s.height, s.width), "the workload's size must be a multiple of 16"
-        store = targets.TargetStore([targets._pitched_uint8(rgba, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
+        store = targets.TargetStore([targets._pitched(rgba, DEV)], torch.tensor([[0.0, 0.0, 0.0, 1.0]]), torch.zeros(1, 3), [info], DEV)
 
         def iteration(with_weight):
             def it():
