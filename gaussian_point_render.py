@@ -21,6 +21,8 @@ before it is written and measured, every other frame is rendered as without the 
 derived from the rendered depth (geometry.depth_normals) as an 8-bit PNG (n + 1) / 2, (0,0,0) where there is none:
 DIR/normal_<i:03>.png, in the camera frame of the rasteriser (x right, y down, z forward); --normals_max_rel_jump J (default 0.1)
 leaves out the normals across a depth change of more than J times the depth.  With --normals_to, --output_prefix is optional.
+--normals_source gaussians writes the rendered per-Gaussian normals instead (normals.rendered_normals), normalised per pixel where
+the blend is at least --normals_min_length (default 0.5) long and (0,0,0) elsewhere.
 """
 import argparse
 import json
@@ -57,6 +59,10 @@ if __name__ == "__main__":
     parser.add_argument("--appearance", type=str, default="", help="an appearance_<iteration>.pt of the trainer: per-view colour transforms")
     parser.add_argument("--normals_to", type=str, default="", help="write the depth-derived normal map of every pose into this directory")
     parser.add_argument("--normals_max_rel_jump", type=float, default=0.1, help="no normal across a depth change above this share of the depth")
+    parser.add_argument("--normals_source", choices=("depth", "gaussians"), default="depth", help="with --normals_to: the normal of the rendered "
+                        "depth, or the rendered per-Gaussian normals")
+    parser.add_argument("--normals_min_length", type=float, default=0.5, help="with --normals_source gaussians: a pixel whose blended normal "
+                        "is shorter than this is written as (0,0,0)")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
     if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to or args.normals_to)):
@@ -113,8 +119,9 @@ if __name__ == "__main__":
             raise SystemExit(0)
 
     if args.normals_to:
-        count = renderer.write_normals(args.normals_to, targets=targets, max_rel_jump=args.normals_max_rel_jump)
-        print(json.dumps({"normals": args.normals_to, "frames": count}))
+        count = renderer.write_normals(args.normals_to, targets=targets, max_rel_jump=args.normals_max_rel_jump, source=args.normals_source,
+                                       min_length=args.normals_min_length)
+        print(json.dumps(dict({"normals": args.normals_to, "frames": count}, **({"source": "gaussians"} if args.normals_source == "gaussians" else {}))))
         if not args.output_prefix:
             raise SystemExit(0)
 

@@ -6,7 +6,9 @@
 depth_path maps (INTEGRATION.md "Depth supervision in the trainer");
 --depth_smooth W [--smooth_order 1|2 --smooth_space depth|inverse --smooth_edge_lambda L] adds an edge-aware smoothness of the
 rendered depth, and --normal_prior W [--normal_convention opencv|opengl] a normal loss against the dataset's normal_path priors
-(INTEGRATION.md "Geometry regularisers")."""
+(INTEGRATION.md "Geometry regularisers");
+--normal_consistency W [--consistency_min_length L --consistency_start N] adds the consistency of the rendered Gaussian normals
+with the normal of the rendered depth, which needs no data (INTEGRATION.md "Normal consistency")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -38,7 +40,15 @@ if __name__ == "__main__":
     parser.add_argument("--normal_prior", type=float, default=None, metavar="W", help="weight of the normal loss against the dataset's "
                         "normal_path priors")
     parser.add_argument("--normal_convention", choices=("opencv", "opengl"), default=None, help="with --normal_prior: the priors' camera frame")
+    parser.add_argument("--normal_consistency", type=float, default=None, metavar="W", help="weight of the consistency between the rendered "
+                        "Gaussian normals and the normal of the rendered depth (needs no data)")
+    parser.add_argument("--consistency_min_length", type=float, default=None, help="with --normal_consistency: a pixel whose blended normal "
+                        "is shorter than this is left out")
+    parser.add_argument("--consistency_start", type=int, default=None, metavar="N", help="with --normal_consistency: the first iteration of the "
+                        "geometry terms (GeometryConfig.start_iteration)")
     args = parser.parse_args()
+    if args.normal_consistency is None and (args.consistency_min_length is not None or args.consistency_start is not None):
+        parser.error("--consistency_min_length and --consistency_start need --normal_consistency")
     if args.depth_smooth is None and (args.smooth_order is not None or args.smooth_space is not None or args.smooth_edge_lambda is not None):
         parser.error("--smooth_order, --smooth_space and --smooth_edge_lambda need --depth_smooth")
     if args.normal_prior is None and args.normal_convention is not None:
@@ -72,10 +82,12 @@ if __name__ == "__main__":
         if args.depth_norm is not None:
             depth_config.norm = args.depth_norm
     geometry_config = None
-    if args.depth_smooth is not None or args.normal_prior is not None:
+    if args.depth_smooth is not None or args.normal_prior is not None or args.normal_consistency is not None:
         from taichi_3d_gaussian_splatting_amd.geometry import GeometryConfig
         chosen = dict(smooth_weight=args.depth_smooth, smooth_order=args.smooth_order, smooth_space=args.smooth_space,
-                      smooth_edge_lambda=args.smooth_edge_lambda, normal_weight=args.normal_prior, normal_convention=args.normal_convention)
+                      smooth_edge_lambda=args.smooth_edge_lambda, normal_weight=args.normal_prior, normal_convention=args.normal_convention,
+                      consistency_weight=args.normal_consistency, consistency_min_length=args.consistency_min_length,
+                      start_iteration=args.consistency_start)
         geometry_config = GeometryConfig(**{name: value for name, value in chosen.items() if value is not None})
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
                                         mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,

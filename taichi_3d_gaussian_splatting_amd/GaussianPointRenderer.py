@@ -93,9 +93,10 @@ class GaussianPointRenderer:
         return q_rows.reshape(-1, K, 4), t_rows.reshape(-1, K, 3)
 
     def render(self, q_rows: torch.Tensor, t_rows: torch.Tensor, camera_info: Optional[CameraInfo] = None, depth: bool = False,
-               alpha: bool = False):
+               alpha: bool = False, keep_frame: bool = False):
         """one frame under the (K,4), (K,3) pose rows -> (image (H,W,3) f32, depth (H,W) or None), band 3, no gradient; with
-        alpha=True (which takes the depth rasteriser) a third value, the accumulated alpha (H,W)"""
+        alpha=True (which takes the depth rasteriser) a third value, the accumulated alpha (H,W).  keep_frame (with depth or
+        alpha): the depth rasteriser keeps the frame for render_channels"""
         Rast = GaussianPointCloudRasterisation
         with torch.no_grad():
             outputs = (self._with_depth() if depth or alpha else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
@@ -107,7 +108,7 @@ class GaussianPointRenderer:
                 q_pointcloud_camera=q_rows,
                 t_pointcloud_camera=t_rows,
                 color_max_sh_band=3,
-            ), **({"return_accumulated_alpha": True} if alpha else {}))
+            ), **({"return_accumulated_alpha": True} if alpha else {}), **({"keep_frame": True} if keep_frame else {}))
         image, image_depth = outputs[0], outputs[1]
         if alpha:
             return image, (image_depth if depth else None), outputs[3]
@@ -131,13 +132,19 @@ class GaussianPointRenderer:
                              alpha=[r[2] for r in rendered], image=[r[0] for r in rendered])
         return volume
 
-    def write_normals(self, directory, targets=None, max_rel_jump: float = 0.1):
+    def write_normals(self, directory, targets=None, max_rel_jump: float = 0.1, source: str = "depth", min_length: float = 0.5):
         """Render every camera of the config (or every view of `targets`, a targets.TargetStore, under its own pose and camera)
         with depth and write the depth-derived camera-space normal map (geometry.depth_normals: x right, y down, z forward)
         to <directory>/normal_<i:03>.png as the 8-bit RGB image (n + 1) / 2, (0,0,0) where there is no normal -- the encoding
-        ImagePoseDataset.load_normal reads.  The intrinsics are read by the host once per camera.  -> the number of files"""
+        ImagePoseDataset.load_normal reads.  The intrinsics are read by the host once per camera.  -> the number of files
+        source="gaussians": the rendered per-Gaussian normals instead (normals.rendered_normals over the kept frame), normalised
+        per pixel where the blend is at least min_length long, (0,0,0) elsewhere; same encoder."""
         import PIL.Image
         from . import geometry
+        from . import normals as _normals
+        if source not in ("depth", "gaussians"):
+            raise ValueError(f'source must be "depth" or "gaussians", got {source!r}')
+        min_length = _normals._positive(min_length, "min_length")
         os.makedirs(str(directory), exist_ok=True)
         if targets is None:
             q_rows, t_rows = self.pose_rows()
@@ -149,6 +156,14 @@ class GaussianPointRenderer:
             infos = [targets.target(i, 1)[3] for i in range(len(targets))]
         intrinsics = {}
         for i, info in enumerate(infos):
+            if source == "gaussians":
+                rast = self._with_depth()
+                self.render(q_rows[i], t_rows[i], camera_info=info, depth=True, keep_frame=True)
+                with torch.no_grad():
+                    rendered = _normals.rendered_normals(rast, self.scene, (q_rows[i].contiguous(), t_rows[i].contiguous()))
+                    coded = geometry.normals_to_uint8(_normals.unit_normals(rendered, min_length))
+                PIL.Image.fromarray(coded.cpu().numpy()).save(os.path.join(str(directory), f"normal_{i:03d}.png"))
+                continue
             if id(info.camera_intrinsics) not in intrinsics:
                 intrinsics[id(info.camera_intrinsics)] = geometry.intrinsics_tuple(info.camera_intrinsics)
             _, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=True)

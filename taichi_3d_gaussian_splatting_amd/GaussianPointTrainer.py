@@ -322,7 +322,13 @@ class GaussianPointCloudTrainer:
             self.rasterisation.config.differentiable_depth = True
         for term in self.terms:
             term.load(self.train_dataset, self.val_dataset, self.device)
-        stores = {term.name: (term.stores["train"], term.stores["val"]) for term in self.terms}
+            if hasattr(term, "bind"):
+                term.bind(self)
+        # (q, t) of the view being rendered, and whether validation keeps its frames: for a term that renders more over the
+        # step's frame than the depth (normals.ConsistencyTerm)
+        self.current_pose = None
+        self._keep_validation_frame = any(term.name == "consistency" for term in self.terms)
+        stores ={term.name: (term.stores["train"], term.stores["val"]) for term in self.terms}
         self.train_depth, self.val_depth = stores.get("depth", (None, None))
         self.train_normals, self.val_normals = stores.get("normal", (None, None))
         # the order the training views are visited in: one seeded permutation per epoch, appended as the run goes
@@ -425,7 +431,8 @@ class GaussianPointCloudTrainer:
             view = self._view_at(iteration)
             image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self._target(
                 self.train_targets, train_items, view, downsample_factor)
-            rasterisation_input = self._rasterisation_input(
+            self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
+            rasterisation_input =self._rasterisation_input(
                 camera_info, q_pointcloud_camera, t_pointcloud_camera,
                 color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval))
             image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
@@ -494,6 +501,7 @@ class GaussianPointCloudTrainer:
                         print(f"train_ssim_{iteration}={ssim_score.item()};")
             del image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, rasterisation_input, image_pred, loss, l1_loss, ssim_loss
             del pixel_weight, image_depth, values, total
+            self.current_pose = None
             # they use 7000 in paper, it's hard to set a interval so hard code it here (TRAIN:274)
             if (iteration % config.val_interval == 0 and iteration != 0) or iteration == 7000 or iteration == 5000:
                 self.validation(iteration)
@@ -535,8 +543,9 @@ class GaussianPointCloudTrainer:
                 start_event = torch.cuda.Event(enable_timing=True)
                 end_event = torch.cuda.Event(enable_timing=True)
                 rasterisation_input = self._rasterisation_input(camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band=3)
+                self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
                 start_event.record()
-                image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
+                image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input, keep_frame=self._keep_validation_frame)
                 end_event.record()
                 torch.cuda.synchronize()
                 sums["inference_time"] += start_event.elapsed_time(end_event)

@@ -19,6 +19,7 @@
 #include "../../include/gs_vq.h"
 #include "../../include/gs_depth.h"
 #include "../../include/gs_geometry.h"
+#include "../../include/gs_normals.h"
 #include "gs_common.h"
 #include "gs_sort_key.h"
 
@@ -2237,6 +2238,88 @@ extern "C" int gs_depth_smooth_backward(gs_ctx* c, const float* D, const float* 
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_depth_smooth_backward(D, I, w_p, H, W, edge_lambda, flags, terms, upstream, grad_D, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- Gaussian normals and their consistency with the depth normal (include/gs_normals.h, k_normals.hip) --------------------------
+static int gaussian_normals_check(const std::string& who, gs_ctx* c, const float* pc, const float* feat, const float* q_pc, const float* t_pc,
+                                  int64_t N, int32_t K, const void* a, const void* b)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (N < 0 || N > (int64_t)INT32_MAX - GS_NORMALS_BLOCK) return fail(GS_ERR_INVALID_ARGUMENT, who + ": N must be in [0, 2^31 - 256]");
+    if (K < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": K must be >= 1");
+    if (!q_pc || !t_pc) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL pose array");
+    if (N > 0 && (!pc || !feat || !a || !b)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array");
+    return GS_OK;
+}
+
+extern "C" int gs_gaussian_normals_forward(gs_ctx* c, const float* pc, const float* feat, const int32_t* obj, const float* q_pc,
+                                           const float* t_pc, int64_t N, int32_t K, float* normals, gs_stream stream_)
+{
+    if (const int rc = gaussian_normals_check("gs_gaussian_normals_forward", c, pc, feat, q_pc, t_pc, N, K, normals, normals)) return rc;
+    if (N == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_gaussian_normals_forward(pc, feat, obj, q_pc, t_pc, N, K, normals, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_gaussian_normals_backward(gs_ctx* c, const float* pc, const float* feat, const int32_t* obj, const float* q_pc,
+                                            const float* t_pc, int64_t N, int32_t K, const float* grad_normals, float* grad_features,
+                                            gs_stream stream_)
+{
+    if (const int rc = gaussian_normals_check("gs_gaussian_normals_backward", c, pc, feat, q_pc, t_pc, N, K, grad_normals, grad_features)) return rc;
+    if (N == 0) return GS_OK;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_gaussian_normals_backward(pc, feat, obj, q_pc, t_pc, N, K, grad_normals, grad_features, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+static int normal_consistency_check(const std::string& who, gs_ctx* c, const float* D, const float* R, int32_t H, int32_t W, float fx, float fy,
+                                    float cx, float cy, float max_rel_jump, float min_length, const float* terms)
+{
+    if (const int rc = geometry_check(who, c, D, H, W, 0, 0)) return rc;
+    if ((int64_t)H * (int64_t)W > (int64_t)GS_NORMALS_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
+    if (!R) return fail(GS_ERR_INVALID_ARGUMENT, who + ": R is NULL");
+    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
+    if (!(std::isfinite(min_length) && min_length > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": min_length must be finite and > 0");
+    return geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump);
+}
+
+extern "C" int gs_normal_consistency_forward(gs_ctx* c, const float* D, const float* R, const float* w_p, int32_t H, int32_t W, float fx,
+                                             float fy, float cx, float cy, float max_rel_jump, float min_length, float* terms,
+                                             gs_stream stream_)
+{
+    if (const int rc = normal_consistency_check("gs_normal_consistency_forward", c, D, R, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms))
+        return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
+    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
+        return fail(GS_ERR_OUT_OF_MEMORY, "gs_normal_consistency_forward: workspace");
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_normal_consistency_forward(D, R, w_p, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms, c->geometry_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_normal_consistency_backward(gs_ctx* c, const float* D, const float* R, const float* w_p, int32_t H, int32_t W, float fx,
+                                              float fy, float cx, float cy, float max_rel_jump, float min_length, const float* terms,
+                                              const float* upstream, float* grad_D, float* grad_R, gs_stream stream_)
+{
+    if (const int rc = normal_consistency_check("gs_normal_consistency_backward", c, D, R, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms))
+        return rc;
+    if (!grad_D || !grad_R) return fail(GS_ERR_INVALID_ARGUMENT, "gs_normal_consistency_backward: grad_D or grad_R is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_normal_consistency_backward(D, R, w_p, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms, upstream, grad_D, grad_R, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

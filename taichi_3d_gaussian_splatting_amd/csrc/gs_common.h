@@ -673,6 +673,18 @@ void gs_launch_depth_smooth_forward(const float* D, const float* I, const float*
 void gs_launch_depth_smooth_backward(const float* D, const float* I, const float* wp, int H, int W, float lambda, int flags, const float* terms,
                                      const float* upstream, float* G, hipStream_t s);
 
+// k_normals.hip (include/gs_normals.h): the per-Gaussian normals (N >= 1 rows) and the consistency of their render with the depth
+// normal.  ws: gs_geometry_ws_size(H, W) bytes, as above.
+void gs_launch_gaussian_normals_forward(const float* pc, const float* feat, const int32_t* obj, const float* q_pc, const float* t_pc, int64_t N,
+                                        int K, float* normals, hipStream_t s);
+void gs_launch_gaussian_normals_backward(const float* pc, const float* feat, const int32_t* obj, const float* q_pc, const float* t_pc, int64_t N,
+                                         int K, const float* grad_normals, float* grad_feat, hipStream_t s);
+void gs_launch_normal_consistency_forward(const float* D, const float* R, const float* wp, int H, int W, float fx, float fy, float cx, float cy,
+                                          float jump, float min_length, float* terms, void* ws, hipStream_t s);
+void gs_launch_normal_consistency_backward(const float* D, const float* R, const float* wp, int H, int W, float fx, float fy, float cx, float cy,
+                                           float jump, float min_length, const float* terms, const float* upstream, float* G, float* GR,
+                                           hipStream_t s);
+
 // k_fusion.hip (include/gs_fusion.h): depth frames into a TSDF volume (n_views cut into launches of GS_TSDF_VIEWS_PER_LAUNCH, in
 // order), and the two halves of the isosurface around the caller's read of the totals.  The launchers trust what the entry
 // points checked: a non-empty volume, non-NULL arrays and work buffers, counts below 2^31.

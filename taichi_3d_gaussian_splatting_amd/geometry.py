@@ -290,7 +290,8 @@ def depth_smoothness(depth, guide=None, pixel_weight=None, space: str = "inverse
 class GeometryConfig:
     """The trainer's geometry terms; a weight of 0 switches a term off, and the weights are constant from start_iteration on.
     smooth_*: of depth_smoothness (the guide is the colour target).  normal_*: of normal_loss against the dataset's normal_path
-    priors."""
+    priors.  consistency_*: of normals.normal_consistency between the rendered Gaussian normals and the normal of the rendered
+    depth, which needs no data."""
     smooth_weight: float = 0.0
     smooth_space: str = "inverse"
     smooth_order: int = 1
@@ -299,6 +300,9 @@ class GeometryConfig:
     normal_convention: str = "opencv"
     normal_max_rel_jump: float = 0.1
     start_iteration: int = 0
+    consistency_weight: float = 0.0
+    consistency_min_length: float = 0.5
+    consistency_max_rel_jump: float = 0.1
 
     def check(self):
         smooth_flags(self.smooth_space, self.smooth_order)
@@ -309,8 +313,12 @@ class GeometryConfig:
         _non_negative(self.normal_max_rel_jump, "normal_max_rel_jump")
         if int(self.start_iteration) != self.start_iteration or self.start_iteration < 0:
             raise ValueError(f"start_iteration must be an integer >= 0, got {self.start_iteration}")
-        if self.smooth_weight == 0.0 and self.normal_weight == 0.0:
-            raise ValueError("a GeometryConfig needs smooth_weight > 0 or normal_weight > 0")
+        _non_negative(self.consistency_weight, "consistency_weight")
+        _non_negative(self.consistency_max_rel_jump, "consistency_max_rel_jump")
+        if not (math.isfinite(float(self.consistency_min_length)) and self.consistency_min_length > 0.0):
+            raise ValueError(f"consistency_min_length must be finite and > 0, got {self.consistency_min_length}")
+        if self.smooth_weight == 0.0 and self.normal_weight == 0.0 and self.consistency_weight == 0.0:
+            raise ValueError("a GeometryConfig needs smooth_weight > 0, normal_weight > 0 or consistency_weight > 0")
 
 
 # ---- the normal priors of a dataset -----------------------------------------------------------------------------------------
@@ -387,6 +395,10 @@ class _GeometryTerm(_terms.TrainerTerm):
     def weight_at(self, iteration):
         return self.weight
 
+    def bind(self, trainer):
+        """called once by the trainer that sums the term, before the first value(): a term that needs more of a step than
+        value() is given (normals.ConsistencyTerm) keeps the trainer"""
+
 
 class SmoothTerm(_GeometryTerm):
     """depth_smoothness of the rendered depth with the colour target as its guide: it needs no data of its own"""
@@ -426,8 +438,8 @@ class NormalTerm(_GeometryTerm):
 
 
 def trainer_terms(geometry: Optional[GeometryConfig], train_config) -> list:
-    """the terms of a trainer's geometry argument, checked against its TrainConfig, over a copy of it: smoothness, then normal
-    prior, each if its weight is > 0; nothing is read from disk and no device is touched before their load()"""
+    """the terms of a trainer's geometry argument, checked against its TrainConfig, over a copy of it: smoothness, normal prior,
+    then normal consistency, each if its weight is > 0; nothing is read from disk and no device is touched before their load()"""
     if geometry is None:
         return []
     if not isinstance(geometry, GeometryConfig):
@@ -435,7 +447,8 @@ def trainer_terms(geometry: Optional[GeometryConfig], train_config) -> list:
     geometry.check()
     _terms.check_depth_is_rendered(train_config, "geometry", "its guide and priors are made on the device")
     config = dataclasses.replace(geometry)
-    return [term(config) for term in (SmoothTerm, NormalTerm) if getattr(config, f"{term.name}_weight") > 0.0]
+    from .normals import ConsistencyTerm                 # (normals.py builds on this module)
+    return [term(config) for term in (SmoothTerm, NormalTerm, ConsistencyTerm) if getattr(config, f"{term.name}_weight") > 0.0]
 
 
 def normals_to_uint8(normals: torch.Tensor) -> torch.Tensor:
