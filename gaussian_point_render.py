@@ -17,7 +17,8 @@ box's longest side / 255) and --mesh_trunc the truncation distance (default: 4 v
 optional: without it only the mesh is written.  --appearance FILE (an appearance_<iteration>.pt of a trainer run with --appearance
 affine) with a dataset JSON as --poses: a frame whose image_path is in the file is corrected by its trained colour transform
 before it is written and measured, every other frame is rendered as without the flag, and metrics.json gains psnr_cc per view
-(the PSNR after the best affine fit of the rendering to its ground truth).  --normals_to DIR writes, per pose, the normal map
+(the PSNR after the best affine fit of the rendering to its ground truth).  --bilateral_grid FILE (a bilateral_<iteration>.pt of a
+trainer run with --bilateral_grid) does the same with the views' trained bilateral grids.  --normals_to DIR writes, per pose, the normal map
 derived from the rendered depth (geometry.depth_normals) as an 8-bit PNG (n + 1) / 2, (0,0,0) where there is none:
 DIR/normal_<i:03>.png, in the camera frame of the rasteriser (x right, y down, z forward); --normals_max_rel_jump J (default 0.1)
 leaves out the normals across a depth change of more than J times the depth.  With --normals_to, --output_prefix is optional.
@@ -57,6 +58,7 @@ if __name__ == "__main__":
     parser.add_argument("--mesh_bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                         help="the volume's box (default: mixture.bounding_box of the scene)")
     parser.add_argument("--appearance", type=str, default="", help="an appearance_<iteration>.pt of the trainer: per-view colour transforms")
+    parser.add_argument("--bilateral_grid", type=str, default="", help="a bilateral_<iteration>.pt of the trainer: per-view bilateral grids")
     parser.add_argument("--normals_to", type=str, default="", help="write the depth-derived normal map of every pose into this directory")
     parser.add_argument("--normals_max_rel_jump", type=float, default=0.1, help="no normal across a depth change above this share of the depth")
     parser.add_argument("--normals_source", choices=("depth", "gaussians"), default="depth", help="with --normals_to: the normal of the rendered "
@@ -70,8 +72,10 @@ if __name__ == "__main__":
     if args.mesh_to and not (args.poses or "").endswith(".pt"):
         parser.error("--mesh_to fuses the poses of a .pt file")
 
-    if args.appearance and not (args.poses or "").endswith(".json"):
-        parser.error("--appearance corrects the views of a dataset json given as --poses")
+    if (args.appearance or args.bilateral_grid) and not (args.poses or "").endswith(".json"):
+        parser.error("--appearance and --bilateral_grid correct the views of a dataset json given as --poses")
+    if args.appearance and args.bilateral_grid:
+        parser.error("--appearance and --bilateral_grid are alternatives: a grid contains the affine transform")
 
     parquet_path = args.parquet_path[0] if len(args.parquet_path) == 1 else list(args.parquet_path)
     targets = image_paths = None
@@ -135,6 +139,10 @@ if __name__ == "__main__":
     if args.appearance:
         from taichi_3d_gaussian_splatting_amd.appearance import AppearanceTable
         table, table_paths = AppearanceTable.load(args.appearance, device=renderer.device)
+        transforms = table.by_image_path(table_paths)
+    if args.bilateral_grid:
+        from taichi_3d_gaussian_splatting_amd.bilateral import BilateralGridTable
+        table, table_paths = BilateralGridTable.load(args.bilateral_grid, device=renderer.device)
         transforms = table.by_image_path(table_paths)
     metrics = renderer.run(output_prefix, depth=args.depth, targets=targets, gt_prefix=gt_prefix, appearance=transforms,
                            image_paths=image_paths if transforms is not None else None)

@@ -2,6 +2,8 @@
 --pixel_weights alpha|file [--mask_erode K] trains with per-pixel weights (INTEGRATION.md "Masked and weighted training");
 --density mcmc [--mcmc_cap N] trains with a fixed budget of Gaussians (INTEGRATION.md "Fixed-budget densification");
 --appearance affine trains a colour transform per training image with the scene (INTEGRATION.md "Exposure compensation");
+--bilateral_grid [--bilateral_shape X Y L --bilateral_tv W --bilateral_lr LR] trains a bilateral grid of colour transforms per
+training image instead (INTEGRATION.md "Bilateral grids");
 --depth metric|relative [--depth_weight W --depth_space depth|inverse --depth_norm l1|l2] adds a depth term from the dataset's
 depth_path maps (INTEGRATION.md "Depth supervision in the trainer");
 --depth_smooth W [--smooth_order 1|2 --smooth_space depth|inverse --smooth_edge_lambda L] adds an edge-aware smoothness of the
@@ -26,6 +28,13 @@ if __name__ == "__main__":
                         "(default: every row the scene allocates, max_num_points_ratio)")
     parser.add_argument("--appearance", choices=("none", "affine"), default="none",
                         help="exposure compensation: a learnable 3x4 affine colour transform per training image")
+    parser.add_argument("--bilateral_grid", action="store_true", default=False,
+                        help="a learnable bilateral grid of 3x4 colour transforms per training image: spatially varying colour correction")
+    parser.add_argument("--bilateral_shape", type=int, nargs=3, default=None, metavar=("X", "Y", "L"),
+                        help="with --bilateral_grid: vertices across, down and along the luminance (default 16 16 8)")
+    parser.add_argument("--bilateral_tv", type=float, default=None, metavar="W", help="with --bilateral_grid: weight of the grid's total variation")
+    parser.add_argument("--bilateral_lr", type=float, default=None, metavar="LR", help="with --bilateral_grid: the grids' learning rate at "
+                        "iteration 0 (it falls to a hundredth of it over the run)")
     parser.add_argument("--depth", choices=("none", "metric", "relative"), default="none",
                         help="depth supervision from the dataset's depth_path maps: metres, or a monocular network's relative "
                         "inverse depth aligned per view by scale and shift")
@@ -55,6 +64,10 @@ if __name__ == "__main__":
         parser.error("--normal_convention needs --normal_prior")
     if args.depth == "none" and (args.depth_weight is not None or args.depth_space is not None or args.depth_norm is not None):
         parser.error("--depth_weight, --depth_space and --depth_norm need --depth metric or relative")
+    if not args.bilateral_grid and (args.bilateral_shape is not None or args.bilateral_tv is not None or args.bilateral_lr is not None):
+        parser.error("--bilateral_shape, --bilateral_tv and --bilateral_lr need --bilateral_grid")
+    if args.bilateral_grid and args.appearance == "affine":
+        parser.error("--bilateral_grid and --appearance affine are alternatives: a grid contains the affine transform")
     if args.mcmc_cap is not None and args.density != "mcmc":
         parser.error("--mcmc_cap needs --density mcmc")
     if args.gen_template_only:
@@ -81,6 +94,16 @@ if __name__ == "__main__":
             depth_config.space = args.depth_space
         if args.depth_norm is not None:
             depth_config.norm = args.depth_norm
+    bilateral_config = None
+    if args.bilateral_grid:
+        from taichi_3d_gaussian_splatting_amd.bilateral import BilateralGridConfig
+        bilateral_config = BilateralGridConfig()
+        if args.bilateral_shape is not None:
+            bilateral_config.grid_x, bilateral_config.grid_y, bilateral_config.grid_l = args.bilateral_shape
+        if args.bilateral_tv is not None:
+            bilateral_config.tv_weight = args.bilateral_tv
+        if args.bilateral_lr is not None:
+            bilateral_config.lr, bilateral_config.lr_final = args.bilateral_lr, args.bilateral_lr / 100.0
     geometry_config = None
     if args.depth_smooth is not None or args.normal_prior is not None or args.normal_consistency is not None:
         from taichi_3d_gaussian_splatting_amd.geometry import GeometryConfig
@@ -91,5 +114,5 @@ if __name__ == "__main__":
         geometry_config = GeometryConfig(**{name: value for name, value in chosen.items() if value is not None})
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
                                         mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,
-                                        geometry=geometry_config)
+                                        geometry=geometry_config, bilateral_grid=bilateral_config)
     trainer.train()

@@ -14,7 +14,8 @@ multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. a
     SSIM the trainer's validation() logs, from the same LossFunction kernels -- all read from the device once, at the end;
   - run(appearance=...) corrects the frames of the views a trained appearance table knows (appearance.py: the per-view affine
     colour transform of exposure compensation) before they are converted to 8 bits, and adds psnr_cc per view: the PSNR after
-    the best affine fit of the rendering to its ground truth;
+    the best affine fit of the rendering to its ground truth; an entry that is a (Gy,Gx,L,12) bilateral grid (bilateral.py) is
+    sliced over its frame instead;
   - fuse() renders the poses with depth and accumulated alpha and integrates them into a fusion.TSDFVolume on the device, from
     which a triangle mesh is extracted (fusion.py).
 """
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import appearance as _appearance
+from . import bilateral as _bilateral
 from . import frames, fusion
 from .Camera import CameraInfo
 from .compose import SceneComposition
@@ -182,7 +184,8 @@ class GaussianPointRenderer:
 
         appearance ({image path: (12,) transform on the device}, AppearanceTable.by_image_path) with image_paths (the path of
         every view of `targets`, in order): a view whose path is in the dict is corrected by its transform before it is
-        converted to 8 bits and measured; every other frame is rendered as without it.  Every view then also gets psnr_cc:
+        converted to 8 bits and measured; every other frame is rendered as without it.  A value may also be the view's
+        (Gy,Gx,L,12) bilateral grid (BilateralGridTable.by_image_path), which is sliced over the frame.  Every view then also gets psnr_cc:
         the float PSNR after appearance.fit_affine(rendering, ground truth), which reads 23 numbers to the host per view."""
         if appearance is not None:
             if targets is None or image_paths is None or len(image_paths) != len(targets):
@@ -211,7 +214,9 @@ class GaussianPointRenderer:
             image, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=depth)
             if appearance is not None and str(image_paths[i]) in appearance:
                 # in the rasteriser's layout, so the corrected frame is again a contiguous (H,W,3)
-                image = _appearance.apply_forward(image.permute(2, 0, 1), appearance[str(image_paths[i])]).permute(1, 2, 0)
+                correction = appearance[str(image_paths[i])]
+                correct = _bilateral.slice_forward if correction.dim() == 4 else _appearance.apply_forward
+                image = correct(image.permute(2, 0, 1), correction).permute(1, 2, 0)
             stored = targets.images[i]
             if stored.dtype == torch.uint8:
                 gt_bytes = stored

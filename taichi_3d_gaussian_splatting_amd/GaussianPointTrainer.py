@@ -22,6 +22,13 @@ What differs from the reference
     balance differ between views.  The transform is applied to the rendered image in front of the loss; validation views have
     none and are rendered uncorrected, and additionally measured after the best affine fit to their ground truth (val/psnr_cc,
     val/ssim_cc, val/loss_cc).  "none", the default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, bilateral_grid=BilateralGridConfig(...)) trains a bilateral grid per training image with
+    the scene (bilateral.py): a lattice of 3x4 colour transforms over the image plane and the rendered luminance, sliced at
+    every pixel in front of the loss -- it contains the affine transform and also absorbs what varies across the picture
+    (vignetting, local tone mapping).  After the backward the total variation of the step's own grid, times tv_weight, is
+    added to that grid's gradient (gsplat regularises every view's grid every step; here a step's cost does not grow with the
+    number of views), then that grid alone takes an Adam step.  Validation is as with appearance="affine".  None, the
+    default, is the loop as it was.
   - GaussianPointCloudTrainer(config, depth="metric" | "relative", depth_config=DepthConfig(...)) adds a depth term to the loss
     (depth.py): the dataset's depth_path maps -- metres for "metric", a monocular network's relative inverse depth for
     "relative", aligned per view by a closed-form scale and shift -- resident on the device, one launch per step for the
@@ -54,6 +61,8 @@ from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .GaussianPointCloudScene import GaussianPointCloudScene
 from . import appearance as _appearance
 from .appearance import AppearanceConfig, AppearanceTable
+from . import bilateral as _bilateral
+from .bilateral import BilateralGridConfig, BilateralGridTable
 from . import depth as _depth
 from .depth import DepthConfig
 from . import geometry as _geometry
@@ -224,7 +233,7 @@ class GaussianPointCloudTrainer:
     def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
                  density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
                  appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None,
-                 geometry: Optional[GeometryConfig] = None):
+                 geometry: Optional[GeometryConfig] = None, bilateral_grid: Optional[BilateralGridConfig] = None):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -235,7 +244,9 @@ class GaussianPointCloudTrainer:
         self.appearance_table) -- and its AppearanceConfig (None: the defaults, over config.num_iterations); whether the
         dataset's depth maps supervise the rendered depth -- "none", "metric" (metres) or "relative" (relative inverse depth,
         aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations); geometry:
-        the GeometryConfig of the regularisers on the rendered depth (None: none)"""
+        the GeometryConfig of the regularisers on the rendered depth (None: none); bilateral_grid: the BilateralGridConfig of a
+        learnable bilateral grid of colour transforms per training image (bilateral.BilateralGridTable, in self.bilateral_table;
+        None: none; its schedule runs over config.num_iterations unless it names its own)"""
         self.config = config
         # the extra loss terms, in the order they are summed and logged in; each checks its arguments where it is made
         geometry_terms = _geometry.trainer_terms(geometry, config)
@@ -251,8 +262,13 @@ class GaussianPointCloudTrainer:
             raise ValueError(f'appearance must be "none" or "affine", got {appearance!r}')
         if appearance == "none" and appearance_config is not None:
             raise ValueError('appearance_config needs appearance="affine"')
+        if bilateral_grid is not None:
+            if appearance == "affine":
+                raise ValueError('bilateral_grid cannot be combined with appearance="affine": a grid contains the affine transform')
+            bilateral_grid.check()
         self.appearance = appearance
         self.appearance_table = None
+        self.bilateral_table = None
         if density not in ("adaptive", "mcmc"):
             raise ValueError(f'density must be "adaptive" or "mcmc", got {density!r}')
         if density == "mcmc" and self.config.sparse_adam:
@@ -316,6 +332,12 @@ class GaussianPointCloudTrainer:
             if appearance_config.num_iterations is None:
                 appearance_config = dataclasses.replace(appearance_config, num_iterations=max(int(self.config.num_iterations), 1))
             self.appearance_table = AppearanceTable(len(self.train_dataset), self.device, appearance_config)
+        if bilateral_grid is not None:
+            if bilateral_grid.num_iterations is None:
+                bilateral_grid = dataclasses.replace(bilateral_grid, num_iterations=max(int(self.config.num_iterations), 1))
+            self.bilateral_table = BilateralGridTable(len(self.train_dataset), self.device, bilateral_grid)
+        # validation views have no trained correction: the colour-corrected metrics are reported whenever one is trained
+        self._colour_corrected = self.appearance_table is not None or self.bilateral_table is not None
         if self.terms:
             # their gradients reach the scene: set on the trainer's own rasteriser, not on the caller's config object
             self.rasterisation.config = copy.copy(self.rasterisation.config)
@@ -390,7 +412,8 @@ class GaussianPointCloudTrainer:
             yield self._target(self.val_targets, host_items, view, 1)
 
     def train_image_paths(self) -> List[str]:
-        """the image_path of every training view, in the dataset's order: what the rows of the appearance table belong to"""
+        """the image_path of every training view, in the dataset's order: what the rows of the appearance table and the grids of
+        the bilateral table belong to"""
         return [str(p) for p in self.train_dataset.df["image_path"].tolist()]
 
     def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band):
@@ -441,6 +464,9 @@ class GaussianPointCloudTrainer:
             if self.appearance_table is not None:
                 # the view's colour transform, in the rasteriser's layout: the loss reads the corrected image where it lies
                 image_pred = _appearance.apply(image_pred, self.appearance_table.row(view))
+            if self.bilateral_table is not None:
+                # the view's grid, sliced at every pixel; same layout, so the loss reads the corrected image where it lies
+                image_pred = _bilateral.slice(image_pred, self.bilateral_table.row(view))
             loss, l1_loss, ssim_loss = self.loss_function(
                 image_pred,
                 image_gt,
@@ -455,6 +481,10 @@ class GaussianPointCloudTrainer:
                 if values.get(term) is not None:
                     total = total + term.weight_at(iteration) * values[term]
             total.backward()
+            if self.bilateral_table is not None:
+                # tv_weight * d tv / d grid of this view's grid, added to the gradient the backward wrote; the value stays on the device
+                table = self.bilateral_table
+                _bilateral.tv(table.grids[view], weight=table.config.tv_weight, grad_grid=table.grad, value=table.tv_value)
             if self.mcmc is not None:
                 self.mcmc.before_step(iteration)
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
@@ -462,6 +492,8 @@ class GaussianPointCloudTrainer:
             position_optimizer.step(rows=rows)
             if self.appearance_table is not None:
                 self.appearance_table.step(view, iteration)
+            if self.bilateral_table is not None:
+                self.bilateral_table.step(view, iteration)
 
             if self.mcmc is not None:
                 self.mcmc.after_step(iteration, position_optimizer.lr)       # the rate this iteration stepped with
@@ -477,6 +509,8 @@ class GaussianPointCloudTrainer:
                 self.writer.add_scalar("train/loss", loss_value, iteration)
                 self.writer.add_scalar("train/l1 loss", l1_loss.item(), iteration)
                 self.writer.add_scalar("train/ssim loss", ssim_loss.item(), iteration)
+                if self.bilateral_table is not None:
+                    self.writer.add_scalar("train/bilateral_tv", self.bilateral_table.tv_value.item(), iteration)     # the one host read
                 for term in self.terms:
                     if values.get(term) is not None:
                         for tag, value in term.train_scalars(values[term].terms.tolist()):       # one read per term
@@ -533,7 +567,7 @@ class GaussianPointCloudTrainer:
         out of every mean: it has no weighted pixel to measure."""
         with torch.no_grad():
             sums = dict(loss=0.0, psnr=0.0, ssim=0.0, inference_time=0.0)
-            if self.appearance_table is not None:
+            if self._colour_corrected:
                 sums.update(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
             count = 0
             total_terms, term_count = {term: 0.0 for term in self.terms}, {term: 0 for term in self.terms}
@@ -551,7 +585,7 @@ class GaussianPointCloudTrainer:
                 sums["inference_time"] += start_event.elapsed_time(end_event)
                 image_pred = torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
                 images = {"": image_pred}
-                if self.appearance_table is not None:
+                if self._colour_corrected:
                     # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
                     fitted = _appearance.fit_affine(image_pred, image_gt, pixel_weight)
                     images["_cc"] = torch.clamp(_appearance.apply_forward(image_pred, fitted), 0, 1)
@@ -582,11 +616,15 @@ class GaussianPointCloudTrainer:
             self.scene.to_parquet(os.path.join(self.config.output_model_dir, f"scene_{iteration}.parquet"))
             if self.appearance_table is not None:
                 self.appearance_table.save(os.path.join(self.config.output_model_dir, f"appearance_{iteration}.pt"), self.train_image_paths())
+            if self.bilateral_table is not None:
+                self.bilateral_table.save(os.path.join(self.config.output_model_dir, f"bilateral_{iteration}.pt"), self.train_image_paths())
             if means["psnr"] > self.best_psnr_score:
                 self.best_psnr_score = means["psnr"]
                 self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
                 if self.appearance_table is not None:
                     self.appearance_table.save(os.path.join(self.config.output_model_dir, "best_appearance.pt"), self.train_image_paths())
+                if self.bilateral_table is not None:
+                    self.bilateral_table.save(os.path.join(self.config.output_model_dir, "best_bilateral.pt"), self.train_image_paths())
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
             self.last_validation = (iteration, means)

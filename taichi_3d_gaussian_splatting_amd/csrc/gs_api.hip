@@ -16,6 +16,7 @@
 #include "../../include/gs_fusion.h"
 #include "../../include/gs_mcmc.h"
 #include "../../include/gs_appearance.h"
+#include "../../include/gs_bilateral.h"
 #include "../../include/gs_vq.h"
 #include "../../include/gs_depth.h"
 #include "../../include/gs_geometry.h"
@@ -160,6 +161,7 @@ struct gs_ctx {
     DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
     DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
     DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
+    DevBuf bilateral_ws;                // gs_bilateral_slice_backward: the block sums of split footprints, read by nothing else
     DevBuf depth_ws;                    // gs_depth_loss_forward: its finished moments and per-block sums, read by nothing else
     DevBuf geometry_ws;                 // gs_normal_loss_forward / gs_depth_smooth_forward: their per-tile sums, read by nothing else
     DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
@@ -234,7 +236,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
-                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->depth_ws,
+                      &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->bilateral_ws, &c->depth_ws,
                       &c->geometry_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
@@ -2058,6 +2060,78 @@ extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, cons
     hipStream_t s;
     if (const int rc = enter_call(c, stream_, &s)) return rc;
     gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+// ---- per-view bilateral grids (include/gs_bilateral.h, k_bilateral.hip) -----------------------------------------------------
+static int bilateral_grid_check(const char* who, gs_ctx* c, const float* grid, int32_t Gx, int32_t Gy, int32_t L)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
+    if (!grid || ((uintptr_t)grid & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grid must be 16-byte aligned and not NULL");
+    if (Gx < GS_BILATERAL_MIN_GRID || Gx > GS_BILATERAL_MAX_XY || Gy < GS_BILATERAL_MIN_GRID || Gy > GS_BILATERAL_MAX_XY ||
+        L < GS_BILATERAL_MIN_GRID || L > GS_BILATERAL_MAX_L)
+        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grid dimensions outside their limits");
+    return GS_OK;
+}
+
+static int bilateral_check(const char* who, gs_ctx* c, const gs_loss_image* image, const float* grid, int32_t Gx, int32_t Gy, int32_t L,
+                           int32_t H, int32_t W)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
+    if (!image || !image->data) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL image");
+    if (const int rc = bilateral_grid_check(who, c, grid, Gx, Gy, L)) return rc;
+    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": H and W must be >= 1");
+    if ((int64_t)H * (int64_t)W > (int64_t)GS_BILATERAL_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many pixels");
+    return GS_OK;
+}
+
+extern "C" int gs_bilateral_slice(gs_ctx* c, const gs_loss_image* image, const float* grid, int32_t Gx, int32_t Gy, int32_t L, int32_t H,
+                                  int32_t W, const gs_loss_image* corrected, gs_stream stream_)
+{
+    if (const int rc = bilateral_check("gs_bilateral_slice", c, image, grid, Gx, Gy, L, H, W)) return rc;
+    if (!corrected || !corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice: NULL corrected image");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_bilateral_slice(loss_image(image, 0), grid, Gx, Gy, L, H, W, loss_image(corrected, 0), s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_bilateral_slice_backward(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* grad_corrected, const float* grid,
+                                           int32_t Gx, int32_t Gy, int32_t L, int32_t H, int32_t W, const gs_loss_image* grad_image,
+                                           float* grad_grid, gs_stream stream_)
+{
+    if (const int rc = bilateral_check("gs_bilateral_slice_backward", c, image, grid, Gx, Gy, L, H, W)) return rc;
+    if (!grad_corrected || !grad_corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice_backward: NULL grad_corrected");
+    const bool want_image = grad_image && grad_image->data;
+    if (!want_image && !grad_grid) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice_backward: grad_image and grad_grid are both NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (grad_grid) {
+        HIP_TRY(hipSetDevice(c->device));       // the workspace grows before the stream enters: a call that fails here leaves it alone
+        if (c->bilateral_ws.ensure(gs_bilateral_ws_size(Gx, Gy, L), &c->device_bytes) != hipSuccess)
+            return fail(GS_ERR_OUT_OF_MEMORY, "gs_bilateral_slice_backward: workspace");
+    }
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    const GsLossImage none{ nullptr, 0, 0, 0, 0 };
+    gs_launch_bilateral_backward(loss_image(image, 0), loss_image(grad_corrected, 0), grid, Gx, Gy, L, H, W,
+                                 want_image ? loss_image(grad_image, 0) : none, grad_grid, c->bilateral_ws.p, s);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" int gs_bilateral_tv(gs_ctx* c, const float* grid, int32_t Gx, int32_t Gy, int32_t L, float weight, float* grad_grid, float* value,
+                               gs_stream stream_)
+{
+    if (const int rc = bilateral_grid_check("gs_bilateral_tv", c, grid, Gx, Gy, L)) return rc;
+    if (!value) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_tv: value is NULL");
+    if (!std::isfinite(weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_tv: weight must be finite");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s;
+    if (const int rc = enter_call(c, stream_, &s)) return rc;
+    gs_launch_bilateral_tv(grid, Gx, Gy, L, weight, grad_grid, value, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }

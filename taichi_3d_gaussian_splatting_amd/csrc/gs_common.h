@@ -650,6 +650,14 @@ void gs_launch_appearance_backward(const GsLossImage& X, const GsLossImage& G, c
                                    float* grad_transform, void* ws, hipStream_t s);
 void gs_launch_appearance_moments(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, double* moments, void* ws,
                                   hipStream_t s);
+// k_bilateral.hip (include/gs_bilateral.h): the bilateral grid of colour transforms of an image.  The launchers trust what the
+// entry points checked.  ws: gs_bilateral_ws_size(Gx, Gy, L) bytes of the context's (the block sums of a split footprint; 0
+// where no footprint is split).  GI.p NULL: no image gradient; grad_grid NULL: no gather.
+size_t gs_bilateral_ws_size(int Gx, int Gy, int L);
+void gs_launch_bilateral_slice(const GsLossImage& X, const float* grid, int Gx, int Gy, int L, int H, int W, const GsLossImage& C, hipStream_t s);
+void gs_launch_bilateral_backward(const GsLossImage& X, const GsLossImage& G, const float* grid, int Gx, int Gy, int L, int H, int W,
+                                  const GsLossImage& GI, float* grad_grid, void* ws, hipStream_t s);
+void gs_launch_bilateral_tv(const float* grid, int Gx, int Gy, int L, float weight, float* grad_grid, float* value, hipStream_t s);
 // k_depth.hip (include/gs_depth.h): the depth target with its weight plane, and the depth loss.  The launchers trust what the
 // entry points checked.  ws: gs_depth_ws_size(H, W) bytes of the context's, 8-byte aligned (finished moments, per-block sums).
 void gs_launch_depth_resample(const void* src, int src_format, int H_in, int W_in, int64_t pitch_bytes, float depth_scale, GsResampleAxis ax,
