@@ -1,18 +1,23 @@
 """GPU (-m gpu): the three calls of include/gs_mcmc.h against tests/mcmc_ref.py, the header restated in numpy.
 
 Sizes: one row, around one wave (63, 64, 65), around one block (255, 256, 257) and several blocks with a partial last one (1500).
-Every scene of five rows or more mixes valid, free (mask 1) and mask-2 rows; a scene of one row is one valid row."""
+Every scene of five rows or more mixes valid, free (mask 1) and mask-2 rows; a scene of one row is one valid row.
+Past 1024 blocks (MC.N_LARGE = 1025 x 256 + 3 rows, where the one-block kernels give a thread two block sums, and the sizes around
+1024 x 256) and where the sampler's draws land on a prefix: the scenes of tests/mcmc_cases.py, whose conditions
+tests/test_mcmc_ref_host.py asserts on the CPU.  On the host the large noise case takes 2 s (two float64 references), the large
+regulariser case 0.6 s, each large relocation case 0.6 s to 1.3 s and 0.6 s for its moment tensors."""
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import mcmc_cases as MC
 import mcmc_ref
+from mcmc_cases import MASK_PATTERN
 
 pytestmark = pytest.mark.gpu
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1500]
-MASK_PATTERN = (0, 0, 1, 0, 2, 0, 1, 0, 0, 1)
 DEV = "cuda:0"
 _scenes = {}
 
@@ -72,7 +77,7 @@ def delta_from_zero(s, scale, step=NOISE["step"], seed=NOISE["seed"]):
     return dev.point_cloud.cpu().numpy()
 
 
-@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("n", SIZES + [MC.N_LARGE])
 def test_noise_against_float64(n):
     from taichi_3d_gaussian_splatting_amd import mcmc
     s = noise_scene(n)
@@ -117,14 +122,21 @@ def test_noise_depends_on_the_row_alone_and_on_the_step():
     assert (bits(other)[moved] != bits(whole)[moved]).any(1).all()
     seeded = delta_from_zero(s, LARGE, seed=NOISE["seed"] + 1)
     assert (bits(seeded)[moved] != bits(whole)[moved]).any(1).all()
+    # and with 1026 blocks behind the 257 rows
+    s = noise_scene(MC.N_LARGE)
+    whole = delta_from_zero(s, LARGE)
+    part = delta_from_zero({k: v[:257] for k, v in s.items()}, LARGE)
+    assert np.array_equal(bits(whole)[:257], bits(part))
+    assert (whole[MC.N_FULL:] != 0).any() and (whole != 0).any(1).sum() > 150_000
 
 
 # ---- regulariser -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("upstream", [None, 0.37])
-@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("n, upstream", [(n, upstream) for n in SIZES for upstream in (None, 0.37)] + [(MC.N_LARGE, 0.37)])
 def test_regulariser_against_float64(n, upstream):
+    """MC.N_LARGE: 157 442 valid rows in 1026 blocks, so each thread of k_mcmc_reg_total sums two partials (0.6 s on the host)"""
     from taichi_3d_gaussian_splatting_amd import mcmc
     s = make_scene(n)
+    assert n != MC.N_LARGE or (MC.per_thread(n) == 2 and (s["mask"] == 0).sum() == 157_442)
     lo, ls = 0.01, 0.02
     value, added = mcmc_ref.regulariser(s["ft"], s["mask"], lo, ls, 1.0 if upstream is None else upstream)
     dev = on_device(s)
@@ -173,8 +185,8 @@ def test_regulariser_without_a_valid_row_and_through_the_parameter_grad():
 
 
 # ---- relocate ----------------------------------------------------------------------------------------------------------
-def run_relocate(s, moments=True, call_index=0, seed=3, **settings):
-    """-> (got: dict of numpy arrays after the call, ref: mcmc_ref.relocate's, moments before)"""
+def run_relocate(s, moments=True, call_index=0, seed=3, ref=None, **settings):
+    """-> (got: dict of numpy arrays after the call, ref: mcmc_ref.relocate's (or `ref`, the same computed before), moments before)"""
     from taichi_3d_gaussian_splatting_amd import mcmc
     dev = on_device(s)
     n = s["pc"].shape[0]
@@ -197,8 +209,9 @@ def run_relocate(s, moments=True, call_index=0, seed=3, **settings):
                multiplicity=plan.multiplicity.cpu().numpy(), pc=dev.point_cloud.cpu().numpy(), ft=dev.point_cloud_features.cpu().numpy(),
                mask=dev.point_invalid_mask.cpu().numpy(), obj=dev.point_object_id.cpu().numpy(),
                moments=[x.cpu().numpy() for x in t] if moments else None)
-    ref = mcmc_ref.relocate(s["pc"], s["ft"], s["mask"], s["obj"], seed, call_index, n_max=config.n_max, grow_permille=config.grow_permille,
-                            cap_max=config.cap_max, min_logit=mcmc_ref.min_opacity_logit(config.min_opacity))
+    if ref is None:
+        ref = mcmc_ref.relocate(s["pc"], s["ft"], s["mask"], s["obj"], seed, call_index, n_max=config.n_max, grow_permille=config.grow_permille,
+                                cap_max=config.cap_max, min_logit=mcmc_ref.min_opacity_logit(config.min_opacity))
     return got, ref, mom
 
 
@@ -224,8 +237,8 @@ def check_relocate(s, got, ref, mom):
         print(f"relocate n={n}: D={D}, sources={ref['counts'][6]}, largest multiplicity={ref['multiplicity'].max()}, "
               f"new logit and log-scales within {ulps.max():.2f} f32 ulp (bar 2)")
         assert ulps.max() <= 2.0
-        for j in range(D):                                          # the same bits within a group
-            assert np.array_equal(bits(got["ft"][ref["dest_row"][j], 4:8]), bits(got["ft"][ref["source_of"][j], 4:8]))
+        dest, source = np.array(ref["dest_row"], np.int64), np.array(ref["source_of"], np.int64)
+        assert np.array_equal(bits(got["ft"][dest, 4:8]), bits(got["ft"][source, 4:8]))                    # the same bits within a group
     if got["moments"] is not None:
         for after, before in zip(got["moments"], mom):
             assert (bits(after[touched]) == 0).all() and np.array_equal(bits(after[~touched]), bits(before[~touched]))
@@ -325,6 +338,74 @@ def test_relocate_without_moments_and_with_another_call_index():
     assert not np.array_equal(bits(first["ft"]), bits(other["ft"]))
     seeded, _, _ = run_relocate(s, seed=4)
     assert not np.array_equal(first["source_of"], seeded["source_of"])
+
+
+# ---- relocate past 1024 blocks, and where a draw lands on a prefix (tests/mcmc_cases.py) ------------------------------------------
+def relocate_case(name, **override):
+    s = MC.scene(name)
+    settings = dict(s["settings"], **override)
+    call_index = settings.pop("call_index", 0)
+    got, ref, mom = run_relocate(s, call_index=call_index, seed=MC.SEED, ref=MC.reference(name, **override), **settings)
+    print(name, override, dict(zip(mcmc_ref.COUNTS, got["counts"])))
+    check_relocate(s, got, ref, mom)
+    return s, got, ref
+
+
+@pytest.mark.parametrize("name", MC.LARGE_SPARSE)
+def test_relocate_with_two_blocks_per_scan_thread(name):
+    """More than 1024 blocks of 256 rows: k_mcmc_scan's threads own two blocks each, write three exclusive prefixes back over two
+    entries, and the threads behind the last block own none.  Nearly every row has mask 2, so the reference stays fast (0.6 s on
+    the host per case, and 0.5 s for the four moment tensors).  Counts on the device, as the reference's
+    (valid / dead / alive / free / new / D / sources):
+      past_1024_blocks        262 403 rows, 1026 blocks   712 / 241 / 471 / 228 / 142 / 383 / 231, 66 destinations and 66 draws in blocks 1024 and 1025
+      blocks_1024             262 144 rows, 1024 blocks   440 / 139 / 301 / 166 / 88 / 227 / 136   (one block per thread: the last such size)
+      blocks_1025_last_alive  262 145 rows, 1025 blocks   440 / 140 / 300 / 166 / 88 / 228 / 139   (block 1024 is one alive row, and it is drawn)
+      blocks_1025_last_dead   262 145 rows, 1025 blocks   440 / 141 / 299 / 166 / 88 / 229 / 144   (block 1024 is one dead row, the last dead destination)"""
+    s, got, ref = relocate_case(name)
+    n = s["pc"].shape[0]
+    assert (MC.per_thread(n) == 2) == (n > MC.N_FULL)
+    if name == "past_1024_blocks":
+        assert (got["source_of"][:ref["counts"][5]] >= MC.N_FULL).any() and (got["dest_row"][:ref["counts"][5]] >= MC.N_FULL).any()
+        # the partial block: its dead row was filled, its free row is behind the n_new that were brought in
+        assert got["mask"][-3:].tolist() == [0, 1, 0] and (got["mask"] == 1).sum() == ref["counts"][3] - ref["counts"][4] > 0
+
+
+@pytest.mark.parametrize("n_max", [51, 5])
+def test_relocate_with_more_destinations_than_one_turn_of_the_grid_holds(n_max):
+    """262 443 rows: 262 403 valid, all dead but five (rows 7, 255, 256, 131 072 and 262 402), and 40 free rows behind them.
+    D = 262 398 + 40 = 262 438 > 1024 x 256, so the 1024 blocks of k_mcmc_sample and k_mcmc_apply_dest take a second turn, over 254
+    dead rows and the 40 free ones.  The five sources are drawn 74 264, 52 534, 31 636, 61 809 and 42 195 times: M = n_max.
+    Counts on the device: 262 403 / 262 398 / 5 / 40 / 40 / 262 438 / 5.  On the host the reference takes 1.3 s (it is linear in
+    sources x D, so the sources are few), the four moment tensors 0.6 s."""
+    s, got, ref = relocate_case("second_turn", n_max=n_max)
+    assert got["counts"][5] > MC.N_FULL and (got["mask"] == 0).all()
+    late = got["dest_row"][MC.N_FULL:got["counts"][5]]
+    assert len(late) == 294 and (s["mask"][late] == 1).sum() == 40
+    assert len(np.unique(bits(got["ft"][:, 4:8]), axis=0)) == 5                 # five groups, one set of bits each
+
+
+def test_relocate_where_every_draw_lands_on_a_prefix():
+    """Scene C of tests/mcmc_cases.py: 1500 rows at min_opacity 1e-9 with opacities of 2^-24 and below.  Every weight is 1 or 2
+    (393 of the 523 alive rows by the clamp max(w, 1)), W = 572, and of the D = 557 draws 501 have t == C(source): the searches'
+    `<=` decides them.  Rows 512..767 hold no weight; one draw has t = 232, the prefix that this block shares with the next, and
+    its source is row 771, the first alive row behind the empty block.  Draws also pick the last alive row of blocks 3 and 4 and the
+    first of blocks 4 and 5.  Every p is clamped up to 0.005 (o / M is 1e-8 at most), so each group ends at logit(0.005) and its
+    log-scales move by log(o / d), about -15.
+    Counts on the device: 900 valid / 377 dead / 523 alive / 450 free / 180 new / D 557 / 337 sources.
+
+    What this catches, tried once each on an MI355X in a build of k_mcmc_sample that was not kept:
+      `ws.wpre[mid] < t` for `<=` (block search): the other 48 tests of this file pass, the cases past 1024 blocks among them;
+          this one fails on source_of, first at destination 183: row 511, the last row of the block before the empty one, for 771
+      `ws.excl[first + mid] < local` for `<=` (row search): the other 48 tests pass; this one fails on the counts, 340 sources
+          for 337 (a draw on a row's own prefix goes to the row before it, alive or not)
+    The suite as it was before this test passes on both."""
+    f = MC.unit_facts()
+    s, got, ref = relocate_case("unit_weights")
+    D = got["counts"][5]
+    assert f["W"] < 1000 and 2 * f["draws_on_a_prefix"] >= D
+    first = f["first_alive_after_the_empty_block"]
+    assert first in f["draws_on_the_shared_prefix"] and got["multiplicity"][first] >= 1
+    assert (got["multiplicity"][MC.UNIT_EMPTY_BLOCK * MC.BLOCK:(MC.UNIT_EMPTY_BLOCK + 1) * MC.BLOCK] == 0).all()
 
 
 def test_relocate_of_an_empty_scene():

@@ -5,6 +5,7 @@ import math
 import numpy as np
 import pytest
 
+import mcmc_cases as MC
 import mcmc_ref
 
 OPACITIES = [0.006, 0.01, 0.05, 0.2, 0.5, 0.8, 0.95, 0.999, 1.0 - 2.0 ** -20, 1.0 - 2.0 ** -24]
@@ -130,3 +131,89 @@ def test_regulariser_gradient_is_the_derivative_of_the_value():
     assert np.allclose(added[valid, 7], 0.01 * o * (1 - o) / valid.sum(), rtol=1e-5)
     assert np.allclose(added[valid, 4:7], 0.02 * np.exp(ft[valid, 4:7].astype(np.float64)) / (3 * valid.sum()), rtol=1e-5)
     assert (mcmc_ref.regulariser(ft, np.ones(n, np.int8), 0.01, 0.02)[0] == 0).all()
+
+
+# ---- the scenes of tests/mcmc_cases.py are the ones the kernels change path at ------------------------------------------------
+# Each test asserts, from tests/mcmc_ref.py alone, what its scene exists for.  One that fails means the scene must change.
+def _thread_of(block, n):
+    return block // MC.per_thread(n)
+
+
+def test_case_past_1024_blocks_gives_every_scan_thread_two_blocks():
+    s, ref = MC.scene("past_1024_blocks"), MC.reference("past_1024_blocks")
+    n = s["pc"].shape[0]
+    assert n == MC.N_LARGE and MC.blocks(n) == 1026 and MC.per_thread(n) == 2
+    f, c = MC.block_facts("past_1024_blocks"), MC.counts(ref)
+    print(c)
+    both = [t for t in range(MC.blocks(n) // 2) if all(f[k][2 * t] > 0 and f[k][2 * t + 1] > 0 for k in ("weight", "dead"))]
+    assert 150 in both and any(t < 512 for t in both)              # a thread whose second block adds to a running prefix
+    assert _thread_of(1024, n) == _thread_of(1025, n) == 512 and 513 * MC.per_thread(n) >= MC.blocks(n)     # 513.. own nothing
+    for b in (1024, 1025):                                          # the last full block and the partial one
+        assert f["dead"][b] > 0 and f["free"][b] > 0 and f["alive"][b] > 0, b
+    assert any(r >= MC.N_FULL for r in ref["source_of"]) and any(r >= MC.N_FULL for r in ref["dest_row"])
+    assert c["new"] > 0 and c["dead"] > 0 and c["free"] > c["new"]                                          # some free rows stay free
+    assert int((s["mask"] == 2).sum()) > n - 1200
+
+
+def test_case_second_turn_has_destinations_past_1024_blocks_of_them():
+    s = MC.scene("second_turn")
+    for n_max in (51, 5):
+        ref = MC.reference("second_turn", n_max=n_max)
+        c = MC.counts(ref)
+        print(n_max, c)
+        assert c["destinations"] > MC.N_FULL and c["alive"] == c["sources"] == 5 and c["new"] == MC.SECOND_TURN_FREE
+        rows = MC.second_turn_rows("second_turn", n_max=n_max)
+        assert len(rows) == c["destinations"] - MC.N_FULL == 294
+        assert int((s["mask"][rows] == 0).sum()) == 254 and int((s["mask"][rows] == 1).sum()) == 40         # dead rows, then free rows
+        assert min(ref["multiplicity"][r] for r, _ in MC.SECOND_TURN_ALIVE) > 10_000 > n_max               # M is clamped to n_max
+        assert {ref["source_of"][j] for j in range(MC.N_FULL, c["destinations"])} >= {7, MC.N_LARGE - 1}
+
+
+def test_case_unit_weights_puts_draws_on_every_kind_of_prefix_boundary():
+    s, ref = MC.scene("unit_weights"), MC.reference("unit_weights")
+    f = MC.unit_facts()
+    print(MC.counts(ref), f)
+    assert s["settings"]["min_opacity"] == 1e-9 and s["settings"]["call_index"] == MC.UNIT_CALL_INDEX
+    assert f["weights"] == [1, 2] and f["raised_to_one"] > 0 and f["W"] < 1000
+    assert 2 * f["draws_on_a_prefix"] >= f["D"] > 0
+    # the all-dead block between two blocks with weight, and a draw on the prefix it shares with its successor
+    assert f["empty_block_weight"] == 0 and 0 < f["weight_before_the_empty_block"] < f["W"]
+    hit = f["draws_on_the_shared_prefix"]
+    assert len(hit) >= 1 and set(hit) == {f["first_alive_after_the_empty_block"]}
+    assert f["first_alive_after_the_empty_block"] >= (MC.UNIT_EMPTY_BLOCK + 1) * MC.BLOCK
+    assert len(f["seams_drawn_on_both_sides"]) >= 1                 # the last alive row of a block and the first of the next
+    assert f["sources_clamped_up"] >= 1
+    _, _, (o, p, d) = mcmc_ref.relocated(s["ft"][hit[0], 7], s["ft"][hit[0], 4:7], int(ref["multiplicity"][hit[0]]), 51)
+    assert p == mcmc_ref.P_MIN and o < 2.0 ** -22 and -17.0 < math.log(o / d) < -9.0
+
+
+@pytest.mark.parametrize("name, n, nb, per", [("blocks_1024", MC.N_FULL, 1024, 1), ("blocks_1025_last_alive", MC.N_FULL + 1, 1025, 2),
+                                              ("blocks_1025_last_dead", MC.N_FULL + 1, 1025, 2)])
+def test_case_boundary_sizes_around_one_block_per_scan_thread(name, n, nb, per):
+    s, ref = MC.scene(name), MC.reference(name)
+    c = MC.counts(ref)
+    print(c)
+    assert s["pc"].shape[0] == n and MC.blocks(n) == nb and MC.per_thread(n) == per
+    assert c["dead"] > 0 and c["new"] > 0 and c["sources"] > 0
+    f = MC.block_facts(name)
+    if name == "blocks_1025_last_alive":                            # block 1024 is one row, alone with scan thread 512
+        assert f["alive"][1024] == 1 and ref["weights"][-1] > 0 and n - 1 in ref["source_of"]
+    if name == "blocks_1025_last_dead":
+        assert f["dead"][1024] == 1 and ref["dest_row"][c["dead"] - 1] == n - 1
+    if name == "blocks_1024":
+        assert f["weight"][1023] > 0 and f["dead"][1023] > 0
+
+
+def test_case_loop_scene_has_rows_the_noise_moves_and_rows_that_are_dead():
+    import trainer_util as TU
+    pc, ft, rows = MC.loop_initial(*TU.perturbed(TU.ground_truth_scene()))
+    assert len(rows) == MC.LOOP_PLANTED == 40 and rows.max() < TU.N_POINTS
+    logit = ft[rows, 7]
+    threshold = mcmc_ref.min_opacity_logit()
+    assert logit.min() == -6.0 and logit.max() == -2.5 and 5 <= int((logit <= threshold).sum()) <= 35
+    mask = np.zeros(len(pc), np.int8)
+    scale = MC.LOOP["noise_lr"] * MC.LOOP["position_learning_rate"]
+    for step in (0, 1, 2):
+        moved = MC.rows_moved_by_more_than_an_ulp(pc, ft, mask, scale, MC.LOOP["seed"], step)
+        print(f"step {step}: {len(moved)} rows move by more than an ulp of their position, {len(set(moved) & set(rows))} of them planted")
+        assert len(moved) >= 10
