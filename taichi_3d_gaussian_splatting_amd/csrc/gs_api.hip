@@ -1,75 +1,19 @@
-// gs_api.hip -- the C ABI of libgsrast.so (include/gs_rasterizer.h): context, device
-// arena, frame pool and the forward / backward orchestration that replaces
-// _module_function.forward / .backward of the reference (RAST:830-1163).
-#include "../../include/gs_rasterizer.h"
+// gs_api.hip -- the part of libgsrast.so's C ABI (include/gs_rasterizer.h) that knows a Frame: context, device arena, frame
+// pool, the counter hand-over and the forward / backward orchestration that replaces _module_function.forward / .backward
+// of the reference (RAST:830-1163), and the calls bound to a frame (gs_channels_*, gs_touched_rows, gs_frame_*).  The entry
+// points that hold no frame are gs_api_calls.hip's; what both share is gs_host.h.
 #include "../../include/gs_channels.h"
 #include "../../include/gs_sparse.h"
-#include "../../include/gs_knn.h"
-#include "../../include/gs_exchange.h"
-#include "../../include/gs_targets.h"
-#include "../../include/gs_targets_rgba.h"
-#include "../../include/gs_loss_weighted.h"
-#include "../../include/gs_mixture.h"
-#include "../../include/gs_mixture_grad.h"
-#include "../../include/gs_compose.h"
-#include "../../include/gs_frames.h"
-#include "../../include/gs_fusion.h"
-#include "../../include/gs_mcmc.h"
-#include "../../include/gs_appearance.h"
-#include "../../include/gs_bilateral.h"
-#include "../../include/gs_vq.h"
-#include "../../include/gs_depth.h"
-#include "../../include/gs_geometry.h"
-#include "../../include/gs_normals.h"
-#include "gs_common.h"
+#include "gs_host.h"
 #include "gs_sort_key.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
-#include <initializer_list>
-#include <mutex>
-#include <string>
-#include <vector>
-#include <cstdio>
 #include <cstring>
 #include <cstdlib>
 
-static thread_local std::string g_last_error;
-
-static int fail(int code, const std::string& msg)
-{
-    g_last_error = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return fail(e__ == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP,            \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                       \
-    } while (0)
-
-// Grow-only device buffer.  Growth (hipFree + hipMalloc) happens only when a frame is larger
-// than anything seen before; steady-state frames allocate nothing.
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes, int64_t* total)
-    {
-        if (bytes <= cap) return hipSuccess;
-        size_t want = bytes + bytes / 4 + 256;     // 25 % slack: K drifts from frame to frame
-        if (p) { (void)hipFree(p); *total -= (int64_t)cap; p = nullptr; cap = 0; }
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want; *total += (int64_t)want;
-        return hipSuccess;
-    }
-    void release(int64_t* total) { if (p) { (void)hipFree(p); *total -= (int64_t)cap; } p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+thread_local std::string g_last_error;
 
 // What RAST:998-1019 saves for backward, in this library's layouts (DESIGN.md "HBM layout").
 struct FrameBufs {
@@ -107,15 +51,6 @@ struct Frame {
     hipStream_t pending_stream = nullptr;
 };
 
-struct GsProf {
-    uint64_t mask = 0;
-    struct Rec { int kid; hipEvent_t a, b; };
-    std::vector<Rec> recs;          // records in flight since the last read
-    std::vector<hipEvent_t> spare;  // recycled events
-    double total_ms[KID_COUNT_] = {};
-    int64_t launches[KID_COUNT_] = {};
-};
-
 int gs_prof_begin(GsProf* p, int kid, hipStream_t s)
 {
     if (!p || !((p->mask >> kid) & 1ull)) return -1;
@@ -135,65 +70,6 @@ void gs_prof_end(GsProf* p, int rec, hipStream_t s)
     if (!p || rec < 0) return;
     (void)hipEventRecord(p->recs[rec].b, s);
 }
-
-// gs_image_resample: both axes of one geometry on the device (start, count, weight of x, then of y, in one buffer)
-struct ResampleTable {
-    int H_in = 0, W_in = 0, h_full = 0, w_full = 0;
-    DevBuf buf;
-    GsResampleAxis ax{}, ay{};
-    std::vector<unsigned char> host;    // what the upload reads: lives as long as the table
-};
-
-#define GS_COUNTER_SLOTS 64
-struct gs_ctx {
-    int device = 0;
-    GsProf prof;
-    std::mutex mu;
-    int64_t device_bytes = 0;
-    std::vector<Frame*> frames;         // slot i of the ticket space (recycled, generation-tagged)
-    int transient = -1;                 // slot of the frame of the last keep_for_backward == 0 call
-    // scratch shared by all frames (stream ordered)
-    DevBuf block_counts, block_offsets, tile_block_sums, hist, scan_tmp, counters, partial, visited, zero_row, sums, loss_ws;
-    // the per-point stage's [digit][block] pair counts + their row scans (k_project.hip: gs_bin_digits_*; k_binning.hip: k_keygen's first
-    // pass).  Written by the frame's per-point kernel, read by every binning of the SAME call (the second one of a re-sized frame too):
-    // nothing else touches it, and the K-sized hist of the later passes is a buffer of its own
-    DevBuf first_hist;
-    DevBuf pose_scratch;                // per-block pose-gradient records (k_pose.hip), grown on demand
-    DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
-    DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
-    DevBuf bilateral_ws;                // gs_bilateral_slice_backward: the block sums of split footprints, read by nothing else
-    DevBuf depth_ws;                    // gs_depth_loss_forward: its finished moments and per-block sums, read by nothing else
-    DevBuf geometry_ws;                 // gs_normal_loss_forward / gs_depth_smooth_forward: their per-tile sums, read by nothing else
-    DevBuf ch_partial, ch_flags;        // gs_channels_backward: partial rows and row flags of one channel chunk; never shared with partial / visited
-    uint8_t visit_gen = 0;                 // tag of the last backward's flags in `visited` (0: the buffer is all zero)
-    // The last backward blend of the context: its number (visit_gen wraps, this does not) and where its per-point `touched` bytes
-    // begin in `visited`.  A frame whose bwd_serial is not this one no longer owns the tags (gs_touched_rows).
-    uint64_t bwd_serial = 0;
-    size_t touched_offset = 0;
-    DevBuf row_block_totals;               // gs_touched_rows: one count per compaction block
-    DevBuf merge_tags, merge_ids;          // gs_merge_rows: one tag byte per point-cloud row, the id words of all lists (block totals: row_block_totals)
-    DevBuf knn_sort, knn_hist, knn_points, knn_tree;   // gs_knn: its own work memory, read by nothing else (a kept frame never sees it)
-    DevBuf mix_records, mix_sums, mix_partial;         // gs_mixture_*: their own work memory, read by nothing else
-    DevBuf mixg_queries, mixg_partial, mixg_sums, mixg_x_partial;   // gs_mixture_*_backward: theirs (and mix_records, mix_sums)
-    std::vector<struct ResampleTable*> resample_tables;   // gs_image_resample: the tables of the geometries seen, oldest first
-    GsCounters* host_counters = nullptr;   // pinned, device-visible, GS_COUNTER_SLOTS of them; written by gs_publish_counters (k_keygen's last block or k_scan_tiles_publish)
-    GsCounters* host_counters_dev = nullptr;   // the device's address of it
-    uint64_t slots_busy = 1ull;            // slot 0 serves the calls that wait at once; the others belong to frames begun and not yet read
-    int32_t ticket = 0;                    // sequence number of the last forward
-    int64_t counter_wait_ns = 0;           // host time spent waiting for frame counters so far (gs_ctx_counter_wait_ns)
-    // Predicted sizing of the per-pixel half (run_forward_tail): what the last frame of this ctx needed, for an image of this
-    // size.  The next frame's binning, sort and blend are queued on it without waiting for the frame's own counters.
-    struct { bool valid = false; int H = 0, W = 0; uint32_t K = 0; int max_code = 0; } seen;
-    // dispatch order for the next forward blend: the last backward's tile order (heaviest first).  Only ever a complete
-    // permutation of [0, order_hint_T) written by k_tile_order; 0 = none.  A hint only moves work in time.
-    DevBuf order_hint;
-    int order_hint_T = 0;
-    // stream hand-over: the scratch above is recycled in stream order, so work arriving on another stream waits for
-    // everything issued on the previous one
-    bool has_stream = false;
-    hipStream_t last_stream = nullptr;
-    hipEvent_t switch_event = nullptr;
-};
 
 extern "C" int gs_abi_version(void) { return GS_ABI_VERSION; }
 extern "C" const char* gs_last_error(void) { return g_last_error.c_str(); }
@@ -277,43 +153,6 @@ extern "C" int gs_profile_read(gs_ctx* c, double* total_ms, int64_t* launches, i
 
 extern "C" int64_t gs_ctx_device_bytes(const gs_ctx* c) { return c ? c->device_bytes : 0; }
 extern "C" int64_t gs_ctx_counter_wait_ns(const gs_ctx* c) { return c ? c->counter_wait_ns : 0; }
-
-// Entering a call that launches on stream s (mutex held).
-static hipError_t enter_stream(gs_ctx* c, hipStream_t s)
-{
-    if (c->has_stream && c->last_stream != s) {
-        hipError_t e = hipEventRecord(c->switch_event, c->last_stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(s, c->switch_event, 0);
-        if (e != hipSuccess) return e;
-    }
-    c->has_stream = true; c->last_stream = s;
-    return hipSuccess;
-}
-
-// The prologue of every call that launches work (mutex held), after the checks that can refuse the call: the ctx's device,
-// then the stream hand-over.  *s_out = the call's stream.
-static int enter_call(gs_ctx* c, gs_stream stream_, hipStream_t* s_out)
-{
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(enter_stream(c, s));
-    *s_out = s;
-    return GS_OK;
-}
-
-// A buffer a stage grows before it queues anything; the out-of-memory error names the first one that cannot grow.
-struct Need { DevBuf* buf; size_t bytes; const char* name; };
-#define NEED(buf, bytes) Need{ &(buf), (bytes), #buf }
-
-static int grow(gs_ctx* c, std::initializer_list<Need> needs)
-{
-    for (const Need& n : needs)
-        if (n.buf->ensure(n.bytes, &c->device_bytes) != hipSuccess)
-            return fail(GS_ERR_OUT_OF_MEMORY, std::string("device allocation failed: ") + n.name);
-    return GS_OK;
-}
-
 // ---- frame tickets ------------------------------------------------------------------------------------------------
 static gs_frame* ticket_of(int slot, uint32_t generation)
 {
@@ -448,7 +287,7 @@ static int resolve_pending(gs_ctx* c, Frame* f)
 static int lookup(gs_ctx* c, const gs_frame* h, const char* who, bool pending, Frame** out)
 {
     Frame* f = resolve(c, h);
-    if (!f) return fail(GS_ERR_STATE, std::string(who) + ": not a live frame of this context");
+    if (!f) return fail(GS_ERR_STATE, who, "not a live frame of this context");
     if (pending)
         if (const int rc = resolve_pending(c, f)) return rc;
     *out = f;
@@ -459,34 +298,34 @@ static int check_geometry(const gs_camera* cam, const gs_config* cfg, const char
 {
     const int H = cam->camera_height, W = cam->camera_width;
     if (W <= 0 || H <= 0 || (!cfg->allow_partial_tiles && (W % GS_TILE != 0 || H % GS_TILE != 0)))        // RAST:1193-1194
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": camera_width and camera_height must be positive multiples of 16 "
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "camera_width and camera_height must be positive multiples of 16 "
                                              "(or set gs_config.allow_partial_tiles)");
     *tiles_x = (W + GS_TILE - 1) / GS_TILE; *tiles_y = (H + GS_TILE - 1) / GS_TILE;
-    if (*tiles_x > 65535 || *tiles_y > 65535) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": image too large");
+    if (*tiles_x > 65535 || *tiles_y > 65535) return fail(GS_ERR_INVALID_ARGUMENT, who, "image too large");
     return GS_OK;
 }
 
 static int check_scene(const gs_scene* sc, const gs_camera* cam, const char* who)
 {
     const int64_t N = sc->n_points;
-    if (N < 0 || N >= (int64_t)1 << 31) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_points out of range");
-    if (cam->n_objects <= 0) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_objects must be >= 1");
+    if (N < 0 || N >= (int64_t)1 << 31) return fail(GS_ERR_INVALID_ARGUMENT, who, "n_points out of range");
+    if (cam->n_objects <= 0) return fail(GS_ERR_INVALID_ARGUMENT, who, "n_objects must be >= 1");
     if (N > 0 && (!sc->point_cloud || !sc->point_cloud_features || !sc->point_invalid_mask || !sc->point_object_id))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL scene array");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "NULL scene array");
     if (!cam->q_pointcloud_camera || !cam->t_pointcloud_camera || !cam->camera_intrinsics)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL camera array");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "NULL camera array");
     if (((uintptr_t)sc->point_cloud_features & 15u) != 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": point_cloud_features must be 16-byte aligned");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "point_cloud_features must be 16-byte aligned");
     return GS_OK;
 }
 
 static int check_forward_out(const gs_forward_out* out, const gs_config* cfg, int keep, const char* who)
 {
-    if (!out->rasterized_image) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": rasterized_image is NULL");
+    if (!out->rasterized_image) return fail(GS_ERR_INVALID_ARGUMENT, who, "rasterized_image is NULL");
     if (!cfg->rgb_only && (!out->rasterized_depth || !out->pixel_accumulated_alpha ||
                            !out->pixel_offset_of_last_effective_point || !out->pixel_valid_point_count))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": an output is NULL although rgb_only is false");
-    if (keep && cfg->rgb_only) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": rgb_only frames cannot be kept for backward (RAST:478-484)");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "an output is NULL although rgb_only is false");
+    if (keep && cfg->rgb_only) return fail(GS_ERR_INVALID_ARGUMENT, who, "rgb_only frames cannot be kept for backward (RAST:478-484)");
     return GS_OK;
 }
 
@@ -541,7 +380,7 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     const int T = f->info.n_tiles;
     const size_t nb = (size_t)((N + 255) / 256);
     const size_t Np = (size_t)(N > 0 ? N : 1);
-    int rc = grow(c, { NEED(B.mask, Np), NEED(B.ids, 4 * Np), NEED(B.cam_index, 4 * Np),
+    int rc = grow(c, "forward", { NEED(B.mask, Np), NEED(B.ids, 4 * Np), NEED(B.cam_index, 4 * Np),
                        NEED(B.rec, 64 * Np),
                        NEED(B.box, 8 * Np), NEED(B.ntiles, 4 * Np), NEED(B.depth_codes, 4 * Np), NEED(B.offsets, 4 * Np),
                        NEED(B.tile_start, 4 * GS_TILE_INTS(T)),    // tile_start | tile_end | tile_work | tile_cut | four ints, cleared together
@@ -553,7 +392,7 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     // the digit table only for a call that goes on to bin these points (gs_forward, the one caller that waits later): the shard entry
     // points hand records out, and whoever renders them has k_boxes_from_records build the table over ITS blocks
     const bool first_pass = wait == WAIT_LATER && sort_first_pass_enabled(N);
-    if (first_pass && (rc = grow(c, { NEED(c->first_hist, 4 * gs_first_hist_elems(N)) })) != GS_OK) return rc;
+    if (first_pass && (rc = grow(c, "forward", { NEED(c->first_hist, 4 * gs_first_hist_elems(N)) })) != GS_OK) return rc;
     f->n_objects = cam->n_objects;
 
     GsProjectArgs pa{};
@@ -600,12 +439,12 @@ static int run_records_stage(gs_ctx* c, Frame* f, const float* records, int64_t 
     const int T = f->info.n_tiles;
     const size_t Mp = (size_t)(m > 0 ? m : 1);
     const size_t nb = (size_t)((m + 255) / 256);
-    const int rc = grow(c, { NEED(B.rec, 64 * Mp), NEED(B.box, 8 * Mp), NEED(B.ntiles, 4 * Mp), NEED(B.depth_codes, 4 * Mp), NEED(B.offsets, 4 * Mp),
+    const int rc = grow(c, "forward", { NEED(B.rec, 64 * Mp), NEED(B.box, 8 * Mp), NEED(B.ntiles, 4 * Mp), NEED(B.depth_codes, 4 * Mp), NEED(B.offsets, 4 * Mp),
                              NEED(B.tile_start, 4 * GS_TILE_INTS(T)), NEED(B.tile_order, 4 * GS_ORDER_INTS(T)),
                              NEED(c->tile_block_sums, 4 * (nb + 1)) });
     if (rc != GS_OK) return rc;
     const bool first_pass = sort_first_pass_enabled(m);
-    if (first_pass) if (const int rc2 = grow(c, { NEED(c->first_hist, 4 * gs_first_hist_elems(m)) })) return rc2;
+    if (first_pass) if (const int rc2 = grow(c, "forward", { NEED(c->first_hist, 4 * gs_first_hist_elems(m)) })) return rc2;
     if (m > 0) HIP_TRY(hipMemcpyAsync(B.rec.p, records, (size_t)m * 64, hipMemcpyDeviceToDevice, s));
     GsProjectArgs pa{};
     pa.prof = &c->prof; pa.N = m; pa.H = f->info.camera_height; pa.W = f->info.camera_width; pa.depth_scale = cfg->depth_to_sort_key_scale;
@@ -643,7 +482,7 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
         // is claimed at run time: a capacity that could run out would make WHICH lists get cuts, and with it the last bits of the
         // gradients, depend on the order of the claims.)
         cut_cap = (int)std::min<uint64_t>((uint64_t)K_bound / GS_SEG + (uint64_t)T + 2, 0x7fffffffu);
-        if (const int rc = grow(c, { NEED(B.cuts, (size_t)cut_cap * 256 * sizeof(float4)), NEED(B.cut_mag, (size_t)cut_cap * 256 * sizeof(float2)) }))
+        if (const int rc = grow(c, "forward", { NEED(B.cuts, (size_t)cut_cap * 256 * sizeof(float4)), NEED(B.cut_mag, (size_t)cut_cap * 256 * sizeof(float2)) }))
             return rc;
     }
     f->cut_cap = cut_cap;
@@ -654,7 +493,7 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     if (depth_bits + tile_bits > 63) return fail(GS_ERR_INVALID_ARGUMENT, "sort key needs more than 63 bits");
     const size_t Kp = K_bound > 0 ? K_bound : 1;
     const size_t hist_elems = gs_sort_hist_elems(K_bound);
-    if (const int rc = grow(c, { NEED(B.keys_a, (size_t)key_bytes * Kp), NEED(B.keys_b, (size_t)key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
+    if (const int rc = grow(c, "forward", { NEED(B.keys_a, (size_t)key_bytes * Kp), NEED(B.keys_b, (size_t)key_bytes * Kp), NEED(B.vals_a, 4 * Kp), NEED(B.vals_b, 4 * Kp),
                                  NEED(c->hist, 4 * hist_elems), NEED(c->scan_tmp, 4 * GS_SORT_DIGITS) }))
         return rc;
 
@@ -1047,13 +886,13 @@ static int check_backward_points_args(const Frame* f, const gs_scene* sc, const 
                                       bool pose_only = false)
 {
     if (sc->n_points > 0 && !pose_only && (!out->grad_pointcloud || !out->grad_pointcloud_features))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grad_pointcloud / grad_pointcloud_features are mandatory");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "grad_pointcloud / grad_pointcloud_features are mandatory");
     if (sc->n_points != f->info.n_points || cam->camera_height != f->info.camera_height || cam->camera_width != f->info.camera_width)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": scene/camera do not match the frame");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "scene/camera do not match the frame");
     if (((uintptr_t)out->grad_pointcloud_features & 15u) != 0 || ((uintptr_t)sc->point_cloud_features & 15u) != 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": feature arrays must be 16-byte aligned");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "feature arrays must be 16-byte aligned");
     if (out->hook_grad_pointfeatures_in_camera && ((uintptr_t)out->hook_grad_pointfeatures_in_camera & 15u) != 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": hook feature array must be 16-byte aligned");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "hook feature array must be 16-byte aligned");
     return GS_OK;
 }
 
@@ -1175,12 +1014,12 @@ extern "C" int gs_backward_shard(gs_ctx* c, gs_frame* h, const gs_scene* sc, con
 static int channels_enter(gs_ctx* c, const gs_frame* h, int32_t n_channels, const char* who, gs_stream stream_, Frame** f_out, hipStream_t* s_out)
 {
     if (n_channels < 1 || n_channels > GS_CHANNELS_MAX)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_channels must be in 1.." + std::to_string(GS_CHANNELS_MAX));
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "n_channels must be in 1.." + std::to_string(GS_CHANNELS_MAX));
     Frame* f;
     if (const int rc = lookup(c, h, who, true, &f)) return rc;
     if (f->info.stages != (GS_STAGE_PROJECT | GS_STAGE_RASTER))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": the frame must come from gs_forward (frames made from records or shards are not supported)");
-    if (f->rgb_only) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": an rgb_only frame has no pixel_offset_of_last_effective_point");
+        return fail(GS_ERR_INVALID_ARGUMENT, who, "the frame must come from gs_forward (frames made from records or shards are not supported)");
+    if (f->rgb_only) return fail(GS_ERR_INVALID_ARGUMENT, who, "an rgb_only frame has no pixel_offset_of_last_effective_point");
     if (const int rc = enter_call(c, stream_, s_out)) return rc;
     *f_out = f;
     return GS_OK;
@@ -1230,7 +1069,7 @@ extern "C" int gs_channels_backward(gs_ctx* c, const gs_frame* h, const float* g
     if (a.K == 0u || a.M <= 0) return GS_OK;
     // scratch of one channel chunk: four partial rows (one per quadrant) per (point, tile) pair, their flags, one byte per point
     const size_t rows = (size_t)a.K * 4, row_flags = (rows + 15) / 16 * 16;
-    if (const int rc = grow(c, { NEED(c->ch_partial, rows * (size_t)gs_channels_chunk(n_channels) * sizeof(float)),
+    if (const int rc = grow(c, "gs_channels_backward", { NEED(c->ch_partial, rows * (size_t)gs_channels_chunk(n_channels) * sizeof(float)),
                                  NEED(c->ch_flags, row_flags + (size_t)a.M) }))
         return rc;
     a.partial = c->ch_partial.as<float>(); a.flags = c->ch_flags.as<uint8_t>(); a.touched = a.flags + row_flags;
@@ -1240,154 +1079,8 @@ extern "C" int gs_channels_backward(gs_ctx* c, const gs_frame* h, const float* g
     return GS_OK;
 }
 
-static GsLossImage loss_image(const gs_loss_image* im, int clamp)
-{
-    GsLossImage r; r.p = im->data; r.sc = im->stride_channel; r.sy = im->stride_row; r.sx = im->stride_column; r.clamp = clamp;
-    return r;
-}
-static int loss_check(const char* who, const gs_loss_image* a, const gs_loss_image* b, int32_t H, int32_t W)
-{
-    if (!a || !b || !a->data || !b->data) return fail(GS_ERR_INVALID_ARGUMENT, (std::string(who) + ": NULL image"));
-    if (H < 11 || W < 11) return fail(GS_ERR_INVALID_ARGUMENT, (std::string(who) + ": image smaller than the 11x11 SSIM window"));
-    return GS_OK;
-}
-
-extern "C" int64_t gs_loss_maps_floats(int32_t H, int32_t W) { return (H < 1 || W < 1) ? 0 : (int64_t)gs_loss_maps_size((int)H, (int)W); }
-
-extern "C" int gs_loss_l1_ssim_forward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, int32_t H, int32_t W, int32_t clamp_pred,
-                                       float lambda_value, float* maps, float* loss_terms, gs_stream stream_)
-{
-    if (!c || !maps || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_forward: NULL argument");
-    if (int rc = loss_check("gs_loss_l1_ssim_forward", pred, gt, H, W)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    hipError_t e = c->loss_ws.ensure(gs_loss_partials_floats(H, W) * sizeof(float), &c->device_bytes);
-    if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_loss_forward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, c->loss_ws.as<float>(), loss_terms, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_loss_l1_ssim_backward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, int32_t H, int32_t W, int32_t clamp_pred,
-                                        float lambda_value, const float* maps, const float* upstream, const gs_loss_image* grad_pred,
-                                        gs_stream stream_)
-{
-    if (!c || !maps || !grad_pred || !grad_pred->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_backward: NULL argument");
-    if (int rc = loss_check("gs_loss_l1_ssim_backward", pred, gt, H, W)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_loss_backward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), H, W, lambda_value, maps, upstream, loss_image(grad_pred, 0), s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- per-pixel weights (include/gs_loss_weighted.h) ----
-extern "C" int gs_loss_l1_ssim_weighted_forward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, const float* pixel_weight,
-                                                int32_t H, int32_t W, int32_t clamp_pred, float lambda_value, float* maps, float* loss_terms,
-                                                gs_stream stream_)
-{
-    if (!c || !pixel_weight || !maps || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_weighted_forward: NULL argument");
-    if (int rc = loss_check("gs_loss_l1_ssim_weighted_forward", pred, gt, H, W)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    hipError_t e = c->loss_ws.ensure(gs_loss_weighted_partials_floats(H, W) * sizeof(float), &c->device_bytes);
-    if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim_weighted_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_loss_weighted_forward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), pixel_weight, H, W, lambda_value, maps,
-                                    c->loss_ws.as<float>(), loss_terms, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_loss_l1_ssim_weighted_backward(gs_ctx* c, const gs_loss_image* pred, const gs_loss_image* gt, const float* pixel_weight,
-                                                 int32_t H, int32_t W, int32_t clamp_pred, float lambda_value, const float* maps,
-                                                 const float* loss_terms, const float* upstream, const gs_loss_image* grad_pred,
-                                                 gs_stream stream_)
-{
-    if (!c || !pixel_weight || !maps || !loss_terms || !grad_pred || !grad_pred->data)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim_weighted_backward: NULL argument");
-    if (int rc = loss_check("gs_loss_l1_ssim_weighted_backward", pred, gt, H, W)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_loss_weighted_backward(loss_image(pred, clamp_pred != 0), loss_image(gt, 0), pixel_weight, H, W, lambda_value, maps, loss_terms,
-                                     upstream, loss_image(grad_pred, 0), s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// the one-call form: contiguous (3,H,W) images, the maps in the context's own workspace, upstream = 1
-extern "C" int gs_loss_l1_ssim(gs_ctx* c, const float* pred, const float* gt, int32_t H, int32_t W, float lambda_value,
-                               float* loss_terms, float* grad_pred, gs_stream stream_)
-{
-    if (!c || !pred || !gt || !loss_terms) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim: NULL argument");
-    if (H < 11 || W < 11) return fail(GS_ERR_INVALID_ARGUMENT, "gs_loss_l1_ssim: image smaller than the 11x11 SSIM window");
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    const size_t maps_floats = gs_loss_maps_size(H, W);
-    hipError_t e = c->loss_ws.ensure((maps_floats + gs_loss_partials_floats(H, W)) * sizeof(float), &c->device_bytes);
-    if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_loss_l1_ssim: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    GsLossImage X{ pred, (long long)H * W, (long long)W, 1, 0 }, Y{ gt, (long long)H * W, (long long)W, 1, 0 };
-    float* maps = c->loss_ws.as<float>();
-    gs_launch_loss_forward(X, Y, H, W, lambda_value, maps, maps + maps_floats, loss_terms, s);
-    if (grad_pred) {
-        GsLossImage G{ grad_pred, (long long)H * W, (long long)W, 1, 0 };
-        gs_launch_loss_backward(X, Y, H, W, lambda_value, maps, nullptr, G, s);
-    }
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_scale_regulariser(gs_ctx* c, const float* feat, const int8_t* mask, int64_t n, float* out, gs_stream stream_)
-{
-    if (!c || !out || (n > 0 && (!feat || !mask))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser: NULL argument");
-    if (n < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser: n_points < 0");
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    hipError_t e = c->loss_ws.ensure((size_t)(2 * ((n + 255) / 256) + 16) * sizeof(float), &c->device_bytes);
-    if (e != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "gs_scale_regulariser: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_reg_value(feat, mask, n, c->loss_ws.as<float>(), out, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_scale_regulariser_grad(gs_ctx* c, const float* feat, const int8_t* mask, int64_t n, const float* value_and_count,
-                                         const float* upstream, float* grad, gs_stream stream_)
-{
-    if (!c || (n > 0 && (!feat || !mask || !value_and_count || !upstream || !grad)))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser_grad: NULL argument");
-    if (grad && ((uintptr_t)grad & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scale_regulariser_grad: grad must be 16-byte aligned");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_reg_grad(feat, mask, n, value_and_count, upstream, grad, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_adam_step(gs_ctx* c, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                            float lr, float beta1, float beta2, float eps, int64_t step, gs_stream stream_)
-{
-    if (!c || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step: NULL argument");
-    if (n < 0 || step < 1) return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step: n must be >= 0 and step >= 1");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_adam(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- touched rows and the row-selective Adam step (include/gs_sparse.h, k_sparse.hip) ------------------------------------
-// No host synchronisation and no device-to-host copy in either: the count stays on the device.
+// ---- touched rows (include/gs_sparse.h, k_sparse.hip; the row-selective Adam step that reads the list: gs_api_calls.hip) ----
+// No host synchronisation and no device-to-host copy: the count stays on the device.
 extern "C" int gs_touched_rows(gs_ctx* c, const gs_frame* h, int32_t* ids_out, int64_t capacity, int32_t* count_out, gs_stream stream_)
 {
     if (!c || !h || !ids_out || !count_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_touched_rows: NULL argument");
@@ -1405,495 +1098,11 @@ extern "C" int gs_touched_rows(gs_ctx* c, const gs_frame* h, int32_t* ids_out, i
     // no pair: the blend did not run and wrote no tag (stale bytes never equal this backward's tag, but nothing needs reading)
     const int M_eff = (f->info.n_keys > 0 && f->info.n_tiles > 0) ? M : 0;
     HIP_TRY(hipSetDevice(c->device));           // the scratch grows before the stream enters: a call that fails here leaves it alone
-    if ((rc = grow(c, { NEED(c->row_block_totals, (size_t)(gs_rows_blocks(M_eff) + 1) * sizeof(uint32_t)) })) != GS_OK) return rc;
+    if ((rc = grow(c, "gs_touched_rows", { NEED(c->row_block_totals, (size_t)(gs_rows_blocks(M_eff) + 1) * sizeof(uint32_t)) })) != GS_OK) return rc;
     hipStream_t s;
     if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     gs_launch_touched_rows(c->visited.as<uint8_t>() + c->touched_offset, c->visit_gen, frame_view(*f).ids, M_eff,
                            c->row_block_totals.as<uint32_t>(), ids_out, capacity, count_out, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_adam_step_rows(gs_ctx* c, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_rows,
-                                 int32_t row_len, const int32_t* ids, const int32_t* count, int64_t max_count,
-                                 float lr, float beta1, float beta2, float eps, int64_t step, gs_stream stream_)
-{
-    if (!c || (n_rows > 0 && max_count > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !ids || !count)))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step_rows: NULL argument");
-    if (row_len < 1 || step < 1 || n_rows < 0 || max_count < 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_adam_step_rows: row_len and step must be >= 1, n_rows and max_count >= 0");
-    if (n_rows == 0 || max_count == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_adam_rows(param, grad, exp_avg, exp_avg_sq, n_rows, row_len, ids, count, max_count, lr, beta1, beta2, eps, step, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- packed rows and their merge (include/gs_exchange.h, k_exchange.hip) -----------------------------------------------------
-// No host synchronisation and no device-to-host copy in either: every count stays on the device.
-extern "C" int gs_pack_rows(gs_ctx* c, const float* grad_features, const float* grad_pointcloud, int64_t n_rows, const int32_t* ids,
-                            const int32_t* count, int64_t max_count, float* packed_out, gs_stream stream_)
-{
-    if (!c || (n_rows > 0 && max_count > 0 && (!grad_features || !grad_pointcloud || !ids || !count || !packed_out)))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: NULL argument");
-    if (n_rows < 0 || max_count < 0 || n_rows > 0x7fffffffll)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: n_rows and max_count must be >= 0, n_rows <= 2^31 - 1");
-    if (n_rows == 0 || max_count == 0) return GS_OK;
-    if ((uintptr_t)packed_out & 15u) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pack_rows: packed_out must be 16-byte aligned");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_pack_rows(grad_features, grad_pointcloud, n_rows, ids, count, max_count, packed_out, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_merge_rows(gs_ctx* c, const float* packed, const int32_t* counts, int32_t n_lists, int64_t list_stride, int64_t n_rows,
-                             float* grad_features_out, float* grad_pointcloud_out, int32_t* union_ids_out, int64_t union_capacity,
-                             int32_t* union_count_out, gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: NULL argument");
-    if (n_lists < 1 || n_lists > GS_MERGE_MAX_LISTS) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: n_lists must be >= 1 and <= 64");
-    if (list_stride < 0 || n_rows < 0 || n_rows > 0x7fffffffll - 4096 || list_stride > (int64_t)1 << 40)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: list_stride and n_rows must be >= 0, n_rows <= 2^31 - 2^12");
-    const int64_t entries = (int64_t)n_lists * list_stride, max_union = n_rows < entries ? n_rows : entries;
-    if (union_capacity < max_union)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: union_capacity must be >= min(n_rows, n_lists * list_stride)");
-    if (max_union == 0) {                       // nothing to merge: an empty union
-        if (!union_count_out) return GS_OK;
-        std::lock_guard<std::mutex> lock(c->mu);
-        hipStream_t s;
-        if (const int rc = enter_call(c, stream_, &s)) return rc;
-        HIP_TRY(hipMemsetAsync(union_count_out, 0, sizeof(int32_t), s));
-        return GS_OK;
-    }
-    if (!packed || !counts || !grad_features_out || !grad_pointcloud_out || !union_ids_out || !union_count_out)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: NULL argument");
-    if ((uintptr_t)packed & 15u) return fail(GS_ERR_INVALID_ARGUMENT, "gs_merge_rows: packed must be 16-byte aligned");
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the scratch grows before the stream enters: a call that fails here leaves it alone
-    int rc;
-    if ((rc = grow(c, { NEED(c->merge_tags, gs_merge_tag_bytes(n_rows)), NEED(c->merge_ids, (size_t)entries * sizeof(int32_t)),
-                        NEED(c->row_block_totals, (size_t)(gs_rows_blocks((int)n_rows) + 1) * sizeof(uint32_t)) })) != GS_OK) return rc;
-    hipStream_t s;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    gs_launch_merge_rows(packed, counts, n_lists, list_stride, n_rows, grad_features_out, grad_pointcloud_out, union_ids_out, union_capacity,
-                         union_count_out, c->merge_tags.as<uint8_t>(), c->merge_ids.as<int32_t>(), c->row_block_totals.as<uint32_t>(), s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- exact k nearest neighbours (include/gs_knn.h, k_knn.hip) --------------------------------------------------------------
-// Everything is queued on the call's stream; nothing is read back.
-extern "C" int gs_knn(gs_ctx* c, const float* xyz, const int8_t* invalid_mask, int64_t n_points, int32_t k, float* d2_out,
-                      int32_t* idx_out, gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: ctx is NULL");
-    if (k < 1 || k > 8) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: k must be in [1, 8]");
-    if (n_points < 0 || n_points > (int64_t)GS_KNN_MAX_POINTS)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: n_points must be in [0, 2^30]");
-    if (n_points > 0 && (!xyz || !d2_out)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn: NULL xyz or d2_out with n_points > 0");
-    if (n_points == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
-    int rc;
-    if ((rc = grow(c, { NEED(c->knn_sort, gs_knn_sort_bytes(n_points)), NEED(c->knn_hist, gs_knn_hist_bytes(n_points)),
-                        NEED(c->knn_points, gs_knn_points_bytes(n_points)), NEED(c->knn_tree, gs_knn_tree_bytes(n_points)) })) != GS_OK) return rc;
-    hipStream_t s;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    gs_launch_knn(xyz, invalid_mask, n_points, k, d2_out, idx_out, c->knn_sort.p, c->knn_hist.p, c->knn_points.p, c->knn_tree.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- the scene as a Gaussian mixture (include/gs_mixture.h, k_mixture.hip) ----------------------------------------------------
-// Everything is queued on the call's stream; nothing is read back.
-static int mixture_call(const char* name, gs_ctx* c, const float* point_cloud, const float* features, const int8_t* invalid_mask,
-                        int64_t n_points, const float* queries, int64_t n_q, int fourier, const float* centre, float* out, gs_stream stream_)
-{
-    const std::string who(name);
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (n_points < 0 || n_points > (int64_t)GS_MIXTURE_MAX_POINTS)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": n_points must be in [0, 2^30]");
-    if (n_q < 0 || n_q > (int64_t)GS_MIXTURE_MAX_QUERIES)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + (fourier ? ": n_k must be in [0, 2^30]" : ": n_x must be in [0, 2^30]"));
-    if (n_points == 0 || n_q == 0) return GS_OK;
-    if (!point_cloud || !features || !queries || !out || (fourier && !centre))
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array with n_points > 0 and " + (fourier ? "n_k > 0" : "n_x > 0"));
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
-    int rc;
-    if ((rc = grow(c, { NEED(c->mix_records, gs_mix_record_bytes(n_points)), NEED(c->mix_sums, gs_mix_sum_bytes(n_points)),
-                        NEED(c->mix_partial, gs_mix_partial_bytes(n_points, n_q)) })) != GS_OK) return rc;
-    hipStream_t s;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    gs_launch_mixture(point_cloud, features, invalid_mask, n_points, queries, n_q, fourier, centre, out, c->mix_records.p, c->mix_sums.p,
-                      c->mix_partial.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_mixture_log_density(gs_ctx* c, const float* point_cloud, const float* point_cloud_features, const int8_t* point_invalid_mask,
-                                      int64_t n_points, const float* x, int64_t n_x, float* log_density_out, gs_stream stream_)
-{
-    return mixture_call("gs_mixture_log_density", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, x, n_x, 0, nullptr,
-                        log_density_out, stream_);
-}
-
-extern "C" int gs_mixture_fourier(gs_ctx* c, const float* point_cloud, const float* point_cloud_features, const int8_t* point_invalid_mask,
-                                  int64_t n_points, const float* k, int64_t n_k, const float* centre, float* re_im_out, gs_stream stream_)
-{
-    return mixture_call("gs_mixture_fourier", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, k, n_k, 1, centre,
-                        re_im_out, stream_);
-}
-
-// ---- its gradients (include/gs_mixture_grad.h, k_mixture_grad.hip) ------------------------------------------------------------
-static int mixture_grad_call(const char* name, gs_ctx* c, const float* point_cloud, const float* features, const int8_t* invalid_mask,
-                             int64_t n_points, const float* queries, int64_t n_q, int fourier, const float* centre, const float* log_density,
-                             const float* grad_out, float* grad_point_cloud, float* grad_features, float* grad_x, gs_stream stream_)
-{
-    const std::string who(name);
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (n_points < 0 || n_points > (int64_t)GS_MIXTURE_MAX_POINTS)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": n_points must be in [0, 2^30]");
-    if (n_q < 0 || n_q > (int64_t)GS_MIXTURE_MAX_QUERIES)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + (fourier ? ": n_k must be in [0, 2^30]" : ": n_x must be in [0, 2^30]"));
-    if (n_points == 0 || n_q == 0) return GS_OK;
-    if (!point_cloud || !features || !queries || !grad_out || !grad_point_cloud || !grad_features || (fourier ? !centre : !log_density))
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array with n_points > 0 and " + (fourier ? "n_k > 0" : "n_x > 0"));
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the work memory grows before the stream enters
-    int rc;
-    if ((rc = grow(c, { NEED(c->mix_records, gs_mix_record_bytes(n_points)), NEED(c->mix_sums, gs_mix_sum_bytes(n_points)),
-                        NEED(c->mixg_queries, gs_mixg_query_bytes(n_q)), NEED(c->mixg_partial, gs_mixg_partial_bytes(n_points, n_q)),
-                        NEED(c->mixg_sums, gs_mixg_sum_bytes(n_points, n_q)),
-                        NEED(c->mixg_x_partial, fourier ? 0 : gs_mixg_x_partial_bytes(n_points, n_q)) })) != GS_OK) return rc;
-    hipStream_t s;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    gs_launch_mixture_grad(point_cloud, features, invalid_mask, n_points, queries, n_q, fourier, centre, log_density, grad_out,
-                           grad_point_cloud, grad_features, grad_x, c->mix_records.p, c->mix_sums.p, c->mixg_queries.p, c->mixg_partial.p,
-                           c->mixg_sums.p, c->mixg_x_partial.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_mixture_log_density_backward(gs_ctx* c, const float* point_cloud, const float* point_cloud_features,
-                                               const int8_t* point_invalid_mask, int64_t n_points, const float* x, int64_t n_x,
-                                               const float* log_density, const float* grad_log_density, float* grad_point_cloud,
-                                               float* grad_features, float* grad_x, gs_stream stream_)
-{
-    return mixture_grad_call("gs_mixture_log_density_backward", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, x, n_x, 0,
-                             nullptr, log_density, grad_log_density, grad_point_cloud, grad_features, grad_x, stream_);
-}
-
-extern "C" int gs_mixture_fourier_backward(gs_ctx* c, const float* point_cloud, const float* point_cloud_features,
-                                           const int8_t* point_invalid_mask, int64_t n_points, const float* k, int64_t n_k, const float* centre,
-                                           const float* grad_re_im, float* grad_point_cloud, float* grad_features, gs_stream stream_)
-{
-    return mixture_grad_call("gs_mixture_fourier_backward", c, point_cloud, point_cloud_features, point_invalid_mask, n_points, k, n_k, 1,
-                             centre, nullptr, grad_re_im, grad_point_cloud, grad_features, nullptr, stream_);
-}
-
-// ---- training targets (include/gs_targets.h, k_targets.hip) -------------------------------------------------------------------
-// One axis of ATen's _upsample_bilinear2d_aa (align_corners = false) for in >= out, in float64: window and normalised weights of
-// every output, the zero weights at either end of a window dropped.  -> the largest tap count.
-static int resample_axis(int in, int out, std::vector<int32_t>& start, std::vector<int32_t>& count, std::vector<std::vector<double>>& weights)
-{
-    const double scale = (double)in / (double)out, support = scale;
-    int taps = 0;
-    start.resize(out); count.resize(out); weights.resize(out);
-    for (int i = 0; i < out; ++i) {
-        const double center = scale * (i + 0.5);
-        const int64_t lo = std::max<int64_t>((int64_t)(center - support + 0.5), 0);
-        const int64_t hi = std::min<int64_t>((int64_t)(center + support + 0.5), in);
-        std::vector<double> w;
-        double sum = 0.0;
-        for (int64_t j = lo; j < hi; ++j) {
-            const double x = ((double)j - center + 0.5) / scale;
-            w.push_back(std::max(0.0, 1.0 - std::fabs(x)));
-            sum += w.back();
-        }
-        for (double& v : w) v /= sum;
-        size_t a = 0, b = w.size();
-        while (b - a > 1 && w[b - 1] == 0.0) --b;
-        while (b - a > 1 && w[a] == 0.0) ++a;
-        start[i] = (int32_t)(lo + (int64_t)a); count[i] = (int32_t)(b - a);
-        weights[i].assign(w.begin() + a, w.begin() + b);
-        taps = std::max(taps, count[i]);
-    }
-    return taps;
-}
-
-// what k_image_resample relies on: windows inside the input, moving right, at most GS_RS_MAX_TAPS wide, and a tile's span bounded
-static bool resample_axis_ok(int in, const std::vector<int32_t>& start, const std::vector<int32_t>& count, int tile)
-{
-    const int out = (int)start.size();
-    for (int i = 0; i < out; ++i) {
-        if (count[i] < 1 || count[i] > GS_RS_MAX_TAPS || start[i] < 0 || start[i] + count[i] > in) return false;
-        if (i > 0 && (start[i] < start[i - 1] || start[i] + count[i] < start[i - 1] + count[i - 1])) return false;
-    }
-    for (int i0 = 0; i0 < out; i0 += tile) {
-        const int i1 = std::min(out, i0 + tile) - 1;
-        if (start[i1] + count[i1] - start[i0] > GS_RS_MAX_SPAN) return false;
-    }
-    return true;
-}
-
-// the cached tables of a geometry, or new ones: made, allocated and queued for upload on s (mutex held, device current)
-static int resample_tables(gs_ctx* c, int H_in, int W_in, int h_full, int w_full, hipStream_t s, ResampleTable** out)
-{
-    for (ResampleTable* rt : c->resample_tables)
-        if (rt->H_in == H_in && rt->W_in == W_in && rt->h_full == h_full && rt->w_full == w_full) { *out = rt; return GS_OK; }
-    std::vector<int32_t> xs, xc, ys, yc;
-    std::vector<std::vector<double>> xw, yw;
-    const int tx = resample_axis(W_in, w_full, xs, xc, xw), ty = resample_axis(H_in, h_full, ys, yc, yw);
-    if (!resample_axis_ok(W_in, xs, xc, GS_RESAMPLE_TILE_W) || !resample_axis_ok(H_in, ys, yc, GS_RESAMPLE_TILE_H))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_image_resample: the windows of this geometry do not fit the kernel's tile");
-    // layout (4-byte words): x start, x count, x weights (w_full * tx), y start, y count, y weights (h_full * ty)
-    const size_t words = 2 * (size_t)w_full + (size_t)w_full * tx + 2 * (size_t)h_full + (size_t)h_full * ty;
-    ResampleTable* rt = new ResampleTable();
-    rt->H_in = H_in; rt->W_in = W_in; rt->h_full = h_full; rt->w_full = w_full;
-    rt->host.assign(words * 4, 0);
-    int32_t* hi = reinterpret_cast<int32_t*>(rt->host.data());
-    float* hf = reinterpret_cast<float*>(rt->host.data());
-    size_t o = 0;
-    const size_t o_xs = o; for (int i = 0; i < w_full; ++i) hi[o++] = xs[i];
-    const size_t o_xc = o; for (int i = 0; i < w_full; ++i) hi[o++] = xc[i];
-    const size_t o_xw = o; for (int i = 0; i < w_full; ++i) for (int k = 0; k < tx; ++k) hf[o++] = k < xc[i] ? (float)xw[i][k] : 0.0f;
-    const size_t o_ys = o; for (int i = 0; i < h_full; ++i) hi[o++] = ys[i];
-    const size_t o_yc = o; for (int i = 0; i < h_full; ++i) hi[o++] = yc[i];
-    const size_t o_yw = o; for (int i = 0; i < h_full; ++i) for (int k = 0; k < ty; ++k) hf[o++] = k < yc[i] ? (float)yw[i][k] : 0.0f;
-    if (rt->buf.ensure(words * 4, &c->device_bytes) != hipSuccess) { delete rt; return fail(GS_ERR_OUT_OF_MEMORY, "device allocation failed: resample tables"); }
-    const hipError_t e = hipMemcpyAsync(rt->buf.p, rt->host.data(), words * 4, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { rt->buf.release(&c->device_bytes); delete rt; return fail(GS_ERR_HIP, std::string("resample tables: ") + hipGetErrorString(e)); }
-    const int32_t* di = rt->buf.as<int32_t>();
-    const float* df = rt->buf.as<float>();
-    rt->ax = GsResampleAxis{ di + o_xs, di + o_xc, df + o_xw, tx };
-    rt->ay = GsResampleAxis{ di + o_ys, di + o_yc, df + o_yw, ty };
-    if (c->resample_tables.size() >= GS_RESAMPLE_MAX_GEOMETRIES) {       // the oldest goes (hipFree waits for what still reads it)
-        ResampleTable* old = c->resample_tables.front();
-        c->resample_tables.erase(c->resample_tables.begin());
-        old->buf.release(&c->device_bytes);
-        delete old;
-    }
-    c->resample_tables.push_back(rt);
-    *out = rt;
-    return GS_OK;
-}
-
-// gs_image_resample (dst_channels 3) and gs_image_resample_rgba (4, include/gs_targets_rgba.h): the same checks, tables and launch
-static int image_resample(const char* who_, int dst_channels, gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in,
-                          int32_t W_in, int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
-                          gs_stream stream_)
-{
-    const std::string who(who_);
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (src_format != GS_IMAGE_U8_HWC && src_format != GS_IMAGE_F32_CHW) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown src_format");
-    if (src_channels != 4 && (dst_channels == 4 || src_channels != 3)) return fail(GS_ERR_INVALID_ARGUMENT, who + (dst_channels == 4 ? ": src_channels must be 4" : ": src_channels must be 3 or 4"));
-    for (int32_t v : { H_in, W_in, h_full, w_full, h_out, w_out })
-        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, who + ": every size must be in [0, 32768]");
-    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, who + ": the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
-    if (src_format == GS_IMAGE_U8_HWC ? src_row_pitch_bytes < (int64_t)W_in * src_channels : src_row_pitch_bytes != (int64_t)W_in * 4)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": src_row_pitch_bytes must be >= W_in * src_channels (uint8), W_in * 4 (f32)");
-    if (h_out == 0 || w_out == 0) return GS_OK;
-    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL src or dst");
-    if (H_in < h_full || W_in < w_full || (int64_t)H_in > (int64_t)GS_RESAMPLE_MAX_SCALE * h_full || (int64_t)W_in > (int64_t)GS_RESAMPLE_MAX_SCALE * w_full)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": the scale in / out must be in [1, 8] on both axes (no upscaling)");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    int rc;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    ResampleTable* rt = nullptr;
-    if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
-    gs_launch_image_resample(src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, rt->ax, rt->ay, h_out, w_out, dst, dst_channels, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_image_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
-                                 int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
-                                 gs_stream stream_)
-{
-    return image_resample("gs_image_resample", 3, c, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out, w_out,
-                          dst, stream_);
-}
-
-extern "C" int gs_image_resample_rgba(gs_ctx* c, const void* src, int32_t src_format, int32_t src_channels, int32_t H_in, int32_t W_in,
-                                      int64_t src_row_pitch_bytes, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float* dst,
-                                      gs_stream stream_)
-{
-    return image_resample("gs_image_resample_rgba", 4, c, src, src_format, src_channels, H_in, W_in, src_row_pitch_bytes, h_full, w_full, h_out,
-                          w_out, dst, stream_);
-}
-
-// ---- baking a placed scene (k_compose.hip) ----------------------------------------------------------------------------
-static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-extern "C" int gs_scene_bake(gs_ctx* c, const float* xyz_in, const float* features_in, int64_t n, const float* q_A, const float* t_A,
-                             float scale, const float* sh_matrices, float* xyz_out, float* features_out, int64_t row_offset,
-                             gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: ctx is NULL");
-    if (n < 0 || row_offset < 0 || n > INT32_MAX || row_offset > INT32_MAX || n + row_offset > INT32_MAX)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: n and row_offset must not be negative, and row_offset + n below 2^31");
-    if (!q_A || !t_A || !sh_matrices) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: NULL q_A, t_A or sh_matrices");
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: scale must be finite and > 0");
-    const double qn = std::sqrt((double)q_A[0] * q_A[0] + (double)q_A[1] * q_A[1] + (double)q_A[2] * q_A[2] + (double)q_A[3] * q_A[3]);
-    if (!std::isfinite(qn) || !(qn > 0.0)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: q_A must have a finite norm > 0");
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(t_A[k])) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: t_A must be finite");
-    for (int k = 0; k < GS_BAKE_SH_FLOATS; ++k)
-        if (!std::isfinite(sh_matrices[k])) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: sh_matrices must be finite");
-    if (n == 0) return GS_OK;
-    if (!xyz_in || !features_in || !xyz_out || !features_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: NULL array");
-    const size_t xyz_bytes = (size_t)n * 3 * sizeof(float), feat_bytes = (size_t)n * GS_BAKE_FEATURES * sizeof(float);
-    const float* xyz_w = xyz_out + row_offset * 3;
-    const float* feat_w = features_out + row_offset * GS_BAKE_FEATURES;
-    if (ranges_overlap(xyz_in, xyz_bytes, xyz_w, xyz_bytes) || ranges_overlap(xyz_in, xyz_bytes, feat_w, feat_bytes) ||
-        ranges_overlap(features_in, feat_bytes, xyz_w, xyz_bytes) || ranges_overlap(features_in, feat_bytes, feat_w, feat_bytes) ||
-        ranges_overlap(xyz_w, xyz_bytes, feat_w, feat_bytes))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_scene_bake: the rows read and the rows written overlap (the call runs out of place)");
-    // the transform in float64, rounded once
-    GsBakeTransform A;
-    const double x = q_A[0] / qn, y = q_A[1] / qn, z = q_A[2] / qn, w = q_A[3] / qn, s = (double)scale;
-    const double R[9] = { 1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                          2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                          2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y) };
-    for (int k = 0; k < 9; ++k) A.m[k] = (float)(s * R[k]);
-    for (int k = 0; k < 3; ++k) A.t[k] = t_A[k];
-    A.q[0] = (float)x; A.q[1] = (float)y; A.q[2] = (float)z; A.q[3] = (float)w;
-    A.log_scale = (float)std::log(s);
-    std::memcpy(A.sh, sh_matrices, sizeof(A.sh));
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t st;
-    if (const int rc = enter_call(c, stream_, &st)) return rc;
-    gs_launch_scene_bake(xyz_in, features_in, n, A, xyz_out, features_out, row_offset, st);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- frames out (k_frames.hip) ------------------------------------------------------------------------------------------
-extern "C" int gs_frame_to_u8(gs_ctx* c, const float* src, int32_t mode, int32_t h, int32_t w, uint8_t* dst, int64_t dst_row_pitch_bytes,
-                              const uint8_t* gt, int32_t gt_channels, int64_t gt_row_pitch_bytes, int64_t* sse, gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: ctx is NULL");
-    if (mode != GS_FRAME_RGB_TRUNC && mode != GS_FRAME_RGB_ROUND && mode != GS_FRAME_DEPTH_CMAP)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: unknown mode");
-    if (h < 0 || w < 0 || h > GS_FRAME_MAX_SIZE || w > GS_FRAME_MAX_SIZE)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: every size must be in [0, 32768]");
-    if (dst_row_pitch_bytes < (int64_t)3 * w) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: dst_row_pitch_bytes must be >= 3 * w");
-    if (gt) {
-        if (gt_channels != 3 && gt_channels != 4) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: gt_channels must be 3 or 4");
-        if (gt_row_pitch_bytes < (int64_t)w * gt_channels) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: gt_row_pitch_bytes must be >= w * gt_channels");
-        if (!sse) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: a ground truth needs the sse word");
-    } else if (sse) {
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: the sse word needs a ground truth");
-    }
-    if (h == 0 || w == 0) return GS_OK;
-    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, "gs_frame_to_u8: NULL src or dst");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_frame_to_u8(src, mode, h, w, dst, dst_row_pitch_bytes, gt, gt_channels, gt_row_pitch_bytes, sse, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- meshes from a scene (k_fusion.hip) --------------------------------------------------------------------------------------
-static bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
-
-// the checks the three calls share on (nx, ny, nz, origin, step); *n_out = nx ny nz
-static int fusion_grid(const char* who, int32_t nx, int32_t ny, int32_t nz, const float* origin, const float* step, const char* step_name,
-                       int64_t* n_out)
-{
-    if (nx < 0 || ny < 0 || nz < 0) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": a dimension is negative");
-    // each factor is below 2^31: the product of two fits 63 bits, and is compared before the third enters
-    const int64_t nxy = (int64_t)nx * ny;
-    if (nxy > GS_FUSION_MAX_VOXELS || (nz > 0 && nxy > GS_FUSION_MAX_VOXELS / nz))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": nx * ny * nz exceeds GS_FUSION_MAX_VOXELS (2^30)");
-    for (int a = 0; a < 3; ++a) {
-        if (!positive_finite(step[a])) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": " + step_name + " must be finite and > 0");
-        if (!std::isfinite(origin[a])) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": origin must be finite");
-    }
-    *n_out = nxy * nz;
-    return GS_OK;
-}
-
-extern "C" int gs_tsdf_integrate(gs_ctx* c, const gs_tsdf_volume* vol, const gs_tsdf_view* views, int32_t n_views, gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: ctx is NULL");
-    if (!vol) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: volume is NULL");
-    if (n_views < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: n_views is negative");
-    int64_t n = 0;
-    if (const int rc = fusion_grid("gs_tsdf_integrate", vol->nx, vol->ny, vol->nz, vol->origin, vol->voxel, "voxel", &n)) return rc;
-    if (!positive_finite(vol->trunc)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: trunc must be finite and > 0");
-    if (!positive_finite(vol->max_weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: max_weight must be finite and > 0");
-    if (!std::isfinite(vol->min_alpha) || !std::isfinite(vol->near)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: min_alpha and near must be finite");
-    if (n > 0 && (!vol->tsdf || !vol->weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: NULL tsdf or weight");
-    if (n_views > 0 && !views) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: views is NULL");
-    for (int32_t v = 0; v < n_views; ++v) {
-        const gs_tsdf_view& V = views[v];
-        if (!V.depth) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + " has a NULL depth");
-        if (V.h < 0 || V.w < 0 || V.h > GS_FUSION_MAX_IMAGE_SIZE || V.w > GS_FUSION_MAX_IMAGE_SIZE)
-            return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + ": h and w must be in [0, 32768]");
-        bool finite = std::isfinite(V.fx) && std::isfinite(V.fy) && std::isfinite(V.cx) && std::isfinite(V.cy);
-        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(V.m[k / 4][k % 4]);
-        if (!finite) return fail(GS_ERR_INVALID_ARGUMENT, "gs_tsdf_integrate: view " + std::to_string(v) + ": fx, fy, cx, cy and m must be finite");
-    }
-    if (n == 0 || n_views == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_tsdf_integrate(*vol, views, n_views, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-static int iso_volume_checks(const char* who, gs_ctx* c, const gs_iso_volume* vol, const void* cell_ws, const void* block_ws, int64_t* n_out)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
-    if (!vol) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": volume is NULL");
-    if (const int rc = fusion_grid(who, vol->nx, vol->ny, vol->nz, vol->origin, vol->spacing, "spacing", n_out)) return rc;
-    if (!std::isfinite(vol->level)) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": level must be finite");
-    if (*n_out > 0 && !vol->values) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values");
-    if (*n_out > 0 && (!cell_ws || !block_ws)) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL work buffer");
-    return GS_OK;
-}
-
-extern "C" int gs_isosurface_plan(gs_ctx* c, const gs_iso_volume* vol, void* cell_ws, void* block_ws, int64_t* totals, gs_stream stream_)
-{
-    int64_t n = 0;
-    if (const int rc = iso_volume_checks("gs_isosurface_plan", c, vol, cell_ws, block_ws, &n)) return rc;
-    if (n == 0) return GS_OK;
-    if (!totals) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_plan: NULL totals");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_iso_plan(*vol, cell_ws, block_ws, totals, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_isosurface_emit(gs_ctx* c, const gs_iso_volume* vol, const void* cell_ws, const void* block_ws, void* voxel_ws,
-                                  int64_t n_vertices, int64_t n_faces, float* vertices, float* colours, int32_t* faces, gs_stream stream_)
-{
-    int64_t n = 0;
-    if (const int rc = iso_volume_checks("gs_isosurface_emit", c, vol, cell_ws, block_ws, &n)) return rc;
-    if (n_vertices < 0 || n_faces < 0 || n_vertices > INT32_MAX || n_faces > INT32_MAX)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: n_vertices and n_faces must be in [0, 2^31 - 1]");
-    if (n == 0 || (n_vertices == 0 && n_faces == 0)) return GS_OK;
-    if (!voxel_ws) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: NULL work buffer");
-    if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_isosurface_emit: NULL vertices or faces");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_iso_emit(*vol, cell_ws, block_ws, voxel_ws, n_vertices, n_faces, vertices, colours, faces, s);
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1922,601 +1131,6 @@ extern "C" int gs_frame_release(gs_ctx* c, gs_frame* h)
     Frame* f = resolve(c, h);
     if (!f) return fail(GS_ERR_STATE, "gs_frame_release: not a live frame of this context (already released?)");
     drop_frame(c, f);
-    return GS_OK;
-}
-
-// ---- fixed-budget densification (k_mcmc.hip) ------------------------------------------------------------------------------
-extern "C" int64_t gs_mcmc_scratch_bytes(int64_t n_points) { return n_points < 0 ? 0 : (int64_t)gs_mcmc_scratch_size(n_points); }
-
-static int mcmc_rows_check(const char* who, gs_ctx* c, int64_t N)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
-    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_points must be in [0, 2^31)");
-    return GS_OK;
-}
-
-extern "C" int gs_mcmc_noise(gs_ctx* c, float* point_cloud, const float* features, const int8_t* mask, int64_t N, float noise_scale,
-                             float gate_k, float gate_x0, uint64_t seed, uint32_t step_index, gs_stream stream_)
-{
-    if (const int rc = mcmc_rows_check("gs_mcmc_noise", c, N)) return rc;
-    if (N > 0 && (!point_cloud || !features || !mask)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: NULL array");
-    if (((uintptr_t)features & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: features must be 16-byte aligned");
-    if (!std::isfinite(noise_scale) || !std::isfinite(gate_k) || !std::isfinite(gate_x0))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_noise: noise_scale, gate_k and gate_x0 must be finite");
-    if (N == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_mcmc_noise(point_cloud, features, mask, N, noise_scale, gate_k, gate_x0, seed, step_index, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_mcmc_regulariser(gs_ctx* c, const float* features, const int8_t* mask, int64_t N, float lambda_opacity, float lambda_scale,
-                                   const float* upstream, float* grad_features, float* value_and_count, gs_stream stream_)
-{
-    if (const int rc = mcmc_rows_check("gs_mcmc_regulariser", c, N)) return rc;
-    if (N > 0 && (!features || !mask)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: NULL array");
-    if ((((uintptr_t)features | (uintptr_t)grad_features) & 15u) != 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: features and grad_features must be 16-byte aligned");
-    if (!std::isfinite(lambda_opacity) || !std::isfinite(lambda_scale))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_regulariser: lambda_opacity and lambda_scale must be finite");
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    if (c->mcmc_ws.ensure(gs_mcmc_reg_ws_size(N), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_mcmc_regulariser: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_mcmc_regulariser(features, mask, N, lambda_opacity, lambda_scale, upstream, grad_features, value_and_count, c->mcmc_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_mcmc_relocate(gs_ctx* c, const gs_density_scene* scene, float* features_exp_avg, float* features_exp_avg_sq,
-                                float* point_cloud_exp_avg, float* point_cloud_exp_avg_sq, const gs_mcmc_config* cfg,
-                                const gs_mcmc_plan* plan, uint64_t seed, uint32_t call_index, gs_stream stream_)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: ctx is NULL");
-    if (!scene || !cfg || !plan || !plan->counts) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL scene, config, plan or plan->counts");
-    const int64_t N = scene->n_points;
-    if (const int rc = mcmc_rows_check("gs_mcmc_relocate", c, N)) return rc;
-    if (plan->n_points < N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: plan is smaller than the scene");
-    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask || !scene->point_object_id))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL scene array");
-    if (N > 0 && (!plan->source_of || !plan->dest_row || !plan->multiplicity || !plan->scratch))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: NULL plan array");
-    if ((((uintptr_t)scene->point_cloud_features | (uintptr_t)features_exp_avg | (uintptr_t)features_exp_avg_sq) & 15u) != 0 ||
-        ((uintptr_t)plan->scratch & 7u) != 0)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: features and their moments must be 16-byte aligned, scratch 8-byte aligned");
-    if (cfg->n_max < 1 || cfg->n_max > GS_MCMC_N_MAX) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: n_max must be in [1, 51]");
-    if (cfg->grow_permille < 0 || cfg->cap_max < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: grow_permille and cap_max must be >= 0");
-    if (std::isnan(cfg->min_opacity_logit)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_mcmc_relocate: min_opacity_logit is NaN");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    float* const moments[4] = { features_exp_avg, features_exp_avg_sq, point_cloud_exp_avg, point_cloud_exp_avg_sq };
-    gs_launch_mcmc_relocate(*scene, moments, *cfg, *plan, seed, call_index, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- per-view exposure compensation (include/gs_appearance.h, k_appearance.hip) ---------------------------------------------
-static int appearance_check(const char* who, gs_ctx* c, const gs_loss_image* image, int32_t H, int32_t W)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
-    if (!image || !image->data) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL image");
-    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": H and W must be >= 1");
-    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many pixels");
-    return GS_OK;
-}
-
-extern "C" int gs_appearance_apply(gs_ctx* c, const gs_loss_image* image, const float* transform, int32_t H, int32_t W,
-                                   const gs_loss_image* corrected, gs_stream stream_)
-{
-    if (const int rc = appearance_check("gs_appearance_apply", c, image, H, W)) return rc;
-    if (!transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_apply: transform is NULL");
-    if (!corrected || !corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_apply: NULL corrected image");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_appearance_apply(loss_image(image, 0), transform, H, W, loss_image(corrected, 0), s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_appearance_backward(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* grad_corrected, const float* transform,
-                                      int32_t H, int32_t W, const gs_loss_image* grad_image, float* grad_transform, gs_stream stream_)
-{
-    if (const int rc = appearance_check("gs_appearance_backward", c, image, H, W)) return rc;
-    if (!grad_corrected || !grad_corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: NULL grad_corrected");
-    if (!transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: transform is NULL");
-    const bool want_image = grad_image && grad_image->data;
-    if (!want_image && !grad_transform) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_backward: grad_image and grad_transform are both NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (grad_transform) {
-        HIP_TRY(hipSetDevice(c->device));       // the workspace grows before the stream enters: a call that fails here leaves it alone
-        if (c->appearance_ws.ensure(gs_appearance_ws_size(H, W), &c->device_bytes) != hipSuccess)
-            return fail(GS_ERR_OUT_OF_MEMORY, "gs_appearance_backward: workspace");
-    }
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    const GsLossImage none{ nullptr, 0, 0, 0, 0 };
-    gs_launch_appearance_backward(loss_image(image, 0), loss_image(grad_corrected, 0), transform, H, W,
-                                  want_image ? loss_image(grad_image, 0) : none, grad_transform, c->appearance_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* target, const float* pixel_weight,
-                                     int32_t H, int32_t W, double* moments, gs_stream stream_)
-{
-    if (const int rc = appearance_check("gs_appearance_moments", c, image, H, W)) return rc;
-    if (!target || !target->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_moments: NULL target");
-    if (!moments || ((uintptr_t)moments & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_moments: moments must be 8-byte aligned and not NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    if (c->appearance_ws.ensure(gs_appearance_ws_size(H, W), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_appearance_moments: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- per-view bilateral grids (include/gs_bilateral.h, k_bilateral.hip) -----------------------------------------------------
-static int bilateral_grid_check(const char* who, gs_ctx* c, const float* grid, int32_t Gx, int32_t Gy, int32_t L)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
-    if (!grid || ((uintptr_t)grid & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grid must be 16-byte aligned and not NULL");
-    if (Gx < GS_BILATERAL_MIN_GRID || Gx > GS_BILATERAL_MAX_XY || Gy < GS_BILATERAL_MIN_GRID || Gy > GS_BILATERAL_MAX_XY ||
-        L < GS_BILATERAL_MIN_GRID || L > GS_BILATERAL_MAX_L)
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": grid dimensions outside their limits");
-    return GS_OK;
-}
-
-static int bilateral_check(const char* who, gs_ctx* c, const gs_loss_image* image, const float* grid, int32_t Gx, int32_t Gy, int32_t L,
-                           int32_t H, int32_t W)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": ctx is NULL");
-    if (!image || !image->data) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL image");
-    if (const int rc = bilateral_grid_check(who, c, grid, Gx, Gy, L)) return rc;
-    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": H and W must be >= 1");
-    if ((int64_t)H * (int64_t)W > (int64_t)GS_BILATERAL_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many pixels");
-    return GS_OK;
-}
-
-extern "C" int gs_bilateral_slice(gs_ctx* c, const gs_loss_image* image, const float* grid, int32_t Gx, int32_t Gy, int32_t L, int32_t H,
-                                  int32_t W, const gs_loss_image* corrected, gs_stream stream_)
-{
-    if (const int rc = bilateral_check("gs_bilateral_slice", c, image, grid, Gx, Gy, L, H, W)) return rc;
-    if (!corrected || !corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice: NULL corrected image");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_bilateral_slice(loss_image(image, 0), grid, Gx, Gy, L, H, W, loss_image(corrected, 0), s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_bilateral_slice_backward(gs_ctx* c, const gs_loss_image* image, const gs_loss_image* grad_corrected, const float* grid,
-                                           int32_t Gx, int32_t Gy, int32_t L, int32_t H, int32_t W, const gs_loss_image* grad_image,
-                                           float* grad_grid, gs_stream stream_)
-{
-    if (const int rc = bilateral_check("gs_bilateral_slice_backward", c, image, grid, Gx, Gy, L, H, W)) return rc;
-    if (!grad_corrected || !grad_corrected->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice_backward: NULL grad_corrected");
-    const bool want_image = grad_image && grad_image->data;
-    if (!want_image && !grad_grid) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_slice_backward: grad_image and grad_grid are both NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (grad_grid) {
-        HIP_TRY(hipSetDevice(c->device));       // the workspace grows before the stream enters: a call that fails here leaves it alone
-        if (c->bilateral_ws.ensure(gs_bilateral_ws_size(Gx, Gy, L), &c->device_bytes) != hipSuccess)
-            return fail(GS_ERR_OUT_OF_MEMORY, "gs_bilateral_slice_backward: workspace");
-    }
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    const GsLossImage none{ nullptr, 0, 0, 0, 0 };
-    gs_launch_bilateral_backward(loss_image(image, 0), loss_image(grad_corrected, 0), grid, Gx, Gy, L, H, W,
-                                 want_image ? loss_image(grad_image, 0) : none, grad_grid, c->bilateral_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_bilateral_tv(gs_ctx* c, const float* grid, int32_t Gx, int32_t Gy, int32_t L, float weight, float* grad_grid, float* value,
-                               gs_stream stream_)
-{
-    if (const int rc = bilateral_grid_check("gs_bilateral_tv", c, grid, Gx, Gy, L)) return rc;
-    if (!value) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_tv: value is NULL");
-    if (!std::isfinite(weight)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_bilateral_tv: weight must be finite");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_bilateral_tv(grid, Gx, Gy, L, weight, grad_grid, value, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- depth supervision (include/gs_depth.h, k_depth.hip) ------------------------------------------------------------------------
-extern "C" int gs_depth_resample(gs_ctx* c, const void* src, int32_t src_format, int32_t H_in, int32_t W_in, int64_t src_row_pitch_bytes,
-                                 float depth_scale, int32_t h_full, int32_t w_full, int32_t h_out, int32_t w_out, float min_coverage,
-                                 float* dst, gs_stream stream_)
-{
-    const std::string who("gs_depth_resample");
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (src_format != GS_DEPTH_U16 && src_format != GS_DEPTH_F32) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown src_format");
-    if (!(min_coverage >= 0.0f && min_coverage <= 1.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": min_coverage must be in [0, 1]");
-    if (!(depth_scale > 0.0f && std::isfinite(depth_scale))) return fail(GS_ERR_INVALID_ARGUMENT, who + ": depth_scale must be finite and > 0");
-    for (int32_t v : { H_in, W_in, h_full, w_full, h_out, w_out })
-        if (v < 0 || v > GS_RESAMPLE_MAX_SIZE) return fail(GS_ERR_INVALID_ARGUMENT, who + ": every size must be in [0, 32768]");
-    if (h_out > h_full || w_out > w_full) return fail(GS_ERR_INVALID_ARGUMENT, who + ": the crop (h_out, w_out) exceeds the resize (h_full, w_full)");
-    if (src_format == GS_DEPTH_U16 ? src_row_pitch_bytes < (int64_t)W_in * 2 : src_row_pitch_bytes != (int64_t)W_in * 4)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": src_row_pitch_bytes must be >= W_in * 2 (uint16), W_in * 4 (f32)");
-    if (h_out == 0 || w_out == 0) return GS_OK;
-    if (!src || !dst) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL src or dst");
-    if (H_in < h_full || W_in < w_full || (int64_t)H_in > (int64_t)GS_RESAMPLE_MAX_SCALE * h_full || (int64_t)W_in > (int64_t)GS_RESAMPLE_MAX_SCALE * w_full)
-        return fail(GS_ERR_INVALID_ARGUMENT, who + ": the scale in / out must be in [1, 8] on both axes (no upscaling)");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    int rc;
-    if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
-    ResampleTable* rt = nullptr;
-    if ((rc = resample_tables(c, H_in, W_in, h_full, w_full, s, &rt)) != GS_OK) return rc;
-    gs_launch_depth_resample(src, src_format, H_in, W_in, src_row_pitch_bytes, depth_scale, rt->ax, rt->ay, h_out, w_out, min_coverage, dst, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-static int depth_loss_check(const char* who_, gs_ctx* c, const float* D, const float* Z, const float* w_t, int32_t H, int32_t W, int32_t flags,
-                            const float* terms)
-{
-    const std::string who(who_);
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (!D || !Z || !w_t) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL plane (D, Z or w_t)");
-    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": loss_terms is NULL");
-    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": H and W must be >= 1");
-    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
-    if ((flags & ~GS_DEPTH_FLAGS_ALL) != 0) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown flag bits");
-    return GS_OK;
-}
-
-extern "C" int gs_depth_loss_forward(gs_ctx* c, const float* D, const float* Z, const float* w_t, const float* w_p, int32_t H, int32_t W,
-                                     int32_t flags, float* loss_terms, gs_stream stream_)
-{
-    if (const int rc = depth_loss_check("gs_depth_loss_forward", c, D, Z, w_t, H, W, flags, loss_terms)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    if (c->depth_ws.ensure(gs_depth_ws_size(H, W), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_depth_loss_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_depth_loss_forward(D, Z, w_t, w_p, H, W, flags, loss_terms, c->depth_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_depth_loss_backward(gs_ctx* c, const float* D, const float* Z, const float* w_t, const float* w_p, int32_t H, int32_t W,
-                                      int32_t flags, const float* loss_terms, const float* upstream, float* grad_D, gs_stream stream_)
-{
-    if (const int rc = depth_loss_check("gs_depth_loss_backward", c, D, Z, w_t, H, W, flags, loss_terms)) return rc;
-    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_depth_loss_backward: grad_D is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_depth_loss_backward(D, Z, w_t, w_p, H, W, flags, loss_terms, upstream, grad_D, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- geometry regularisers (include/gs_geometry.h, k_geometry.hip) ---------------------------------------------------------------
-static int geometry_check(const std::string& who, gs_ctx* c, const float* D, int32_t H, int32_t W, int32_t flags, int32_t flags_all)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (!D) return fail(GS_ERR_INVALID_ARGUMENT, who + ": D is NULL");
-    if (H < 1 || W < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": H and W must be >= 1");
-    if ((int64_t)H * (int64_t)W > (int64_t)GS_APPEARANCE_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
-    if ((flags & ~flags_all) != 0) return fail(GS_ERR_INVALID_ARGUMENT, who + ": unknown flag bits");
-    return GS_OK;
-}
-
-static int geometry_check_camera(const std::string& who, float fx, float fy, float cx, float cy, float max_rel_jump)
-{
-    if (!(std::isfinite(fx) && std::isfinite(fy) && fx > 0.0f && fy > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": fx and fy must be finite and > 0");
-    if (!(std::isfinite(cx) && std::isfinite(cy))) return fail(GS_ERR_INVALID_ARGUMENT, who + ": cx and cy must be finite");
-    if (!(std::isfinite(max_rel_jump) && max_rel_jump >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": max_rel_jump must be finite and >= 0");
-    return GS_OK;
-}
-
-extern "C" int gs_depth_normals(gs_ctx* c, const float* D, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float max_rel_jump,
-                                float* normals, gs_stream stream_)
-{
-    const std::string who("gs_depth_normals");
-    if (const int rc = geometry_check(who, c, D, H, W, 0, 0)) return rc;
-    if (!normals) return fail(GS_ERR_INVALID_ARGUMENT, who + ": normals is NULL");
-    if (const int rc = geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_depth_normals(D, H, W, fx, fy, cx, cy, max_rel_jump, normals, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-static int normal_loss_check(const std::string& who, gs_ctx* c, const float* D, const float* N, const float* w_n, int32_t H, int32_t W, float fx,
-                             float fy, float cx, float cy, float max_rel_jump, int32_t flags, const float* terms)
-{
-    if (const int rc = geometry_check(who, c, D, H, W, flags, GS_GEOM_NORMAL_FLAGS_ALL)) return rc;
-    if (!N || !w_n) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL plane (N or w_n)");
-    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
-    return geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump);
-}
-
-extern "C" int gs_normal_loss_forward(gs_ctx* c, const float* D, const float* N, const float* w_n, const float* w_p, int32_t H, int32_t W,
-                                      float fx, float fy, float cx, float cy, float max_rel_jump, int32_t flags, float* terms, gs_stream stream_)
-{
-    if (const int rc = normal_loss_check("gs_normal_loss_forward", c, D, N, w_n, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_normal_loss_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_normal_loss_forward(D, N, w_n, w_p, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms, c->geometry_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_normal_loss_backward(gs_ctx* c, const float* D, const float* N, const float* w_n, const float* w_p, int32_t H, int32_t W,
-                                       float fx, float fy, float cx, float cy, float max_rel_jump, int32_t flags, const float* terms,
-                                       const float* upstream, float* grad_D, gs_stream stream_)
-{
-    if (const int rc = normal_loss_check("gs_normal_loss_backward", c, D, N, w_n, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms)) return rc;
-    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_normal_loss_backward: grad_D is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_normal_loss_backward(D, N, w_n, w_p, H, W, fx, fy, cx, cy, max_rel_jump, flags, terms, upstream, grad_D, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-static int depth_smooth_check(const std::string& who, gs_ctx* c, const float* D, int32_t H, int32_t W, float edge_lambda, int32_t flags,
-                              const float* terms)
-{
-    if (const int rc = geometry_check(who, c, D, H, W, flags, GS_GEOM_SMOOTH_FLAGS_ALL)) return rc;
-    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
-    if (!(std::isfinite(edge_lambda) && edge_lambda >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": edge_lambda must be finite and >= 0");
-    return GS_OK;
-}
-
-extern "C" int gs_depth_smooth_forward(gs_ctx* c, const float* D, const float* I, const float* w_p, int32_t H, int32_t W, float edge_lambda,
-                                       int32_t flags, float* terms, gs_stream stream_)
-{
-    if (const int rc = depth_smooth_check("gs_depth_smooth_forward", c, D, H, W, edge_lambda, flags, terms)) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_depth_smooth_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_depth_smooth_forward(D, I, w_p, H, W, edge_lambda, flags, terms, c->geometry_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_depth_smooth_backward(gs_ctx* c, const float* D, const float* I, const float* w_p, int32_t H, int32_t W, float edge_lambda,
-                                        int32_t flags, const float* terms, const float* upstream, float* grad_D, gs_stream stream_)
-{
-    if (const int rc = depth_smooth_check("gs_depth_smooth_backward", c, D, H, W, edge_lambda, flags, terms)) return rc;
-    if (!grad_D) return fail(GS_ERR_INVALID_ARGUMENT, "gs_depth_smooth_backward: grad_D is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_depth_smooth_backward(D, I, w_p, H, W, edge_lambda, flags, terms, upstream, grad_D, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- Gaussian normals and their consistency with the depth normal (include/gs_normals.h, k_normals.hip) --------------------------
-static int gaussian_normals_check(const std::string& who, gs_ctx* c, const float* pc, const float* feat, const float* q_pc, const float* t_pc,
-                                  int64_t N, int32_t K, const void* a, const void* b)
-{
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
-    if (N < 0 || N > (int64_t)INT32_MAX - GS_NORMALS_BLOCK) return fail(GS_ERR_INVALID_ARGUMENT, who + ": N must be in [0, 2^31 - 256]");
-    if (K < 1) return fail(GS_ERR_INVALID_ARGUMENT, who + ": K must be >= 1");
-    if (!q_pc || !t_pc) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL pose array");
-    if (N > 0 && (!pc || !feat || !a || !b)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": NULL array");
-    return GS_OK;
-}
-
-extern "C" int gs_gaussian_normals_forward(gs_ctx* c, const float* pc, const float* feat, const int32_t* obj, const float* q_pc,
-                                           const float* t_pc, int64_t N, int32_t K, float* normals, gs_stream stream_)
-{
-    if (const int rc = gaussian_normals_check("gs_gaussian_normals_forward", c, pc, feat, q_pc, t_pc, N, K, normals, normals)) return rc;
-    if (N == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_gaussian_normals_forward(pc, feat, obj, q_pc, t_pc, N, K, normals, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_gaussian_normals_backward(gs_ctx* c, const float* pc, const float* feat, const int32_t* obj, const float* q_pc,
-                                            const float* t_pc, int64_t N, int32_t K, const float* grad_normals, float* grad_features,
-                                            gs_stream stream_)
-{
-    if (const int rc = gaussian_normals_check("gs_gaussian_normals_backward", c, pc, feat, q_pc, t_pc, N, K, grad_normals, grad_features)) return rc;
-    if (N == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_gaussian_normals_backward(pc, feat, obj, q_pc, t_pc, N, K, grad_normals, grad_features, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-static int normal_consistency_check(const std::string& who, gs_ctx* c, const float* D, const float* R, int32_t H, int32_t W, float fx, float fy,
-                                    float cx, float cy, float max_rel_jump, float min_length, const float* terms)
-{
-    if (const int rc = geometry_check(who, c, D, H, W, 0, 0)) return rc;
-    if ((int64_t)H * (int64_t)W > (int64_t)GS_NORMALS_MAX_PIXELS) return fail(GS_ERR_INVALID_ARGUMENT, who + ": too many pixels");
-    if (!R) return fail(GS_ERR_INVALID_ARGUMENT, who + ": R is NULL");
-    if (!terms) return fail(GS_ERR_INVALID_ARGUMENT, who + ": terms is NULL");
-    if (!(std::isfinite(min_length) && min_length > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, who + ": min_length must be finite and > 0");
-    return geometry_check_camera(who, fx, fy, cx, cy, max_rel_jump);
-}
-
-extern "C" int gs_normal_consistency_forward(gs_ctx* c, const float* D, const float* R, const float* w_p, int32_t H, int32_t W, float fx,
-                                             float fy, float cx, float cy, float max_rel_jump, float min_length, float* terms,
-                                             gs_stream stream_)
-{
-    if (const int rc = normal_consistency_check("gs_normal_consistency_forward", c, D, R, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms))
-        return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));           // the workspace grows before the stream enters: a call that fails here leaves it alone
-    if (c->geometry_ws.ensure(gs_geometry_ws_size(H, W), &c->device_bytes) != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, "gs_normal_consistency_forward: workspace");
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_normal_consistency_forward(D, R, w_p, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms, c->geometry_ws.p, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_normal_consistency_backward(gs_ctx* c, const float* D, const float* R, const float* w_p, int32_t H, int32_t W, float fx,
-                                              float fy, float cx, float cy, float max_rel_jump, float min_length, const float* terms,
-                                              const float* upstream, float* grad_D, float* grad_R, gs_stream stream_)
-{
-    if (const int rc = normal_consistency_check("gs_normal_consistency_backward", c, D, R, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms))
-        return rc;
-    if (!grad_D || !grad_R) return fail(GS_ERR_INVALID_ARGUMENT, "gs_normal_consistency_backward: grad_D or grad_R is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_normal_consistency_backward(D, R, w_p, H, W, fx, fy, cx, cy, max_rel_jump, min_length, terms, upstream, grad_D, grad_R, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- vector quantisation (include/gs_vq.h, k_vq.hip) --------------------------------------------------------------------------
-static int vq_check(const char* who, gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* codebook, int64_t ldc,
-                    int32_t K)
-{
-    const std::string w(who);
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
-    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, w + ": n_rows must be in [0, 2^31)");
-    if (dim < 1 || dim > GS_VQ_MAX_DIM) return fail(GS_ERR_INVALID_ARGUMENT, w + ": dim must be in [1, 64]");
-    if (K < 1 || K > GS_VQ_MAX_CODES) return fail(GS_ERR_INVALID_ARGUMENT, w + ": n_codes must be in [1, 65536]");
-    if (ldx < dim || (ldx & 3) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ldx must be a multiple of 4 and >= dim");
-    if (ldc < dim || (ldc & 3) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": ldc must be a multiple of 4 and >= dim");
-    if ((((uintptr_t)x | (uintptr_t)codebook) & 15u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, w + ": x and codebook must be 16-byte aligned");
-    return GS_OK;
-}
-
-extern "C" int64_t gs_vq_scratch_bytes(int64_t n_rows, int32_t n_codes, int32_t dim)
-{
-    if (n_rows < 0 || n_rows > INT32_MAX || n_codes < 1 || n_codes > GS_VQ_MAX_CODES || dim < 1 || dim > GS_VQ_MAX_DIM) return 0;
-    return (int64_t)gs_vq_scratch_size(n_rows, n_codes, dim);
-}
-
-extern "C" int gs_vq_assign(gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* codebook, int64_t ldc, int32_t K,
-                            int32_t* labels, float* dist, void* scratch, gs_stream stream_)
-{
-    if (const int rc = vq_check("gs_vq_assign", c, x, ldx, N, dim, codebook, ldc, K)) return rc;
-    if (N > 0 && (!x || !codebook || !labels || !scratch)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_assign: NULL array");
-    if (((uintptr_t)scratch & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_assign: scratch must be 8-byte aligned");
-    if (N == 0) return GS_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_vq_assign(x, ldx, N, dim, codebook, ldc, K, labels, dist, scratch, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_vq_update(gs_ctx* c, const float* x, int64_t ldx, int64_t N, int32_t dim, const float* weights, const int32_t* labels,
-                            float* codebook, int64_t ldc, int32_t K, int32_t* counts, double* weight_sums, void* scratch, gs_stream stream_)
-{
-    (void)scratch;
-    if (const int rc = vq_check("gs_vq_update", c, x, ldx, N, dim, codebook, ldc, K)) return rc;
-    if (!codebook || !counts || (N > 0 && (!x || !labels))) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_update: NULL array");
-    if (((uintptr_t)weight_sums & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_update: weight_sums must be 8-byte aligned");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_vq_update(x, ldx, N, dim, weights, labels, codebook, ldc, K, counts, weight_sums, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-// ---- adaptive density control (k_density.hip) -------------------------------------------------------------------------
-extern "C" int64_t gs_density_scratch_bytes(int64_t n_points) { return n_points < 0 ? 0 : (int64_t)gs_density_scratch_size(n_points); }
-
-static int density_plan_check(const char* who, const gs_density_plan* p, int64_t N)
-{
-    if (!p || !p->counts) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": plan or plan->counts is NULL");
-    if (N < 0 || N > INT32_MAX) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_points must be in [0, 2^31)");
-    if (p->n_points < N) return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": plan is smaller than the scene");
-    if (N > 0 && (!p->flags || !p->densify_point_id || !p->densify_point_position_before_optimization || !p->densify_point_grad_position ||
-                  !p->densify_size_reduction_factor || !p->fill_point_id || !p->scratch))
-        return fail(GS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL plan array");
-    return GS_OK;
-}
-
-extern "C" int gs_density_select(gs_ctx* c, const gs_scene* scene, const gs_controller_accumulators* acc, const int32_t* ids,
-                                 const int32_t* npix, const float* depth, const float* mag, int64_t M, int32_t remove_floaters,
-                                 const gs_density_config* cfg, const gs_density_plan* plan, gs_stream stream_)
-{
-    if (!c || !scene || !acc || !cfg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL argument");
-    const int64_t N = scene->n_points;
-    if (int rc = density_plan_check("gs_density_select", plan, N)) return rc;
-    if (M < 0 || M > N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: n_in_camera must be in [0, n_points]");
-    if (M > 0 && (!ids || !npix || !depth || !mag)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL hook array");
-    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: NULL scene array");
-    if (N > 0 && (!acc->accumulated_num_in_camera || !acc->accumulated_num_pixels || !acc->accumulated_view_space_position_gradients ||
-                  !acc->accumulated_view_space_position_gradients_avg || !acc->accumulated_position_gradients ||
-                  !acc->accumulated_position_gradients_norm))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_select: the controller accumulators must all be given");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_density_select(*scene, *acc, ids, npix, depth, mag, M, remove_floaters != 0, *cfg, *plan, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_density_apply(gs_ctx* c, const gs_density_scene* scene, const gs_density_config* cfg, const gs_density_plan* plan,
-                                uint64_t seed, uint32_t call_index, gs_stream stream_)
-{
-    if (!c || !scene || !cfg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_apply: NULL argument");
-    const int64_t N = scene->n_points;
-    if (int rc = density_plan_check("gs_density_apply", plan, N)) return rc;
-    if (N > 0 && (!scene->point_cloud || !scene->point_cloud_features || !scene->point_invalid_mask || !scene->point_object_id))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_density_apply: NULL scene array");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_density_apply(*scene, *cfg, *plan, seed, call_index, s);
-    HIP_TRY(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" int gs_controller_accumulate(gs_ctx* c, const int32_t* ids, const int32_t* npix, const float* mag, const float* gpc, int64_t M,
-                                        int64_t N, const gs_controller_accumulators* acc, gs_stream stream_)
-{
-    if (!c || !acc) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: NULL argument");
-    if (N < 0 || N > INT32_MAX || M < 0 || M > N) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: need 0 <= n_in_camera <= n_points < 2^31");
-    if (M > 0 && (!ids || !npix || !mag || !gpc)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: NULL hook array");
-    if (M > 0 && (!acc->accumulated_num_in_camera || !acc->accumulated_num_pixels || !acc->accumulated_view_space_position_gradients ||
-                  !acc->accumulated_view_space_position_gradients_avg || !acc->accumulated_position_gradients ||
-                  !acc->accumulated_position_gradients_norm))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_controller_accumulate: the controller accumulators must all be given");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s;
-    if (const int rc = enter_call(c, stream_, &s)) return rc;
-    gs_launch_controller_accumulate(ids, npix, mag, gpc, M, N, *acc, s);
-    HIP_TRY(hipGetLastError());
     return GS_OK;
 }
 

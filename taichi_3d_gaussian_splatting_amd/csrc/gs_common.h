@@ -566,7 +566,7 @@ void gs_launch_mixture_grad(const float* point_cloud, const float* features, con
                             float* grad_point_cloud, float* grad_features, float* grad_x, void* record_ws, void* sum_ws, void* query_ws,
                             void* partial_ws, void* gsum_ws, void* x_partial_ws, hipStream_t s);
 // k_targets.hip (include/gs_targets.h): the (h_out, w_out) crop of the antialiased resize of a resident image.  One axis of the
-// resize as the host made it (gs_api.hip: float64, rounded once): output i reads `count[i]` inputs from `start[i]` on with the
+// resize as the host made it (gs_api_calls.hip: float64, rounded once): output i reads `count[i]` inputs from `start[i]` on with the
 // weights weight[i * taps .. + count[i]); taps <= GS_RS_MAX_TAPS.  The launcher trusts what gs_image_resample checked: the
 // window of GS_RESAMPLE_TILE_W consecutive outputs spans at most GS_RS_MAX_SPAN input pixels.
 #define GS_RS_MAX_TAPS 18
@@ -610,7 +610,7 @@ __device__ __forceinline__ void gs_controller_add(int64_t n, int32_t npix, float
 }
 
 #include "../../include/gs_rasterizer.h"
-// select (CTRL:170-265), apply (CTRL:290-353) and the hook-side accumulation (CTRL:133-141); argument checks are gs_api.hip's
+// select (CTRL:170-265), apply (CTRL:290-353) and the hook-side accumulation (CTRL:133-141); argument checks are gs_api_calls.hip's
 void gs_launch_density_select(const gs_scene& scene, const gs_controller_accumulators& acc, const int32_t* ids, const int32_t* npix,
                               const float* depth, const float* mag, int64_t M, int remove_floaters, const gs_density_config& cfg,
                               const gs_density_plan& plan, hipStream_t s);
