@@ -4,6 +4,7 @@
 // points that hold no frame are gs_api_calls.hip's; what both share is gs_host.h.
 #include "../../include/gs_channels.h"
 #include "../../include/gs_sparse.h"
+#include "../../include/gs_view_hints.h"
 #include "gs_host.h"
 #include "gs_sort_key.h"
 
@@ -42,6 +43,10 @@ struct Frame {
     int n_objects = 0;                  // pose rows of the forward that made the frame (the backward's pose gradient has as many)
     bool rgb_only = false;              // gs_forward ran with gs_config.rgb_only: no `last` exists for the frame (gs_channels_* refuse it)
     bool max_tiles_known = false;       // k_project of this frame left the largest tile count of one point in the tile arrays (frames from records: no)
+    // the view table (gs_common.h) as this frame's forward found it: the layout it belongs to (0: none), and whether k_filter left the
+    // frame's read and write slot behind the tile order (frames from records, or of an empty scene: no)
+    uint32_t view_epoch = 0;
+    bool view_keyed = false;
     uint32_t generation = 0;
     uint64_t bwd_serial = 0;            // gs_ctx::bwd_serial of the last backward blend on this frame (0: none has run)
     // gs_project_shard_begin: the hand-over of M (and the object-id check) has not been read yet; slot of the pinned counters
@@ -109,7 +114,7 @@ extern "C" int gs_destroy(gs_ctx* c)
     (void)hipDeviceSynchronize();
     for (Frame* f : c->frames) { f->bufs.release(&c->device_bytes); delete f; }
     DevBuf* all[] = { &c->block_counts, &c->block_offsets, &c->tile_block_sums, &c->hist, &c->scan_tmp, &c->first_hist,
-                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->order_hint, &c->pose_scratch,
+                      &c->counters, &c->partial, &c->visited, &c->zero_row, &c->sums, &c->loss_ws, &c->view_table, &c->pose_scratch,
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
                       &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->bilateral_ws, &c->depth_ws,
@@ -198,6 +203,7 @@ static Frame* begin_frame(gs_ctx* c, const gs_camera* cam, int T, int keep, int*
     Frame* f = acquire_frame(c, slot);
     f->info = gs_frame_info{};
     f->bwd_serial = 0;
+    f->view_epoch = 0; f->view_keyed = false;
     // (known before the stages run: a kept frame gets list cuts for its backward, and the tile count lays out the tile arrays)
     f->info.kept_for_backward = keep ? 1 : 0;
     f->info.n_tiles = T; f->info.camera_height = cam->camera_height; f->info.camera_width = cam->camera_width;
@@ -364,6 +370,46 @@ static int check_required_key_class(const Frame* f)
     return GS_OK;
 }
 
+// ---- the view table (gs_common.h): per-view dispatch orders of the forward blend ---------------------------------------------
+// GS_VIEW_HINTS, read on every call like GS_SORT_NARROW_KEYS: the number of slots at every image size, at most GS_VIEW_MAX_SLOTS; 1 = one
+// slot that every pose matches (the last backward's order, whatever its view; no frame looks its pose up); 0 = no hint.  Unset:
+// GS_VIEW_SLOTS_DEFAULT (64 views: 2 MB of orders at 8160 tiles) from GS_VIEW_MIN_TILES tiles on, one slot below.  An order can only
+// help a launch of more workgroups than the chip holds at once (k_blend_fwd: 8 workgroups on each of 256 CUs = 2048), and below that the
+// lookup is pure cost: measured at 8160 tiles (cfg3_headline: k_blend_fwd 0.144 -> 0.135 ms) and at 2074 (cfg2_clustered: k_blend_fwd
+// unchanged, k_filter, whose 899 blocks are all resident so that block 0's chain is the kernel's, 0.0074 -> 0.0085 ms, the step 0.2 to
+// 0.7 % slower).  Nothing was measured between the two sizes; the threshold is the power of two between them, twice the resident slots.
+#define GS_VIEW_SLOTS_DEFAULT 64
+#define GS_VIEW_MIN_TILES 4096
+static int view_slots_wanted(int T)
+{
+    const char* e = getenv("GS_VIEW_HINTS");
+    if (!e || !e[0]) return T >= GS_VIEW_MIN_TILES ? GS_VIEW_SLOTS_DEFAULT : 1;
+    const long n = strtol(e, nullptr, 10);
+    return n < 0 ? 0 : (n > GS_VIEW_MAX_SLOTS ? GS_VIEW_MAX_SLOTS : (int)n);
+}
+// The table as a forward over T tiles uses it (mutex held, stream entered): laid out again, and emptied, when the tile count or the slot
+// count is not the table's -- frames of the old layout still in flight then leave it alone (backward_views).  base NULL: none.
+static int view_table(gs_ctx* c, int T, hipStream_t s, GsViewTable* out)
+{
+    *out = GsViewTable{ nullptr, 0, 0 };
+    const int S = view_slots_wanted(T);
+    if (S == 0 || T <= 0) return GS_OK;
+    if (c->view_T != T || c->view_S != S) {
+        c->view_T = 0; c->view_S = 0;
+        if (const int rc = grow(c, "forward", { NEED(c->view_table, 4 * GS_VIEW_INTS(S, T)) })) return rc;
+        HIP_TRY(hipMemsetAsync(c->view_table.p, 0, 4 * (size_t)(GS_VIEW_HDR_INTS + GS_VIEW_KEY_INTS * S), s));     // cursor, last slot, every key's tag
+        c->view_T = T; c->view_S = S; c->view_epoch += 1;
+    }
+    *out = GsViewTable{ c->view_table.as<int32_t>(), S, T };
+    return GS_OK;
+}
+// The table as the backward of frame f writes it: the layout the frame's forward saw, or none.
+static GsViewTable backward_views(const gs_ctx* c, const Frame* f)
+{
+    if (f->view_epoch == 0 || f->view_epoch != c->view_epoch || c->view_T != f->info.n_tiles) return GsViewTable{ nullptr, 0, 0 };
+    return GsViewTable{ c->view_table.as<int32_t>(), c->view_S, c->view_T };
+}
+
 // ---- per-point half: filter, compaction, projection (+ tile counts, scan, publication) ----------------------------
 // On success the frame's buffers hold mask / ids / cam_index / records / box / ntiles.  The counters (M, K, depth-code range,
 // bad object ids) are handed over through pinned memory; `wait` says when the host reads them:
@@ -413,6 +459,12 @@ static int run_project_stage(gs_ctx* c, Frame* f, const gs_scene* sc, const gs_c
     }
     pa.host_mirror = c->host_counters_dev + slot; pa.ticket = ++c->ticket;
     if (c->ticket == 0x7fffffff) c->ticket = 0;
+    // only a frame that goes on to its own blend looks its pose up (the shard entry points hand records out: no blend, no tile order)
+    if (wait == WAIT_LATER && N > 0) {
+        if ((rc = view_table(c, T, s, &pa.views)) != GS_OK) return rc;
+        if (pa.views.S < 2) pa.views = GsViewTable{ nullptr, 0, 0 };      // one slot: nothing to look up
+        f->view_keyed = pa.views.base != nullptr;
+    }
     gs_launch_project(pa, s, wait != WAIT_LATER);      // WAIT_LATER: the caller decides who publishes the counters (run_forward_tail)
     f->max_tiles_known = true;
     HIP_TRY(hipGetLastError());
@@ -522,8 +574,16 @@ static int run_raster_stage(gs_ctx* c, Frame* f, const GsProjectArgs& pa, int64_
     fa.image = out->rasterized_image; fa.depth = out->rasterized_depth; fa.acc_alpha = out->pixel_accumulated_alpha;
     fa.last = out->pixel_offset_of_last_effective_point; fa.count = out->pixel_valid_point_count;
     fa.cut_cap = cut_cap;
+    // the dispatch order: the frame's read slot of the view table where k_filter left one, otherwise whichever slot was written last
     static const bool use_hint = []{ const char* e = getenv("GS_FWD_ORDER_HINT"); return !(e && e[0] == '0'); }();
-    fa.order_hint = (use_hint && c->order_hint_T == T && T > 0) ? c->order_hint.as<int32_t>() : nullptr;
+    GsViewTable views;
+    if (const int rc = view_table(c, T, s, &views)) return rc;
+    f->view_epoch = views.base ? c->view_epoch : 0;
+    if (views.base && use_hint) {
+        fa.views = views;
+        fa.view_slot = f->view_keyed ? fa.v.n_heavy + GS_ORDER_READ_SLOT : views.base + 1;
+        fa.view_slot_bias = f->view_keyed ? 0 : 1;
+    }
     // tile ranges are all zero when K == 0, so the kernel writes the "no contributor" values itself
     gs_launch_blend_fwd(fa, s);
     HIP_TRY(hipGetLastError());
@@ -812,14 +872,10 @@ static int prepare_backward_blend(gs_ctx* c, Frame* f, const float* grad_image, 
         if (c->zero_row.ensure(64, &c->device_bytes) != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "backward: zero row");
         HIP_TRY(hipMemsetAsync(c->zero_row.p, 0, c->zero_row.cap, stream));
     }
-    if (c->order_hint_T != f->info.n_tiles) {          // another tile grid: the old ordering is void from here on
-        c->order_hint_T = 0;
-        if (c->order_hint.ensure(4 * (size_t)(f->info.n_tiles > 0 ? f->info.n_tiles : 1), &c->device_bytes) != hipSuccess)
-            return fail(GS_ERR_OUT_OF_MEMORY, "backward: tile order buffer");
-    }
     GsBackwardArgs a{};
     a.prof = &c->prof;
-    a.order_hint = c->order_hint.as<int32_t>();
+    a.views = backward_views(c, f);
+    a.view_slot = f->view_keyed ? frame_view(*f).n_heavy + GS_ORDER_WRITE_SLOT : nullptr;
     a.N = f->info.n_points; a.M = (int)f->info.n_points_in_camera; a.K = K;
     a.H = f->info.camera_height; a.W = f->info.camera_width;
     a.tiles_x = (a.W + GS_TILE - 1) / GS_TILE;
@@ -873,13 +929,6 @@ static int prepare_backward_points(const Frame* f, const gs_scene* sc, const gs_
         a->c_pos_grad = ca->accumulated_position_gradients; a->c_pos_grad_norm = ca->accumulated_position_gradients_norm;
     }
     return GS_OK;
-}
-
-// The blend half of a backward (tile order, blend backward, per-splat sums); the tile order it writes is the next forward's hint.
-static void launch_backward_blend(gs_ctx* c, const GsBackwardArgs& a, hipStream_t s)
-{
-    gs_launch_backward_blend(a, s);
-    if (a.v.T > 0 && a.K > 0) c->order_hint_T = a.v.T;      // k_tile_order ran: the hint is a complete permutation
 }
 
 static int check_backward_points_args(const Frame* f, const gs_scene* sc, const gs_camera* cam, const gs_backward_out* out, const char* who,
@@ -937,7 +986,7 @@ static int backward_impl(gs_ctx* c, gs_frame* h, const gs_scene* sc, const gs_ca
     // this call and the blend is launched at all.  GS_BWD_PREFILL=0: the points stage writes everything itself (and k_sum_rows runs
     // in its previous mapping: prepare_backward_blend).  Read per call (not cached), so that one process can compare the two forms.
     a.prefill = points && a.grad_feat && a.v.T > 0 && a.K > 0 && bwd_prefill_enabled();
-    launch_backward_blend(c, a, s);
+    gs_launch_backward_blend(a, s);        // (the tile order it writes goes into the view table too)
     if (points) gs_launch_backward_points(a, s);            // pose-only: no point gradients, hook arrays or controller statistics
     if (pose) gs_launch_pose_grad(a, f->n_objects, c->pose_scratch.p, out->grad_q_pointcloud_camera, out->grad_t_pointcloud_camera, s);
     HIP_TRY(hipGetLastError());
@@ -978,7 +1027,7 @@ extern "C" int gs_backward_projected(gs_ctx* c, gs_frame* h, const float* grad_i
     if ((rc = enter_call(c, stream_, &s)) != GS_OK) return rc;
     GsBackwardArgs a{};
     if ((rc = prepare_backward_blend(c, f, grad_image, acc_alpha, last, mag_image, reinterpret_cast<float4*>(splat_sums_out), f->bwd_reference_order, s, &a)) != GS_OK) return rc;
-    launch_backward_blend(c, a, s);
+    gs_launch_backward_blend(a, s);        // (the tile order it writes goes into the view table too)
     HIP_TRY(hipGetLastError());
     return GS_OK;
 }
@@ -1156,3 +1205,39 @@ extern "C" int gs_debug_stats_read(unsigned long long* out32, int reset)
     return 0;
 }
 #endif
+
+// ---- include/gs_view_hints.h: the view table, copied out for tests and diagnostics -------------------------------------------
+extern "C" int gs_view_hints_read(gs_ctx* c, const gs_frame* frame, int32_t slot, int32_t* n_slots, int32_t* n_tiles,
+                                  float* keys, int32_t* filled, int32_t slot_cap, int32_t* order, int32_t order_cap, int32_t* frame_slots)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_view_hints_read: ctx is NULL");
+    if (slot_cap < 0 || order_cap < 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_view_hints_read: negative capacity");
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const int S = c->view_S, T = c->view_T;
+    if (slot > S) return fail(GS_ERR_INVALID_ARGUMENT, "gs_view_hints_read: no such slot");
+    if (n_slots) *n_slots = S;
+    if (n_tiles) *n_tiles = T;
+    const GsViewTable tab{ c->view_table.as<int32_t>(), S, T };
+    if (S > 0 && (keys || filled)) {
+        std::vector<int32_t> words((size_t)GS_VIEW_KEY_INTS * S);
+        HIP_TRY(hipMemcpy(words.data(), tab.key(0), 4 * words.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < S && i < slot_cap; ++i) {
+            if (keys) std::memcpy(keys + (size_t)GS_VIEW_KEY_FLOATS * i, &words[(size_t)GS_VIEW_KEY_INTS * i], 4 * GS_VIEW_KEY_FLOATS);
+            if (filled) filled[i] = words[(size_t)GS_VIEW_KEY_INTS * i + 7] == T ? 1 : 0;
+        }
+    }
+    if (order && slot >= 0 && S > 0 && T > 0 && order_cap > 0)
+        HIP_TRY(hipMemcpy(order, tab.order(slot), 4 * (size_t)std::min(T, order_cap), hipMemcpyDeviceToHost));
+    if (frame_slots) {
+        frame_slots[0] = frame_slots[1] = -2;
+        if (frame) {
+            Frame* f;
+            if (const int rc = lookup(c, frame, "gs_view_hints_read", false, &f)) return rc;
+            if (f->view_keyed && f->view_epoch != 0 && f->view_epoch == c->view_epoch)
+                HIP_TRY(hipMemcpy(frame_slots, frame_view(*f).n_heavy + GS_ORDER_READ_SLOT, 8, hipMemcpyDeviceToHost));
+        }
+    }
+    return GS_OK;
+}

@@ -59,6 +59,38 @@ extern __device__ unsigned long long gs_stats_wave_times[2 * 65536];   // start,
 // tile_order buffer: order (T) | n_heavy | n_items | pad pad | item_base (GS_HEAVY_CAP + 1)
 #define GS_ORDER_INTS(T) ((size_t)(T) + 4 + GS_HEAVY_CAP + 4 + GS_HEAVY_CAP)
 #define GS_ORDER_REDO_OFFSET (4 + GS_HEAVY_CAP + 4)      // from n_heavy: one flag per heavy tile, "walk this tile again in one piece" (k_backward.hip)
+// the two pad words, from n_heavy: the frame's slots of the context's view table (below), written by block 0 of k_filter
+#define GS_ORDER_READ_SLOT 2
+#define GS_ORDER_WRITE_SLOT 3
+
+// ---- the view table: dispatch orders of the forward blend, per view (scheduling only) -------------------------------------
+// A context keeps the tile order (heaviest first) of the last backward of each of S views and dispatches the next forward blend of a
+// view in the order its own last visit left: a trainer revisits a fixed set of cameras in shuffled order, so the LAST backward's order
+// belongs to an unrelated view, the same view's order of an epoch ago nearly fits.  The poses are device memory, so the table lives on
+// the device and is consulted there: block 0 of k_filter (the first kernel to read the pose) looks the pose of object 0 up among the keys
+// and leaves two words in the frame's tile-order buffer; k_blend_fwd reads the order of the frame's read slot, k_tile_order writes its
+// order, then the key, into the frame's write slot.  Any permutation of the tiles gives the same bits.
+// A forward only reads the table: a frame that is never back-propagated changes nothing in it (the cursor too moves in k_tile_order).
+// Words: cursor (the slot the next eviction takes) | last slot written + 1 (0: none) | two spare | S keys of 8 words (q xyzw, t xyz of object 0 as
+// given, then the tag: the tile count T once the slot's order is complete, 0 = unfilled) | S + 1 orders of T tiles.  Order S belongs to the
+// frames that did not come through k_filter (records-built ones: no pose to key them by); they read whichever slot was written last.
+#define GS_VIEW_HDR_INTS 4
+#define GS_VIEW_KEY_INTS 8
+#define GS_VIEW_MAX_SLOTS 1024
+#define GS_VIEW_INTS(S, T) (GS_VIEW_HDR_INTS + (size_t)GS_VIEW_KEY_INTS * (size_t)(S) + ((size_t)(S) + 1) * (size_t)(T))
+// Two poses are the same view while d = |q - q'|^2 + |t - t'|^2 / (1 + |t|^2) stays below this (q and -q being one rotation, the
+// nearer sign counts).  A rotation by a about any axis moves a unit quaternion by 2 sin(a / 4): d = 1.9e-5 is a rotation of 0.5 degrees, or a
+// camera moved by 0.44 % of sqrt(1 + |t|^2).  It separates the drift of pose optimisation (a few hundredths of a degree per epoch: d below
+// 1e-6, and the key follows the pose at every backward) from the benchmark's neighbouring views, 2 degrees apart: d = 3.05e-4.
+#define GS_VIEW_SAME_D 1.9e-5f
+struct GsViewTable {
+    int32_t* base;      // NULL: no table (GS_VIEW_HINTS=0, or no tile)
+    int S, T;
+    __host__ __device__ int32_t* key(int slot) const { return base + GS_VIEW_HDR_INTS + GS_VIEW_KEY_INTS * slot; }
+    __host__ __device__ int32_t* order(int slot) const { return base + GS_VIEW_HDR_INTS + GS_VIEW_KEY_INTS * S + (size_t)slot * (size_t)T; }
+    // S = 1: one slot for everything, the behaviour before the table -- every pose matches it, so no frame looks its pose up: all are keyless
+    __host__ __device__ int keyless_slot() const { return S > 1 ? S : 0; }
+};
 
 // Per-object pose record built once per frame (every k_filter block derives it, block 0 stores it).
 struct GsPose {
@@ -378,6 +410,7 @@ struct GsProjectArgs {
     uint32_t* first_hist;
     GsCounters* counters;
     GsCounters* host_mirror; int32_t ticket;    // pinned host copy of the counters; .reserved = ticket once they are valid
+    GsViewTable views;                          // base != NULL: block 0 of k_filter looks the pose up and writes the frame's two slot words
 };
 void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish);
 void gs_launch_publish(const GsProjectArgs& a, int n_blocks, hipStream_t s);    // the hand-over of the counters as a launch of its own
@@ -416,7 +449,9 @@ struct GsBlendFwdArgs {
     int key_bytes, depth_bits; uint32_t K; const GsCounters* counters;   // min(counters->K, K) pairs (see GsBinArgs)
     float* image; float* depth; float* acc_alpha; int32_t* last; int32_t* count;
     int cut_cap;
-    const int32_t* order_hint;     // (T) or NULL: a permutation of the tiles, heaviest first, from an earlier frame of this ctx (scheduling only)
+    // the dispatch order (scheduling only): order *view_slot - view_slot_bias of the view table, a permutation of the tiles, heaviest first,
+    // from an earlier frame of this ctx; a negative slot, or views.base NULL, is the natural order
+    GsViewTable views; const int32_t* view_slot; int view_slot_bias;
 };
 void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s);
 
@@ -424,7 +459,9 @@ struct GsBackwardArgs {
     GsProf* prof;
     int64_t N; int M; uint32_t K; int H, W, tiles_x;
     GsFrameView v;                                   // the frame's records, pairs, tile arrays, tile order and cuts
-    int32_t* order_hint;                             // (T) or NULL: a second copy of tile_order that outlives the frame (the next forward's dispatch order)
+    // base != NULL: k_tile_order leaves a second copy of the order, which outlives the frame, in slot *view_slot of the view table (view_slot
+    // NULL: in the keyless slot) and then keys the slot with the frame's pose of object 0
+    GsViewTable views; const int32_t* view_slot;
     const float* grad_image; const float* acc_alpha; const int32_t* last;
     // gs_backward_ex: upstream gradients of rasterized_depth (with the forward's depth) and of pixel_accumulated_alpha, (H,W) or
     // NULL; aux = 1 selects the AUX kernels (k_blend_bwd_tile, k_sum_rows, k_bwd_points, k_pose_points) and requires v.cuts = NULL

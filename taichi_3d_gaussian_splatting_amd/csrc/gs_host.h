@@ -112,10 +112,12 @@ struct gs_ctx {
     // Predicted sizing of the per-pixel half (run_forward_tail): what the last frame of this ctx needed, for an image of this
     // size.  The next frame's binning, sort and blend are queued on it without waiting for the frame's own counters.
     struct { bool valid = false; int H = 0, W = 0; uint32_t K = 0; int max_code = 0; } seen;
-    // dispatch order for the next forward blend: the last backward's tile order (heaviest first).  Only ever a complete
-    // permutation of [0, order_hint_T) written by k_tile_order; 0 = none.  A hint only moves work in time.
-    DevBuf order_hint;
-    int order_hint_T = 0;
+    // dispatch orders for the forward blend: the view table (gs_common.h), view_S slots of view_T tiles each, every filled one a complete
+    // permutation of [0, view_T) written by k_tile_order.  Laid out (and emptied) by the first forward with another tile count or slot
+    // count (gs_api.hip: view_table); view_epoch counts the layouts, and a frame of an earlier one writes nothing.  A hint only moves work in time.
+    DevBuf view_table;
+    int view_T = 0, view_S = 0;
+    uint32_t view_epoch = 0;
     // stream hand-over: the scratch above is recycled in stream order, so work arriving on another stream waits for
     // everything issued on the previous one
     bool has_stream = false;

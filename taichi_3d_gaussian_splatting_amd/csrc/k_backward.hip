@@ -51,6 +51,7 @@
 #define ORDER_BINS 2048
 #define ORDER_BIN_WIDTH 4
 #define ORDER_PER 8
+#define ORDER_STAGE 8192        // tiles whose order k_tile_order stages in LDS (32 KB): 1920x1088 has 8160
 // HEAVY tiles: the first n_heavy entries of the order -- tiles whose work is at least heavy_factor_x2 / 2 times the mean (the host's
 // choice: twice the mean) and at least HEAVY_MIN_WORK evaluations (at most T / 8 of them, HEAVY_CAP in all).  k_blend_bwd_tile gives each of them a whole
 // workgroup (four cooperating waves, one per quadrant) instead of one wave: on a clustered scene a few tiles carry lists
@@ -125,26 +126,41 @@ __device__ __forceinline__ void gs_zero_fill(const GsZeroFill& z)
 // A heavy tile whose list the forward CUT (k_blend_fwd: every GS_SEG entries each pixel's T and the colour since the last cut) is handed out
 // as one work item per segment: item_base[h] .. item_base[h + 1] are the items of heavy tile h (n_heavy_out[1] = their number,
 // n_heavy_out[4 ..] = item_base).  A heavy tile without cuts is one item.
-__global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__ tile_work, int T, int32_t* __restrict__ order, int32_t* __restrict__ hint,
+__global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__ tile_work, int T, int32_t* __restrict__ order,
+                                                     GsViewTable views, const int32_t* __restrict__ view_slot, const GsPose* __restrict__ pose,
                                                      int32_t* __restrict__ n_heavy_out, int heavy_factor_x2,
                                                      const int32_t* __restrict__ tile_start, const int32_t* __restrict__ tile_end,
                                                      const int32_t* __restrict__ tile_cut, int item_cap)
 {
     __shared__ uint32_t bins[ORDER_BINS];
     __shared__ int32_t sHeavy[HEAVY_CAP];
+    __shared__ int32_t sOrder[ORDER_STAGE];
     __shared__ int32_t sNHeavy;
     __shared__ uint32_t wsum[16];
     __shared__ unsigned long long wtot[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // the copy of the order that outlives the frame: the frame's write slot of the view table (gs_common.h), the keyless one without a slot word
+    const int vslot = views.base ? (view_slot ? *view_slot : views.keyless_slot()) : -1;
+    int32_t* const hint = (vslot >= 0 && vslot <= views.S && views.T == T) ? views.order(vslot) : nullptr;
+    // (the slot's key-to-be, loaded now: at the end of the kernel the load would be waited for)
+    const bool keyed = hint && view_slot && vslot < views.S;
+    GsPose P0{};
+    if (keyed && t == 0) P0 = pose[0];
+    // ORDER_PER loads in flight per thread (the kernel is one workgroup deep in load latency, not in work).  Up to 1024 * ORDER_PER tiles
+    // (block-uniform) that is all of them: they are loaded once, ahead of the clearing and its barrier, and stay in registers for the second pass
+    const bool one_round = T <= 1024 * ORDER_PER;
+    int work[ORDER_PER];
+    auto load_work = [&](int base) {
+#pragma unroll
+        for (int k = 0; k < ORDER_PER; ++k) { const int i = base + k * 1024 + t; work[k] = i < T ? tile_work[i] : -1; }
+    };
+    if (one_round) load_work(0);
     for (int i = t; i < ORDER_BINS; i += 1024) bins[i] = 0;
     if (t < HEAVY_CAP) n_heavy_out[GS_ORDER_REDO_OFFSET + t] = 0;          // no heavy tile has asked to be walked again yet
     __syncthreads();
     unsigned long long total = 0ull;
-    // ORDER_PER loads in flight per thread (the kernel is one workgroup deep in load latency, not in work)
     for (int base = 0; base < T; base += 1024 * ORDER_PER) {
-        int work[ORDER_PER];
-#pragma unroll
-        for (int k = 0; k < ORDER_PER; ++k) { const int i = base + k * 1024 + t; work[k] = i < T ? tile_work[i] : -1; }
+        if (!one_round) load_work(base);
 #pragma unroll
         for (int k = 0; k < ORDER_PER; ++k) {
             if (base + k * 1024 + t >= T) continue;
@@ -191,24 +207,44 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
         *n_heavy_out = sNHeavy;
     }
     __syncthreads();
+    // up to ORDER_STAGE tiles (block-uniform) the order is put together in LDS and leaves in rows, to the frame and to the view table:
+    // two scattered 4-byte stores per tile were what the end of this pass waited for
+    const bool staged = T <= ORDER_STAGE;
     for (int base = 0; base < T; base += 1024 * ORDER_PER) {
-        int work[ORDER_PER];
-#pragma unroll
-        for (int k = 0; k < ORDER_PER; ++k) { const int i = base + k * 1024 + t; work[k] = i < T ? tile_work[i] : -1; }
+        if (!one_round) load_work(base);
 #pragma unroll
         for (int k = 0; k < ORDER_PER; ++k) {
             const int i = base + k * 1024 + t;
             if (i >= T) continue;
             int w = work[k] / ORDER_BIN_WIDTH; w = w < 0 ? 0 : (w > ORDER_BINS - 1 ? ORDER_BINS - 1 : w);
             const uint32_t pos = atomicAdd(&bins[ORDER_BINS - 1 - w], 1u);
-            order[pos] = i;
-            if (hint) hint[pos] = i;
+            if (staged) sOrder[pos] = i;
+            else { order[pos] = i; if (hint) hint[pos] = i; }
             if (pos < HEAVY_CAP) sHeavy[pos] = i;
         }
     }
     __syncthreads();
+    if (staged)
+        for (int i = t; i < T; i += 1024) { const int32_t v = sOrder[i]; order[i] = v; if (hint) hint[i] = v; }
+    // the slot's order is complete: now its key (the pose of object 0 as the caller gave it: q = conj(q_cp), t = origin_bwd) and the tag that
+    // makes it valid, so that no later forward of the stream finds a slot half written
+    if (hint && t == 0) {
+        int32_t* key = views.key(vslot < views.S ? vslot : 0);
+        if (keyed) {
+            key[0] = __float_as_int(-P0.q_cp[0]); key[1] = __float_as_int(-P0.q_cp[1]); key[2] = __float_as_int(-P0.q_cp[2]); key[3] = __float_as_int(P0.q_cp[3]);
+            key[4] = __float_as_int(P0.origin_bwd[0]); key[5] = __float_as_int(P0.origin_bwd[1]); key[6] = __float_as_int(P0.origin_bwd[2]);
+        }
+        if (vslot < views.S) key[7] = T;
+        views.base[1] = vslot + 1;
+        // the slot the cursor stood on is filled (again): the next view without a slot evicts the one behind it
+        if (keyed && (uint32_t)views.base[0] % (uint32_t)views.S == (uint32_t)vslot) views.base[0] = (vslot + 1) % views.S;
+    }
     // work items of the heavy tiles: one per segment of a cut list (exclusive scan over at most 1024 tiles, one per thread)
     const int n_heavy = sNHeavy;
+    if (n_heavy == 0) {                           // (block-uniform) no items: nothing to scan
+        if (t == 0) { n_heavy_out[4] = 0; n_heavy_out[1] = 0; }
+        return;
+    }
     int nseg = 0;
     if (t < n_heavy) {
         const int tile = sHeavy[t];
@@ -1414,7 +1450,7 @@ void gs_launch_backward_blend(const GsBackwardArgs& a, hipStream_t s)
             fill.n_blocks = (unsigned)((bytes + GS_FILL_BLOCK_BYTES - 1) / GS_FILL_BLOCK_BYTES);
         }
         // (the `visited` / `touched` flags are not cleared per backward: a flag counts only if it holds THIS backward's tag, a.gen)
-        GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(v.tile_work, v.T, v.tile_order, a.order_hint, v.n_heavy, a.heavy_factor_x2,
+        GS_TIMED(a.prof, KID_TILE_ORDER, s, k_tile_order<<<1, 1024, 0, s>>>(v.tile_work, v.T, v.tile_order, a.views, a.view_slot, v.pose, v.n_heavy, a.heavy_factor_x2,
                                                                               v.tile_start, v.tile_end, v.cuts ? v.tile_cut : nullptr, v.cuts ? a.item_cap : gs_heavy_cap(v.T)));
 #define GS_BWD_LAUNCH_(NQ_, STRICT_, AUX_)                                                                                             \
         GS_TIMED(a.prof, KID_BLEND_BWD, s, k_blend_bwd_tile<NQ_, STRICT_, AUX_><<<groups + fill.n_blocks, 256, 0, s>>>(v.tile_order, v.n_heavy, v.T,      \

@@ -50,14 +50,17 @@ __global__ __launch_bounds__(256) void k_blend_fwd(int32_t* __restrict__ tile_st
                                                    float* __restrict__ image, float* __restrict__ depth_out,
                                                    float* __restrict__ acc_alpha, int32_t* __restrict__ last_out,
                                                    int32_t* __restrict__ count_out, int32_t* __restrict__ tile_work,
-                                                   const int32_t* __restrict__ order_hint,
+                                                   const int32_t* __restrict__ view_orders, const int32_t* __restrict__ view_slot,
+                                                   int view_slot_bias, int view_slot_max,
                                                    float4* __restrict__ cuts, int32_t* __restrict__ tile_cut, int cut_cap)
 {
     __shared__ float4 sRec[4][64][3];          // the batch's splat records, one slab per wave
+    // Dispatch order: heaviest tiles first when an earlier frame of this context left its ordering in the view table (gs_common.h: the
+    // frame's read slot, chosen by k_filter; the slot written last for a frame that did not come through it) -- the launch otherwise ends
+    // on the long walks of the image's dense region, started late.  Any permutation gives the same results.  (The slot word is loaded beside K.)
+    const int slot = view_orders ? *view_slot - view_slot_bias : -1;
     const uint32_t K = min(ctr->K, K_cap);     // pairs of this frame, read on the device (gs_api.hip: predicted sizing)
-    // Dispatch order: heaviest tiles first when an earlier frame of this context left its ordering (same tile count) -- the
-    // launch otherwise ends on the long walks of the image's dense region, started late.  Any permutation gives the same results.
-    const int tile = order_hint ? order_hint[blockIdx.x] : (int)blockIdx.x;
+    const int tile = (slot >= 0 && slot <= view_slot_max) ? view_orders[(size_t)slot * gridDim.x + blockIdx.x] : (int)blockIdx.x;
     // the wave index as a scalar: LDS addresses of the wave's slab are then SGPR arithmetic + one v_mov instead of a 64-bit VALU mad per splat
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const GsQuadPixel qp = gs_quad_pixel(tile, wave, lane, tiles_x, W, H);
@@ -220,7 +223,8 @@ void gs_launch_blend_fwd(const GsBlendFwdArgs& a, hipStream_t s)
     if (v.T <= 0) return;
     auto launch = [&](auto kernel) {
         GS_TIMED(a.prof, KID_BLEND_FWD, s, kernel<<<v.T, 256, 0, s>>>(v.tile_start, v.tile_end, v.keys_sorted, a.key_bytes, a.depth_bits - gs_key_dropped_bits(a.key_bytes), a.counters, a.K, v.vals_sorted, v.PA, v.PB, v.PC, a.W, a.H,
-                                                                   a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.order_hint, v.cuts, v.tile_cut, a.cut_cap));
+                                                                   a.tiles_x, a.image, a.depth, a.acc_alpha, a.last, a.count, v.tile_work, a.views.base ? a.views.order(0) : nullptr, a.view_slot, a.view_slot_bias, a.views.S,
+                                                                   v.cuts, v.tile_cut, a.cut_cap));
     };
     if (a.rgb_only) launch(k_blend_fwd<true>);
     else launch(k_blend_fwd<false>);

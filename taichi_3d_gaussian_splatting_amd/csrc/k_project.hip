@@ -59,6 +59,59 @@ __device__ __forceinline__ void project_point(const float* __restrict__ R, const
     uv[1] = v1 / pc[2];
 }
 
+// The frame's slots of the view table (gs_common.h), by one wave of k_filter's block 0: the pose of object 0 against the filled keys, one
+// slot per lane and round.  read slot = the nearest filled slot (a bit-equal key is distance 0; ties go to the lowest slot), -1 when none is
+// filled; write slot = the same one while it is the same view (GS_VIEW_SAME_D), otherwise the lowest unfilled slot, otherwise the slot
+// the round-robin cursor stands on.  Nothing of the table is written here.  Only tables of two slots or more are looked up (gs_api.hip).
+// A key that is not a number is infinitely far from everything but its own bits.
+__device__ __forceinline__ void gs_view_lookup(const GsViewTable& views, const float* __restrict__ q_pc, const float* __restrict__ t_pc, int lane,
+                                               int32_t* __restrict__ view_slots)
+{
+    const int S = views.S;
+    float k[7];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) k[j] = q_pc[j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) k[4 + j] = t_pc[j];
+    const float t_scale = 1.0f / (1.0f + (k[4] * k[4] + k[5] * k[5] + k[6] * k[6]));
+    unsigned long long best = ~0ull;             // (distance bits << 32) | slot: distances are >= 0, so their bits order as they do
+    int unfilled = S;
+    for (int slot = lane; slot < S; slot += 64) {
+        const int32_t* key = views.key(slot);
+        if (key[7] != views.T) { unfilled = unfilled < slot ? unfilled : slot; continue; }
+        bool same_bits = true;
+        float dp = 0.0f, dm = 0.0f, dt = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const float o = __int_as_float(key[j]);
+            same_bits = same_bits && key[j] == __float_as_int(k[j]);
+            if (j < 4) { dp += (k[j] - o) * (k[j] - o); dm += (k[j] + o) * (k[j] + o); }
+            else dt += (k[j] - o) * (k[j] - o);
+        }
+        float d = (dp < dm ? dp : dm) + dt * t_scale;
+        d = same_bits ? 0.0f : (d >= 0.0f && d < 3.0e38f ? d : 3.0e38f);
+        const unsigned long long cand = ((unsigned long long)(uint32_t)__float_as_int(d) << 32) | (unsigned long long)(uint32_t)slot;
+        best = cand < best ? cand : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long ob = __shfl_xor(best, o, 64);
+        const int ou = __shfl_xor(unfilled, o, 64);
+        best = ob < best ? ob : best;
+        unfilled = ou < unfilled ? ou : unfilled;
+    }
+    if (lane != 0) return;
+    const bool found = best != ~0ull;
+    const int nearest = (int)(uint32_t)(best & 0xffffffffull);
+    const float d = __int_as_float((int)(uint32_t)(best >> 32));
+    int write;
+    if (found && d < GS_VIEW_SAME_D) write = nearest;
+    else if (unfilled < S) write = unfilled;
+    else write = (int)((uint32_t)views.base[0] % (uint32_t)S);          // (k_tile_order moves the cursor on when it fills the slot: a forward writes nothing)
+    view_slots[GS_ORDER_READ_SLOT] = found ? nearest : -1;
+    view_slots[GS_ORDER_WRITE_SLOT] = write;
+}
+
 // ---------------------------------------------------------------------------------
 #define FILTER_POSE_CACHE 8
 __global__ __launch_bounds__(256) void k_filter(const float* __restrict__ pc, const int8_t* __restrict__ invalid,
@@ -67,7 +120,8 @@ __global__ __launch_bounds__(256) void k_filter(const float* __restrict__ pc, co
                                                 GsPose* __restrict__ pose, GsCounters* __restrict__ counters,
                                                 int64_t N, int W, int H, float near_plane, float far_plane,
                                                 int8_t* __restrict__ mask, int32_t* __restrict__ block_counts,
-                                                int32_t* __restrict__ tile_arrays, int tile_ints)
+                                                int32_t* __restrict__ tile_arrays, int tile_ints,
+                                                GsViewTable views, int32_t* __restrict__ view_slots)
 {
     __shared__ int wave_cnt[4];
     __shared__ GsPose sp[FILTER_POSE_CACHE];
@@ -80,6 +134,7 @@ __global__ __launch_bounds__(256) void k_filter(const float* __restrict__ pc, co
     if (cached && threadIdx.x < n_objects) sp[threadIdx.x] = make_pose(q_pc, t_pc, threadIdx.x);
     if (blockIdx.x == 0) {            // (the frame counters were reset when the previous frame's were published)
         for (int o = threadIdx.x; o < n_objects; o += 256) pose[o] = make_pose(q_pc, t_pc, o);
+        if (views.base && threadIdx.x < 64) gs_view_lookup(views, q_pc, t_pc, threadIdx.x, view_slots);
     }
     __syncthreads();
     bool in = false;
@@ -379,7 +434,7 @@ void gs_launch_project(const GsProjectArgs& a, hipStream_t s, bool publish)
     if (nb == 0) { (void)hipMemsetAsync(v.tile_start, 0, sizeof(int32_t) * (size_t)v.tile_ints, s); return; }     // empty scene: nothing else clears them
     GS_TIMED(a.prof, KID_FILTER, s, k_filter<<<nb, 256, 0, s>>>(a.point_cloud, a.invalid, a.object_id, a.Kmat, a.q_pc, a.t_pc, a.n_objects,
                                                             v.pose, a.counters, a.N, a.W, a.H, a.near_plane, a.far_plane, v.mask,
-                                                            a.block_counts, v.tile_start, v.tile_ints));
+                                                            a.block_counts, v.tile_start, v.tile_ints, a.views, v.n_heavy));
     GS_TIMED(a.prof, KID_PROJECT, s, k_project<<<nb, 256, 0, s>>>(a.point_cloud, a.features, a.object_id, a.Kmat, v.pose, v.mask, a.block_counts, a.N,
                                                               v.ids, v.cam_index, a.block_offsets, a.W, a.H,
                                                               a.depth_scale, v.PA, v.PB, v.PC, v.PD, v.box, v.ntiles,
