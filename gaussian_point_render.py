@@ -24,6 +24,9 @@ DIR/normal_<i:03>.png, in the camera frame of the rasteriser (x right, y down, z
 leaves out the normals across a depth change of more than J times the depth.  With --normals_to, --output_prefix is optional.
 --normals_source gaussians writes the rendered per-Gaussian normals instead (normals.rendered_normals), normalised per pixel where
 the blend is at least --normals_min_length (default 0.5) long and (0,0,0) elsewhere.
+--background black|white|R,G,B|FILE composites every frame over a solid colour or over the background a trainer run with
+--background saved (a background_<iteration>.pt) before it is converted to 8 bits; this renders with the depth rasteriser
+for the accumulated alpha, which is slower than the default rgb_only path.
 """
 import argparse
 import json
@@ -65,6 +68,7 @@ if __name__ == "__main__":
                         "depth, or the rendered per-Gaussian normals")
     parser.add_argument("--normals_min_length", type=float, default=0.5, help="with --normals_source gaussians: a pixel whose blended normal "
                         "is shorter than this is written as (0,0,0)")
+    parser.add_argument("--background", type=str, default="", help="black, white, R,G,B in [0, 1], or a background_<iteration>.pt of the trainer")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
     if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to or args.normals_to)):
@@ -144,8 +148,12 @@ if __name__ == "__main__":
         from taichi_3d_gaussian_splatting_amd.bilateral import BilateralGridTable
         table, table_paths = BilateralGridTable.load(args.bilateral_grid, device=renderer.device)
         transforms = table.by_image_path(table_paths)
+    background = None
+    if args.background:
+        from taichi_3d_gaussian_splatting_amd.background import BackgroundModel
+        background = BackgroundModel.from_spec(args.background, renderer.device)
     metrics = renderer.run(output_prefix, depth=args.depth, targets=targets, gt_prefix=gt_prefix, appearance=transforms,
-                           image_paths=image_paths if transforms is not None else None)
+                           image_paths=image_paths if transforms is not None else None, background=background)
     if metrics is not None:
         with open(args.metrics_json or output_prefix / "metrics.json", "w") as fh:
             json.dump(metrics, fh, indent=1)

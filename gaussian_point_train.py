@@ -10,7 +10,10 @@ depth_path maps (INTEGRATION.md "Depth supervision in the trainer");
 rendered depth, and --normal_prior W [--normal_convention opencv|opengl] a normal loss against the dataset's normal_path priors
 (INTEGRATION.md "Geometry regularisers");
 --normal_consistency W [--consistency_min_length L --consistency_start N] adds the consistency of the rendered Gaussian normals
-with the normal of the rendered depth, which needs no data (INTEGRATION.md "Normal consistency")."""
+with the normal of the rendered depth, which needs no data (INTEGRATION.md "Normal consistency");
+--background colour|random|sky [--background_colour R G B --background_bands B --background_lr LR --composite_targets] puts a
+solid colour, a random colour per step or a learnable spherical-harmonics sky behind the splats, and composites RGBA pictures
+over the same background (INTEGRATION.md "Backgrounds")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -55,7 +58,19 @@ if __name__ == "__main__":
                         "is shorter than this is left out")
     parser.add_argument("--consistency_start", type=int, default=None, metavar="N", help="with --normal_consistency: the first iteration of the "
                         "geometry terms (GeometryConfig.start_iteration)")
+    parser.add_argument("--background", choices=("none", "colour", "random", "sky"), default="none",
+                        help="what lies behind the splats: a solid colour, a random colour per step, or a learnable sky")
+    parser.add_argument("--background_colour", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                        help="with --background: the colour, the validation colour of random, the sky's start (default 0 0 0)")
+    parser.add_argument("--background_bands", type=int, choices=(0, 1, 2, 3), default=None, help="with --background sky: its spherical-harmonics bands")
+    parser.add_argument("--background_lr", type=float, default=None, metavar="LR", help="with --background sky: its learning rate at "
+                        "iteration 0 (it falls to a tenth of it over the run)")
+    parser.add_argument("--composite_targets", action="store_true", default=False,
+                        help="with --background: composite the RGBA pictures over the step's background")
     args = parser.parse_args()
+    if args.background == "none" and (args.background_colour is not None or args.background_bands is not None or
+                                      args.background_lr is not None or args.composite_targets):
+        parser.error("--background_colour, --background_bands, --background_lr and --composite_targets need --background")
     if args.normal_consistency is None and (args.consistency_min_length is not None or args.consistency_start is not None):
         parser.error("--consistency_min_length and --consistency_start need --normal_consistency")
     if args.depth_smooth is None and (args.smooth_order is not None or args.smooth_space is not None or args.smooth_edge_lambda is not None):
@@ -112,7 +127,18 @@ if __name__ == "__main__":
                       consistency_weight=args.normal_consistency, consistency_min_length=args.consistency_min_length,
                       start_iteration=args.consistency_start)
         geometry_config = GeometryConfig(**{name: value for name, value in chosen.items() if value is not None})
+    background_config = None
+    if args.background != "none":
+        from taichi_3d_gaussian_splatting_amd.background import BackgroundConfig
+        background_config = BackgroundConfig()
+        if args.background_colour is not None:
+            background_config.colour = tuple(args.background_colour)
+        if args.background_bands is not None:
+            background_config.bands = args.background_bands
+        if args.background_lr is not None:
+            background_config.lr, background_config.lr_final = args.background_lr, args.background_lr / 10.0
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
                                         mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,
-                                        geometry=geometry_config, bilateral_grid=bilateral_config)
+                                        geometry=geometry_config, bilateral_grid=bilateral_config, background=args.background,
+                                        background_config=background_config, composite_targets=args.composite_targets)
     trainer.train()

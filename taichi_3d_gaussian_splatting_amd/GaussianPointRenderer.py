@@ -16,6 +16,9 @@ multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. a
     colour transform of exposure compensation) before they are converted to 8 bits, and adds psnr_cc per view: the PSNR after
     the best affine fit of the rendering to its ground truth; an entry that is a (Gy,Gx,L,12) bilateral grid (bilateral.py) is
     sliced over its frame instead;
+  - render(background=...) and run(background=...) composite every frame over a background.BackgroundModel (a solid colour,
+    or the sky a trainer saved) before it is converted to 8 bits.  This takes the depth rasteriser for the accumulated alpha,
+    which is slower than the rgb_only path.  The sky's frame is that of the composition's first scene;
   - fuse() renders the poses with depth and accumulated alpha and integrates them into a fusion.TSDFVolume on the device, from
     which a triangle mesh is extracted (fusion.py).
 """
@@ -27,6 +30,7 @@ import numpy as np
 import torch
 
 from . import appearance as _appearance
+from . import background as _background
 from . import bilateral as _bilateral
 from . import frames, fusion
 from .Camera import CameraInfo
@@ -95,11 +99,13 @@ class GaussianPointRenderer:
         return q_rows.reshape(-1, K, 4), t_rows.reshape(-1, K, 3)
 
     def render(self, q_rows: torch.Tensor, t_rows: torch.Tensor, camera_info: Optional[CameraInfo] = None, depth: bool = False,
-               alpha: bool = False, keep_frame: bool = False):
+               alpha: bool = False, keep_frame: bool = False, background=None):
         """one frame under the (K,4), (K,3) pose rows -> (image (H,W,3) f32, depth (H,W) or None), band 3, no gradient; with
         alpha=True (which takes the depth rasteriser) a third value, the accumulated alpha (H,W).  keep_frame (with depth or
-        alpha): the depth rasteriser keeps the frame for render_channels"""
+        alpha): the depth rasteriser keeps the frame for render_channels.  background (a background.BackgroundModel): the image
+        is composited over it, which takes the depth rasteriser too; the view direction of a sky is that of pose row 0"""
         Rast = GaussianPointCloudRasterisation
+        wanted_alpha, alpha = alpha, alpha or background is not None
         with torch.no_grad():
             outputs = (self._with_depth() if depth or alpha else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
                 point_cloud=self.scene.point_cloud,
@@ -112,7 +118,12 @@ class GaussianPointRenderer:
                 color_max_sh_band=3,
             ), **({"return_accumulated_alpha": True} if alpha else {}), **({"keep_frame": True} if keep_frame else {}))
         image, image_depth = outputs[0], outputs[1]
-        if alpha:
+        if background is not None:
+            info = self.camera_info if camera_info is None else camera_info
+            with torch.no_grad():       # in the rasteriser's layout, so the composited frame is again a contiguous (H,W,3)
+                image = _background.composite_forward(image.permute(2, 0, 1), outputs[3], background.coef, background.bands,
+                                                      q_rows[:1].contiguous(), info.camera_intrinsics.contiguous()).permute(1, 2, 0)
+        if wanted_alpha:
             return image, (image_depth if depth else None), outputs[3]
         return image, (image_depth if depth else None)
 
@@ -173,7 +184,7 @@ class GaussianPointRenderer:
             PIL.Image.fromarray(geometry.normals_to_uint8(normals).cpu().numpy()).save(os.path.join(str(directory), f"normal_{i:03d}.png"))
         return len(infos)
 
-    def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None, appearance=None, image_paths=None):
+    def run(self, output_prefix, depth: bool = False, targets=None, gt_prefix=None, appearance=None, image_paths=None, background=None):
         """Render every camera of the config to <output_prefix>/frame_<i:03>.<format> (and depth_<i:03> with depth=True).
         output_prefix None: the frames still cross to the host, nothing is written.
 
@@ -186,7 +197,9 @@ class GaussianPointRenderer:
         every view of `targets`, in order): a view whose path is in the dict is corrected by its transform before it is
         converted to 8 bits and measured; every other frame is rendered as without it.  A value may also be the view's
         (Gy,Gx,L,12) bilateral grid (BilateralGridTable.by_image_path), which is sliced over the frame.  Every view then also gets psnr_cc:
-        the float PSNR after appearance.fit_affine(rendering, ground truth), which reads 23 numbers to the host per view."""
+        the float PSNR after appearance.fit_affine(rendering, ground truth), which reads 23 numbers to the host per view.
+
+        background (a background.BackgroundModel): every frame is composited over it before anything else is done with it."""
         if appearance is not None:
             if targets is None or image_paths is None or len(image_paths) != len(targets):
                 raise ValueError("appearance needs targets and the image path of every one of its views")
@@ -198,7 +211,7 @@ class GaussianPointRenderer:
         if targets is None:
             q_rows, t_rows = self.pose_rows()
             for i in range(q_rows.shape[0]):
-                image, image_depth = self.render(q_rows[i], t_rows[i], depth=depth)
+                image, image_depth = self.render(q_rows[i], t_rows[i], depth=depth, background=background)
                 sink.submit(image, depth=image_depth)
             sink.close()
             return None
@@ -211,7 +224,7 @@ class GaussianPointRenderer:
         for i in range(n):
             image_gt, _, _, info = targets.target(i, 1)
             h, w = info.camera_height, info.camera_width
-            image, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=depth)
+            image, image_depth = self.render(q_rows[i], t_rows[i], camera_info=info, depth=depth, background=background)
             if appearance is not None and str(image_paths[i]) in appearance:
                 # in the rasteriser's layout, so the corrected frame is again a contiguous (H,W,3)
                 correction = appearance[str(image_paths[i])]

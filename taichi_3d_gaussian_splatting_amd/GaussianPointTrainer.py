@@ -38,6 +38,13 @@ What differs from the reference
     on the rendered depth (geometry.py): an edge-aware smoothness with the colour target as its guide -- it needs no extra data
     -- and a cosine loss of the depth-derived normal against the dataset's normal_path priors, resident on the device.  None,
     the default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, background="colour" | "random" | "sky", background_config=BackgroundConfig(...),
+    composite_targets=False) puts a background behind the splats (background.py): the step's forward also returns the
+    accumulated alpha, and the rendered image is composited over a solid colour, a random colour drawn per step, or a learnable
+    spherical-harmonics sky, before any appearance transform or bilateral grid (the camera's processing acts on the whole
+    picture).  composite_targets=True composites the RGBA training pictures over the step's colour too, so the transparent
+    pixels tell the scene to be empty; "random" needs it.  "sky" takes its Adam step beside the scene's.  Validation composites
+    with the model's stored background (config.colour for "random").  "none", the default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -61,11 +68,14 @@ from .GaussianPointCloudRasterisation import GaussianPointCloudRasterisation
 from .GaussianPointCloudScene import GaussianPointCloudScene
 from . import appearance as _appearance
 from .appearance import AppearanceConfig, AppearanceTable
+from . import background as _background
+from .background import BackgroundConfig, BackgroundModel
 from . import bilateral as _bilateral
 from .bilateral import BilateralGridConfig, BilateralGridTable
 from . import depth as _depth
 from .depth import DepthConfig
 from . import geometry as _geometry
+from . import _terms
 from .geometry import GeometryConfig
 from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
@@ -233,7 +243,8 @@ class GaussianPointCloudTrainer:
     def __init__(self, config: TrainConfig, device="cuda", writer=None, pixel_weights: str = "none", mask_erode: int = 0,
                  density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
                  appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None,
-                 geometry: Optional[GeometryConfig] = None, bilateral_grid: Optional[BilateralGridConfig] = None):
+                 geometry: Optional[GeometryConfig] = None, bilateral_grid: Optional[BilateralGridConfig] = None,
+                 background: str = "none", background_config: Optional[BackgroundConfig] = None, composite_targets: bool = False):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -246,8 +257,28 @@ class GaussianPointCloudTrainer:
         aligned per view) -- and its DepthConfig (None: the defaults, its weight schedule over config.num_iterations); geometry:
         the GeometryConfig of the regularisers on the rendered depth (None: none); bilateral_grid: the BilateralGridConfig of a
         learnable bilateral grid of colour transforms per training image (bilateral.BilateralGridTable, in self.bilateral_table;
-        None: none; its schedule runs over config.num_iterations unless it names its own)"""
+        None: none; its schedule runs over config.num_iterations unless it names its own); background: what lies behind the
+        splats -- "none", "colour" (background_config.colour), "random" (a colour drawn per step) or "sky" (learnable spherical
+        harmonics of the view direction; background.BackgroundModel, in self.background_model) -- its BackgroundConfig (None: the
+        defaults, black, its schedule over config.num_iterations), and composite_targets: whether the RGBA training and
+        validation pictures are composited over the same background"""
         self.config = config
+        if background not in ("none",) + _background.KINDS:
+            raise ValueError(f'background must be "none", "colour", "random" or "sky", got {background!r}')
+        if background == "none" and (background_config is not None or composite_targets):
+            raise ValueError('background_config and composite_targets need a background: "colour", "random" or "sky"')
+        if background != "none":
+            _terms.check_depth_is_rendered(config, f'background="{background}"', "the accumulated alpha and the targets are made on the device")
+            if background == "random" and not composite_targets:
+                raise ValueError('background="random" needs composite_targets=True: a random colour behind the splats means nothing '
+                                 "against pictures that were not composited over it")
+            if composite_targets and pixel_weights == "file":
+                raise ValueError('composite_targets cannot be combined with pixel_weights="file": the stored fourth channel is the mask, '
+                                 "not the pictures' alpha")
+            if composite_targets and mask_erode:
+                raise ValueError("composite_targets cannot be combined with mask_erode: the pictures are composited with their own alpha")
+        self.background, self.composite_targets = background, bool(composite_targets)
+        self.background_model = None
         # the extra loss terms, in the order they are summed and logged in; each checks its arguments where it is made
         geometry_terms = _geometry.trainer_terms(geometry, config)
         depth_terms = _depth.trainer_terms(depth, depth_config, config)
@@ -322,6 +353,8 @@ class GaussianPointCloudTrainer:
             raise ValueError('mask_erode must be >= 0, and needs pixel_weights="alpha" or "file"')
         if self.config.targets_on_device:
             mask = dict(mask_source=self.pixel_weights, mask_erode=self.mask_erode) if self.weighted else {}
+            if self.composite_targets:
+                mask = dict(mask_source="alpha")            # the pictures' alpha: what they are composited with, and the weight if one is asked for
             self.train_targets = TargetStore.from_dataset(self.train_dataset, self.device, **mask)
             self.val_targets = TargetStore.from_dataset(self.val_dataset, self.device, **mask)
         else:
@@ -332,6 +365,11 @@ class GaussianPointCloudTrainer:
             if appearance_config.num_iterations is None:
                 appearance_config = dataclasses.replace(appearance_config, num_iterations=max(int(self.config.num_iterations), 1))
             self.appearance_table = AppearanceTable(len(self.train_dataset), self.device, appearance_config)
+        if self.background != "none":
+            background_config = background_config or BackgroundConfig()
+            if background_config.num_iterations is None:
+                background_config = dataclasses.replace(background_config, num_iterations=max(int(self.config.num_iterations), 1))
+            self.background_model = BackgroundModel(self.background, self.device, background_config)
         if bilateral_grid is not None:
             if bilateral_grid.num_iterations is None:
                 bilateral_grid = dataclasses.replace(bilateral_grid, num_iterations=max(int(self.config.num_iterations), 1))
@@ -401,9 +439,27 @@ class GaussianPointCloudTrainer:
         weight when the loss has one, or (store None) the next item of the host path's loader, which walks the same views"""
         if store is None:
             return self._host_target(next(host_items), downsample_factor) + (None,)
-        if self.weighted:
+        if self.weighted or self.composite_targets:
             return store.target(view, downsample_factor, with_weight=True)
         return store.target(view, downsample_factor) + (None,)
+
+    def _over_background(self, coef, image_gt, alpha_gt, q_pointcloud_camera, camera_info):
+        """-> (the target, the loss's pixel weight): with composite_targets the RGBA picture over the background `coef` in one
+        launch (composite_straight's), read from the store's buffer where it lies; the alpha stays the weight only if the loss
+        has one"""
+        if self.composite_targets:
+            with torch.no_grad():
+                image_gt = _background.composite_forward(image_gt, alpha_gt, coef.detach(), self.background_model.bands, q_pointcloud_camera,
+                                                         camera_info.camera_intrinsics, straight=True)
+        return image_gt, (alpha_gt if self.weighted else None)
+
+    def _render_over_background(self, rasterisation_input, coef, **forward):
+        """-> (image (3,h,w) composited over `coef`, depth, count): the full forward with its accumulated alpha, then one
+        composite node"""
+        image_pred, image_depth, pixel_valid_point_count, alpha = self.rasterisation(rasterisation_input, return_accumulated_alpha=True, **forward)
+        image_pred = _background.composite(image_pred.permute(2, 0, 1), alpha, coef, self.background_model.bands,
+                                           rasterisation_input.q_pointcloud_camera, rasterisation_input.camera_info.camera_intrinsics)
+        return image_pred, image_depth, pixel_valid_point_count
 
     def _validation_targets(self):
         """-> (image, q, t, CameraInfo, weight or None) of every validation view"""
@@ -458,9 +514,15 @@ class GaussianPointCloudTrainer:
             rasterisation_input =self._rasterisation_input(
                 camera_info, q_pointcloud_camera, t_pointcloud_camera,
                 color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval))
-            image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
-            # hxwx3->3xhxw, read where it lies; the clamp to [0, 1] runs inside the loss kernels
-            image_pred = image_pred.permute(2, 0, 1)
+            if self.background_model is not None:
+                # the step's background: behind the splats, and behind the RGBA target if that is composited
+                background_coef = self.background_model.coef_for_step()
+                image_gt, pixel_weight = self._over_background(background_coef, image_gt, pixel_weight, q_pointcloud_camera, camera_info)
+                image_pred, image_depth, pixel_valid_point_count = self._render_over_background(rasterisation_input, background_coef)
+            else:
+                image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
+                # hxwx3->3xhxw, read where it lies; the clamp to [0, 1] runs inside the loss kernels
+                image_pred = image_pred.permute(2, 0, 1)
             if self.appearance_table is not None:
                 # the view's colour transform, in the rasteriser's layout: the loss reads the corrected image where it lies
                 image_pred = _appearance.apply(image_pred, self.appearance_table.row(view))
@@ -490,6 +552,8 @@ class GaussianPointCloudTrainer:
             rows = self.rasterisation.last_touched_rows if config.sparse_adam else None
             optimizer.step(rows=rows)
             position_optimizer.step(rows=rows)
+            if self.background_model is not None:
+                self.background_model.step(iteration)           # "sky" alone moves
             if self.appearance_table is not None:
                 self.appearance_table.step(view, iteration)
             if self.bilateral_table is not None:
@@ -572,6 +636,9 @@ class GaussianPointCloudTrainer:
             count = 0
             total_terms, term_count = {term: 0.0 for term in self.terms}, {term: 0 for term in self.terms}
             for val_view, (image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight) in enumerate(self._validation_targets()):
+                if self.background_model is not None:
+                    image_gt, pixel_weight = self._over_background(self.background_model.coef, image_gt, pixel_weight, q_pointcloud_camera,
+                                                                   camera_info)
                 if pixel_weight is not None and not bool((pixel_weight > 0).any()):
                     continue
                 start_event = torch.cuda.Event(enable_timing=True)
@@ -579,11 +646,16 @@ class GaussianPointCloudTrainer:
                 rasterisation_input = self._rasterisation_input(camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band=3)
                 self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
                 start_event.record()
-                image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input, keep_frame=self._keep_validation_frame)
+                if self.background_model is not None:
+                    image_pred, image_depth, pixel_valid_point_count = self._render_over_background(
+                        rasterisation_input, self.background_model.coef, keep_frame=self._keep_validation_frame)
+                else:
+                    image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input, keep_frame=self._keep_validation_frame)
                 end_event.record()
                 torch.cuda.synchronize()
                 sums["inference_time"] += start_event.elapsed_time(end_event)
-                image_pred = torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
+                # (composited: already 3xhxw)
+                image_pred = torch.clamp(image_pred, 0, 1) if self.background_model is not None else torch.clamp(image_pred, 0, 1).permute(2, 0, 1)
                 images = {"": image_pred}
                 if self._colour_corrected:
                     # a validation view has no trained transform: the best affine map onto its ground truth, then the same metrics
@@ -618,6 +690,8 @@ class GaussianPointCloudTrainer:
                 self.appearance_table.save(os.path.join(self.config.output_model_dir, f"appearance_{iteration}.pt"), self.train_image_paths())
             if self.bilateral_table is not None:
                 self.bilateral_table.save(os.path.join(self.config.output_model_dir, f"bilateral_{iteration}.pt"), self.train_image_paths())
+            if self.background_model is not None:
+                self.background_model.save(os.path.join(self.config.output_model_dir, f"background_{iteration}.pt"))
             if means["psnr"] > self.best_psnr_score:
                 self.best_psnr_score = means["psnr"]
                 self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
@@ -625,6 +699,8 @@ class GaussianPointCloudTrainer:
                     self.appearance_table.save(os.path.join(self.config.output_model_dir, "best_appearance.pt"), self.train_image_paths())
                 if self.bilateral_table is not None:
                     self.bilateral_table.save(os.path.join(self.config.output_model_dir, "best_bilateral.pt"), self.train_image_paths())
+                if self.background_model is not None:
+                    self.background_model.save(os.path.join(self.config.output_model_dir, "best_background.pt"))
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
             self.last_validation = (iteration, means)

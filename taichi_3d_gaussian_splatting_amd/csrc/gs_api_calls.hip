@@ -14,6 +14,7 @@
 #include "../../include/gs_fusion.h"
 #include "../../include/gs_mcmc.h"
 #include "../../include/gs_appearance.h"
+#include "../../include/gs_background.h"
 #include "../../include/gs_bilateral.h"
 #include "../../include/gs_vq.h"
 #include "../../include/gs_depth.h"
@@ -687,6 +688,51 @@ extern "C" int gs_appearance_moments(gs_ctx* c, const gs_loss_image* image, cons
     if (!moments || ((uintptr_t)moments & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_appearance_moments: moments must be 8-byte aligned and not NULL");
     return queued_call(c, stream_, "gs_appearance_moments", { NEED(c->appearance_ws, gs_appearance_ws_size(H, W)) }, [&](hipStream_t s) {
         gs_launch_appearance_moments(loss_image(image, 0), loss_image(target, 0), pixel_weight, H, W, moments, c->appearance_ws.p, s);
+    });
+}
+
+// ---- a background behind the splats (include/gs_background.h, k_background.hip) ---------------------------------------------
+static int background_check(const char* who, gs_ctx* c, const float* coef, int32_t bands, const float* q, const float* intrinsics, int32_t H,
+                            int32_t W)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who, "ctx is NULL");
+    if (!coef) return fail(GS_ERR_INVALID_ARGUMENT, who, "coef is NULL");
+    if (bands < 0 || bands > GS_BACKGROUND_MAX_BANDS) return fail(GS_ERR_INVALID_ARGUMENT, who, "bands must be 0 .. 3");
+    if (bands > 0 && (!q || !intrinsics)) return fail(GS_ERR_INVALID_ARGUMENT, who, "bands > 0 needs q and intrinsics");
+    return image_size_check(who, H, W, GS_BACKGROUND_MAX_PIXELS);
+}
+
+extern "C" int gs_background_composite(gs_ctx* c, const gs_loss_image* image, const float* alpha, const float* coef, int32_t bands,
+                                       const float* q, const float* intrinsics, int32_t H, int32_t W, int32_t flags,
+                                       const gs_loss_image* out, gs_stream stream_)
+{
+    if (const int rc = background_check("gs_background_composite", c, coef, bands, q, intrinsics, H, W)) return rc;
+    if ((flags & ~(GS_BACKGROUND_STRAIGHT | GS_BACKGROUND_COLOURS_ONLY)) != 0 || flags == (GS_BACKGROUND_STRAIGHT | GS_BACKGROUND_COLOURS_ONLY))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_composite: flags must be 0, GS_BACKGROUND_STRAIGHT or GS_BACKGROUND_COLOURS_ONLY");
+    const bool colours_only = (flags & GS_BACKGROUND_COLOURS_ONLY) != 0;
+    if (!colours_only && (!image || !image->data)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_composite: NULL image");
+    if (!colours_only && !alpha) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_composite: alpha is NULL");
+    if (!out || !out->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_composite: NULL out image");
+    return queued_call(c, stream_, "gs_background_composite", {}, [&](hipStream_t s) {
+        const GsLossImage none{ nullptr, 0, 0, 0, 0 };
+        gs_launch_background_composite(colours_only ? none : loss_image(image, 0), colours_only ? nullptr : alpha, coef, bands, q, intrinsics, H, W,
+                                       flags, loss_image(out, 0), s);
+    });
+}
+
+extern "C" int gs_background_backward(gs_ctx* c, const gs_loss_image* grad_out, const float* alpha, const float* coef, int32_t bands,
+                                      const float* q, const float* intrinsics, int32_t H, int32_t W, float* grad_alpha, float* grad_coef,
+                                      gs_stream stream_)
+{
+    if (const int rc = background_check("gs_background_backward", c, coef, bands, q, intrinsics, H, W)) return rc;
+    if (!grad_out || !grad_out->data) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_backward: NULL grad_out");
+    if (!alpha) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_backward: alpha is NULL");
+    if (!grad_alpha && !grad_coef) return fail(GS_ERR_INVALID_ARGUMENT, "gs_background_backward: grad_alpha and grad_coef are both NULL");
+    // (the block sums only when the coefficients' gradient is wanted)
+    return queued_call(c, stream_, "gs_background_backward", { NEED(c->background_ws, grad_coef ? gs_background_ws_size(H, W) : 0) },
+                       [&](hipStream_t s) {
+        gs_launch_background_backward(loss_image(grad_out, 0), alpha, coef, bands, q, intrinsics, H, W, grad_alpha, grad_coef,
+                                      c->background_ws.p, s);
     });
 }
 

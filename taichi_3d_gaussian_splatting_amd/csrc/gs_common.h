@@ -687,6 +687,14 @@ void gs_launch_appearance_backward(const GsLossImage& X, const GsLossImage& G, c
                                    float* grad_transform, void* ws, hipStream_t s);
 void gs_launch_appearance_moments(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, double* moments, void* ws,
                                   hipStream_t s);
+// k_background.hip (include/gs_background.h): a colour or a spherical-harmonics sky behind an image.  The launchers trust what
+// the entry points checked.  ws: gs_background_ws_size(H, W) bytes of the context's (the per-block sums), unused when grad_coef
+// is NULL.  X.p NULL: colours only.
+size_t gs_background_ws_size(int H, int W);
+void gs_launch_background_composite(const GsLossImage& X, const float* alpha, const float* coef, int bands, const float* q, const float* Km,
+                                    int H, int W, int flags, const GsLossImage& O, hipStream_t s);
+void gs_launch_background_backward(const GsLossImage& G, const float* alpha, const float* coef, int bands, const float* q, const float* Km,
+                                   int H, int W, float* grad_alpha, float* grad_coef, void* ws, hipStream_t s);
 // k_bilateral.hip (include/gs_bilateral.h): the bilateral grid of colour transforms of an image.  The launchers trust what the
 // entry points checked.  ws: gs_bilateral_ws_size(Gx, Gy, L) bytes of the context's (the block sums of a split footprint; 0
 // where no footprint is split).  GI.p NULL: no image gradient; grad_grid NULL: no gather.
