@@ -27,6 +27,8 @@ the blend is at least --normals_min_length (default 0.5) long and (0,0,0) elsewh
 --background black|white|R,G,B|FILE composites every frame over a solid colour or over the background a trainer run with
 --background saved (a background_<iteration>.pt) before it is converted to 8 bits; this renders with the depth rasteriser
 for the accumulated alpha, which is slower than the default rgb_only path.
+--filter3d FILE renders the scene under the 3D smoothing filter a trainer run with --filter3d saved beside it (a
+filter3d_<iteration>.pt or best_filter3d.pt; one scene only), as wide as for a frame at --filter3d_factor (default 1).
 """
 import argparse
 import json
@@ -69,6 +71,8 @@ if __name__ == "__main__":
     parser.add_argument("--normals_min_length", type=float, default=0.5, help="with --normals_source gaussians: a pixel whose blended normal "
                         "is shorter than this is written as (0,0,0)")
     parser.add_argument("--background", type=str, default="", help="black, white, R,G,B in [0, 1], or a background_<iteration>.pt of the trainer")
+    parser.add_argument("--filter3d", type=str, default="", help="a filter3d_<iteration>.pt of the trainer: the scene is rendered under it")
+    parser.add_argument("--filter3d_factor", type=float, default=1.0, help="with --filter3d: the downsample factor whose filter is applied")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
     if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to or args.normals_to)):
@@ -104,7 +108,7 @@ if __name__ == "__main__":
     if args.camera_intrinsics is not None:
         fx, fy, cx, cy = args.camera_intrinsics
         config.camera_intrinsics = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
-    renderer = GaussianPointRenderer(config, frame_format=args.format)
+    renderer = GaussianPointRenderer(config, frame_format=args.format, filter3d=args.filter3d or None, filter3d_factor=args.filter3d_factor)
     if args.placements:
         with open(args.placements) as fh:
             for k, placement in enumerate(json.load(fh)):

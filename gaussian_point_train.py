@@ -13,7 +13,9 @@ rendered depth, and --normal_prior W [--normal_convention opencv|opengl] a norma
 with the normal of the rendered depth, which needs no data (INTEGRATION.md "Normal consistency");
 --background colour|random|sky [--background_colour R G B --background_bands B --background_lr LR --composite_targets] puts a
 solid colour, a random colour per step or a learnable spherical-harmonics sky behind the splats, and composites RGBA pictures
-over the same background (INTEGRATION.md "Backgrounds")."""
+over the same background (INTEGRATION.md "Backgrounds");
+--filter3d [--filter3d_variance V --filter3d_interval N] trains under the 3D smoothing filter of Mip-Splatting and writes
+filter3d_<iteration>.pt beside every scene file (INTEGRATION.md "3D smoothing filter")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -67,7 +69,14 @@ if __name__ == "__main__":
                         "iteration 0 (it falls to a tenth of it over the run)")
     parser.add_argument("--composite_targets", action="store_true", default=False,
                         help="with --background: composite the RGBA pictures over the step's background")
+    parser.add_argument("--filter3d", action="store_true", default=False, help="train under the 3D smoothing filter of Mip-Splatting")
+    parser.add_argument("--filter3d_variance", type=float, default=None, metavar="V", help="with --filter3d: the filter's variance in "
+                        "square pixels (default 0.2)")
+    parser.add_argument("--filter3d_interval", type=int, default=None, metavar="N", help="with --filter3d: iterations between two "
+                        "refreshes of the sampling rates (default 100)")
     args = parser.parse_args()
+    if not args.filter3d and (args.filter3d_variance is not None or args.filter3d_interval is not None):
+        parser.error("--filter3d_variance and --filter3d_interval need --filter3d")
     if args.background == "none" and (args.background_colour is not None or args.background_bands is not None or
                                       args.background_lr is not None or args.composite_targets):
         parser.error("--background_colour, --background_bands, --background_lr and --composite_targets need --background")
@@ -137,8 +146,14 @@ if __name__ == "__main__":
             background_config.bands = args.background_bands
         if args.background_lr is not None:
             background_config.lr, background_config.lr_final = args.background_lr, args.background_lr / 10.0
+    filter3d_config = None
+    if args.filter3d:
+        from taichi_3d_gaussian_splatting_amd.filter3d import Filter3DConfig
+        chosen = dict(variance=args.filter3d_variance, interval=args.filter3d_interval)
+        filter3d_config = Filter3DConfig(**{name: value for name, value in chosen.items() if value is not None})
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
                                         mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,
                                         geometry=geometry_config, bilateral_grid=bilateral_config, background=args.background,
-                                        background_config=background_config, composite_targets=args.composite_targets)
+                                        background_config=background_config, composite_targets=args.composite_targets,
+                                        filter3d=filter3d_config)
     trainer.train()

@@ -19,6 +19,11 @@ multiples of 16, near_plane=0.8, far_plane=1000., depth_to_sort_key_scale=100. a
   - render(background=...) and run(background=...) composite every frame over a background.BackgroundModel (a solid colour,
     or the sky a trainer saved) before it is converted to 8 bits.  This takes the depth rasteriser for the accumulated alpha,
     which is slower than the rgb_only path.  The sky's frame is that of the composition's first scene;
+  - GaussianPointRenderer(config, filter3d=FILE or a filter3d.Filter3D) renders the scene under the 3D smoothing filter a
+    trainer saved beside it (filter3d_<iteration>.pt): the features the rasteriser is given are the filtered ones for a frame
+    at factor filter3d_factor (1: the filter of a run's last, full-resolution iterations; the factor a run was trained at:
+    that run's own filter, for frames finer than it ever saw), made once.  A single scene only; None, the default, is the loop
+    as it was;
   - fuse() renders the poses with depth and accumulated alpha and integrates them into a fusion.TSDFVolume on the device, from
     which a triangle mesh is extracted (fusion.py).
 """
@@ -59,7 +64,8 @@ class GaussianPointRenderer:
 
     ExtraSceneInfo = SceneComposition.ExtraSceneInfo
 
-    def __init__(self, config: "GaussianPointRenderer.GaussianPointRendererConfig", frame_format: str = "png", slots: int = 4) -> None:
+    def __init__(self, config: "GaussianPointRenderer.GaussianPointRendererConfig", frame_format: str = "png", slots: int = 4,
+                 filter3d=None, filter3d_factor=1) -> None:
         self.config = config
         self.config.image_height = self.config.image_height - self.config.image_height % 16
         self.config.image_width = self.config.image_width - self.config.image_width % 16
@@ -81,6 +87,15 @@ class GaussianPointRenderer:
         self._rasteriser_with_depth = None
         self.frame_format, self.slots = frame_format, slots
         self.loss_function = LossFunction(LossFunction.LossFunctionConfig(enable_regularization=False))
+        self.filter3d = None
+        self._filtered = None
+        if filter3d is not None:
+            from .filter3d import Filter3D
+            if len(paths) != 1:
+                raise ValueError("filter3d needs a single scene: a saved table belongs to the rows of one scene file")
+            self.filter3d = Filter3D.load(str(filter3d), self.scene) if isinstance(filter3d, (str, bytes, os.PathLike)) else filter3d
+            with torch.no_grad():           # the scene does not change between frames: filtered once
+                self._filtered = self.filter3d.features(filter3d_factor).detach()
 
     def _with_depth(self):
         if self._rasteriser_with_depth is None:
@@ -109,7 +124,7 @@ class GaussianPointRenderer:
         with torch.no_grad():
             outputs = (self._with_depth() if depth or alpha else self.rasteriser)(Rast.GaussianPointCloudRasterisationInput(
                 point_cloud=self.scene.point_cloud,
-                point_cloud_features=self.scene.point_cloud_features,
+                point_cloud_features=self.scene.point_cloud_features if self._filtered is None else self._filtered,
                 point_invalid_mask=self.scene.point_invalid_mask,
                 point_object_id=self.scene.point_object_id,
                 camera_info=self.camera_info if camera_info is None else camera_info,

@@ -45,6 +45,13 @@ What differs from the reference
     picture).  composite_targets=True composites the RGBA training pictures over the step's colour too, so the transparent
     pixels tell the scene to be empty; "random" needs it.  "sky" takes its Adam step beside the scene's.  Validation composites
     with the model's stored background (config.colour for "random").  "none", the default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, filter3d=Filter3DConfig(...)) trains under the 3D smoothing filter of Mip-Splatting
+    (filter3d.py): every Gaussian carries the largest sampling rate any training view had of it, and the rasteriser is given
+    the scene's features under the matching low-pass, at the step's downsample factor in training and at factor 1 in
+    validation.  The rates are recomputed at iteration 0, every filter3d.interval iterations and after every refinement that
+    changed rows.  The loss's regulariser, the controller, the fixed-budget strategy and FusedAdam keep reading the raw
+    parameters.  filter3d_<iteration>.pt and best_filter3d.pt are written beside the scene files, which stay raw.  None, the
+    default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -73,6 +80,8 @@ from .background import BackgroundConfig, BackgroundModel
 from . import bilateral as _bilateral
 from .bilateral import BilateralGridConfig, BilateralGridTable
 from . import depth as _depth
+from . import filter3d as _filter3d
+from .filter3d import Filter3D, Filter3DConfig
 from .depth import DepthConfig
 from . import geometry as _geometry
 from . import _terms
@@ -244,7 +253,8 @@ class GaussianPointCloudTrainer:
                  density: str = "adaptive", mcmc_config: Optional[MCMCConfig] = None, appearance: str = "none",
                  appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None,
                  geometry: Optional[GeometryConfig] = None, bilateral_grid: Optional[BilateralGridConfig] = None,
-                 background: str = "none", background_config: Optional[BackgroundConfig] = None, composite_targets: bool = False):
+                 background: str = "none", background_config: Optional[BackgroundConfig] = None, composite_targets: bool = False,
+                 filter3d: Optional[Filter3DConfig] = None):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -261,8 +271,12 @@ class GaussianPointCloudTrainer:
         splats -- "none", "colour" (background_config.colour), "random" (a colour drawn per step) or "sky" (learnable spherical
         harmonics of the view direction; background.BackgroundModel, in self.background_model) -- its BackgroundConfig (None: the
         defaults, black, its schedule over config.num_iterations), and composite_targets: whether the RGBA training and
-        validation pictures are composited over the same background"""
+        validation pictures are composited over the same background; filter3d: the Filter3DConfig of the 3D smoothing filter
+        (filter3d.Filter3D over the training views, in self.filter3d; None: none; its near plane is the rasteriser's unless it
+        names its own)"""
         self.config = config
+        if filter3d is not None:
+            filter3d.check()
         if background not in ("none",) + _background.KINDS:
             raise ValueError(f'background must be "none", "colour", "random" or "sky", got {background!r}')
         if background == "none" and (background_config is not None or composite_targets):
@@ -339,6 +353,13 @@ class GaussianPointCloudTrainer:
                 backward_valid_point_hook=self.adaptive_controller.update,
             )
         self.rasterisation.track_touched_rows = bool(self.config.sparse_adam)
+        self.filter3d = None
+        if filter3d is not None:
+            if filter3d.near is None:
+                filter3d = dataclasses.replace(filter3d, near=float(self.config.rasterisation_config.near_plane))
+            # one table of the training cameras at factor 1; the rates are taken now, so a validation before train() has them
+            self.filter3d = Filter3D(filter3d, self.scene, _filter3d.view_table(self.train_dataset, device=self.device))
+        self._filter3d_refinements = 0          # the refinements the filter's rates have seen
         self.loss_function = LossFunction(config=self.config.loss_function_config)
         self.best_psnr_score = 0.
 
@@ -472,10 +493,12 @@ class GaussianPointCloudTrainer:
         the bilateral table belong to"""
         return [str(p) for p in self.train_dataset.df["image_path"].tolist()]
 
-    def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band):
+    def _rasterisation_input(self, camera_info, q_pointcloud_camera, t_pointcloud_camera, color_max_sh_band, downsample_factor=1):
+        """the scene under the camera; with a 3D filter the features are the filtered ones for a frame at downsample_factor"""
+        features = self.scene.point_cloud_features if self.filter3d is None else self.filter3d.features(downsample_factor)
         return GaussianPointCloudRasterisation.GaussianPointCloudRasterisationInput(
             point_cloud=self.scene.point_cloud,
-            point_cloud_features=self.scene.point_cloud_features,
+            point_cloud_features=features,
             point_object_id=self.scene.point_object_id,
             point_invalid_mask=self.scene.point_invalid_mask,
             camera_info=camera_info,
@@ -483,6 +506,21 @@ class GaussianPointCloudTrainer:
             t_pointcloud_camera=t_pointcloud_camera,
             color_max_sh_band=color_max_sh_band,
         )
+
+    def _refinements(self) -> int:
+        """the refinements that have changed rows so far, by whichever strategy runs"""
+        strategy = self.mcmc if self.mcmc is not None else self.adaptive_controller
+        return 0 if strategy is None else int(strategy.refinement_calls)
+
+    def _refresh_filter3d(self, iteration: Optional[int] = None):
+        """the filter's rates again: at a multiple of its interval (iteration given), or when a refinement has changed rows
+        since they were taken -- new rows have no rate otherwise"""
+        if self.filter3d is None:
+            return
+        due = iteration is not None and iteration % self.filter3d.config.interval == 0
+        if due or self._refinements() != self._filter3d_refinements:
+            self.filter3d.refresh()
+            self._filter3d_refinements = self._refinements()
 
     # ---- the loop ---------------------------------------------------------------------------------------------------------
     def train(self):
@@ -506,6 +544,7 @@ class GaussianPointCloudTrainer:
                 downsample_factor = downsample_factor // 2
             optimizer.zero_grad()
             position_optimizer.zero_grad()
+            self._refresh_filter3d(iteration)
 
             view = self._view_at(iteration)
             image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self._target(
@@ -513,7 +552,8 @@ class GaussianPointCloudTrainer:
             self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
             rasterisation_input =self._rasterisation_input(
                 camera_info, q_pointcloud_camera, t_pointcloud_camera,
-                color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval))
+                color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval),
+                downsample_factor=downsample_factor)
             if self.background_model is not None:
                 # the step's background: behind the splats, and behind the RGBA target if that is composited
                 background_coef = self.background_model.coef_for_step()
@@ -565,6 +605,7 @@ class GaussianPointCloudTrainer:
                 position_optimizer.lr *= config.position_learning_rate_decay_rate
             if self.adaptive_controller is not None:
                 self.adaptive_controller.refinement()
+            self._refresh_filter3d()            # a refinement of this iteration: its new rows get their rates now
 
             # (the reference reads loss.item() every iteration to pick "problematic" images for its image log; there is no
             # image log here, so the loss is read -- and the host waits for the device -- only where it is logged)
@@ -692,6 +733,8 @@ class GaussianPointCloudTrainer:
                 self.bilateral_table.save(os.path.join(self.config.output_model_dir, f"bilateral_{iteration}.pt"), self.train_image_paths())
             if self.background_model is not None:
                 self.background_model.save(os.path.join(self.config.output_model_dir, f"background_{iteration}.pt"))
+            if self.filter3d is not None:
+                self.filter3d.save(os.path.join(self.config.output_model_dir, f"filter3d_{iteration}.pt"))
             if means["psnr"] > self.best_psnr_score:
                 self.best_psnr_score = means["psnr"]
                 self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
@@ -701,6 +744,8 @@ class GaussianPointCloudTrainer:
                     self.bilateral_table.save(os.path.join(self.config.output_model_dir, "best_bilateral.pt"), self.train_image_paths())
                 if self.background_model is not None:
                     self.background_model.save(os.path.join(self.config.output_model_dir, "best_background.pt"))
+                if self.filter3d is not None:
+                    self.filter3d.save(os.path.join(self.config.output_model_dir, "best_filter3d.pt"))
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
             self.last_validation = (iteration, means)

@@ -118,7 +118,7 @@ extern "C" int gs_destroy(gs_ctx* c)
                       &c->ch_partial, &c->ch_flags, &c->row_block_totals, &c->merge_tags, &c->merge_ids,
                       &c->knn_sort, &c->knn_hist, &c->knn_points, &c->knn_tree, &c->mix_records, &c->mix_sums, &c->mix_partial,
                       &c->mixg_queries, &c->mixg_partial, &c->mixg_sums, &c->mixg_x_partial, &c->mcmc_ws, &c->appearance_ws, &c->bilateral_ws, &c->depth_ws,
-                      &c->geometry_ws, &c->background_ws };
+                      &c->geometry_ws, &c->background_ws, &c->filter3d_ws };
     for (DevBuf* b : all) b->release(&c->device_bytes);
     for (ResampleTable* rt : c->resample_tables) { rt->buf.release(&c->device_bytes); delete rt; }
     for (GsProf::Rec& r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

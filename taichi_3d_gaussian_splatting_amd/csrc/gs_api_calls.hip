@@ -16,6 +16,7 @@
 #include "../../include/gs_appearance.h"
 #include "../../include/gs_background.h"
 #include "../../include/gs_bilateral.h"
+#include "../../include/gs_filter3d.h"
 #include "../../include/gs_vq.h"
 #include "../../include/gs_depth.h"
 #include "../../include/gs_geometry.h"
@@ -736,7 +737,66 @@ extern "C" int gs_background_backward(gs_ctx* c, const gs_loss_image* grad_out, 
     });
 }
 
-// ---- per-view bilateral grids (include/gs_bilateral.h, k_bilateral.hip) -----------------------------------------------------
+// ---- the 3D smoothing filter (include/gs_filter3d.h, k_filter3d.hip) ------------------------------------------------------------
+static int filter3d_rows_check(const char* who, gs_ctx* c, int64_t n)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who, "ctx is NULL");
+    if (n < 0 || n > (int64_t)GS_FILTER3D_MAX_POINTS) return fail(GS_ERR_INVALID_ARGUMENT, who, "n_points must be in [0, 2^30]");
+    return GS_OK;
+}
+
+static int filter3d_k_check(const char* who, float k)
+{
+    if (!std::isfinite(k) || k < 0.0f) return fail(GS_ERR_INVALID_ARGUMENT, who, "k must be finite and >= 0");
+    return GS_OK;
+}
+
+extern "C" int gs_filter3d_rate(gs_ctx* c, const float* point_cloud, const int8_t* mask, int64_t n, const float* views, int32_t n_views,
+                                int32_t W, int32_t H, float near, float margin, float* rate_out, gs_stream stream_)
+{
+    if (const int rc = filter3d_rows_check("gs_filter3d_rate", c, n)) return rc;
+    if (n_views < 0 || n_views > GS_FILTER3D_MAX_VIEWS) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_rate: n_views must be in [0, 2^20]");
+    if (W < 1 || H < 1) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_rate: W and H must be >= 1");
+    if (!std::isfinite(near) || !(near > 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_rate: near must be finite and > 0");
+    if (!std::isfinite(margin) || margin < 0.0f) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_rate: margin must be finite and >= 0");
+    if (n == 0) return GS_OK;
+    if (!point_cloud || !mask || !rate_out || (n_views > 0 && !views)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_rate: NULL array");
+    return queued_call(c, stream_, "gs_filter3d_rate", { NEED(c->filter3d_ws, gs_filter3d_ws_size()) }, [&](hipStream_t s) {
+        gs_launch_filter3d_rate(point_cloud, mask, n, views, n_views, W, H, near, margin, rate_out, c->filter3d_ws.p, s);
+    });
+}
+
+extern "C" int gs_filter3d_apply(gs_ctx* c, float* features, const float* rate, int64_t n, float k, float* features_out, gs_stream stream_)
+{
+    if (const int rc = filter3d_rows_check("gs_filter3d_apply", c, n)) return rc;
+    if (const int rc = filter3d_k_check("gs_filter3d_apply", k)) return rc;
+    if (n == 0) return GS_OK;
+    if (!features || !rate || !features_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply: NULL array");
+    if ((((uintptr_t)features | (uintptr_t)features_out) & 15u) != 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply: features and features_out must be 16-byte aligned");
+    const size_t bytes = (size_t)n * GS_FILTER3D_FEATURES * sizeof(float);
+    if (ranges_overlap(features, bytes, features_out, bytes))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply: features_out overlaps features (the call runs out of place)");
+    return queued_call(c, stream_, "gs_filter3d_apply", {}, [&](hipStream_t s) { gs_launch_filter3d_apply(features, rate, n, k, features_out, s); });
+}
+
+extern "C" int gs_filter3d_apply_backward(gs_ctx* c, const float* grad_out, const float* features, const float* rate, int64_t n, float k,
+                                          float* grad_in, gs_stream stream_)
+{
+    if (const int rc = filter3d_rows_check("gs_filter3d_apply_backward", c, n)) return rc;
+    if (const int rc = filter3d_k_check("gs_filter3d_apply_backward", k)) return rc;
+    if (n == 0) return GS_OK;
+    if (!grad_out || !features || !rate || !grad_in) return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply_backward: NULL array");
+    if ((((uintptr_t)grad_out | (uintptr_t)features | (uintptr_t)grad_in) & 15u) != 0)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply_backward: grad_out, features and grad_in must be 16-byte aligned");
+    const size_t bytes = (size_t)n * GS_FILTER3D_FEATURES * sizeof(float);
+    if ((grad_in != grad_out && ranges_overlap(grad_out, bytes, grad_in, bytes)) || ranges_overlap(features, bytes, grad_in, bytes))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_filter3d_apply_backward: grad_in overlaps grad_out (other than being it) or features");
+    return queued_call(c, stream_, "gs_filter3d_apply_backward", {},
+                       [&](hipStream_t s) { gs_launch_filter3d_backward(grad_out, features, rate, n, k, grad_in, s); });
+}
+
+// ---- per-view bilateral grids (include/gs_bilateral.h, k_bilateral.hip)-----------------------------------------------------
 static int bilateral_grid_check(const char* who, gs_ctx* c, const float* grid, int32_t Gx, int32_t Gy, int32_t L)
 {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who, "ctx is NULL");

@@ -703,6 +703,14 @@ void gs_launch_bilateral_slice(const GsLossImage& X, const float* grid, int Gx, 
 void gs_launch_bilateral_backward(const GsLossImage& X, const GsLossImage& G, const float* grid, int Gx, int Gy, int L, int H, int W,
                                   const GsLossImage& GI, float* grad_grid, void* ws, hipStream_t s);
 void gs_launch_bilateral_tv(const float* grid, int Gx, int Gy, int L, float weight, float* grad_grid, float* value, hipStream_t s);
+// k_filter3d.hip (include/gs_filter3d.h): the 3D smoothing filter.  The launchers trust what the entry points checked; n > 0.
+// ws: gs_filter3d_ws_size() bytes of the context's (the bits of the smallest seen rate).  grad_in == grad_out: in place.
+size_t gs_filter3d_ws_size();
+void gs_launch_filter3d_rate(const float* point_cloud, const int8_t* mask, int64_t n, const float* views, int n_views, int W, int H, float near,
+                             float margin, float* rate, void* ws, hipStream_t s);
+void gs_launch_filter3d_apply(float* features, const float* rate, int64_t n, float k, float* features_out, hipStream_t s);
+void gs_launch_filter3d_backward(const float* grad_out, const float* features, const float* rate, int64_t n, float k, float* grad_in,
+                                 hipStream_t s);
 // k_depth.hip (include/gs_depth.h): the depth target with its weight plane, and the depth loss.  The launchers trust what the
 // entry points checked.  ws: gs_depth_ws_size(H, W) bytes of the context's, 8-byte aligned (finished moments, per-block sums).
 void gs_launch_depth_resample(const void* src, int src_format, int H_in, int W_in, int64_t pitch_bytes, float depth_scale, GsResampleAxis ax,

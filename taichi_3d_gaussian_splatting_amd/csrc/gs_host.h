@@ -90,6 +90,7 @@ struct gs_ctx {
     DevBuf mcmc_ws;                     // gs_mcmc_regulariser: its per-block sums and totals, read by nothing else
     DevBuf appearance_ws;               // gs_appearance_backward / _moments: their per-block sums, read by nothing else
     DevBuf background_ws;               // gs_background_backward: its per-block sums, read by nothing else
+    DevBuf filter3d_ws;                 // gs_filter3d_rate: the bits of the smallest seen rate, read by nothing else
     DevBuf bilateral_ws;                // gs_bilateral_slice_backward: the block sums of split footprints, read by nothing else
     DevBuf depth_ws;                    // gs_depth_loss_forward: its finished moments and per-block sums, read by nothing else
     DevBuf geometry_ws;                 // gs_normal_loss_forward / gs_depth_smooth_forward: their per-tile sums, read by nothing else
