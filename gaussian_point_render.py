@@ -29,6 +29,8 @@ the blend is at least --normals_min_length (default 0.5) long and (0,0,0) elsewh
 for the accumulated alpha, which is slower than the default rgb_only path.
 --filter3d FILE renders the scene under the 3D smoothing filter a trainer run with --filter3d saved beside it (a
 filter3d_<iteration>.pt or best_filter3d.pt; one scene only), as wide as for a frame at --filter3d_factor (default 1).
+--pose_table FILE (a poses_<iteration>.pt of a trainer run with --pose_refinement) with a dataset JSON as --poses: a view whose
+image_path is in the file is rendered under its corrected pose, every other view as without the flag.
 """
 import argparse
 import json
@@ -73,8 +75,11 @@ if __name__ == "__main__":
     parser.add_argument("--background", type=str, default="", help="black, white, R,G,B in [0, 1], or a background_<iteration>.pt of the trainer")
     parser.add_argument("--filter3d", type=str, default="", help="a filter3d_<iteration>.pt of the trainer: the scene is rendered under it")
     parser.add_argument("--filter3d_factor", type=float, default=1.0, help="with --filter3d: the downsample factor whose filter is applied")
+    parser.add_argument("--pose_table", type=str, default="", help="a poses_<iteration>.pt of the trainer: per-view pose corrections")
     parser.add_argument("--device", type=str, default="cuda")
     args = parser.parse_args()
+    if args.pose_table and not (args.poses or "").endswith(".json"):
+        parser.error("--pose_table corrects the views of a dataset json given as --poses")
     if not args.bake_to and not (args.poses and (args.output_prefix or args.mesh_to or args.normals_to)):
         parser.error("--poses and --output_prefix (or --mesh_to, or --normals_to) are required unless --bake_to is given")
     if args.mesh_to and not (args.poses or "").endswith(".pt"):
@@ -96,6 +101,18 @@ if __name__ == "__main__":
         targets = TargetStore.from_dataset(dataset, device=args.device)
         image_paths = [str(p) for p in dataset.df["image_path"].tolist()]
         cameras = torch.eye(4).unsqueeze(0)             # the views carry their own poses and cameras
+        if args.pose_table:
+            # the views of the file under their corrected poses: one launch over all views, in which a view that is not in the
+            # file has a correction of zeros and keeps its pose bit for bit
+            from taichi_3d_gaussian_splatting_amd import pose_table
+            table, table_paths = pose_table.PoseTable.load(args.pose_table, device=args.device)
+            rows = table.by_image_path(table_paths)
+            delta = torch.zeros(len(image_paths), pose_table.DELTA_FLOATS, dtype=torch.float32, device=table.device)
+            for view, path in enumerate(image_paths):
+                if path in rows:
+                    delta[view] = rows[path]
+            q, t = pose_table.compose_forward(targets.q.unsqueeze(1).contiguous(), targets.t.unsqueeze(1).contiguous(), delta)
+            targets.q, targets.t = q[:, 0].contiguous(), t[:, 0].contiguous()
     else:
         raise ValueError(f"Unrecognized poses file format: {args.poses}, Must be .pt or .json file")
     config = GaussianPointRenderer.GaussianPointRendererConfig(parquet_path, cameras, device=args.device)

@@ -15,7 +15,9 @@ with the normal of the rendered depth, which needs no data (INTEGRATION.md "Norm
 solid colour, a random colour per step or a learnable spherical-harmonics sky behind the splats, and composites RGBA pictures
 over the same background (INTEGRATION.md "Backgrounds");
 --filter3d [--filter3d_variance V --filter3d_interval N] trains under the 3D smoothing filter of Mip-Splatting and writes
-filter3d_<iteration>.pt beside every scene file (INTEGRATION.md "3D smoothing filter")."""
+filter3d_<iteration>.pt beside every scene file (INTEGRATION.md "3D smoothing filter");
+--pose_refinement [--pose_lr LR --pose_lr_final LR --pose_reg W --pose_start N --val_pose_steps N] trains a pose correction per
+training image with the scene and writes poses_<iteration>.pt beside every scene file (INTEGRATION.md "Pose refinement")."""
 import argparse
 
 from taichi_3d_gaussian_splatting_amd.GaussianPointTrainer import GaussianPointCloudTrainer
@@ -74,7 +76,19 @@ if __name__ == "__main__":
                         "square pixels (default 0.2)")
     parser.add_argument("--filter3d_interval", type=int, default=None, metavar="N", help="with --filter3d: iterations between two "
                         "refreshes of the sampling rates (default 100)")
+    parser.add_argument("--pose_refinement", action="store_true", default=False, help="train a camera pose correction per training image")
+    parser.add_argument("--pose_lr", type=float, default=None, metavar="LR", help="with --pose_refinement: the corrections' learning rate "
+                        "at its first iteration (default 1e-3)")
+    parser.add_argument("--pose_lr_final", type=float, default=None, metavar="LR", help="with --pose_refinement: their learning rate at the "
+                        "last iteration (default 1e-4)")
+    parser.add_argument("--pose_reg", type=float, default=None, metavar="W", help="with --pose_refinement: weight of the L2 pull to the "
+                        "dataset's pose (default 1e-6)")
+    parser.add_argument("--pose_start", type=int, default=None, metavar="N", help="with --pose_refinement: the first refined iteration")
+    parser.add_argument("--val_pose_steps", type=int, default=0, metavar="N", help="align every validation view against the frozen scene "
+                        "by N pose steps and log val/psnr_aligned, val/ssim_aligned and val/loss_aligned as well")
     args = parser.parse_args()
+    if not args.pose_refinement and any(v is not None for v in (args.pose_lr, args.pose_lr_final, args.pose_reg, args.pose_start)):
+        parser.error("--pose_lr, --pose_lr_final, --pose_reg and --pose_start need --pose_refinement")
     if not args.filter3d and (args.filter3d_variance is not None or args.filter3d_interval is not None):
         parser.error("--filter3d_variance and --filter3d_interval need --filter3d")
     if args.background == "none" and (args.background_colour is not None or args.background_bands is not None or
@@ -151,9 +165,14 @@ if __name__ == "__main__":
         from taichi_3d_gaussian_splatting_amd.filter3d import Filter3DConfig
         chosen = dict(variance=args.filter3d_variance, interval=args.filter3d_interval)
         filter3d_config = Filter3DConfig(**{name: value for name, value in chosen.items() if value is not None})
+    pose_config = None
+    if args.pose_refinement:
+        from taichi_3d_gaussian_splatting_amd.pose_table import PoseRefinementConfig
+        chosen = dict(lr=args.pose_lr, lr_final=args.pose_lr_final, reg=args.pose_reg, start_iteration=args.pose_start)
+        pose_config = PoseRefinementConfig(**{name: value for name, value in chosen.items() if value is not None})
     trainer = GaussianPointCloudTrainer(config, pixel_weights=args.pixel_weights, mask_erode=args.mask_erode, density=args.density,
                                         mcmc_config=mcmc_config, appearance=args.appearance, depth=args.depth, depth_config=depth_config,
                                         geometry=geometry_config, bilateral_grid=bilateral_config, background=args.background,
                                         background_config=background_config, composite_targets=args.composite_targets,
-                                        filter3d=filter3d_config)
+                                        filter3d=filter3d_config, pose_refinement=pose_config, validation_pose_steps=args.val_pose_steps)
     trainer.train()

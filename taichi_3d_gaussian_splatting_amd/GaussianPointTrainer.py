@@ -52,6 +52,14 @@ What differs from the reference
     changed rows.  The loss's regulariser, the controller, the fixed-budget strategy and FusedAdam keep reading the raw
     parameters.  filter3d_<iteration>.pt and best_filter3d.pt are written beside the scene files, which stay raw.  None, the
     default, is the loop as it was.
+  - GaussianPointCloudTrainer(config, pose_refinement=PoseRefinementConfig(...), validation_pose_steps=0) trains a pose
+    correction per training image with the scene (pose_table.py): six floats in the camera's own frame, composed on the right
+    of the dataset's pose in front of the rasteriser, trained from the rasteriser's pose gradients and stepped after the two
+    scene optimisers, from config.start_iteration on.  self.current_pose and the pose handed to the background are the composed
+    values, detached: the sky's gradient to the pose is not taken.  Validation views have no correction and render under the
+    dataset's poses; with validation_pose_steps > 0 each is additionally aligned against the frozen scene (refine_pose) and
+    measured again (val/psnr_aligned, val/ssim_aligned, val/loss_aligned).  poses_<iteration>.pt and best_poses.pt are written
+    beside the scene files.  None, the default, is the loop as it was.
   - TrainConfig.from_yaml_file needs no dataclass_wizard; keys it does not know are listed, not fatal.
   - Logging falls back to a JSON-lines writer when tensorboard is not installed; image grids, figures and histograms are not
     produced, and with them the reference's per-iteration loss.item() (it picks "problematic" images to log): the host waits
@@ -90,6 +98,8 @@ from .ImagePoseDataset import ImagePoseDataset, resize_antialias
 from .LossFunction import LossFunction
 from .mcmc import MCMCConfig, MCMCStrategy
 from .optim import FusedAdam
+from . import pose_table as _pose_table
+from .pose_table import PoseRefinementConfig, PoseTable
 from .targets import TargetStore, downsampled_geometry, downsampled_intrinsics
 
 
@@ -254,7 +264,8 @@ class GaussianPointCloudTrainer:
                  appearance_config: Optional[AppearanceConfig] = None, depth: str = "none", depth_config: Optional[DepthConfig] = None,
                  geometry: Optional[GeometryConfig] = None, bilateral_grid: Optional[BilateralGridConfig] = None,
                  background: str = "none", background_config: Optional[BackgroundConfig] = None, composite_targets: bool = False,
-                 filter3d: Optional[Filter3DConfig] = None):
+                 filter3d: Optional[Filter3DConfig] = None, pose_refinement: Optional[PoseRefinementConfig] = None,
+                 validation_pose_steps: int = 0):
         """device, writer, pixel_weights, mask_erode, density, mcmc_config, appearance and appearance_config are extensions: the GPU to train on; a summary
         writer to use instead of the one make_summary_writer() picks (tensorboard's when it imports, JsonlSummaryWriter
         otherwise); where the per-pixel weights of the loss come from -- "none", "alpha" (the RGBA images' alpha) or "file" (the
@@ -273,8 +284,19 @@ class GaussianPointCloudTrainer:
         defaults, black, its schedule over config.num_iterations), and composite_targets: whether the RGBA training and
         validation pictures are composited over the same background; filter3d: the Filter3DConfig of the 3D smoothing filter
         (filter3d.Filter3D over the training views, in self.filter3d; None: none; its near plane is the rasteriser's unless it
-        names its own)"""
+        names its own); pose_refinement: the PoseRefinementConfig of a learnable pose correction per training view
+        (pose_table.PoseTable, in self.pose_table; None: none; its schedule runs over config.num_iterations unless it names its
+        own), and validation_pose_steps: with it > 0 every validation view is additionally aligned against the frozen scene by
+        that many steps of pose_table.refine_pose and measured again (val/psnr_aligned, val/ssim_aligned, val/loss_aligned)"""
         self.config = config
+        if pose_refinement is not None:
+            pose_refinement.check()
+        if int(validation_pose_steps) < 0:
+            raise ValueError("validation_pose_steps must be >= 0")
+        if validation_pose_steps and background != "none":
+            raise ValueError("validation_pose_steps cannot be combined with a background: the aligned render is the bare rasteriser's")
+        self.validation_pose_steps = int(validation_pose_steps)
+        self.pose_table = None
         if filter3d is not None:
             filter3d.check()
         if background not in ("none",) + _background.KINDS:
@@ -395,6 +417,13 @@ class GaussianPointCloudTrainer:
             if bilateral_grid.num_iterations is None:
                 bilateral_grid = dataclasses.replace(bilateral_grid, num_iterations=max(int(self.config.num_iterations), 1))
             self.bilateral_table = BilateralGridTable(len(self.train_dataset), self.device, bilateral_grid)
+        if pose_refinement is not None:
+            if self.filter3d is not None and self.train_targets is None:
+                raise ValueError("pose_refinement with filter3d needs targets_on_device=True: the filter's views are made from the "
+                                 "store's poses")
+            if pose_refinement.num_iterations is None:
+                pose_refinement = dataclasses.replace(pose_refinement, num_iterations=max(int(self.config.num_iterations), 1))
+            self.pose_table = PoseTable(len(self.train_dataset), self.device, pose_refinement)
         # validation views have no trained correction: the colour-corrected metrics are reported whenever one is trained
         self._colour_corrected = self.appearance_table is not None or self.bilateral_table is not None
         if self.terms:
@@ -479,7 +508,7 @@ class GaussianPointCloudTrainer:
         composite node"""
         image_pred, image_depth, pixel_valid_point_count, alpha = self.rasterisation(rasterisation_input, return_accumulated_alpha=True, **forward)
         image_pred = _background.composite(image_pred.permute(2, 0, 1), alpha, coef, self.background_model.bands,
-                                           rasterisation_input.q_pointcloud_camera, rasterisation_input.camera_info.camera_intrinsics)
+                                           rasterisation_input.q_pointcloud_camera.detach(), rasterisation_input.camera_info.camera_intrinsics)
         return image_pred, image_depth, pixel_valid_point_count
 
     def _validation_targets(self):
@@ -519,8 +548,32 @@ class GaussianPointCloudTrainer:
             return
         due = iteration is not None and iteration % self.filter3d.config.interval == 0
         if due or self._refinements() != self._filter3d_refinements:
+            if self.pose_table is not None and any(self.pose_table.steps):
+                # (until a correction has taken a step the dataset's own table stands: its rows come from the float64 matrices)
+                self.filter3d.views = self._corrected_view_table()
             self.filter3d.refresh()
             self._filter3d_refinements = self._refinements()
+
+    def _corrected_view_table(self):
+        """the filter's view table under the training views' corrected poses (PoseTable.corrected: one launch), the intrinsics
+        those of the table it replaces.  The rows are made on the host in float64 like the first table's: one host read per
+        refresh of the rates."""
+        from .utils import quaternion_to_rotation_matrix_torch
+        old = self.filter3d.views
+        q, t = self.pose_table.corrected(self.train_targets.q, self.train_targets.t)
+        q, t = q.cpu().to(torch.float64), t.cpu().to(torch.float64)
+        T = torch.eye(4, dtype=torch.float64).repeat(q.shape[0], 1, 1)
+        T[:, :3, :3] = quaternion_to_rotation_matrix_torch(q / q.norm(dim=1, keepdim=True))
+        T[:, :3, 3] = t
+        K = torch.zeros(q.shape[0], 3, 3, dtype=torch.float64)
+        fx_fy_cx_cy = old[:, 12:16].cpu().to(torch.float64)
+        K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = fx_fy_cx_cy[:, 0], fx_fy_cx_cy[:, 1], fx_fy_cx_cy[:, 2], fx_fy_cx_cy[:, 3], 1.0
+        table = torch.from_numpy(_filter3d.view_rows(T.numpy(), K.numpy())).to(self.device)
+        table.width, table.height = getattr(old, "width", None), getattr(old, "height", None)
+        return table
+
+    def _refining_poses(self, iteration: int) -> bool:
+        return self.pose_table is not None and iteration >= self.pose_table.config.start_iteration
 
     # ---- the loop ---------------------------------------------------------------------------------------------------------
     def train(self):
@@ -549,7 +602,14 @@ class GaussianPointCloudTrainer:
             view = self._view_at(iteration)
             image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight = self._target(
                 self.train_targets, train_items, view, downsample_factor)
-            self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
+            if self._refining_poses(iteration):
+                # the view's correction on the right of the dataset's pose; its gradient is written into the table's row.  (The
+                # sky's gradient to the pose is not taken: the background is handed the composed pose detached.)
+                q_pointcloud_camera, t_pointcloud_camera = _pose_table.compose(q_pointcloud_camera, t_pointcloud_camera,
+                                                                               self.pose_table.row(view))
+                self.current_pose = (q_pointcloud_camera.detach(), t_pointcloud_camera.detach())
+            else:
+                self.current_pose = (q_pointcloud_camera, t_pointcloud_camera)
             rasterisation_input =self._rasterisation_input(
                 camera_info, q_pointcloud_camera, t_pointcloud_camera,
                 color_max_sh_band=color_max_sh_band_at(iteration, config.increase_color_max_sh_band_interval),
@@ -557,7 +617,7 @@ class GaussianPointCloudTrainer:
             if self.background_model is not None:
                 # the step's background: behind the splats, and behind the RGBA target if that is composited
                 background_coef = self.background_model.coef_for_step()
-                image_gt, pixel_weight = self._over_background(background_coef, image_gt, pixel_weight, q_pointcloud_camera, camera_info)
+                image_gt, pixel_weight = self._over_background(background_coef, image_gt, pixel_weight, self.current_pose[0], camera_info)
                 image_pred, image_depth, pixel_valid_point_count = self._render_over_background(rasterisation_input, background_coef)
             else:
                 image_pred, image_depth, pixel_valid_point_count = self.rasterisation(rasterisation_input)
@@ -598,6 +658,8 @@ class GaussianPointCloudTrainer:
                 self.appearance_table.step(view, iteration)
             if self.bilateral_table is not None:
                 self.bilateral_table.step(view, iteration)
+            if self._refining_poses(iteration):
+                self.pose_table.step(view, iteration)
 
             if self.mcmc is not None:
                 self.mcmc.after_step(iteration, position_optimizer.lr)       # the rate this iteration stepped with
@@ -674,6 +736,8 @@ class GaussianPointCloudTrainer:
             sums = dict(loss=0.0, psnr=0.0, ssim=0.0, inference_time=0.0)
             if self._colour_corrected:
                 sums.update(loss_cc=0.0, psnr_cc=0.0, ssim_cc=0.0)
+            if self.validation_pose_steps > 0:
+                sums.update(loss_aligned=0.0, psnr_aligned=0.0, ssim_aligned=0.0)
             count = 0
             total_terms, term_count = {term: 0.0 for term in self.terms}, {term: 0 for term in self.terms}
             for val_view, (image_gt, q_pointcloud_camera, t_pointcloud_camera, camera_info, pixel_weight) in enumerate(self._validation_targets()):
@@ -713,6 +777,20 @@ class GaussianPointCloudTrainer:
                     if value is not None:
                         total_terms[term] += value.item()
                         term_count[term] += 1
+                if self.validation_pose_steps > 0:
+                    # a validation view has no trained correction, and a scene trained with refined poses may have moved against
+                    # the dataset's frame: align the view against the frozen scene, then the same metrics (the BARF / nerfstudio
+                    # protocol).  Last: these renders replace the view's frame.
+                    with torch.enable_grad():
+                        q_aligned, t_aligned, _ = _pose_table.refine_pose(self.rasterisation, rasterisation_input, image_gt,
+                                                                          self.validation_pose_steps, pixel_weight=pixel_weight,
+                                                                          loss_function=self.loss_function)
+                    aligned = self.rasterisation(dataclasses.replace(rasterisation_input, q_pointcloud_camera=q_aligned,
+                                                                     t_pointcloud_camera=t_aligned))[0]
+                    loss, psnr_score, ssim_loss = self._metrics(torch.clamp(aligned, 0, 1).permute(2, 0, 1), image_gt, pixel_weight)
+                    sums["loss_aligned"] += loss.item()
+                    sums["psnr_aligned"] += psnr_score.item()
+                    sums["ssim_aligned"] += 1.0 - ssim_loss.item()
                 count += 1
             count = max(count, 1)
             means = {name: total / count for name, total in sums.items()}
@@ -735,6 +813,8 @@ class GaussianPointCloudTrainer:
                 self.background_model.save(os.path.join(self.config.output_model_dir, f"background_{iteration}.pt"))
             if self.filter3d is not None:
                 self.filter3d.save(os.path.join(self.config.output_model_dir, f"filter3d_{iteration}.pt"))
+            if self.pose_table is not None:
+                self.pose_table.save(os.path.join(self.config.output_model_dir, f"poses_{iteration}.pt"), self.train_image_paths())
             if means["psnr"] > self.best_psnr_score:
                 self.best_psnr_score = means["psnr"]
                 self.scene.to_parquet(os.path.join(self.config.output_model_dir, "best_scene.parquet"))
@@ -746,6 +826,8 @@ class GaussianPointCloudTrainer:
                     self.background_model.save(os.path.join(self.config.output_model_dir, "best_background.pt"))
                 if self.filter3d is not None:
                     self.filter3d.save(os.path.join(self.config.output_model_dir, "best_filter3d.pt"))
+                if self.pose_table is not None:
+                    self.pose_table.save(os.path.join(self.config.output_model_dir, "best_poses.pt"), self.train_image_paths())
             if hasattr(self.writer, "flush"):
                 self.writer.flush()
             self.last_validation = (iteration, means)

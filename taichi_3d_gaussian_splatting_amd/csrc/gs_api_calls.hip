@@ -21,6 +21,7 @@
 #include "../../include/gs_depth.h"
 #include "../../include/gs_geometry.h"
 #include "../../include/gs_normals.h"
+#include "../../include/gs_pose_table.h"
 #include "gs_host.h"
 
 #include <algorithm>
@@ -1100,6 +1101,36 @@ extern "C" int gs_vq_update(gs_ctx* c, const float* x, int64_t ldx, int64_t N, i
     if (((uintptr_t)weight_sums & 7u) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "gs_vq_update: weight_sums must be 8-byte aligned");
     return queued_call(c, stream_, "gs_vq_update", {},
                        [&](hipStream_t s) { gs_launch_vq_update(x, ldx, N, dim, weights, labels, codebook, ldc, K, counts, weight_sums, s); });
+}
+
+// ---- per-view camera pose corrections (include/gs_pose_table.h, k_posetable.hip) ------------------------------------------
+static int pose_table_check(const char* who, gs_ctx* c, int32_t V, int32_t K)
+{
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, who, "ctx is NULL");
+    if (V < 0 || V > GS_POSE_MAX_VIEWS) return fail(GS_ERR_INVALID_ARGUMENT, who, "V must be in [0, 2^24]");
+    if (K < 0 || K > GS_POSE_MAX_OBJECTS) return fail(GS_ERR_INVALID_ARGUMENT, who, "K must be in [0, 64]");
+    return GS_OK;
+}
+
+extern "C" int gs_pose_compose(gs_ctx* c, const float* delta, const float* q_base, const float* t_base, int32_t V, int32_t K, float* q_out,
+                               float* t_out, gs_stream stream_)
+{
+    if (const int rc = pose_table_check("gs_pose_compose", c, V, K)) return rc;
+    if (V == 0 || K == 0) return GS_OK;
+    if (!delta || !q_base || !t_base || !q_out || !t_out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pose_compose: NULL array");
+    return queued_call(c, stream_, "gs_pose_compose", {},
+                       [&](hipStream_t s) { gs_launch_pose_compose(delta, q_base, t_base, V, K, q_out, t_out, s); });
+}
+
+extern "C" int gs_pose_compose_backward(gs_ctx* c, const float* delta, const float* q_base, const float* grad_q, const float* grad_t, int32_t V,
+                                        int32_t K, float reg, float* grad_delta, gs_stream stream_)
+{
+    if (const int rc = pose_table_check("gs_pose_compose_backward", c, V, K)) return rc;
+    if (!std::isfinite(reg)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pose_compose_backward: reg must be finite");
+    if (V == 0 || K == 0) return GS_OK;
+    if (!delta || !q_base || !grad_q || !grad_t || !grad_delta) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pose_compose_backward: NULL array");
+    return queued_call(c, stream_, "gs_pose_compose_backward", {},
+                       [&](hipStream_t s) { gs_launch_pose_compose_backward(delta, q_base, grad_q, grad_t, V, K, reg, grad_delta, s); });
 }
 
 // ---- adaptive density control (k_density.hip) -------------------------------------------------------------------------

@@ -687,6 +687,11 @@ void gs_launch_appearance_backward(const GsLossImage& X, const GsLossImage& G, c
                                    float* grad_transform, void* ws, hipStream_t s);
 void gs_launch_appearance_moments(const GsLossImage& X, const GsLossImage& Y, const float* weight, int H, int W, double* moments, void* ws,
                                   hipStream_t s);
+// k_posetable.hip (include/gs_pose_table.h): a view's six floats composed onto its K base poses, and the way back.  The
+// launchers trust what the entry points checked; V, K > 0.
+void gs_launch_pose_compose(const float* delta, const float* q_base, const float* t_base, int V, int K, float* q_out, float* t_out, hipStream_t s);
+void gs_launch_pose_compose_backward(const float* delta, const float* q_base, const float* grad_q, const float* grad_t, int V, int K, float reg,
+                                     float* grad_delta, hipStream_t s);
 // k_background.hip (include/gs_background.h): a colour or a spherical-harmonics sky behind an image.  The launchers trust what
 // the entry points checked.  ws: gs_background_ws_size(H, W) bytes of the context's (the per-block sums), unused when grad_coef
 // is NULL.  X.p NULL: colours only.
